@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SpMM throughput of the MI355X engine on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (config.workload): BASELINE config 4, the configuration the metric "SpMM GFLOP/s + achieved
@@ -15,7 +15,8 @@ A "step" is one full pass  C_out = alpha*A*B + beta*C_in  from the API layout (c
 HBM -> B panel repack -> CSR row-group kernel -> column-major C_out [-> all-gather]).  FLOPs use the
 reference's convention 2*N*(nnz+M) (sextans-host.cpp:255-260).  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times the K steps and prints the headline; --dump-outputs DIR also writes C_out of the
+last timed step (dump_outputs).  Extra objects in the line, measured only with --full:
   roofline      dominant kernel (spmm_csr_rowgroup): algorithmic bytes per launch
                 (8*nnz + 4*(M+1) + 4*K*N + 8*M*N) / mean launch duration measured
                 with HIP events on the launch stream, against the 8 TB/s HBM3E spec peak.
@@ -45,6 +46,25 @@ def alg_bytes(M, K, N, nnz, beta_nonzero=True):
     return 8 * nnz + 4 * (M + 1) + 4 * K * N + 4 * M * N * (2 if beta_nonzero else 1)
 
 
+DUMP_MAX_VALUES = 1 << 22    # 16 MB of float32 per dump
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, torch, Cout, M, N, rowmajor):
+    """--dump-outputs: C_out as a caller of the timed path receives it, as float32 rows.  All M rows when M * N fits in
+    DUMP_MAX_VALUES, else a fixed, seeded, sorted sample of rows (the same for every run with the same arguments):
+      C_out_rows.npy       float32 [R, N], row r of C_out (any layout of the run reads back row-major here)
+      C_out_row_index.npy  float64 [R], the row numbers of C_out_rows"""
+    R = min(M, max(1, DUMP_MAX_VALUES // N))
+    rows = np.arange(M) if R == M else np.sort(np.random.default_rng(DUMP_SEED).choice(M, size=R, replace=False))
+    idx = torch.from_numpy(rows.astype(np.int64)).to(Cout.device)
+    torch.cuda.synchronize()
+    got = Cout.view(M, N).index_select(0, idx) if rowmajor else Cout.view(N, M).index_select(1, idx).t()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "C_out_rows.npy"), np.ascontiguousarray(got.cpu().numpy(), dtype=np.float32))
+    np.save(os.path.join(path, "C_out_row_index.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -67,7 +87,14 @@ def main():
                     help="the same workload with ROW-major B and C (sextans_spmm_device_rm; N>1: sextans_dist_spmm_rm, slabs in place, in-place all-gather). "
                          "Not the default: BASELINE.json's configuration is column-major")
     ap.add_argument("--even-rows", action="store_true", help="N>1: equal row counts per rank instead of nnz-balanced ranges")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (HIP-event kernel time, stored counter traffic), "
+                         "cpu_baseline, the secondary workloads (`also`), compute-only time at N>1, the forced 1-rank distributed check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write C_out of the last step (a fixed, seeded sample of its rows) to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -237,7 +264,9 @@ def main():
     dt = timed(step, args.steps)
     if comm is not None:   # nothing but data collectives inside the steps
         assert eng.get_stat("dist_setup_exchanges") == setup_exchanges, "a timed step exchanged control data or synchronised with the host"
-    dt_compute = timed(compute, args.steps) if multi else dt
+    if args.dump_outputs and rank == 0:   # C_out is complete on every rank after the last step
+        dump_outputs(args.dump_outputs, torch, Cout, M, N, args.rowmajor)
+    dt_compute = timed(compute, args.steps) if multi and args.full else dt
 
     nnz_tot = nnz_loc
     if multi:
@@ -248,43 +277,45 @@ def main():
     sec_per_step = dt / args.steps
     value = flops / sec_per_step / 1e9
 
-    # ---- dominant-kernel roofline: HIP events around each kernel launch on the launch stream
-    eng.set_option("profile", 1)
-    eng.profile_reset()
-    for _ in range(10):
-        compute()
-    torch.cuda.synchronize()
-    k_ns, k_n, rp_ns = eng.profile_read()
-    eng.set_option("profile", 0)
-    eng.profile_reset()
-    # at N > 1 a step launches the kernel once per row chunk: k_ns is the mean per launch, so scale to
-    # the whole slab (k_n launches were timed over 10 steps)
-    launches_per_step = max(1, k_n // 10)
-    k_ns *= launches_per_step
-    bytes_launch = alg_bytes(m_loc, K, N, nnz_loc)
-    achieved = bytes_launch / (k_ns * 1e-9) / 1e9
-    # HBM traffic of this kernel comes from separate rocprofv3 --pmc passes of this same command
-    # (tools/prof.sh -> profiles/*_traffic.json); only valid for the default single-GPU workload.
-    # It is NOT measured in this run: the value and its provenance are reported side by side.
-    traffic = traffic_source = None
-    tpath = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_config4_traffic.json") for r in (6, 5, 4, 3)) if os.path.exists(q)), "")
-    if world == 1 and args.rows == 4_000_000 and args.mean_nnz == 40.0 and N == 16 and not args.opt \
-            and os.path.exists(tpath):
-        tj = json.load(open(tpath))
-        if tj.get("kernel") == eng.last_kernel():
-            traffic = tj.get("traffic_bytes_per_launch")
-            traffic_source = ("stored, not measured in this run: profiles/" + os.path.basename(tpath) + " <- " +
-                              str(tj.get("source")))
-        else:   # the dispatcher picked another kernel than the one the counters were collected on: say so, loudly
-            traffic_source = (f"NOT APPLICABLE: profiles/{os.path.basename(tpath)} was collected on kernel {tj.get('kernel')!r}, this run's dominant kernel is "
-                              f"{eng.last_kernel()!r} -- re-run tools/prof.sh")
-            print("bench.py: WARNING: " + traffic_source, file=sys.stderr)
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "kernel": eng.last_kernel(), "kernel_us": round(k_ns / 1e3, 2),
-                "alg_bytes_per_launch": bytes_launch, "launches_timed": k_n,
-                "kernel_launches_per_step": launches_per_step,
-                "repack_us": round(rp_ns / 1e3, 2)}
+    roofline = None
+    if args.full:
+        # ---- dominant-kernel roofline: HIP events around each kernel launch on the launch stream
+        eng.set_option("profile", 1)
+        eng.profile_reset()
+        for _ in range(10):
+            compute()
+        torch.cuda.synchronize()
+        k_ns, k_n, rp_ns = eng.profile_read()
+        eng.set_option("profile", 0)
+        eng.profile_reset()
+        # at N > 1 a step launches the kernel once per row chunk: k_ns is the mean per launch, so scale to
+        # the whole slab (k_n launches were timed over 10 steps)
+        launches_per_step = max(1, k_n // 10)
+        k_ns *= launches_per_step
+        bytes_launch = alg_bytes(m_loc, K, N, nnz_loc)
+        achieved = bytes_launch / (k_ns * 1e-9) / 1e9
+        # HBM traffic of this kernel comes from separate rocprofv3 --pmc passes of this same command
+        # (tools/prof.sh -> profiles/*_traffic.json); only valid for the default single-GPU workload.
+        # It is NOT measured in this run: the value and its provenance are reported side by side.
+        traffic = traffic_source = None
+        tpath = next((q for q in (os.path.join(ROOT, "profiles", f"r0{r}_config4_traffic.json") for r in (6, 5, 4, 3)) if os.path.exists(q)), "")
+        if world == 1 and args.rows == 4_000_000 and args.mean_nnz == 40.0 and N == 16 and not args.opt \
+                and os.path.exists(tpath):
+            tj = json.load(open(tpath))
+            if tj.get("kernel") == eng.last_kernel():
+                traffic = tj.get("traffic_bytes_per_launch")
+                traffic_source = ("stored, not measured in this run: profiles/" + os.path.basename(tpath) + " <- " +
+                                  str(tj.get("source")))
+            else:   # the dispatcher picked another kernel than the one the counters were collected on: say so, loudly
+                traffic_source = (f"NOT APPLICABLE: profiles/{os.path.basename(tpath)} was collected on kernel {tj.get('kernel')!r}, this run's dominant kernel is "
+                                  f"{eng.last_kernel()!r} -- re-run tools/prof.sh")
+                print("bench.py: WARNING: " + traffic_source, file=sys.stderr)
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel": eng.last_kernel(), "kernel_us": round(k_ns / 1e3, 2),
+                    "alg_bytes_per_launch": bytes_launch, "launches_timed": k_n,
+                    "kernel_launches_per_step": launches_per_step,
+                    "repack_us": round(rp_ns / 1e3, 2)}
 
     out = {
         "metric": "SpMM GFLOP/s + achieved HBM GB/s (fp32, N=16) at 1/2/4/8 MI355X",
@@ -299,11 +330,11 @@ def main():
                                    f"all-gather(C) by {'sextans_dist_spmm_rm (in place, RCCL from the C ABI)' if args.rowmajor else 'sextans_dist_spmm (RCCL from the C ABI)' if args.native_dist else 'torch.distributed'}")
                    if world > 1 else "1 GPU"},
         "hbm_gbs_algorithmic_step": round(alg_bytes(M, K, N, nnz_tot) / sec_per_step / 1e9, 1),
-        "roofline": roofline,
+        **({"roofline": roofline} if roofline is not None else {}),
     }
     out["plan_build_s"] = round(eng.get_stat("plan_build_s"), 3)   # host packing of A, outside every timed region
     also = {}
-    if multi:
+    if multi and args.full:
         also["compute_only_ms_per_step"] = round(dt_compute / args.steps * 1e3, 4)
         also["compute_only_gflops"] = round(flops / (dt_compute / args.steps) / 1e9, 2)
         also["end_to_end_ms_per_step"] = round(sec_per_step * 1e3, 4)
@@ -315,12 +346,12 @@ def main():
                             else "sextans_dist_spmm (RCCL from the C ABI)" if comm is not None
                             else "torch.distributed all_gather_into_tensor"}
 
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if rank == 0 and world > 1 and args.full and not args.no_cpu_baseline:
         # N > 1: the same CPU leg on a smaller bounded sample (the other ranks wait at the final barrier meanwhile);
         # C_out is complete on every rank after the all-gather, so rank 0 also checks the first rows bit for bit
         args.cpu_seconds = min(args.cpu_seconds, 5.0)
         out["cpu_baseline"] = cpu_baseline(api, M, K, N, args, Cout, flops_per_row=None, all_cores=False, rowmajor=args.rowmajor)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if multi:   # forced single-rank distributed run: check the gathered C against the plain path
             ref = torch.empty_like(Cout)
             if args.rowmajor:

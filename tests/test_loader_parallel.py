@@ -9,7 +9,7 @@ import pytest
 
 import sextans_amd.api as api
 from oracle.bindings import CSC, CSR, Ref
-from util import bits_equal
+from util import bits_equal, digest, reference_digest
 
 HDR = "%%MatrixMarket matrix coordinate real general\n% c\n"
 
@@ -95,7 +95,11 @@ def test_float_text_is_rounded_once(oracle, tmp_path, threads):
     same_as_oracle(oracle, str(p), threads, counts=(1, 4))
 
 
-@pytest.mark.skipif(not Ref.available(), reason="oracle/_ref not built (needs /root/reference)")
+def _ref_load(path):
+    d = Ref().load(path)
+    return {f: digest(d[f][0].astype(np.int32), d[f][1].astype(np.int32), d[f][2]) for f in ("csr", "csc")}
+
+
 def test_against_the_reference_loader_itself(tmp_path, threads):
     rs = np.random.RandomState(11)
     n, M, K = 30000, 5000, 4000
@@ -104,13 +108,13 @@ def test_against_the_reference_loader_itself(tmp_path, threads):
         fh.write("%%MatrixMarket matrix coordinate real symmetric\n" + f"{M} {M} {n}\n")
         for a, b, x in zip(rs.randint(1, M + 1, n), rs.randint(1, M + 1, n), rs.uniform(-1, 1, n)):
             fh.write(f"{max(a, b)} {min(a, b)} {x:.9g}\n")
-    d = Ref().load(str(p))
+    d = reference_digest("loader", "random_symmetric_30000", lambda: _ref_load(str(p)))   # recorded; live where oracle/_ref is built
     for t in (1, 3, 8):
         threads(t)
         gp, gi, gv, gM, gK, gnnz = api.read_suitsparse_matrix(str(p), api.FMT_CSR)
-        assert np.array_equal(gp, d["csr"][0]) and np.array_equal(gi, d["csr"][1]) and bits_equal(gv, d["csr"][2])
+        assert digest(gp.astype(np.int32), gi.astype(np.int32), gv) == d["csr"]
         gp, gi, gv, _, _, _ = api.read_suitsparse_matrix(str(p), api.FMT_CSC)
-        assert np.array_equal(gp, d["csc"][0]) and np.array_equal(gi, d["csc"][1]) and bits_equal(gv, d["csc"][2])
+        assert digest(gp.astype(np.int32), gi.astype(np.int32), gv) == d["csc"]
 
 
 def test_first_error_in_file_order_wins(tmp_path, threads):

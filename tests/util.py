@@ -1,4 +1,6 @@
 """Shared test helpers: deterministic dense operands and comparison utilities."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -7,6 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 CASES = os.path.join(GOLDEN, "cases")
 NASA = os.path.join(ROOT, "matrices", "nasa4704", "nasa4704.mtx")
+REFERENCE_DIGESTS = os.path.join(GOLDEN, "reference_digests.json")
 
 ALPHA = np.float32(0.85)    # sextans-host.cpp:29
 BETA = np.float32(-2.06)    # sextans-host.cpp:30
@@ -46,6 +49,39 @@ def bits_equal(a, b):
     if not np.array_equal(na, nb):
         return False
     return np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def digest(*arrays):
+    """sha256 of each array's bytes, as hex strings.  float32 arrays hash their bit patterns with every NaN made the
+    same NaN, so that equal digests mean what bits_equal means; pass integer arrays in the dtype being compared."""
+    out = []
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.float32:
+            a = np.where(np.isnan(a), np.float32(np.nan), a).view(np.uint32)
+        out.append(hashlib.sha256(a.tobytes()).hexdigest())
+    return out
+
+
+def reference_digest(section, key, live):
+    """What the reference's own host functions returned for one test input, as digests recorded in
+    tests/golden/reference_digests.json, so that the comparison runs where the reference is absent.  Where
+    oracle/_ref is built, live() takes the same digests from the library now and they must equal the recording;
+    SEXTANS_RECORD_REFERENCE=1 (re)writes the recording from live() instead:
+        SEXTANS_RECORD_REFERENCE=1 python -m pytest tests/test_oracle_vs_reference.py tests/test_edge_stream.py \\
+            tests/test_loader_parallel.py"""
+    from oracle.bindings import Ref
+    with open(REFERENCE_DIGESTS) as f:
+        stored = json.load(f)
+    if os.environ.get("SEXTANS_RECORD_REFERENCE") == "1":
+        stored.setdefault(section, {})[key] = live()
+        with open(REFERENCE_DIGESTS, "w") as f:
+            json.dump(stored, f, indent=1, sort_keys=True)
+            f.write("\n")
+    want = stored[section][key]
+    if Ref.available():
+        assert json.loads(json.dumps(live())) == want, f"reference library disagrees with the recording {section}/{key}"
+    return want
 
 
 def random_csr(rs, M, K, mean_nnz, empty_frac=0.05, long_rows=0):
