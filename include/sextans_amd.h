@@ -379,7 +379,8 @@ int sextans_export_row_order(sextans_handle_t h, int *order, int *clustered);
  * of B the matrix has columns in: only those are repacked -- a rank of a row-partitioned SpMM over a banded matrix touches
  * 1 / world of B plus a halo), "cluster_decline" (why the graph clustering was not used: 1 not square and "row_similarity" = 0, 2 long-row paths,
  * 3 offsets, 4 natural blocks full, 5 no shared neighbourhoods, 6..9 a builder failed, 10..12 plan unusable / no gain,
- * 13 short rows in a local numbering). */
+ * 13 short rows in a local numbering), "transpose_build_s" (seconds spent building A^T and the plans of its companion engine,
+ * sextans_spmm_t_device_rm). */
 int sextans_get_stat(sextans_handle_t h, const char *key, double *value);
 
 /* Upload a CSR matrix (host pointers) once; later spmm calls reuse the device copy.  This is
@@ -435,7 +436,49 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
  * points prepare lazily.  `stream` is only used for the few device passes of the builders (it is synchronised). */
 #define SEXTANS_LAYOUT_COLMAJOR 0
 #define SEXTANS_LAYOUT_ROWMAJOR 1
+/* SEXTANS_LAYOUT_ROWMAJOR_T: the backward-pass forms -- A^T (sextans_csr_transpose_device) and everything the row-major calls of
+ * sextans_spmm_t_device_rm build (plans, workspaces) on the companion engine, and the row table of sextans_sddmm_device_rm.  After it, a transposed call for N and an SDDMM call allocate nothing
+ * and do not synchronise with the host: they may be captured into a hipGraph.  (Layout 2 is unused.) */
+#define SEXTANS_LAYOUT_ROWMAJOR_T 3
 int sextans_prepare(sextans_handle_t h, int N, int layout, void *stream);
+
+/* ---- Backward products (torch autograd of C = alpha * A * B + beta * C_in: dB = alpha * A^T * G, dA = alpha * (G * B^T) on A's pattern).
+ *
+ * Stable device transpose: the CSR of A^T (K x M) as new device arrays on `device` (sextans_device_free each), byte-identical to what the
+ * reference's CSC_2_CSR (sparse_helper.h:475-509) makes of A's CSR read as the CSC of A^T -- inside a row of A^T the entries come in
+ * ascending row of A and, for duplicate (row, column) entries, in storage order.  One stable radix sort of (column, entry) pairs: no atomics,
+ * the same bits on every run.  Empty rows / columns, M, K or nnz = 0 and duplicates are fine; nnz < 2^31; columns are validated
+ * (SEXTANS_ERR_INDEX outside [0, K)).  Enqueued on `stream` (NULL: the calling thread's default stream), which is synchronised. */
+int sextans_csr_transpose_device(int device, int M, int K, int64_t nnz, const int *d_row_ptr, const int *d_col_idx, const float *d_val,
+                                 int **o_row_ptr, int **o_col_idx, float **o_val, void *stream);
+
+/* C (K x N) = alpha * A^T * B + beta * C_in for the matrix set on h; B is M x N, every operand ROW-major, argument rules of
+ * sextans_spmm_device_rm (ld >= N, N % 8 == 0, C_in may alias C_out; unaligned operands take that entry point's fallback).
+ * The handle builds A^T once (sextans_csr_transpose_device) and holds it in an internal companion engine whose sextans_spmm_device_rm
+ * serves the call: A^T gets every path of the dispatcher (panel, clustered, gather, lane-per-row, long-row chains).  No atomic scatter:
+ *   SEXTANS_MODE_STRICT  bit-identical to cpu_spmm_CSR on CSC_2_CSR(A) (the arrays of sextans_csr_transpose_device);
+ *   SEXTANS_MODE_FAST    the tolerance stated with the modes (bit-equal to the fmaf chain on matrices without hub rows).
+ * Lifecycle: built by the first transposed call or by sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream); dropped by
+ * sextans_set_matrix_*, freed by sextans_destroy.  A^T's VALUES ARE A SNAPSHOT taken when it is built (as the packed plans of A are): a
+ * caller that changes A's values in place sets the matrix again.  Every sextans_set_option on h applies to the transposed form too, also
+ * later ones, with the same validation -- except "row_offset" and "global_nnz" (row slabs of the multi-GPU forms).  sextans_last_kernel(h)
+ * names the kernel the call ran; stat "device_bytes" includes A^T ((K + 1) * 4 + nnz * 8 bytes) and the companion's plans and workspaces;
+ * stat "transpose_build_s" = seconds spent building A^T and its plans. */
+int sextans_spmm_t_device_rm(sextans_handle_t h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
+                             int64_t ldc_in, float *d_C_out, int64_t ldc, void *stream);
+
+/* SDDMM on A's pattern, row-major X (M x N, X[r * ldx + n]) and Y (K x N): for every stored entry e = (r, c) of the matrix set on h, in
+ * the CSR entry order it was set with (not a plan's order):
+ *     acc = +0.0f;  for n = 0 .. N-1: acc = acc + X[r, n] * Y[c, n]      (every product and every sum rounded to fp32, no FMA)
+ *     out[e] = d_vals_in ? alpha * acc + beta * vals_in[e] : alpha * acc   (each product and the sum rounded: cpu_spmm_CSR's epilogue)
+ * -- cpu_spmm_CSR's rounding (sparse_helper.h:262-290) applied to a dot product, in EVERY mode.  d_vals_in may be NULL (not read) or alias
+ * d_vals_out.  Needs N % 8 == 0, ldx, ldy >= N with ld % 4 == 0 and 16-byte aligned d_X, d_Y, d_vals_in, d_vals_out; anything else is
+ * SEXTANS_ERR_INVALID (no fallback).  Work is split by non-zeros (hub rows spread over many wavefronts), no atomics; enqueued on `stream`.
+ * The first call on a matrix validates it (matrices set with sextans_set_matrix_csr_device) and builds a table of the row of every
+ * 256-entry range (nnz / 64 bytes, in stat "device_bytes"); later calls allocate nothing and do not synchronise with the host.
+ * sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) builds it ahead, with the transposed form. */
+int sextans_sddmm_device_rm(sextans_handle_t h, int N, float alpha, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, float beta,
+                            const float *d_vals_in, float *d_vals_out, void *stream);
 
 /* Row-range form: computes rows [row_begin, row_end) only.  d_C_in / d_C_out address row_begin as
  * their row 0 (ldc_in, ldc_out >= row_end - row_begin).  Used to pipeline a rank's slab in chunks so the

@@ -67,7 +67,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_device_rm", "sextans_dist_spmm_rm", "sextans_spmm_bell_device2", "sextans_dist_spmm_bell", "sextans_profile_read_post",
     "sextans_gen_kron_host", "sextans_gen_kron_device", "sextans_csr_slice_rows_device", "sextans_csr_permute_symmetric_device",
     "sextans_export_row_order", "sextans_mtx_read_cached", "sextans_matrix_save", "sextans_matrix_load",
-    "sextans_prepare", "sextans_dist_prepare", "sextans_dist_bind_library", "sextans_device_alloc", "sextans_device_copy"))
+    "sextans_prepare", "sextans_dist_prepare", "sextans_dist_bind_library", "sextans_device_alloc", "sextans_device_copy",
+    "sextans_csr_transpose_device", "sextans_spmm_t_device_rm", "sextans_sddmm_device_rm"))
 
 
 class _Optional:
@@ -249,6 +250,12 @@ def lib():
     L.sextans_device_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     L.sextans_device_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     L.sextans_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.sextans_csr_transpose_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+    L.sextans_spmm_t_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.sextans_sddmm_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.sextans_dist_bind_library.argtypes = [C.c_char_p]
     _lib = raw
@@ -550,9 +557,13 @@ class Engine:
         _check(lib().sextans_dist_spmm_rm(self._h, comm, world, rank, rr, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, stream),
                "dist_spmm_rm")
 
-    def prepare(self, N, rowmajor=False, stream=None):
-        """Build everything the first SpMM call for N columns would build inside itself (sextans_prepare)."""
+    def prepare(self, N, rowmajor=False, stream=None, *, transposed=False):
+        """Build everything the first SpMM call for N columns would build inside itself (sextans_prepare); transposed=True (keyword only,
+        so that prepare(N, rowmajor, stream) keeps its meaning): also A^T and the plans of the transposed row-major calls
+        (SEXTANS_LAYOUT_ROWMAJOR_T)."""
         _check(lib().sextans_prepare(self._h, N, 1 if rowmajor else 0, stream), "sextans_prepare")
+        if transposed:
+            _check(lib().sextans_prepare(self._h, N, 3, stream), "sextans_prepare(transposed)")
 
     def dist_prepare(self, comm, world, rank, ranges, N, nchunks=4, form=0, stream=None):
         """Collective: exchanges, plan build, tables and workspaces of the dist entry point `form` (0 sextans_dist_spmm, 1 _rm, 2 _bell)
@@ -696,6 +707,18 @@ class Engine:
         """ROW-major operands (B[k * ldb + n], C[m * ldc + n]): no layout pass on the LDS-panel paths (include/sextans_amd.h)."""
         _check(lib().sextans_spmm_device_rm(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream),
                "spmm_device_rm")
+
+    def spmm_t_device_rm(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream=None):
+        """C (K x N) = alpha * A^T * B + beta * C_in, B M x N, all ROW-major; A^T is built once and served by a companion engine with
+        this engine's options (sextans_spmm_t_device_rm)."""
+        _check(lib().sextans_spmm_t_device_rm(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream),
+               "spmm_t_device_rm")
+
+    def sddmm_device_rm(self, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream=None):
+        """vals_out[e] = alpha * sum_n X[r, n] * Y[c, n] (+ beta * vals_in[e]) for every entry e = (r, c) of A, in CSR order, with the
+        reference's rounding (sextans_sddmm_device_rm); d_vals_in may be None."""
+        _check(lib().sextans_sddmm_device_rm(self._h, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream),
+               "sddmm_device_rm")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):
@@ -1015,6 +1038,15 @@ def dist_comm_init(device, world, rank, uid):
 
 def dist_comm_destroy(comm):
     _check(lib().sextans_dist_comm_destroy(comm), "dist_comm_destroy")
+
+
+def csr_transpose_device(device, M, K, nnz, d_rp, d_ci, d_v, stream=None):
+    """CSR of A^T (K x M) as new device arrays (row_ptr, col_idx, val; free each with device_free), byte-identical to the reference's
+    CSC_2_CSR of A's CSR read as the CSC of A^T (sextans_csr_transpose_device)."""
+    p, i, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(lib().sextans_csr_transpose_device(device, M, K, nnz, d_rp, d_ci, d_v, C.byref(p), C.byref(i), C.byref(v), stream),
+           "csr_transpose_device")
+    return p.value, i.value, v.value
 
 
 def device_free(device, d_ptr):

@@ -1,0 +1,26 @@
+// csr_transpose.h -- stable transpose of a device-resident CSR matrix (csrc/csr_transpose.hip).
+//
+// A^T of an M x K CSR matrix is the CSR of a K x M matrix: row c of A^T holds the entries of column c of A, in ascending row of A and,
+// for duplicate (row, column) entries, in the order A stores them -- exactly what the reference's CSC_2_CSR (sparse_helper.h:475-509)
+// makes of A's CSR read as the CSC of A^T.  One stable radix sort of (column, entry index) pairs; no atomics decide a position, so the
+// result is a deterministic function of the input.  Users: the transposed SpMM of an engine (its companion engine holds A^T) and the
+// row-similarity / symmetrised graphs of the row clustering (csrc/graph_cluster.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+
+namespace sx {
+
+// t_rp (K + 1 ints), t_ci (nnz ints) and, when d_v is given, t_v (nnz floats) are caller-provided device arrays.  d_v == nullptr: the
+// pattern alone (t_v is not written).  Enqueued on `s`, which is synchronised before the scratch is released.  nnz < 2^31, columns in
+// [0, K) (the caller validates).  Returns 0, or 2 on a HIP error (err set).
+int csr_transpose_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, const float *d_v, int *t_rp, int *t_ci, float *t_v,
+                         hipStream_t s, std::string &err);
+
+// starts[k] = first position of `sorted` (nnz ascending keys) whose key is >= k, for k = 0 .. n (n + 1 ints): the row pointer of a
+// pattern sorted by row.  Enqueued on `s`.
+void segment_starts_device(int n, int64_t nnz, const int *sorted, int *starts, hipStream_t s);
+
+}  // namespace sx

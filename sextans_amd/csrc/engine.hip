@@ -361,6 +361,42 @@ int cc_prepare(sextans_engine *h, int N, bool *ok) {
     return SEXTANS_OK;
 }
 
+static const struct { const char *key; int64_t sextans_engine::*slot; } kOptions[] = {
+    {"kernel", &sextans_engine::opt_kernel}, {"lanes_per_row", &sextans_engine::opt_lpr}, {"stage_a", &sextans_engine::opt_stage},
+    {"xcd_remap", &sextans_engine::opt_xcd}, {"exact", &sextans_engine::opt_exact}, {"profile", &sextans_engine::opt_profile},
+    {"panel_min_reuse_x100", &sextans_engine::opt_min_reuse_x100}, {"panel_min_reuse_wide_x100", &sextans_engine::opt_min_reuse_wide_x100},
+    {"phase_timing", &sextans_engine::opt_phase_timing}, {"split_rows", &sextans_engine::opt_split_rows},
+    {"bucket_rows", &sextans_engine::opt_bucket_rows}, {"global_nnz", &sextans_engine::opt_global_nnz},
+    {"exact_chain", &sextans_engine::opt_exact_chain}, {"fuse_b", &sextans_engine::opt_fuse_b}, {"cols_per_lane", &sextans_engine::opt_cols_per_lane},
+    {"tiles_per_wg", &sextans_engine::opt_tiles_per_wg}, {"panel_v2", &sextans_engine::opt_panel_v2}, {"small_v2", &sextans_engine::opt_small_v2},
+    {"row_cluster", &sextans_engine::opt_row_cluster}, {"pipeline_tiles", &sextans_engine::opt_pipeline_tiles},
+    {"cluster_top", &sextans_engine::opt_cluster_top}, {"small_panel", &sextans_engine::opt_small_panel}, {"row_sets", &sextans_engine::opt_row_sets},
+    {"row_offset", &sextans_engine::opt_row_offset}, {"relabel_columns", &sextans_engine::opt_relabel_columns},
+    {"row_similarity", &sextans_engine::opt_row_similarity}, {"reordered_xcd", &sextans_engine::opt_reordered_xcd},
+    {"run_cluster", &sextans_engine::opt_run_cluster}, {"refine_sweeps", &sextans_engine::opt_refine_sweeps},
+    {"share_index", &sextans_engine::opt_share_index}, {"refine_rows", &sextans_engine::opt_refine_rows},
+    {"colwise_max_len", &sextans_engine::opt_colwise_max_len}, {"colwise_tiles_adjacent", &sextans_engine::opt_colwise_tiles_adjacent},
+    {"split_mixed", &sextans_engine::opt_split_mixed}, {"cluster_shape", &sextans_engine::opt_cluster_shape},
+    {"cluster_group", &sextans_engine::opt_cluster_group}, {"window_rows", &sextans_engine::opt_win_rows},
+    {"window_cols", &sextans_engine::opt_win_cols}, {"window_unroll", &sextans_engine::opt_win_unroll},
+    {"window_auto", &sextans_engine::opt_win_auto}, {"bell_wide", &sextans_engine::opt_bell_wide}, {"bell_generation", &sextans_engine::opt_bell_gen},
+    {"bell_shared", &sextans_engine::opt_bell_shared}, {"bell_debug", &sextans_engine::opt_bell_debug},
+    {"dist_broadcast_runs", &sextans_engine::opt_dist_broadcast_runs}, {"rowblock_tiles", &sextans_engine::opt_rb_tiles},
+    {"mfma_dense_tiles", &sextans_engine::opt_mfma_dense}, {"dense_tile_fill_x100", &sextans_engine::opt_dense_fill_x100},
+};
+
+// The transposed form carries the options of its engine (sextans_spmm_t_device_rm) -- except "row_offset" and "global_nnz", which
+// describe a row slab of the multi-GPU forms, not A^T.  key == nullptr: all of them (the companion was just created).
+int transposed_options(sextans_engine *h, const char *key, int64_t value) {
+    auto skip = [](const char *k) { return !strcmp(k, "row_offset") || !strcmp(k, "global_nnz"); };
+    if (key) return skip(key) ? SEXTANS_OK : sextans_set_option(h->tr, key, value);
+    for (const auto &o : kOptions)
+        if (!skip(o.key) && h->tr->*o.slot != h->*o.slot)
+            if (int rc = sextans_set_option(h->tr, o.key, h->*o.slot)) return rc;
+    h->tr->opt_mode = h->opt_mode;
+    return SEXTANS_OK;
+}
+
 }  // namespace sxe
 
 extern "C" {
@@ -426,54 +462,8 @@ int sextans_destroy(sextans_handle_t h) {
 }
 
 static int64_t *option_slot(sextans_handle_t h, const char *key) {
-    if (!strcmp(key, "kernel")) return &h->opt_kernel;
-    if (!strcmp(key, "lanes_per_row")) return &h->opt_lpr;
-    if (!strcmp(key, "stage_a")) return &h->opt_stage;
-    if (!strcmp(key, "xcd_remap")) return &h->opt_xcd;
-    if (!strcmp(key, "exact")) return &h->opt_exact;
-    if (!strcmp(key, "profile")) return &h->opt_profile;
-    if (!strcmp(key, "panel_min_reuse_x100")) return &h->opt_min_reuse_x100;
-    if (!strcmp(key, "panel_min_reuse_wide_x100")) return &h->opt_min_reuse_wide_x100;
-    if (!strcmp(key, "phase_timing")) return &h->opt_phase_timing;
-    if (!strcmp(key, "split_rows")) return &h->opt_split_rows;
-    if (!strcmp(key, "bucket_rows")) return &h->opt_bucket_rows;
-    if (!strcmp(key, "global_nnz")) return &h->opt_global_nnz;
-    if (!strcmp(key, "exact_chain")) return &h->opt_exact_chain;
-    if (!strcmp(key, "fuse_b")) return &h->opt_fuse_b;
-    if (!strcmp(key, "cols_per_lane")) return &h->opt_cols_per_lane;
-    if (!strcmp(key, "tiles_per_wg")) return &h->opt_tiles_per_wg;
-    if (!strcmp(key, "panel_v2")) return &h->opt_panel_v2;
-    if (!strcmp(key, "small_v2")) return &h->opt_small_v2;
-    if (!strcmp(key, "row_cluster")) return &h->opt_row_cluster;
-    if (!strcmp(key, "pipeline_tiles")) return &h->opt_pipeline_tiles;
-    if (!strcmp(key, "cluster_top")) return &h->opt_cluster_top;
-    if (!strcmp(key, "small_panel")) return &h->opt_small_panel;
-    if (!strcmp(key, "row_sets")) return &h->opt_row_sets;
-    if (!strcmp(key, "row_offset")) return &h->opt_row_offset;
-    if (!strcmp(key, "relabel_columns")) return &h->opt_relabel_columns;
-    if (!strcmp(key, "row_similarity")) return &h->opt_row_similarity;
-    if (!strcmp(key, "reordered_xcd")) return &h->opt_reordered_xcd;
-    if (!strcmp(key, "run_cluster")) return &h->opt_run_cluster;
-    if (!strcmp(key, "refine_sweeps")) return &h->opt_refine_sweeps;
-    if (!strcmp(key, "share_index")) return &h->opt_share_index;
-    if (!strcmp(key, "refine_rows")) return &h->opt_refine_rows;
-    if (!strcmp(key, "colwise_max_len")) return &h->opt_colwise_max_len;
-    if (!strcmp(key, "colwise_tiles_adjacent")) return &h->opt_colwise_tiles_adjacent;
-    if (!strcmp(key, "split_mixed")) return &h->opt_split_mixed;
-    if (!strcmp(key, "cluster_shape")) return &h->opt_cluster_shape;
-    if (!strcmp(key, "cluster_group")) return &h->opt_cluster_group;
-    if (!strcmp(key, "window_rows")) return &h->opt_win_rows;
-    if (!strcmp(key, "window_cols")) return &h->opt_win_cols;
-    if (!strcmp(key, "window_unroll")) return &h->opt_win_unroll;
-    if (!strcmp(key, "window_auto")) return &h->opt_win_auto;
-    if (!strcmp(key, "bell_wide")) return &h->opt_bell_wide;
-    if (!strcmp(key, "bell_generation")) return &h->opt_bell_gen;
-    if (!strcmp(key, "bell_shared")) return &h->opt_bell_shared;
-    if (!strcmp(key, "bell_debug")) return &h->opt_bell_debug;
-    if (!strcmp(key, "dist_broadcast_runs")) return &h->opt_dist_broadcast_runs;
-    if (!strcmp(key, "rowblock_tiles")) return &h->opt_rb_tiles;
-    if (!strcmp(key, "mfma_dense_tiles")) return &h->opt_mfma_dense;
-    if (!strcmp(key, "dense_tile_fill_x100")) return &h->opt_dense_fill_x100;
+    for (const auto &o : kOptions)
+        if (!strcmp(key, o.key)) return &(h->*o.slot);
     return nullptr;
 }
 
@@ -488,6 +478,7 @@ int sextans_set_option(sextans_handle_t h, const char *key, int64_t value) {
         // round 6 it does not beat the VALU kernels either (profiles/r06_rowblock_mfma.jsonl): it stays an option of its own, off in both modes)
         if (int rc = sextans_set_option(h, "mfma_dense_tiles", 0)) return rc;
         h->opt_mode = value;
+        if (h->tr) h->tr->opt_mode = value;
         return SEXTANS_OK;
     }
     int64_t *slot = option_slot(h, key);
@@ -540,7 +531,7 @@ int sextans_set_option(sextans_handle_t h, const char *key, int64_t value) {
         if (h->d_dbg) (void)hipMemset(h->d_dbg, 0, 64);
         if (!value && h->d_dbg) { (void)hipFree(h->d_dbg); h->d_dbg = nullptr; }
     }
-    return SEXTANS_OK;
+    return h->tr ? transposed_options(h, key, value) : SEXTANS_OK;
 }
 
 int sextans_phase_timing_read(sextans_handle_t h, int64_t out[8]) {
@@ -828,6 +819,7 @@ int sextans_get_stat(sextans_handle_t h, const char *key, double *value) {
     else if (!strcmp(key, "row_coherence")) *value = h->row_coherence;
     else if (!strcmp(key, "panel_blocks_clustered")) *value = (double)h->psc.plan_nblk;
     else if (!strcmp(key, "device_bytes")) *value = (double)device_bytes(h);
+    else if (!strcmp(key, "transpose_build_s")) *value = h->transpose_build_s + (h->tr ? h->tr->plan_build_s : 0.0);
     else if (!strcmp(key, "grid_stride_line")) *value = (double)h->cluster_s2;
     else if (!strcmp(key, "grid_stride_plane")) *value = (double)h->cluster_s3;
     else if (!strcmp(key, "panel_rows_natural")) *value = (double)h->plan_total_dict;  // B rows copied into LDS per N tile, natural order
@@ -1469,9 +1461,11 @@ int rm_plan(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
 extern "C" {
 
 int sextans_prepare(sextans_handle_t h, int N, int layout, void *stream) {
-    if (!h || N <= 0 || (N % 8) != 0 || (layout != SEXTANS_LAYOUT_COLMAJOR && layout != SEXTANS_LAYOUT_ROWMAJOR)) return SEXTANS_ERR_INVALID;
+    if (!h || N <= 0 || (N % 8) != 0 || (layout != SEXTANS_LAYOUT_COLMAJOR && layout != SEXTANS_LAYOUT_ROWMAJOR && layout != SEXTANS_LAYOUT_ROWMAJOR_T))
+        return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     SX_HIP(hipSetDevice(h->device));
+    if (layout == SEXTANS_LAYOUT_ROWMAJOR_T) return prepare_transposed(h, N, (hipStream_t)stream);
     if (h->M == 0) return SEXTANS_OK;
     std::vector<Seg> plan;
     int W = 0;

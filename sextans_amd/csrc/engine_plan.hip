@@ -97,6 +97,8 @@ int64_t device_bytes(const sextans_engine *h) {
     if (h->d_dense_Af) b += (int64_t)h->dense_mb * h->dense_W * (2048 + 4);
     if (h->d_bell_Af) b += (int64_t)(h->bell_M / 32) * h->bell_W * (2048 + (h->d_bell_col_owned ? 4 : 0));
     b += (int64_t)h->bell_Bf_cap;
+    if (h->tr) b += ((int64_t)h->K + 1) * 4 + h->nnz * 8 + device_bytes(h->tr);   // A^T and its companion's plans and workspaces
+    b += h->sddmm_row0_n * 4;
     b += 4 * (int64_t)(h->Bp_cap + h->B_cap + (h->d_Cin ? h->C_cap : 0) + h->C_cap + h->P_cap + h->stage_cap + h->chB_cap + h->chC_cap + h->Cs_cap + h->rmB_cap + h->rmC_cap + h->Cfull_cap + h->dist_rows_cap);
     return b;
 }
@@ -149,6 +151,7 @@ void free_dense(sextans_engine *h) {   // dense-tile state and everything downst
 }
 
 void free_matrix(sextans_engine *h) {
+    free_backward(h);
     free_plan(h);
     free_dense(h);
     free_window(h);

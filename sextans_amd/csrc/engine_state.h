@@ -307,6 +307,14 @@ struct sextans_engine {
     std::vector<sxe::EventPair> ev_kernel, ev_repack, ev_post;   // ev_post: passes behind the kernel (C staging -> C)
     const char *last_kernel = "none";
     std::string last_kernel_buf;        // storage for composed names
+    // transposed form (sextans_spmm_t_device_rm, engine_transpose.hip): A^T in arrays this engine owns, served by a companion engine
+    // that carries this engine's options -- a snapshot of A's values when it was built, dropped with the matrix
+    sextans_engine *tr = nullptr;
+    int *d_trp = nullptr, *d_tci = nullptr;
+    float *d_tv = nullptr;
+    double transpose_build_s = 0.0;     // seconds spent transposing A (the companion's plans: its own plan_build_s)
+    int *d_sddmm_row0 = nullptr;        // sextans_sddmm_device_rm: row of the first entry of every 256-entry wavefront range (+ M - 1 at the end)
+    int64_t sddmm_row0_n = 0;           // ints in it
 };
 
 namespace sxe {
@@ -322,6 +330,9 @@ void free_bell(sextans_engine *h);
 void free_split(sextans_engine *h);
 void free_dense(sextans_engine *h);
 void free_matrix(sextans_engine *h);
+void free_backward(sextans_engine *h);                     // engine_transpose.hip: A^T, its companion and the SDDMM row table
+int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)
+int transposed_options(sextans_engine *h, const char *key, int64_t value);   // engine.hip: one option (nullptr: all) onto the companion
 int ensure(float **p, size_t *cap, size_t need);
 int allow_big_lds(sextans_engine *h, const void *kern, int bytes);
 int read_back_row_ptr(sextans_engine *h, std::vector<int> &rp, int level = 2);

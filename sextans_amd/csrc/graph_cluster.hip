@@ -36,6 +36,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "csr_transpose.h"
 #include "graph_cluster.h"
 #include "thread_stream.h"
 
@@ -862,22 +863,9 @@ int local_square_pattern_device(int M, const int *d_rp, const int *d_ci, int row
 namespace {
 constexpr int kRowSimDeg = 16, kRowSimCols = 16, kRowSimHT = 1024;
 
-__global__ __launch_bounds__(256) void expand_row_ids(int M, const int *__restrict__ rp, int *__restrict__ rows) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + wave;
-    if (r >= M) return;
-    for (int j = rp[r] + lane; j < rp[r + 1]; j += 64) rows[j] = r;
-}
 __global__ __launch_bounds__(256) void fixed_degree_row_ptr(int n, int deg, int *rp) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) rp[i] = i * deg;
-}
-__global__ __launch_bounds__(256) void column_starts(int K, long long nnz, const int *__restrict__ sorted_cols, int *__restrict__ cp) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c > K) return;
-    long long lo = 0, hi = nnz;                     // first position whose column is >= c
-    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (sorted_cols[mid] < c) lo = mid + 1; else hi = mid; }
-    cp[c] = (int)lo;
 }
 __global__ __launch_bounds__(256) void row_similarity(int M, int K, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ cp,
                                                       const int *__restrict__ crow, int *__restrict__ g_ci, unsigned char *__restrict__ g_w,
@@ -984,29 +972,18 @@ int row_similarity_graph_device(int M, int K, int64_t nnz, const int *d_rp, cons
     *shared_fraction = *near_fraction = 0.0;
     if (M < 2 || K < 1 || nnz <= 0 || nnz > 0x7fffffffLL || (int64_t)M * kRowSimDeg > 0x7fffffffLL) return 1;
     Scratch tmp;
-    int *rows = nullptr, *cols = nullptr, *srows = nullptr, *scols = nullptr, *cp = nullptr, *orp = nullptr, *oci = nullptr;
+    int *srows = nullptr, *cp = nullptr, *orp = nullptr, *oci = nullptr;
     unsigned char *ow = nullptr;
     unsigned long long *d_acc = nullptr, h_acc[4] = {0, 0, 0, 0};
-    GC_HIP(tmp.alloc(&rows, (size_t)nnz));
-    GC_HIP(tmp.alloc(&cols, (size_t)nnz));
     GC_HIP(tmp.alloc(&srows, (size_t)nnz));
-    GC_HIP(tmp.alloc(&scols, (size_t)nnz));
     GC_HIP(tmp.alloc(&cp, (size_t)K + 1));
     GC_HIP(tmp.alloc(&orp, (size_t)M + 1));
     GC_HIP(tmp.alloc(&oci, (size_t)M * kRowSimDeg));
     GC_HIP(tmp.alloc(&ow, (size_t)M * kRowSimDeg));
     GC_HIP(tmp.alloc(&d_acc, 4));
     GC_HIP(hipMemsetAsync(d_acc, 0, sizeof h_acc, nullptr));
-    hipLaunchKernelGGL(expand_row_ids, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, rows);
-    GC_HIP(hipMemcpyAsync(cols, d_ci, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToDevice, nullptr));
-    int bits = 1;
-    while (bits < 32 && (1LL << bits) < (long long)K) ++bits;
-    void *sort_tmp = nullptr;
-    size_t bytes = 0;
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, cols, scols, rows, srows, (int)nnz, 0, bits, nullptr));
-    GC_HIP(tmp.alloc((char **)&sort_tmp, bytes));
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, cols, scols, rows, srows, (int)nnz, 0, bits, nullptr));   // stable: rows ascending per column
-    hipLaunchKernelGGL(column_starts, dim3(blocks_for((long long)K + 1, 256)), dim3(256), 0, nullptr, K, (long long)nnz, scols, cp);
+    // the pattern sorted by column: cp = row pointer of A^T, srows = its rows, ascending per column (csr_transpose.hip)
+    if (csr_transpose_device(M, K, nnz, d_rp, d_ci, nullptr, cp, srows, nullptr, nullptr, err)) return 2;
     hipLaunchKernelGGL(fixed_degree_row_ptr, dim3(blocks_for((long long)M + 1, 256)), dim3(256), 0, nullptr, M + 1, kRowSimDeg, orp);
     hipLaunchKernelGGL(row_similarity, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, K, d_rp, d_ci, cp, srows, oci, ow, d_acc);
     GC_HIP(hipMemcpy(h_acc, d_acc, sizeof h_acc, hipMemcpyDeviceToHost));
@@ -1116,7 +1093,7 @@ int symmetrize_graph_device(int M, int64_t nnz, const int *d_rp, const int *d_ci
     GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, eid, seid, (int)nnz, 0, bits, nullptr));
     GC_HIP(tmp.alloc((char **)&sort_tmp, bytes));
     GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, skey, eid, seid, (int)nnz, 0, bits, nullptr));   // stable: sources ascending per target
-    hipLaunchKernelGGL(column_starts, dim3(blocks_for((long long)M + 2, 256)), dim3(256), 0, nullptr, M + 1, (long long)nnz, skey, cp);
+    segment_starts_device(M + 1, nnz, skey, cp, nullptr);
     GC_HIP(hipMemsetAsync(cnt + M, 0, sizeof(int), nullptr));
     hipLaunchKernelGGL(sym_rows<false>, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, d_w, cp, seid, src, cnt, (const int *)nullptr,
                        (int *)nullptr, (unsigned char *)nullptr);
