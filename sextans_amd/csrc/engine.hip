@@ -311,9 +311,9 @@ __global__ __launch_bounds__(256) void position_rows(int nblk, int RB, const int
 }
 }  // namespace
 
-bool cc_usable(sextans_engine *h, int N, int W, const std::vector<Seg> &plan) {
-    return h->cluster_state == 2 && h->cluster_cm_pays && W == 16 && N % 16 == 0 && plan.size() == 1 && plan[0].width == 16 && h->nhub == 0 &&
-           h->nchain == 0 && (h->dense_W == 0 && h->rb_n == 0) && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->opt_pipeline_tiles == 0 && h->d_Cs && h->d_slot_row &&
+bool cc_usable(sextans_engine *h, int N, const Tiling &t) {
+    return h->cluster_state == 2 && h->cluster_cm_pays && t.W == 16 && N % 16 == 0 && t.segs.size() == 1 && t.segs[0].width == 16 && h->nhub == 0 &&
+           h->nchain == 0 && csr_only(h) && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->d_Cs && h->d_slot_row &&
            h->Cs_cap >= (size_t)(N / 16) * (size_t)h->M * 16 && h->Bp_cap >= (size_t)h->K * (size_t)N && h->psc.plan_sets == 1 &&
            (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)) && (int)h->psc.h_blk_row.size() == h->psc.plan_nblk + 1;
 }
@@ -352,12 +352,10 @@ void cc_finish(const float *tiles, float *C, int64_t ldc, int M_total, int N, hi
                        M_total, 0, N);
 }
 int cc_prepare(sextans_engine *h, int N, bool *ok) {
-    std::vector<Seg> plan;
-    int W = 0;
-    bool up = false, uw = false;
+    Tiling t;
     *ok = false;
-    if (int rc = prepare(h, N, plan, W, up, uw, true)) return rc;
-    *ok = cc_usable(h, N, W, plan);
+    if (int rc = prepare(h, N, true, &t)) return rc;
+    *ok = cc_usable(h, N, t);
     return SEXTANS_OK;
 }
 
@@ -369,8 +367,7 @@ static const struct { const char *key; int64_t sextans_engine::*slot; } kOptions
     {"bucket_rows", &sextans_engine::opt_bucket_rows}, {"global_nnz", &sextans_engine::opt_global_nnz},
     {"exact_chain", &sextans_engine::opt_exact_chain}, {"fuse_b", &sextans_engine::opt_fuse_b}, {"cols_per_lane", &sextans_engine::opt_cols_per_lane},
     {"tiles_per_wg", &sextans_engine::opt_tiles_per_wg}, {"panel_v2", &sextans_engine::opt_panel_v2}, {"small_v2", &sextans_engine::opt_small_v2},
-    {"row_cluster", &sextans_engine::opt_row_cluster}, {"pipeline_tiles", &sextans_engine::opt_pipeline_tiles},
-    {"cluster_top", &sextans_engine::opt_cluster_top}, {"small_panel", &sextans_engine::opt_small_panel}, {"row_sets", &sextans_engine::opt_row_sets},
+    {"row_cluster", &sextans_engine::opt_row_cluster}, {"cluster_top", &sextans_engine::opt_cluster_top}, {"small_panel", &sextans_engine::opt_small_panel}, {"row_sets", &sextans_engine::opt_row_sets},
     {"row_offset", &sextans_engine::opt_row_offset}, {"relabel_columns", &sextans_engine::opt_relabel_columns},
     {"row_similarity", &sextans_engine::opt_row_similarity}, {"reordered_xcd", &sextans_engine::opt_reordered_xcd},
     {"run_cluster", &sextans_engine::opt_run_cluster}, {"refine_sweeps", &sextans_engine::opt_refine_sweeps},
@@ -448,7 +445,6 @@ int sextans_destroy(sextans_handle_t h) {
     (void)hipFree(h->d_P);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    for (hipEvent_t e : h->ev_pipe) if (e) (void)hipEventDestroy(e);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
     (void)hipFree(h->d_dbg);
     (void)hipFree(h->d_chB); (void)hipFree(h->d_chC);
@@ -612,14 +608,12 @@ int sextans_align_row(sextans_handle_t h, int N, int row, int *aligned) {
     if (!h || !aligned || N <= 0 || (N % 8) != 0 || row < 0 || row > h->M) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     SX_HIP(hipSetDevice(h->device));
-    std::vector<Seg> plan;
-    int W = 0;
-    bool use_panel = false, use_window = false;
-    if (int rc = prepare(h, N, plan, W, use_panel, use_window, false)) return rc;
+    Tiling t;
+    if (int rc = prepare(h, N, false, &t)) return rc;
     *aligned = row;
     if (row == h->M) return SEXTANS_OK;
-    if (use_window) *aligned = row / h->win_rw * h->win_rw;
-    else if (use_panel && !h->ps.h_blk_row.empty())
+    if (t.window) *aligned = row / h->win_rw * h->win_rw;
+    else if (t.panel && !h->ps.h_blk_row.empty())
         *aligned = *(std::upper_bound(h->ps.h_blk_row.begin(), h->ps.h_blk_row.end(), row) - 1);
     return SEXTANS_OK;
 }
@@ -707,11 +701,39 @@ void launch_hub_pieces(sextans_engine *h, const sextans_engine::PieceTable &t, c
     if (rm_ldb > 0) { if (h->opt_exact) go(sx::spmm_csr_pieces<LPR, true, true>); else go(sx::spmm_csr_pieces<LPR, false, true>); }
     else if (h->opt_exact) go(sx::spmm_csr_pieces<LPR, true>); else go(sx::spmm_csr_pieces<LPR, false>);
 }
-}  // namespace
-extern "C" {
 
-}  // extern "C"
-namespace {
+// The partial sums of the long rows [hub0, hub1) of piece table t folded in order into C (rm: the caller's row-major C)
+void launch_fold(sextans_engine *h, const sextans_engine::PieceTable &t, int hub0, int hub1, int N, const float *dCin, int64_t ldc_in,
+                 float *dCout, int64_t ldc, int row_base, float alpha, float beta, bool rm, hipStream_t s) {
+    const int64_t tot = (int64_t)(hub1 - hub0) * N;
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t.d_vfirst, t.d_row, h->d_P, (int64_t)h->split_nv, dCin, ldc_in,
+                           dCout, ldc, hub0, hub1 - hub0, N, row_base, alpha, beta, rm ? 1 : 0);
+    };
+    if (h->opt_exact) go(sx::fold_hub_pieces<true>); else go(sx::fold_hub_pieces<false>);
+}
+
+// f(LPR) with the lanes per row of a tile width as a compile-time constant: 32 / 16 / 8 columns -> 8 / 4 / 2 lanes
+template <class F>
+int by_width(int width, F f) {
+    switch (width) {
+        case 32: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 2>{});
+    }
+}
+
+// N as 32-column tiles, then at most one 16- and one 8-column tile: the launches on the caller's row-major B, whose 32-column tiles
+// take whole 128-byte lines of a B row
+std::vector<Seg> wide_first(int N) {
+    std::vector<Seg> v;
+    int col = 0;
+    if (N / 32) { v.push_back(Seg{32, 0, N / 32}); col = N / 32 * 32; }
+    if ((N - col) / 16) { v.push_back(Seg{16, col, 1}); col += 16; }
+    if (N - col) v.push_back(Seg{8, col, 1});
+    return v;
+}
+
 // Round 6 (VERDICT r05 task 2, "measure first"): how many of a block's dictionary rows does the PREVIOUS block of the walk hold too?
 // One workgroup of 64 lanes per block: the previous dictionary into an LDS hash set (1024 slots, linear probing), this one probed.
 // out[0] += entries of block b found in block b - 1, out[1] += entries of block b  (b >= 1).
@@ -914,6 +936,345 @@ int sextans_reassociated_rows(sextans_handle_t h, int *rows, int capacity, int *
     return SEXTANS_OK;
 }
 
+}  // extern "C"
+namespace {
+// One SpMM as the caller asked for it: operands, row range [row_begin, row_end) (whole: all of the matrix), flags, stream
+struct Call {
+    int N; float alpha; const float *B; int64_t ldb; float beta; const float *C_in; int64_t ldc_in; float *C_out; int64_t ldc;
+    int row_begin, row_end, flags; hipStream_t s; bool whole;
+};
+
+// The chains need one or two wavefronts for about a millisecond: on their own stream, beside the main kernel (fork after the B
+// panels are in place, join before the call's work on `s` is considered complete).  rm: from the caller's row-major B.
+int fork_chains(sextans_engine *h, const Call &c, const std::vector<Seg> &segs, int ch0, int ch1, bool rm) {
+    SX_HIP(hipEventRecord(h->ev_fork, c.s));
+    SX_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
+    launch_chains(h, segs, c.C_in, c.ldc_in, c.C_out, c.ldc, c.N, ch0, ch1, c.row_begin, c.alpha, c.beta, h->aux_stream, false,
+                  rm ? c.B : nullptr, rm ? c.ldb : 0);
+    SX_HIP(hipEventRecord(h->ev_join, h->aux_stream));
+    return SEXTANS_OK;
+}
+
+// Everything sextans_spmm_device_rows decides for one call (route_cm), before anything is launched
+struct RouteCM {
+    enum Path { kWindow, kColwise, kSegments } path = kSegments;
+    enum Launch { kReorderedV2, kV2Wide, kSplitMixed, kV2, kPanel, kRowgroup };   // of a segment; the first four are spmm_csr_panel_v2
+    bool panel = false;                                // the plan's panel kernels serve this range: its row blocks [blk0, blk1)
+    int blk0 = 0, blk1 = 0;
+    const sextans_engine::PieceTable *pt = nullptr;    // long rows of this range: entries [hub0, hub1) of *pt, pieces [v0, v1)
+    int hub0 = 0, hub1 = 0, v0 = 0, v1 = 0;
+    int ch0 = 0, ch1 = 0;                              // chain rows of this range
+    bool hubs = false, chains = false;
+    bool fuse_b = false, reordered = false, clustered = false;
+    int64_t cs_tile = 0;                               // reordered: floats per 16-column tile of the staging buffer
+    std::vector<Seg> segs;                             // the tiling of N, its 8-column tail merged where that pays
+    Launch launch[3] = {};                             // per segment (at most three: tiles W, 16 and 8 columns wide)
+    int layout = 0;                                    // bp_layout of the panels this call runs on
+    bool skip_repack = false;
+};
+
+// The launch of every segment of r.segs (W: the width the plan is built for; wide_fits_b: route_cm)
+void choose_launches(const sextans_engine *h, const Call &c, int W, bool wide_fits_b, RouteCM &r) {
+    // (column-major staging keeps the round-1 kernel unless the rows are short: then the register-resident form fits
+    // 128 registers together with a panel in registers)
+    const bool short_rows = h->M > 0 && h->m_nnz / h->M + 8 <= 32;
+    for (size_t i = 0; i < r.segs.size(); ++i) {
+        const Seg &g = r.segs[i];
+        const bool panel_here = r.panel && g.width == W;   // the plan is built for width W
+        const bool v2_16 = panel_here && g.width == 16 && wide_fits_b;
+        // (long rows + column-major staging: the 256-register instantiation, for launches that cannot fill the chip -- option
+        // "panel_v2" = 1 asks for it, the automatic setting keeps spmm_csr_panel there: measured)
+        const bool big_ok = r.fuse_b && !short_rows && h->opt_panel_v2 == 1 && (int64_t)(r.blk1 - r.blk0) * g.ntiles <= 8192;
+        RouteCM::Launch l = panel_here ? RouteCM::kPanel : RouteCM::kRowgroup;
+        if (r.reordered && g.width == 16) l = RouteCM::kReorderedV2;
+        // N >= 32 on a dictionary-only plan at 4 lanes per row: register-blocked 32-column super tiles with the
+        // tile loop inside the workgroup; an odd 16-column tile at the end goes to the plain panel kernel
+        else if (v2_16 && !h->ps.plan_mixed && h->opt_cols_per_lane == 8 && g.ntiles >= 2) l = RouteCM::kV2Wide;
+        // MIXED plans, split form (round 5): the blocks that have a dictionary run on the register-resident kernel (it leaves the others
+        // alone), the rows of the blocks without one -- no reuse between their rows -- on the gather kernel behind it (its skip table
+        // names the rows that are not its own).  One launch of spmm_csr_panel<MIXED> did both at the speed of neither: FEM rows + 10 / 30 /
+        // 60 % uniformly random rows, N = 16: 311 / 468 / 698 us per step -> 280 / 424 / 644; through the row-major entry point 406 / 581 / 832
+        // (column-major copies around the mixed kernel) -> 235 / 375 / 611 (tools/mixed_rm_probe.py).  Both launches walk compact lists
+        // (blocks with a dictionary; groups of 128 rows with a gather row): a launch over everything whose other workgroups leave at
+        // once hands the XCDs unequal shares -- measured 2 x slower.  (The gather launch on a second stream beside the other one: built,
+        // measured equal -- the first launch fills every workgroup slot of the chip, the second queues behind it either way.)
+        // (whole-matrix calls: the launches walk lists made for the whole plan)
+        else if (v2_16 && h->ps.plan_mixed && h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_panel_v2 != 0 && !r.fuse_b &&
+                 h->opt_kernel == 0 && c.whole) l = RouteCM::kSplitMixed;
+        else if (v2_16 && !h->ps.plan_mixed && h->opt_panel_v2 != 0 && (!r.fuse_b || short_rows || big_ok)) l = RouteCM::kV2;
+        r.launch[i] = l;
+    }
+}
+
+RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
+    RouteCM r;
+    const int N = c.N;
+    // a row range keeps the panel kernel when it starts and ends on row-block boundaries of the plan
+    r.panel = t.panel;
+    r.blk1 = h->ps.plan_nblk;
+    if (r.panel && !c.whole) {
+        const auto &br = h->ps.h_blk_row;
+        const auto i0 = std::lower_bound(br.begin(), br.end(), c.row_begin), i1 = std::lower_bound(br.begin(), br.end(), c.row_end);
+        if (i0 == br.end() || *i0 != c.row_begin || i1 == br.end() || *i1 != c.row_end) r.panel = false;
+        else { r.blk0 = (int)(i0 - br.begin()); r.blk1 = (int)(i1 - br.begin()); }
+    }
+    // ... and the window kernel when it starts and ends on wavefront (rows-per-wave) boundaries
+    const bool window = t.window && c.row_begin % h->win_rw == 0 && (c.row_end % h->win_rw == 0 || c.row_end == h->M);
+    // long rows of this range: entries [hub0, hub1) of a piece table, pieces [v0, v1).  Whole-matrix calls walk the
+    // table sorted by length (workgroups of equally long pieces), row ranges the one sorted by row.
+    r.pt = c.whole ? &h->by_len : &h->by_row;
+    if (h->nhub > 0) {
+        const auto &rows = r.pt->h_row;
+        if (c.whole) { r.hub1 = h->nhub; }
+        else {
+            r.hub0 = (int)(std::lower_bound(rows.begin(), rows.end(), c.row_begin) - rows.begin());
+            r.hub1 = (int)(std::lower_bound(rows.begin(), rows.end(), c.row_end) - rows.begin());
+        }
+        r.v0 = r.pt->h_vfirst[(size_t)r.hub0]; r.v1 = r.pt->h_vfirst[(size_t)r.hub1];
+    }
+    r.hubs = r.hub1 > r.hub0;
+    r.ch1 = h->nchain;
+    if (h->nchain > 0 && !c.whole) {
+        r.ch0 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), c.row_begin) - h->h_chain_row.begin());
+        r.ch1 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), c.row_end) - h->h_chain_row.begin());
+    }
+    r.chains = r.ch1 > r.ch0;
+    if (window) {
+        // (a reuse request is honoured only if the panels in the workspace have this layout: row-range calls of
+        // one pipelined SpMM may alternate between the window kernel's 8-column panels and those of the other kernels)
+        r.path = RouteCM::kWindow;
+        r.layout = 8;
+        r.skip_repack = (c.flags & SEXTANS_ROWS_REUSE_B_PANELS) != 0 && h->bp_layout == 8;
+        return r;
+    }
+    // Short rows in a numbering with locality (or "kernel" = 4): one lane per row on the caller's column-major operands -- no B
+    // repack, no LDS (spmm_colwise_kernel.h).  Rows on the long-row paths need the repacked panels: then the other kernels run.
+    if (colwise_wanted(h) && !r.hubs && !r.chains && csr_only(h) && h->m_nnz > 0) {
+        r.path = RouteCM::kColwise;
+        return r;
+    }
+    // Small B (fits the L2s), dictionary-only plan, one N segment: the panel kernel stages straight from the
+    // caller's column-major B and the repack launch disappears.
+    r.fuse_b = r.panel && !h->ps.plan_mixed && h->opt_fuse_b && !(c.flags & kRowsNoFuseB) && t.segs.size() == 1 && h->rb_n == 0 &&   // (routed row blocks read the repacked panels)
+               t.segs[0].width == t.W && !r.hubs && !r.chains &&
+               (size_t)h->K * (size_t)N * sizeof(float) <= ((size_t)16 << 20) &&
+               // (a graph-clustered plan beats the natural-order blocks of a renumbered matrix also while B fits the L2s, once the
+               // matrix is large enough for three more launches not to matter: 332 K rows 123 -> 85 us per step)
+               // (... and below that size once the call is large enough: a 13 965-row matrix in a random node order, N = 128,
+               // 112 us staged from column-major B on its natural-order plan against 34 us reordered; N = 16: 13.3 against 15.0.
+               // Crossover measured at ~24 M non-zero x column products: tools/small_renumbered.py)
+               !(c.whole && h->cluster_state == 2 && h->cluster_cm_pays && (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)));
+    // (Staging from column-major B for LARGE matrices -- no repack launch at all -- was measured in round 4 and loses everywhere: 4M-row
+    // 3-dof FEM N = 16 kernel 660 -> 872 us against 83 us of repack saved; 1-dof 27-point 379 -> 577; 2-D 9-point 296 -> 427;
+    // 5-point 270 -> 412: 36 four-byte loads per lane and panel through registers instead of nine LDS-DMA requests.)
+    // The reordered form (graph-clustered plan, ensure_cluster_plan): whole-matrix calls, 16-column tiles.  Its B panels hold the
+    // rows of B in the plan's column order and C goes through the block-major staging buffer (reorder_kernels.h); an 8-column
+    // remainder tile keeps the natural-order kernels and panels.  (Layout tag -W: such panels are never reused by a row-range call.)
+    r.reordered = c.whole && h->cluster_state == 2 && h->cluster_cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3 && t.W == 16 && !r.fuse_b &&
+                  (!r.chains || h->d_chain_ci_perm) && csr_only(h) && h->d_Cs &&
+                  // (the staging buffer is sized by prepare() for the N it saw: a plan that survived a set_option("kernel") and a
+                  // larger N since then must not run past its end -- ADVICE r04)
+                  h->Cs_cap >= (size_t)((N + 15) / 16) * (size_t)h->M * 16 && (N >= 16 || (N == 8 && !r.hubs && !r.chains));
+    r.cs_tile = r.reordered ? (int64_t)h->M * 16 : 0;
+    // 32-bit byte offsets inside the wide kernels: panels and C columns (wide_fits), and the caller's B when the kernel stages
+    // from it (wide_fits_b)
+    const bool wide_fits = h->ps.plan_max_dict <= sx::kWideMaxDict && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
+                           std::max(c.ldc, c.ldc_in) * 64 < ((int64_t)1 << 32);
+    const bool wide_fits_b = wide_fits && (!r.fuse_b || c.ldb * 64 < ((int64_t)1 << 32));
+    // N = 16 t + 8 on the register-resident panel kernel: the 8-column tail used to go to the gather kernel (the plan is built for
+    // 16-column tiles) -- 4M-row FEM matrix: N = 24 2 152 us per step against 1 099 at N = 32.  It now runs as one more 16-column tile:
+    // its B panel is zero in the 8 columns that do not exist, the kernel neither loads nor stores C there (`last_cols`), the passes of
+    // the reordered form skip them; rows on the piece path sum 16 columns into their (wider) partial-sum buffer and fold N, the exact
+    // chains take the tail as one 8-column tile of the 16-column panel.  Not with dense tiles on the MFMA path or column-major staging.
+    const bool v2 = r.reordered || (r.panel && !h->ps.plan_mixed && h->opt_panel_v2 != 0 && !r.fuse_b && wide_fits && h->opt_cols_per_lane != 8);
+    std::vector<Seg> &plan = r.segs;
+    plan = std::move(t.segs);
+    if (v2 && t.W == 16 && plan.size() == 2 && plan[0].width == 16 && plan[1].width == 8 && plan[1].ntiles == 1 &&
+        (h->nhub == 0 || h->P_cap >= (size_t)h->split_nv * (size_t)(N + 8)) &&
+        // (with rows on the piece / chain paths only where the main rows are long enough to matter: on the KKT class -- 6 entries per
+        // row, arrow borders as chains -- the wider piece / chain work cost more than the gather tail: 1 510 -> 1 687 us at N = 24)
+        ((h->nhub == 0 && h->nchain == 0) || (h->M > 0 && h->m_nnz / h->M >= 16)) &&
+        csr_only(h) && h->Bp_cap >= (size_t)h->K * (size_t)(N + 8) &&
+        (!r.reordered || h->Cs_cap >= (size_t)(N / 16 + 1) * (size_t)h->M * 16)) {
+        plan[0].ntiles += 1;
+        plan[0].last_cols = 8;
+        plan.pop_back();
+    } else if (v2 && t.W == 16 && plan.size() == 1 && plan[0].width == 8 && plan[0].ntiles == 1 && h->nhub == 0 && h->nchain == 0 &&
+               csr_only(h) && h->Bp_cap >= (size_t)h->K * 16 && (!r.reordered || h->Cs_cap >= (size_t)h->M * 16)) {
+        plan[0] = Seg{16, 0, 1, 8};   // N = 8 on the 16-column plan (engine_plan.hip: prepare, n8_wide)
+    }
+    r.layout = r.reordered ? -t.W : plan[0].last_cols != 0 ? t.W + 100 : t.W;
+    r.skip_repack = r.fuse_b || ((c.flags & SEXTANS_ROWS_REUSE_B_PANELS) != 0 && h->bp_layout == r.layout);
+    // whole-matrix calls on repacked panels: the plan over the rows in clustered (brick) order when the matrix has one
+    r.clustered = c.whole && !r.fuse_b && h->cluster_state == 1;
+    choose_launches(h, c, t.W, wide_fits_b, r);
+    return r;
+}
+
+int run_window(sextans_engine *h, const Call &c, const RouteCM &r) {
+    const int N = c.N;
+    hipStream_t s = c.s;
+    // B in 8-column panels (the reference's N tile), then one tile-major launch
+    if (!r.skip_repack) {
+        Prof p(h, &h->ev_repack, s);
+        launch_repack<8>(c.B, c.ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->d_touched);
+        h->bp_layout = r.layout;
+    }
+    {
+        Prof p(h, &h->ev_kernel, s);
+        const int w0 = c.row_begin / h->win_rw, w1 = (c.row_end + h->win_rw - 1) / h->win_rw;
+        launch_window(h, h->d_Bp, c.C_in, c.ldc_in, c.C_out, c.ldc, N / 8, w0, w1, c.row_begin, c.alpha, c.beta, s);
+        const std::vector<Seg> p8{{8, 0, N / 8}};
+        if (r.hubs) {
+            launch_hub_pieces<2>(h, *r.pt, h->d_Bp, N / 8, 0, r.v0, r.v1, s);
+            launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+        }
+        if (r.chains) launch_chains(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, r.ch0, r.ch1, c.row_begin, c.alpha, c.beta, s);
+        h->last_kernel = kernel_name(2, r.hubs || r.chains, h->dense_W > 0);
+        if (h->rb_n > 0) {
+            if (int rc = launch_rowblocks(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
+            h->last_kernel = with_rowblocks(h, h->last_kernel);
+        }
+    }
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+
+int run_colwise(sextans_engine *h, const Call &c) {
+    Prof p(h, &h->ev_kernel, c.s);
+    const int nrowblk = (c.row_end - c.row_begin + sx::kBlock - 1) / sx::kBlock;
+    auto go = [&](auto kern, int col0, int ntiles) {
+        // (tiles of a row block neighbours in the launch order: the row block's CSR entries come from HBM once -- measured on the 4M-row
+        // 5-point stencil, two boxes: N = 32 0.513 / 0.527 -> 0.532 / 0.550 of the roofline; N = 48 / 64 equal or 1 % behind; N = 128 / 256
+        // 0.51 -> 0.43 .. 0.49: more column streams in flight per XCD than its L2 keeps; "colwise_tiles_adjacent" 1 = two tiles, 2 = always,
+        // 0 = never; profiles/r05_colwise_tile_order_ab.txt)
+        const int adj = ntiles > 1 && (h->opt_colwise_tiles_adjacent == 2 || (h->opt_colwise_tiles_adjacent == 1 && ntiles <= 2)) &&
+                        (int64_t)nrowblk * ntiles < ((int64_t)1 << 31) ? ntiles : 0;
+        hipLaunchKernelGGL(kern, adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)ntiles), dim3(sx::kBlock), 0, c.s, h->m_rp, h->m_ci,
+                           h->m_v, c.B, c.ldb, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.row_end, nrowblk, col0, c.alpha, c.beta, (int)h->opt_xcd,
+                           (const unsigned char *)h->d_skip, adj, 1);
+    };
+    const int n16 = c.N / 16;
+    if (n16 > 0) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 16>, 0, n16); else go(sx::spmm_csr_colwise<false, 16>, 0, n16); }
+    if (c.N % 16) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 8>, n16 * 16, 1); else go(sx::spmm_csr_colwise<false, 8>, n16 * 16, 1); }
+    h->last_kernel = "spmm_csr_colwise";
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+
+// One segment's main launch(es) and, for rows on the piece path, its piece launch
+int launch_segment(sextans_engine *h, const Call &c, const RouteCM &r, const Seg &g, RouteCM::Launch l) {
+    hipStream_t s = c.s;
+    const float *bp = h->d_Bp + (size_t)h->K * (size_t)g.col0;
+    const float *cin = c.C_in + (int64_t)g.col0 * c.ldc_in;
+    float *cout = c.C_out + (int64_t)g.col0 * c.ldc;
+    const float *bsrc = r.fuse_b ? c.B + (int64_t)g.col0 * c.ldb : bp;
+    const int64_t bld = r.fuse_b ? c.ldb : 0;
+    switch (l) {
+        case RouteCM::kReorderedV2:
+            if (int rc = launch_panel_v2<1>(h, bp, h->d_Cs, r.cs_tile, h->d_Cs, r.cs_tile, g.ntiles, c.alpha, c.beta, s, 0, 0, h->psc.plan_nblk, 0, 2))
+                return rc;   // (a merged tail tile needs no mask here: its staging columns exist, the pass below writes back the valid ones)
+            // rows on the piece path: their partial sums from the PERMUTED panels (column c sits at row colpos[c]); folded into C
+            // behind the staging -> C pass below, which leaves C_in in their rows
+            if (r.hubs) launch_hub_pieces<4>(h, *r.pt, bp, g.ntiles, g.col0, r.v0, r.v1, s, h->d_colpos);
+            return SEXTANS_OK;
+        case RouteCM::kV2Wide: {
+            const int nsuper = g.ntiles / 2;
+            if (int rc = launch_panel_v2<2>(h, bsrc, cin, c.ldc_in, cout, c.ldc, nsuper, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin))
+                return rc;
+            if (g.ntiles & 1) {
+                const int64_t c0 = (int64_t)nsuper * 32;
+                if (int rc = launch_panel<4>(h, r.fuse_b ? bsrc + c0 * c.ldb : bsrc + c0 * (int64_t)h->K, cin + c0 * c.ldc_in, c.ldc_in,
+                                             cout + c0 * c.ldc, c.ldc, 1, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin))
+                    return rc;
+            }
+            break;
+        }
+        case RouteCM::kSplitMixed:
+            if (int rc = launch_panel_v2<1>(h, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, 0, r.blk0, r.blk1, c.row_begin, 0, 16, 0, true))
+                return rc;
+            launch_rowgroup<4>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end, g.ntiles,
+                               c.alpha, c.beta, s, 0, false, h->ps.d_rg_groups, h->ps.rg_ngroups);
+            break;
+        case RouteCM::kV2:
+            if (int rc = launch_panel_v2<1>(h, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.clustered ? 0 : r.blk0,
+                                            r.clustered ? h->psc.plan_nblk : r.blk1, c.row_begin, r.clustered ? 1 : 0, g.last_cols ? g.last_cols : 16))
+                return rc;
+            break;
+        default:   // the panel or the gather kernel at the lanes per row of the segment's width
+            return by_width(g.width, [&](auto L) -> int {
+                constexpr int LPR = decltype(L)::value;
+                if (l == RouteCM::kPanel) {
+                    if (int rc = launch_panel<LPR>(h, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin)) return rc;
+                } else {
+                    launch_rowgroup<LPR>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->d_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end,
+                                         g.ntiles, c.alpha, c.beta, s);
+                }
+                if (r.hubs) launch_hub_pieces<LPR>(h, *r.pt, bp, g.ntiles, g.col0, r.v0, r.v1, s);
+                return SEXTANS_OK;
+            });
+    }
+    if (r.hubs) launch_hub_pieces<4>(h, *r.pt, bp, g.ntiles, g.col0, r.v0, r.v1, s);
+    return SEXTANS_OK;
+}
+
+int run_segments(sextans_engine *h, const Call &c, const RouteCM &r) {
+    const int N = c.N;
+    hipStream_t s = c.s;
+    auto seg_cols = [](const Seg &g) { return g.last_cols ? (g.ntiles - 1) * g.width + g.last_cols : g.ntiles * g.width; };
+    if (!r.skip_repack || r.reordered) {
+        Prof p(h, &h->ev_repack, s);
+        if (!r.skip_repack) {
+            h->bp_layout = r.layout;
+            for (const Seg &g : r.segs) {
+                float *dst = h->d_Bp + (size_t)h->K * (size_t)g.col0;
+                if (r.reordered && g.width == 16 && h->d_colpos) {
+                    hipLaunchKernelGGL(sx::repack_b_panels_perm, dim3((unsigned)((h->col_hi - h->col_lo + sx::kBlock - 1) / sx::kBlock), (unsigned)g.ntiles),
+                                       dim3(sx::kBlock), 0, s, c.B, c.ldb, dst, h->K, g.col0, h->d_colpos, h->col_lo, h->col_hi, seg_cols(g), h->d_touched);
+                    continue;
+                }
+                by_width(g.width, [&](auto L) {   // (panels of the segment's width: 4 * LPR columns)
+                    launch_repack<4 * decltype(L)::value>(c.B, c.ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, seg_cols(g), h->d_touched);
+                    return SEXTANS_OK;
+                });
+            }
+        }
+        if (r.reordered)
+            for (const Seg &g : r.segs)
+                if (g.width == 16)
+                    launch_repack<16>(c.C_in, c.ldc_in, h->d_Cs, h->M, g.col0, g.ntiles, s, 0, -1, seg_cols(g));   // C_in -> row-major tiles
+    }
+    {
+        Prof p(h, &h->ev_kernel, s);
+        if (r.chains && !r.reordered)
+            if (int rc = fork_chains(h, c, r.segs, r.ch0, r.ch1, false)) return rc;
+        for (size_t i = 0; i < r.segs.size(); ++i)
+            if (int rc = launch_segment(h, c, r, r.segs[i], r.launch[i])) return rc;
+        if (r.hubs && !r.reordered) launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+        if (r.chains && !r.reordered) SX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
+        const bool v2_used = std::any_of(r.launch, r.launch + r.segs.size(), [](RouteCM::Launch l) { return l < RouteCM::kPanel; });
+        h->last_kernel = r.reordered ? "spmm_csr_panel_v2_reordered" : kernel_name(v2_used ? 3 : r.panel ? 1 : 0, r.hubs || r.chains, h->dense_W > 0);
+        if (h->rb_n > 0) {   // dense blocks of 16 rows on the fp32 matrix cores, from the same panels (the kernels above skipped their rows)
+            if (int rc = launch_rowblocks(h, r.segs, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
+            h->last_kernel = with_rowblocks(h, h->last_kernel);
+        }
+    }
+    if (r.reordered) {
+        Prof p(h, &h->ev_post, s);
+        for (const Seg &g : r.segs)
+            if (g.width == 16)
+                hipLaunchKernelGGL(sx::tiles_to_colmajor, dim3((unsigned)((h->M + sx::kBlock - 1) / sx::kBlock), (unsigned)g.ntiles),
+                                   dim3(sx::kBlock), 0, s, h->d_Cs, c.C_out, c.ldc, h->M, g.col0, seg_cols(g));
+        if (r.hubs) launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+        // chain rows write C themselves: behind the staging -> C pass (which left C_in in their rows), from the permuted panels
+        if (r.chains) launch_chains(h, r.segs, c.C_in, c.ldc_in, c.C_out, c.ldc, N, r.ch0, r.ch1, c.row_begin, c.alpha, c.beta, s, true);
+    }
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+}  // namespace
+extern "C" {
+
 int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float *d_B, int64_t ldb,
                              float beta, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc,
                              int row_begin, int row_end, int flags, void *stream) {
@@ -925,20 +1286,14 @@ int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float
     if (ldb < h->K || ldc < nrows || ldc_in < nrows) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (nrows == 0) {
-        // an empty range still opens a sequence: without the reuse flag the caller announces a new B, and the next call
-        // (which will carry the flag) must not find the panels of some earlier B
-        if (!(flags & SEXTANS_ROWS_REUSE_B_PANELS)) h->bp_layout = 0;
-        return SEXTANS_OK;
-    }
     // A call without the reuse flag announces a new B: whatever panels the workspace holds are stale from here on,
     // also when THIS call does not repack (column-major staging, fuse_b) -- a later chunk of the same pipelined SpMM
-    // that does need panels must not find those of an earlier B.
+    // that does need panels must not find those of an earlier B.  (An empty range too: the next call, which will carry
+    // the flag, must not find the panels of some earlier B.)
     if (!(flags & SEXTANS_ROWS_REUSE_B_PANELS)) h->bp_layout = 0;
-    std::vector<Seg> plan;
-    int W = 0;
-    bool use_panel = false, use_window = false;
-    if (int rc = prepare(h, N, plan, W, use_panel, use_window, whole)) return rc;
+    if (nrows == 0) return SEXTANS_OK;
+    Tiling t;
+    if (int rc = prepare(h, N, whole, &t)) return rc;
     if (h->dense_W > 0) {
         // Dense tiles first, on the matrix cores: C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block
         // rows (and alpha * 0 + beta * C_in below them); the CSR kernels then add alpha * (A_rest * B) on top
@@ -950,363 +1305,13 @@ int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float
         if (int rc = launch_dense_tiles(h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, s)) return rc;
         beta = 1.0f; d_C_in = d_C_out; ldc_in = ldc;
     }
-    // a row range keeps the panel kernel when it starts and ends on row-block boundaries of the plan
-    int blk0 = 0, blk1 = h->ps.plan_nblk;
-    if (use_panel && !whole) {
-        const auto &br = h->ps.h_blk_row;
-        const auto i0 = std::lower_bound(br.begin(), br.end(), row_begin), i1 = std::lower_bound(br.begin(), br.end(), row_end);
-        if (i0 == br.end() || *i0 != row_begin || i1 == br.end() || *i1 != row_end) use_panel = false;
-        else { blk0 = (int)(i0 - br.begin()); blk1 = (int)(i1 - br.begin()); }
+    const Call c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, row_begin, row_end, flags, s, whole};
+    const RouteCM r = route_cm(h, c, std::move(t));
+    switch (r.path) {
+        case RouteCM::kWindow: return run_window(h, c, r);
+        case RouteCM::kColwise: return run_colwise(h, c);
+        default: return run_segments(h, c, r);
     }
-    // ... and the window kernel when it starts and ends on wavefront (rows-per-wave) boundaries
-    if (use_window && (row_begin % h->win_rw != 0 || (row_end % h->win_rw != 0 && row_end != h->M))) use_window = false;
-    // long rows of this range: entries [hub0, hub1) of a piece table, pieces [v0, v1).  Whole-matrix calls walk the
-    // table sorted by length (workgroups of equally long pieces), row ranges the one sorted by row.
-    const sextans_engine::PieceTable &pt = whole ? h->by_len : h->by_row;
-    int hub0 = 0, hub1 = 0, v0 = 0, v1 = 0;
-    if (h->nhub > 0) {
-        if (whole) { hub1 = h->nhub; }
-        else {
-            hub0 = (int)(std::lower_bound(pt.h_row.begin(), pt.h_row.end(), row_begin) - pt.h_row.begin());
-            hub1 = (int)(std::lower_bound(pt.h_row.begin(), pt.h_row.end(), row_end) - pt.h_row.begin());
-        }
-        v0 = pt.h_vfirst[(size_t)hub0]; v1 = pt.h_vfirst[(size_t)hub1];
-    }
-    const bool hubs = hub1 > hub0;
-    int ch0 = 0, ch1 = h->nchain;              // chain rows of this range
-    if (h->nchain > 0 && !whole) {
-        ch0 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), row_begin) - h->h_chain_row.begin());
-        ch1 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), row_end) - h->h_chain_row.begin());
-    }
-    const bool chains = ch1 > ch0;
-    auto fold = [&]() {
-        const int64_t tot = (int64_t)(hub1 - hub0) * N;
-        auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, pt.d_vfirst, pt.d_row, h->d_P,
-                               (int64_t)h->split_nv, d_C_in, ldc_in, d_C_out, ldc, hub0, hub1 - hub0, N, row_begin, alpha, beta, 0);
-        };
-        if (h->opt_exact) go(sx::fold_hub_pieces<true>); else go(sx::fold_hub_pieces<false>);
-    };
-    if (use_window) {
-        // B in 8-column panels (the reference's N tile), then one tile-major launch
-        if (!(flags & SEXTANS_ROWS_REUSE_B_PANELS) || h->bp_layout != 8) {
-            Prof p(h, &h->ev_repack, s);
-            launch_repack<8>(d_B, ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->d_touched);
-            h->bp_layout = 8;
-        }
-        {
-            Prof p(h, &h->ev_kernel, s);
-            const int w0 = row_begin / h->win_rw, w1 = (row_end + h->win_rw - 1) / h->win_rw;
-            launch_window(h, h->d_Bp, d_C_in, ldc_in, d_C_out, ldc, N / 8, w0, w1, row_begin, alpha, beta, s);
-            if (hubs) { launch_hub_pieces<2>(h, pt, h->d_Bp, N / 8, 0, v0, v1, s); fold(); }
-            if (chains) {
-                const std::vector<Seg> p8{{8, 0, N / 8}};
-                launch_chains(h, p8, d_C_in, ldc_in, d_C_out, ldc, N, ch0, ch1, row_begin, alpha, beta, s);
-            }
-            h->last_kernel = kernel_name(2, hubs || chains, h->dense_W > 0);
-            if (h->rb_n > 0) {
-                const std::vector<Seg> p8{{8, 0, N / 8}};
-                if (int rc = launch_rowblocks(h, p8, d_C_in, ldc_in, d_C_out, ldc, N, row_begin, row_end, alpha, beta, s)) return rc;
-                h->last_kernel = with_rowblocks(h, h->last_kernel);
-            }
-        }
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    // Short rows in a numbering with locality (or "kernel" = 4): one lane per row on the caller's column-major operands -- no B
-    // repack, no LDS (spmm_colwise_kernel.h).  Rows on the long-row paths need the repacked panels: then the other kernels run.
-    if ((h->opt_kernel == 4 || (h->opt_kernel == 0 && h->colwise_state == 1)) && !hubs && !chains && (h->dense_W == 0 && h->rb_n == 0) && h->m_nnz > 0) {
-        Prof p(h, &h->ev_kernel, s);
-        const int nrowblk = (nrows + sx::kBlock - 1) / sx::kBlock;
-        auto go = [&](auto kern, int col0, int ntiles) {
-            // (tiles of a row block neighbours in the launch order: the row block's CSR entries come from HBM once -- measured on the 4M-row
-            // 5-point stencil, two boxes: N = 32 0.513 / 0.527 -> 0.532 / 0.550 of the roofline; N = 48 / 64 equal or 1 % behind; N = 128 / 256
-            // 0.51 -> 0.43 .. 0.49: more column streams in flight per XCD than its L2 keeps; "colwise_tiles_adjacent" 1 = two tiles, 2 = always,
-            // 0 = never; profiles/r05_colwise_tile_order_ab.txt)
-            const int adj = ntiles > 1 && (h->opt_colwise_tiles_adjacent == 2 || (h->opt_colwise_tiles_adjacent == 1 && ntiles <= 2)) &&
-                            (int64_t)nrowblk * ntiles < ((int64_t)1 << 31) ? ntiles : 0;
-            hipLaunchKernelGGL(kern, adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)ntiles), dim3(sx::kBlock), 0, s, h->m_rp, h->m_ci,
-                               h->m_v, d_B, ldb, d_C_in, ldc_in, d_C_out, ldc, row_begin, row_end, nrowblk, col0, alpha, beta, (int)h->opt_xcd,
-                               (const unsigned char *)h->d_skip, adj, 1);
-        };
-        const int n16 = N / 16;
-        if (n16 > 0) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 16>, 0, n16); else go(sx::spmm_csr_colwise<false, 16>, 0, n16); }
-        if (N % 16) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 8>, n16 * 16, 1); else go(sx::spmm_csr_colwise<false, 8>, n16 * 16, 1); }
-        h->last_kernel = "spmm_csr_colwise";
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    // Small B (fits the L2s), dictionary-only plan, one N segment: the panel kernel stages straight from the
-    // caller's column-major B and the repack launch disappears.
-    const bool fuse_b = use_panel && !h->ps.plan_mixed && h->opt_fuse_b && !(flags & kRowsNoFuseB) && plan.size() == 1 && h->rb_n == 0 &&   // (routed row blocks read the repacked panels)
-                        plan[0].width == W && !hubs && !chains &&
-                        (size_t)h->K * (size_t)N * sizeof(float) <= ((size_t)16 << 20) &&
-                        // (a graph-clustered plan beats the natural-order blocks of a renumbered matrix also while B fits the L2s, once the
-                        // matrix is large enough for three more launches not to matter: 332 K rows 123 -> 85 us per step)
-                        // (... and below that size once the call is large enough: a 13 965-row matrix in a random node order, N = 128,
-                        // 112 us staged from column-major B on its natural-order plan against 34 us reordered; N = 16: 13.3 against 15.0.
-                        // Crossover measured at ~24 M non-zero x column products: tools/small_renumbered.py)
-                        !(whole && h->cluster_state == 2 && h->cluster_cm_pays && (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)));
-    // (Staging from column-major B for LARGE matrices -- no repack launch at all -- was measured in round 4 and loses everywhere: 4M-row
-    // 3-dof FEM N = 16 kernel 660 -> 872 us against 83 us of repack saved; 1-dof 27-point 379 -> 577; 2-D 9-point 296 -> 427;
-    // 5-point 270 -> 412: 36 four-byte loads per lane and panel through registers instead of nine LDS-DMA requests.)
-    // (a reuse request is honoured only if the panels in the workspace have this layout: row-range calls of
-    // one pipelined SpMM may alternate between the window kernel's 8-column panels and these)
-    // The reordered form (graph-clustered plan, ensure_cluster_plan): whole-matrix calls, 16-column tiles.  Its B panels hold the
-    // rows of B in the plan's column order and C goes through the block-major staging buffer (reorder_kernels.h); an 8-column
-    // remainder tile keeps the natural-order kernels and panels.  (Layout tag -W: such panels are never reused by a row-range call.)
-    const bool reordered = whole && h->cluster_state == 2 && h->cluster_cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3 && W == 16 && !fuse_b &&
-                           (!chains || h->d_chain_ci_perm) && (h->dense_W == 0 && h->rb_n == 0) && h->d_Cs &&
-                           // (the staging buffer is sized by prepare() for the N it saw: a plan that survived a set_option("kernel") and a
-                           // larger N since then must not run past its end -- ADVICE r04)
-                           h->Cs_cap >= (size_t)((N + 15) / 16) * (size_t)h->M * 16 && (N >= 16 || (N == 8 && !hubs && !chains));
-    const int64_t cs_tile = reordered ? (int64_t)h->M * 16 : 0;   // floats per 16-column tile of the staging buffer
-    // N = 16 t + 8 on the register-resident panel kernel: the 8-column tail used to go to the gather kernel (the plan is built for
-    // 16-column tiles) -- 4M-row FEM matrix: N = 24 2 152 us per step against 1 099 at N = 32.  It now runs as one more 16-column tile:
-    // its B panel is zero in the 8 columns that do not exist, the kernel neither loads nor stores C there (`last_cols`), the passes of
-    // the reordered form skip them; rows on the piece path sum 16 columns into their (wider) partial-sum buffer and fold N, the exact
-    // chains take the tail as one 8-column tile of the 16-column panel.  Not with dense tiles on the MFMA path or column-major staging.
-    auto seg_cols = [](const Seg &g) { return g.last_cols ? (g.ntiles - 1) * g.width + g.last_cols : g.ntiles * g.width; };
-    {
-        const bool wide0 = h->ps.plan_max_dict <= sx::kWideMaxDict && (int64_t)h->K * 64 < ((int64_t)1 << 32) && std::max(ldc, ldc_in) * 64 < ((int64_t)1 << 32);
-        const bool v2_here = reordered || (use_panel && !h->ps.plan_mixed && h->opt_panel_v2 != 0 && !fuse_b && wide0 && h->opt_cols_per_lane != 8);
-        if (v2_here && W == 16 && plan.size() == 2 && plan[0].width == 16 && plan[1].width == 8 && plan[1].ntiles == 1 &&
-            (h->nhub == 0 || h->P_cap >= (size_t)h->split_nv * (size_t)(N + 8)) &&
-            // (with rows on the piece / chain paths only where the main rows are long enough to matter: on the KKT class -- 6 entries per
-            // row, arrow borders as chains -- the wider piece / chain work cost more than the gather tail: 1 510 -> 1 687 us at N = 24)
-            ((h->nhub == 0 && h->nchain == 0) || (h->M > 0 && h->m_nnz / h->M >= 16)) &&
-            (h->dense_W == 0 && h->rb_n == 0) && h->opt_pipeline_tiles == 0 && h->Bp_cap >= (size_t)h->K * (size_t)(N + 8) &&
-            (!reordered || h->Cs_cap >= (size_t)(N / 16 + 1) * (size_t)h->M * 16)) {
-            plan[0].ntiles += 1;
-            plan[0].last_cols = 8;
-            plan.pop_back();
-        } else if (v2_here && W == 16 && plan.size() == 1 && plan[0].width == 8 && plan[0].ntiles == 1 && h->nhub == 0 && h->nchain == 0 &&
-                   (h->dense_W == 0 && h->rb_n == 0) && h->Bp_cap >= (size_t)h->K * 16 && (!reordered || h->Cs_cap >= (size_t)h->M * 16)) {
-            plan[0] = Seg{16, 0, 1, 8};   // N = 8 on the 16-column plan (engine_plan.hip: prepare, n8_wide)
-        }
-    }
-    const bool merged_tail = plan[0].last_cols != 0;
-    const int layout = reordered ? -W : merged_tail ? W + 100 : W;
-    const bool skip_repack = fuse_b || ((flags & SEXTANS_ROWS_REUSE_B_PANELS) != 0 && h->bp_layout == layout);
-
-    // Tile-group pipelining (N >= 32 on the register-resident panel kernel, no long rows): the 16-column tiles are cut into two
-    // groups; the layout passes of the second group (B repack, and C staging of the reordered form) run on the engine's side stream
-    // UNDER the first group's SpMM kernel, so only the first group's passes are exposed.  The reference lays B out on the host,
-    // outside its timed call (sextans-host.cpp:150-177); here the layout is inside the step, so it is at least hidden.  Costs a
-    // second pass over the packed A stream (the tile loop of a workgroup covers one group): measured DESIGN 4.3.
-    const bool wide_ok0 = h->ps.plan_max_dict <= sx::kWideMaxDict && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
-                          std::max(ldc, ldc_in) * 64 < ((int64_t)1 << 32);
-    const bool v2_h1 = plan[0].width == 16 && W == 16 && (reordered || (use_panel && !h->ps.plan_mixed && h->opt_panel_v2 != 0 && !fuse_b &&
-                                                                         wide_ok0 && h->opt_cols_per_lane != 8));
-    const bool pipelined = v2_h1 && plan[0].ntiles >= 2 && !skip_repack && !hubs && !chains && h->rb_n == 0 && h->opt_pipeline_tiles != 0 && h->aux_stream &&
-                           h->ev_pipe[0];
-    if (pipelined) {
-        const Seg &g = plan[0];
-        const int t_cut = std::max(1, (g.ntiles + 3) / 4);            // tiles of the first group
-        const bool clustered = !reordered && whole && h->cluster_state == 1;
-        const int mode = reordered ? 2 : clustered ? 1 : 0;
-        const int b0 = mode ? 0 : blk0, b1 = mode ? h->psc.plan_nblk : blk1;
-        auto pre = [&](int t0, int t1, hipStream_t st) {
-            float *dst = h->d_Bp + (size_t)h->K * (size_t)(g.col0 + 16 * t0);
-            if (reordered && !h->d_colpos) {
-                launch_repack<16>(d_B, ldb, dst, h->K, g.col0 + 16 * t0, t1 - t0, st, h->col_lo, h->col_hi, -1, h->d_touched);
-                launch_repack<16>(d_C_in, ldc_in, h->d_Cs + (int64_t)t0 * cs_tile, h->M, g.col0 + 16 * t0, t1 - t0, st);
-            } else if (reordered) {
-                hipLaunchKernelGGL(sx::repack_b_panels_perm, dim3((unsigned)((h->col_hi - h->col_lo + sx::kBlock - 1) / sx::kBlock), (unsigned)(t1 - t0)),
-                                   dim3(sx::kBlock), 0, st, d_B, ldb, dst, h->K, g.col0 + 16 * t0, h->d_colpos, h->col_lo, h->col_hi, 16 * (t1 - t0), h->d_touched);
-                launch_repack<16>(d_C_in, ldc_in, h->d_Cs + (int64_t)t0 * cs_tile, h->M, g.col0 + 16 * t0, t1 - t0, st);
-            } else {
-                launch_repack<16>(d_B, ldb, dst, h->K, g.col0 + 16 * t0, t1 - t0, st, h->col_lo, h->col_hi, -1, h->d_touched);
-            }
-        };
-        auto kern = [&](int t0, int t1) -> int {
-            const float *bp = h->d_Bp + (size_t)h->K * (size_t)(g.col0 + 16 * t0);
-            if (reordered)
-                return launch_panel_v2<1>(h, bp, h->d_Cs + (int64_t)t0 * cs_tile, cs_tile, h->d_Cs + (int64_t)t0 * cs_tile, cs_tile, t1 - t0, alpha,
-                                          beta, s, 0, 0, h->psc.plan_nblk, 0, 2);
-            return launch_panel_v2<1>(h, bp, d_C_in + (int64_t)(g.col0 + 16 * t0) * ldc_in, ldc_in, d_C_out + (int64_t)(g.col0 + 16 * t0) * ldc, ldc,
-                                      t1 - t0, alpha, beta, s, 0, b0, b1, row_begin, mode);
-        };
-        auto post = [&](int t0, int t1, hipStream_t st) {
-            hipLaunchKernelGGL(sx::tiles_to_colmajor, dim3((unsigned)((h->M + sx::kBlock - 1) / sx::kBlock), (unsigned)(t1 - t0)), dim3(sx::kBlock),
-                               0, st, h->d_Cs + (int64_t)t0 * cs_tile, d_C_out, ldc, h->M, g.col0 + 16 * t0, 16 * (t1 - t0));
-        };
-        hipStream_t side = h->aux_stream;
-        h->bp_layout = layout;
-        SX_HIP(hipEventRecord(h->ev_pipe[0], s));                     // the side stream starts behind whatever precedes this call on s
-        SX_HIP(hipStreamWaitEvent(side, h->ev_pipe[0], 0));
-        {
-            Prof p(h, &h->ev_repack, s);
-            pre(0, t_cut, s);
-            for (size_t i = 1; i < plan.size(); ++i) {                  // an 8-column remainder tile keeps the plain panels
-                const Seg &r = plan[i];
-                launch_repack<8>(d_B, ldb, h->d_Bp + (size_t)h->K * (size_t)r.col0, h->K, r.col0, r.ntiles, s, h->col_lo, h->col_hi, -1, h->d_touched);
-            }
-        }
-        pre(t_cut, g.ntiles, side);
-        SX_HIP(hipEventRecord(h->ev_pipe[1], side));
-        {
-            Prof p(h, &h->ev_kernel, s);
-            if (int rc = kern(0, t_cut)) return rc;
-            if (reordered) {                                            // ... and the first group's way back under the second group's kernel
-                SX_HIP(hipEventRecord(h->ev_pipe[2], s));
-                SX_HIP(hipStreamWaitEvent(side, h->ev_pipe[2], 0));
-                post(0, t_cut, side);
-                SX_HIP(hipEventRecord(h->ev_pipe[3], side));
-            }
-            SX_HIP(hipStreamWaitEvent(s, h->ev_pipe[1], 0));
-            if (int rc = kern(t_cut, g.ntiles)) return rc;
-            for (size_t i = 1; i < plan.size(); ++i) {
-                const Seg &r = plan[i];
-                launch_rowgroup<2>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->d_skip, h->d_Bp + (size_t)h->K * (size_t)r.col0,
-                                   d_C_in + (int64_t)r.col0 * ldc_in, ldc_in, d_C_out + (int64_t)r.col0 * ldc, ldc, row_begin, row_end, r.ntiles, alpha,
-                                   beta, s);
-            }
-        }
-        if (reordered) {
-            Prof p(h, &h->ev_post, s);
-            post(t_cut, g.ntiles, s);
-            SX_HIP(hipStreamWaitEvent(s, h->ev_pipe[3], 0));
-        }
-        h->last_kernel = reordered ? "spmm_csr_panel_v2_reordered" : "spmm_csr_panel_v2";
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    if (!skip_repack || reordered) {
-        Prof p(h, &h->ev_repack, s);
-        if (!skip_repack) {
-            h->bp_layout = layout;
-            for (const Seg &g : plan) {
-                float *dst = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-                if (reordered && g.width == 16 && h->d_colpos) {
-                    hipLaunchKernelGGL(sx::repack_b_panels_perm, dim3((unsigned)((h->col_hi - h->col_lo + sx::kBlock - 1) / sx::kBlock), (unsigned)g.ntiles),
-                                       dim3(sx::kBlock), 0, s, d_B, ldb, dst, h->K, g.col0, h->d_colpos, h->col_lo, h->col_hi, seg_cols(g), h->d_touched);
-                    continue;
-                }
-                switch (g.width) {
-                    case 32: launch_repack<32>(d_B, ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, -1, h->d_touched); break;
-                    case 16: launch_repack<16>(d_B, ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, seg_cols(g), h->d_touched); break;
-                    default: launch_repack<8>(d_B, ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, -1, h->d_touched); break;
-                }
-            }
-        }
-        if (reordered)
-            for (const Seg &g : plan)
-                if (g.width == 16)
-                    launch_repack<16>(d_C_in, ldc_in, h->d_Cs, h->M, g.col0, g.ntiles, s, 0, -1, seg_cols(g));   // C_in -> row-major tiles
-    }
-    {
-        Prof p(h, &h->ev_kernel, s);
-        bool v2_used = false;
-        if (chains && !reordered) {
-            // the chains need one or two wavefronts for about a millisecond: on their own stream, beside the main kernel
-            // (fork after the B panels are in place, join before the call's work on `s` is considered complete)
-            SX_HIP(hipEventRecord(h->ev_fork, s));
-            SX_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-            launch_chains(h, plan, d_C_in, ldc_in, d_C_out, ldc, N, ch0, ch1, row_begin, alpha, beta, h->aux_stream);
-            SX_HIP(hipEventRecord(h->ev_join, h->aux_stream));
-        }
-        for (const Seg &g : plan) {
-            const float *bp = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-            const float *cin = d_C_in + (int64_t)g.col0 * ldc_in;
-            float *cout = d_C_out + (int64_t)g.col0 * ldc;
-            if (reordered && g.width == 16) {
-                if (int rc = launch_panel_v2<1>(h, bp, h->d_Cs, cs_tile, h->d_Cs, cs_tile, g.ntiles, alpha, beta, s, 0, 0, h->psc.plan_nblk, 0, 2))
-                    return rc;   // (a merged tail tile needs no mask here: its staging columns exist, the pass below writes back the valid ones)
-                v2_used = true;
-                // rows on the piece path: their partial sums from the PERMUTED panels (column c sits at row colpos[c]); folded into C
-                // behind the staging -> C pass below, which leaves C_in in their rows
-                if (hubs) launch_hub_pieces<4>(h, pt, bp, g.ntiles, g.col0, v0, v1, s, h->d_colpos);
-                continue;
-            }
-            const bool panel_here = use_panel && g.width == W;   // the plan is built for width W
-            const float *bsrc = fuse_b ? d_B + (int64_t)g.col0 * ldb : bp;
-            const int64_t bld = fuse_b ? ldb : 0;
-            // N >= 32 on a dictionary-only plan at 4 lanes per row: register-blocked 32-column super tiles with the
-            // tile loop inside the workgroup; an odd 16-column tile at the end goes to the plain panel kernel
-            // (32-bit byte offsets inside the wide kernels: panels, C columns)
-            const bool wide_ok = h->ps.plan_max_dict <= sx::kWideMaxDict && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
-                                 std::max(ldc, ldc_in) * 64 < ((int64_t)1 << 32) && (!fuse_b || ldb * 64 < ((int64_t)1 << 32));
-            if (panel_here && g.width == 16 && !h->ps.plan_mixed && h->opt_cols_per_lane == 8 && g.ntiles >= 2 && wide_ok) {
-                const int nsuper = g.ntiles / 2;
-                if (int rc = launch_panel_v2<2>(h, bsrc, cin, ldc_in, cout, ldc, nsuper, alpha, beta, s, bld, blk0, blk1, row_begin))
-                    return rc;
-                if (g.ntiles & 1) {
-                    const int64_t c0 = (int64_t)nsuper * 32;
-                    if (int rc = launch_panel<4>(h, fuse_b ? bsrc + c0 * ldb : bsrc + c0 * (int64_t)h->K, cin + c0 * ldc_in, ldc_in,
-                                                 cout + c0 * ldc, ldc, 1, alpha, beta, s, bld, blk0, blk1, row_begin))
-                        return rc;
-                }
-                v2_used = true;
-                if (hubs) launch_hub_pieces<4>(h, pt, bp, g.ntiles, g.col0, v0, v1, s);
-                continue;
-            }
-            // (column-major staging keeps the round-1 kernel unless the rows are short: then the register-resident form fits
-            // 128 registers together with a panel in registers)
-            const bool short_rows = h->M > 0 && h->m_nnz / h->M + 8 <= 32;
-            // (long rows + column-major staging: the 256-register instantiation, for launches that cannot fill the chip -- option
-            // "panel_v2" = 1 asks for it, the automatic setting keeps spmm_csr_panel there: measured)
-            const bool big_ok = fuse_b && !short_rows && h->opt_panel_v2 == 1 && (int64_t)(blk1 - blk0) * g.ntiles <= 8192;
-            // MIXED plans, split form (round 5): the blocks that have a dictionary run on the register-resident kernel (it leaves the others
-            // alone), the rows of the blocks without one -- no reuse between their rows -- on the gather kernel behind it (its skip table
-            // names the rows that are not its own).  One launch of spmm_csr_panel<MIXED> did both at the speed of neither: FEM rows + 10 / 30 /
-            // 60 % uniformly random rows, N = 16: 311 / 468 / 698 us per step -> 280 / 424 / 644; through the row-major entry point 406 / 581 / 832
-            // (column-major copies around the mixed kernel) -> 235 / 375 / 611 (tools/mixed_rm_probe.py).  Both launches walk compact lists
-            // (blocks with a dictionary; groups of 128 rows with a gather row): a launch over everything whose other workgroups leave at
-            // once hands the XCDs unequal shares -- measured 2 x slower.  (The gather launch on a second stream beside the other one: built,
-            // measured equal -- the first launch fills every workgroup slot of the chip, the second queues behind it either way.)
-            const bool split_mixed = panel_here && g.width == 16 && h->ps.plan_mixed && h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_panel_v2 != 0 &&
-                                     !fuse_b && wide_ok && h->opt_kernel == 0 && whole;   // (whole-matrix calls: the launches walk lists made for the whole plan)
-            if (split_mixed) {
-                if (int rc = launch_panel_v2<1>(h, bsrc, cin, ldc_in, cout, ldc, g.ntiles, alpha, beta, s, 0, blk0, blk1, row_begin, 0, 16, 0, true)) return rc;
-                launch_rowgroup<4>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, bp, cin, ldc_in, cout, ldc, row_begin, row_end, g.ntiles, alpha, beta, s, 0, false,
-                                   h->ps.d_rg_groups, h->ps.rg_ngroups);
-                v2_used = true;
-                if (hubs) launch_hub_pieces<4>(h, pt, bp, g.ntiles, g.col0, v0, v1, s);
-                continue;
-            }
-            if (panel_here && g.width == 16 && !h->ps.plan_mixed && h->opt_panel_v2 != 0 && (!fuse_b || short_rows || big_ok) && wide_ok) {
-                // whole-matrix calls on repacked panels: the plan over the rows in clustered (brick) order when the matrix has one
-                const bool clustered = whole && !fuse_b && h->cluster_state == 1;
-                if (int rc = launch_panel_v2<1>(h, bsrc, cin, ldc_in, cout, ldc, g.ntiles, alpha, beta, s, bld, clustered ? 0 : blk0,
-                                                clustered ? h->psc.plan_nblk : blk1, row_begin, clustered ? 1 : 0, g.last_cols ? g.last_cols : 16))
-                    return rc;
-                v2_used = true;
-                if (hubs) launch_hub_pieces<4>(h, pt, bp, g.ntiles, g.col0, v0, v1, s);
-                continue;
-            }
-#define SX_SEG(L)                                                                                                       \
-    if (panel_here) { if (int rc = launch_panel<L>(h, bsrc, cin, ldc_in, cout, ldc, g.ntiles, alpha, beta, s, bld, blk0, blk1, row_begin)) return rc; }  \
-    else launch_rowgroup<L>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->d_skip, bp, cin, ldc_in, cout, ldc, row_begin, row_end, \
-                            g.ntiles, alpha, beta, s);                                                                   \
-    if (hubs) launch_hub_pieces<L>(h, pt, bp, g.ntiles, g.col0, v0, v1, s);
-            switch (g.width) {
-                case 32: SX_SEG(8) break;
-                case 16: SX_SEG(4) break;
-                default: SX_SEG(2) break;
-            }
-#undef SX_SEG
-        }
-        if (hubs && !reordered) fold();
-        if (chains && !reordered) SX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-        h->last_kernel = reordered ? "spmm_csr_panel_v2_reordered" : kernel_name(v2_used ? 3 : use_panel ? 1 : 0, hubs || chains, h->dense_W > 0);
-        if (h->rb_n > 0) {   // dense blocks of 16 rows on the fp32 matrix cores, from the same panels (the kernels above skipped their rows)
-            if (int rc = launch_rowblocks(h, plan, d_C_in, ldc_in, d_C_out, ldc, N, row_begin, row_end, alpha, beta, s)) return rc;
-            h->last_kernel = with_rowblocks(h, h->last_kernel);
-        }
-    }
-    if (reordered) {
-        Prof p(h, &h->ev_post, s);
-        for (const Seg &g : plan)
-            if (g.width == 16)
-                hipLaunchKernelGGL(sx::tiles_to_colmajor, dim3((unsigned)((h->M + sx::kBlock - 1) / sx::kBlock), (unsigned)g.ntiles),
-                                   dim3(sx::kBlock), 0, s, h->d_Cs, d_C_out, ldc, h->M, g.col0, seg_cols(g));
-        if (hubs) fold();
-        // chain rows write C themselves: behind the staging -> C pass (which left C_in in their rows), from the permuted panels
-        if (chains) launch_chains(h, plan, d_C_in, ldc_in, d_C_out, ldc, N, ch0, ch1, row_begin, alpha, beta, s, true);
-    }
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
 }
 
 }  // extern "C"
@@ -1393,10 +1398,7 @@ int sextans_export_row_order(sextans_handle_t h, int *order, int *clustered) {
     if (!h || !order) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     SX_HIP(hipSetDevice(h->device));
-    std::vector<Seg> plan;
-    int W = 0;
-    bool up = false, uw = false;
-    if (int rc = prepare(h, 16, plan, W, up, uw, true)) return rc;
+    if (int rc = prepare(h, 16)) return rc;
     const bool have = h->cluster_state > 0 && h->d_slot_row && h->psc.plan_built && h->nhub == 0 && h->nchain == 0;
     if (clustered) *clustered = have ? h->cluster_state : 0;
     if (!have) {
@@ -1421,7 +1423,7 @@ namespace sxe {
 // reconsideration of a clustered plan declined for column-major calls only, and the clustered plan's dictionaries translated back to
 // the caller's column numbers.  Run by the first row-major call, or ahead of it by sextans_prepare / sextans_dist_prepare so that no
 // timed (or captured) call builds anything.
-int rm_plan(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_panel, bool &use_window, hipStream_t s) {
+int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out) {
     // (N = 8 runs as one half-empty 16-column tile of the 16-column plan: without a repack to pay for there is no reason for a second
     // packed plan at 2 lanes per row)
     const int Nplan = N == 8 ? 16 : N;
@@ -1429,18 +1431,19 @@ int rm_plan(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
     // the fallback at the end plans again through the column-major entry and gets them)
     struct Lean { sextans_engine *h; ~Lean() { h->lean_prepare = false; } } lean{h};
     h->lean_prepare = true;
-    if (int rc = prepare(h, Nplan, plan, W, use_panel, use_window, true)) return rc;
+    Tiling t;
+    if (int rc = prepare(h, Nplan, true, &t)) return rc;
     // A clustered plan that was declined only because the column-major form has to pay two passes over C for it (decline 12) is
     // reconsidered for this layout, where it costs nothing: built once, used by row-major calls only unless it pays for both.
-    if ((h->cluster_state == -1 || h->cluster_runs) && h->cluster_decline == 12 && !h->cluster_rm_tried && W == 16 && h->opt_row_cluster < 0) {
+    if ((h->cluster_state == -1 || h->cluster_runs) && h->cluster_decline == 12 && !h->cluster_rm_tried && t.W == 16 && h->opt_row_cluster < 0) {
         h->cluster_rm_tried = true;
         free_cluster_plan(h);
         h->cluster_for_rm = true;
-        const int rc = prepare(h, Nplan, plan, W, use_panel, use_window, true);
+        const int rc = prepare(h, Nplan, true, &t);
         h->cluster_for_rm = false;
         if (rc) return rc;
     }
-    if (W == 16 && h->cluster_state == 2 && h->d_colpos && !h->d_dict_nat) {   // the plan's dictionaries hold relabelled columns: translate them back once
+    if (t.W == 16 && h->cluster_state == 2 && h->d_colpos && !h->d_dict_nat) {   // the plan's dictionaries hold relabelled columns: translate them back once
         const long long n = (long long)h->psc.plan_nblk * h->psc.plan_dict_stride;
         int *colinv = nullptr;
         if (hipMalloc((void **)&colinv, sizeof(int) * (size_t)std::max(h->K, 1)) != hipSuccess ||
@@ -1455,6 +1458,7 @@ int rm_plan(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
         (void)hipFree(colinv);
         SX_HIP(se);
     }
+    if (out) *out = std::move(t);
     return SEXTANS_OK;
 }
 }  // namespace sxe
@@ -1467,12 +1471,162 @@ int sextans_prepare(sextans_handle_t h, int N, int layout, void *stream) {
     SX_HIP(hipSetDevice(h->device));
     if (layout == SEXTANS_LAYOUT_ROWMAJOR_T) return prepare_transposed(h, N, (hipStream_t)stream);
     if (h->M == 0) return SEXTANS_OK;
-    std::vector<Seg> plan;
-    int W = 0;
-    bool use_panel = false, use_window = false;
-    if (layout == SEXTANS_LAYOUT_ROWMAJOR) return rm_plan(h, N, plan, W, use_panel, use_window, (hipStream_t)stream);
-    return prepare(h, N, plan, W, use_panel, use_window, true);
+    if (layout == SEXTANS_LAYOUT_ROWMAJOR) return rm_plan(h, N, (hipStream_t)stream);
+    return prepare(h, N);
 }
+
+}  // extern "C"
+namespace {
+// Everything sextans_spmm_device_rm decides for one call (route_rm), before anything is launched
+struct RouteRM {
+    enum Path { kColwise, kPanelV2, kRowgroup, kTranspose } path = kTranspose;
+    bool aligned = false;        // 16-byte aligned operands with leading dimensions that are multiples of 4
+    int mode = -1;               // kPanelV2: launch_panel_v2's mode -- 0 natural order, 1 grid bricks, 2 graph clustering
+    bool split = false;          // kPanelV2 on a mixed plan: dictionary blocks there, the other blocks' rows on the gather kernel
+    std::vector<Seg> segs;       // kRowgroup: the tiling of N
+};
+
+RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
+    RouteRM r;
+    const bool colwise = colwise_wanted(h);
+    r.aligned = ((reinterpret_cast<uintptr_t>(c.B) | reinterpret_cast<uintptr_t>(c.C_in) | reinterpret_cast<uintptr_t>(c.C_out)) & 15) == 0 &&
+                c.ldb % 4 == 0 && c.ldc_in % 4 == 0 && c.ldc % 4 == 0;
+    // 32-bit offsets inside the kernel: floats into B (C beyond 4 GB: the kernel's 64-bit form, launch_panel_v2)
+    const bool fits = (int64_t)h->K * c.ldb < ((int64_t)1 << 32);
+    // Rows on the long-row paths (pieces, exact chains): from the caller's row-major B into its row-major C as well -- the piece kernel's
+    // 16-byte gathers and the chain producers' LDS-DMA read B rows ldb floats apart instead of panel rows, the fold and the chain
+    // consumer write C[r * ldc + n].  The main kernels skip those rows (d_skip), so the order between the launches does not matter;
+    // the chains run beside the main kernel on the engine's side stream, as in the column-major form.
+    const bool hubs = h->nhub > 0, chains = h->nchain > 0;
+    const bool long_ok = (!hubs && !chains) || (r.aligned && (!chains || (h->aux_stream && h->ev_fork && h->ev_join && c.ldb < ((int64_t)1 << 31))));
+    if (colwise && r.aligned && !hubs && !chains && csr_only(h) && h->m_nnz > 0) {   // short rows in a local numbering: lane per row, 16-byte accesses
+        r.path = RouteRM::kColwise;
+        return r;
+    }
+    if (t.W == 16 && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && csr_only(h) &&
+        !(colwise && !hubs && !chains) && r.aligned && fits && long_ok && h->m_nnz > 0) {
+        if (h->cluster_state == 2) r.mode = 2;
+        else if (h->cluster_state == 1) r.mode = 1;
+        else if (t.panel && (!h->ps.plan_mixed || (h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_kernel == 0)) && h->ps.plan_max_dict <= sx::kWideMaxDict) r.mode = 0;
+    }
+    if (r.mode == 2 && h->d_colpos && !h->d_dict_nat) r.mode = -1;   // (cannot happen after rm_plan; kept as a guard)
+    if (r.mode >= 0) {
+        r.path = RouteRM::kPanelV2;
+        r.split = r.mode == 0 && h->ps.plan_mixed;
+        return r;
+    }
+    // The gather kernel on a matrix without rows on the piece / chain / dense-tile paths: a row of row-major B IS what its lanes fetch
+    // per non-zero (the 4 * LPR floats of a panel row), and a lane's 4 accumulators are 16 bytes of its C row -- no repack, no passes.
+    if (!t.panel && !t.window && !(colwise && !hubs && !chains) && r.aligned && long_ok && (h->opt_kernel == 0 || h->opt_kernel == 1) && csr_only(h) && h->m_nnz > 0) {
+        r.path = RouteRM::kRowgroup;
+        r.segs = t.segs;
+        if (c.N == 8) r.segs.assign(1, Seg{8, 0, 1});   // (the plan above was made for 16 columns)
+        return r;
+    }
+    // Everything else (lane-per-row / window kernels, mixed plans, rows on the piece and chain paths, dense tiles, unaligned operands):
+    // through column-major copies in the engine's workspaces
+    return r;
+}
+
+
+int run_rm_colwise(sextans_engine *h, const Call &c) {
+    Prof p(h, &h->ev_kernel, c.s);
+    auto go = [&](auto kern, int col0, int ntiles) {
+        // groups of T neighbouring lanes per row, one 16-column tile each (T = the largest divisor of the tile count up to 8): a
+        // wavefront's loads cover T * 64 consecutive bytes of every row it touches
+        int T = 1;
+        if (h->opt_colwise_tiles_adjacent != 0)
+            for (int t = 8; t > 1; --t)
+                if (ntiles % t == 0) { T = t; break; }
+        const int rows_per = sx::kBlock / T, nrowblk = (h->M + rows_per - 1) / rows_per, ygrid = ntiles / T;
+        const int adj = T == 1 && ntiles > 1 && h->opt_colwise_tiles_adjacent != 0 && (int64_t)nrowblk * ntiles < ((int64_t)1 << 31) ? ntiles : 0;
+        hipLaunchKernelGGL(kern, adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)ygrid), dim3(sx::kBlock), 0, c.s, h->m_rp, h->m_ci,
+                           h->m_v, c.B, c.ldb, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, h->M, nrowblk, col0, c.alpha, c.beta, (int)h->opt_xcd, (const unsigned char *)h->d_skip, adj, T);
+    };
+    const int n16 = c.N / 16;
+    if (n16 > 0) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 16, true>, 0, n16); else go(sx::spmm_csr_colwise<false, 16, true>, 0, n16); }
+    if (c.N % 16) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 8, true>, n16 * 16, 1); else go(sx::spmm_csr_colwise<false, 8, true>, n16 * 16, 1); }
+    h->last_kernel = "spmm_csr_colwise_rowmajor";
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+
+// The paths on the caller's row-major operands (kPanelV2, kRowgroup), rows on the long-row paths included
+int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
+    Prof p(h, &h->ev_kernel, c.s);
+    const bool long_rows = h->nhub > 0 || h->nchain > 0;
+    if (h->nchain > 0) {
+        std::vector<Seg> segs;   // tiles of the chain kernel: 16-column tiles and an 8-column tail (never past column N of a B row)
+        if (c.N / 16) segs.push_back(Seg{16, 0, c.N / 16});
+        if (c.N % 16) segs.push_back(Seg{8, c.N / 16 * 16, 1});
+        if (int rc = fork_chains(h, c, segs, 0, h->nchain, true)) return rc;
+    }
+    // the gather kernel: over the rows of the blocks without a dictionary (split form of a mixed plan), or over all rows
+    auto rowgroups = [&](const std::vector<Seg> &segs, const unsigned char *skip, const int *groups, int ngroups) {
+        for (const Seg &g : segs)
+            by_width(g.width, [&](auto L) {
+                launch_rowgroup<decltype(L)::value>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, skip, c.B + g.col0, c.C_in + g.col0, c.ldc_in,
+                                                    c.C_out + g.col0, c.ldc, 0, h->M, g.ntiles, c.alpha, c.beta, c.s, c.ldb, false, groups, ngroups);
+                return SEXTANS_OK;
+            });
+    };
+    if (r.path == RouteRM::kPanelV2) {
+        const int ntiles = (c.N + 15) / 16, last_cols = c.N % 16 ? 8 : 16;
+        const sextans_engine::PanelState &P = r.mode ? h->psc : h->ps;
+        if (int rc = launch_panel_v2<1>(h, c.B, c.C_in, c.ldc_in, c.C_out, c.ldc, ntiles, c.alpha, c.beta, c.s, 0, 0, P.plan_nblk, 0, r.mode, last_cols, c.ldb, r.split))
+            return rc;
+        if (r.split) rowgroups(wide_first(c.N), h->ps.d_rg_skip, h->ps.d_rg_groups, h->ps.rg_ngroups);
+    } else {
+        rowgroups(r.segs, h->d_skip, nullptr, 0);
+    }
+    if (h->nhub > 0) {   // the long rows' pieces and their fold
+        const sextans_engine::PieceTable &pt = h->by_len;
+        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->nhub];
+        for (const Seg &g : wide_first(c.N))
+            by_width(g.width, [&](auto L) {
+                launch_hub_pieces<decltype(L)::value>(h, pt, c.B + g.col0, g.ntiles, g.col0, v0, v1, c.s, nullptr, c.ldb);
+                return SEXTANS_OK;
+            });
+        launch_fold(h, pt, 0, h->nhub, c.N, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+    }
+    if (h->nchain > 0) SX_HIP(hipStreamWaitEvent(c.s, h->ev_join, 0));
+    h->last_kernel = r.path == RouteRM::kRowgroup ? (long_rows ? "spmm_csr_rowgroup_rowmajor+long_rows" : "spmm_csr_rowgroup_rowmajor")
+                     : r.mode == 2 ? (long_rows ? "spmm_csr_panel_v2_rowmajor_clustered+long_rows" : "spmm_csr_panel_v2_rowmajor_clustered")
+                                   : (long_rows ? "spmm_csr_panel_v2_rowmajor+long_rows" : "spmm_csr_panel_v2_rowmajor");
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+
+// Column-major copies in the engine's workspaces -- two transposes in front, one behind -- around the column-major entry point.
+// (workspaces of their own -- not the host-buffer entry points' d_B / d_Cin / d_Cout, which are filled on another stream; C_in and
+// C_out may alias, so one C buffer)
+int run_rm_transpose(sextans_engine *h, const Call &c, bool aligned) {
+    const int N = c.N;
+    h->lean_prepare = false;
+    const size_t nB = (size_t)h->K * (size_t)N, nC = (size_t)h->M * (size_t)N;
+    if (int rc = ensure(&h->d_rmB, &h->rmB_cap, nB)) return rc;
+    if (int rc = ensure(&h->d_rmC, &h->rmC_cap, nC)) return rc;
+    {
+        Prof p(h, &h->ev_repack, c.s);
+        if (aligned) {
+            launch_transpose_skinny(true, c.B, h->d_rmB, c.ldb, h->K, h->K, N, c.s);
+            launch_transpose_skinny(true, c.C_in, h->d_rmC, c.ldc_in, h->M, h->M, N, c.s);
+        } else {
+            launch_transpose(c.B, c.ldb, h->d_rmB, h->K, h->K, N, c.s);
+            launch_transpose(c.C_in, c.ldc_in, h->d_rmC, h->M, h->M, N, c.s);
+        }
+    }
+    if (int rc = sextans_spmm_device_rows(h, N, c.alpha, h->d_rmB, h->K, c.beta, h->d_rmC, h->M, h->d_rmC, h->M, 0, h->M, 0, (void *)c.s)) return rc;
+    {
+        Prof p(h, &h->ev_post, c.s);
+        if (aligned) launch_transpose_skinny(false, h->d_rmC, c.C_out, c.ldc, h->M, h->M, N, c.s);
+        else launch_transpose(h->d_rmC, h->M, c.C_out, c.ldc, N, h->M, c.s);
+    }
+    SX_HIP(hipGetLastError());
+    return SEXTANS_OK;
+}
+}  // namespace
+extern "C" {
 
 int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
                            int64_t ldc_in, float *d_C_out, int64_t ldc, void *stream) {
@@ -1481,148 +1635,15 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->M == 0) return SEXTANS_OK;
-    std::vector<Seg> plan;
-    int W = 0;
-    bool use_panel = false, use_window = false;
-    if (int rc = rm_plan(h, N, plan, W, use_panel, use_window, s)) return rc;
-    const bool colwise = h->opt_kernel == 4 || (h->opt_kernel == 0 && h->colwise_state == 1);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(d_B) | reinterpret_cast<uintptr_t>(d_C_in) | reinterpret_cast<uintptr_t>(d_C_out)) & 15) == 0 &&
-                         ldb % 4 == 0 && ldc_in % 4 == 0 && ldc % 4 == 0;
-    // 32-bit offsets inside the kernel: floats into B (C beyond 4 GB: the kernel's 64-bit form, launch_panel_v2)
-    const bool fits = (int64_t)h->K * ldb < ((int64_t)1 << 32);
-    int mode = -1;
-    if (W == 16 && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 &&
-        (h->dense_W == 0 && h->rb_n == 0) && !(colwise && h->nhub == 0 && h->nchain == 0) && aligned && fits && h->m_nnz > 0) {
-        if (h->cluster_state == 2) mode = 2;
-        else if (h->cluster_state == 1) mode = 1;
-        else if (use_panel && (!h->ps.plan_mixed || (h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_kernel == 0)) && h->ps.plan_max_dict <= sx::kWideMaxDict) mode = 0;
+    Tiling t;
+    if (int rc = rm_plan(h, N, s, &t)) return rc;
+    const Call c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, 0, h->M, 0, s, true};
+    const RouteRM r = route_rm(h, c, t);
+    switch (r.path) {
+        case RouteRM::kColwise: return run_rm_colwise(h, c);
+        case RouteRM::kTranspose: return run_rm_transpose(h, c, r.aligned);
+        default: return run_rm_direct(h, c, r);
     }
-    if (mode == 2 && h->d_colpos && !h->d_dict_nat) mode = -1;   // (cannot happen after rm_plan; kept as a guard)
-    // Rows on the long-row paths (pieces, exact chains): from the caller's row-major B into its row-major C as well -- the piece kernel's
-    // 16-byte gathers and the chain producers' LDS-DMA read B rows ldb floats apart instead of panel rows, the fold and the chain
-    // consumer write C[r * ldc + n].  The main kernels skip those rows (d_skip), so the order between the launches does not matter;
-    // the chains run beside the main kernel on the engine's side stream, as in the column-major form.
-    const bool hubs = h->nhub > 0, chains = h->nchain > 0;
-    std::vector<Seg> lsegs;   // tiles of the long-row kernels: 16-column tiles and an 8-column tail (never past column N of a B row)
-    if (N / 16) lsegs.push_back(Seg{16, 0, N / 16});
-    if (N % 16) lsegs.push_back(Seg{8, N / 16 * 16, 1});
-    auto chains_fork = [&]() -> int {
-        if (!chains) return SEXTANS_OK;
-        SX_HIP(hipEventRecord(h->ev_fork, s));
-        SX_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-        launch_chains(h, lsegs, d_C_in, ldc_in, d_C_out, ldc, N, 0, h->nchain, 0, alpha, beta, h->aux_stream, false, d_B, ldb);
-        SX_HIP(hipEventRecord(h->ev_join, h->aux_stream));
-        return SEXTANS_OK;
-    };
-    auto long_rows_join = [&]() -> int {
-        if (hubs) {
-            const sextans_engine::PieceTable &pt = h->by_len;
-            const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->nhub];
-            // (32-column tiles first: a piece's gathers then take whole 128-byte lines of the B rows)
-            int col = 0;
-            if (N / 32) { launch_hub_pieces<8>(h, pt, d_B, N / 32, 0, v0, v1, s, nullptr, ldb); col = N / 32 * 32; }
-            if ((N - col) / 16) { launch_hub_pieces<4>(h, pt, d_B + col, 1, col, v0, v1, s, nullptr, ldb); col += 16; }
-            if (N - col) launch_hub_pieces<2>(h, pt, d_B + col, 1, col, v0, v1, s, nullptr, ldb);
-            const int64_t tot = (int64_t)h->nhub * N;
-            auto go = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, pt.d_vfirst, pt.d_row, h->d_P, (int64_t)h->split_nv, d_C_in, ldc_in,
-                                   d_C_out, ldc, 0, h->nhub, N, 0, alpha, beta, 1);
-            };
-            if (h->opt_exact) go(sx::fold_hub_pieces<true>); else go(sx::fold_hub_pieces<false>);
-        }
-        if (chains) SX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
-        return SEXTANS_OK;
-    };
-    const bool long_ok = (!hubs && !chains) || (aligned && (!chains || (h->aux_stream && h->ev_fork && h->ev_join && ldb < ((int64_t)1 << 31))));
-    if (!long_ok) mode = -1;
-    if (colwise && aligned && h->nhub == 0 && h->nchain == 0 && (h->dense_W == 0 && h->rb_n == 0) && h->m_nnz > 0) {   // short rows in a local numbering: lane per row, 16-byte accesses
-        Prof p(h, &h->ev_kernel, s);
-        auto go = [&](auto kern, int col0, int ntiles) {
-            // groups of T neighbouring lanes per row, one 16-column tile each (T = the largest divisor of the tile count up to 8): a
-            // wavefront's loads cover T * 64 consecutive bytes of every row it touches
-            int T = 1;
-            if (h->opt_colwise_tiles_adjacent != 0)
-                for (int t = 8; t > 1; --t)
-                    if (ntiles % t == 0) { T = t; break; }
-            const int rows_per = sx::kBlock / T, nrowblk = (h->M + rows_per - 1) / rows_per, ygrid = ntiles / T;
-            const int adj = T == 1 && ntiles > 1 && h->opt_colwise_tiles_adjacent != 0 && (int64_t)nrowblk * ntiles < ((int64_t)1 << 31) ? ntiles : 0;
-            hipLaunchKernelGGL(kern, adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)ygrid), dim3(sx::kBlock), 0, s, h->m_rp, h->m_ci,
-                               h->m_v, d_B, ldb, d_C_in, ldc_in, d_C_out, ldc, 0, h->M, nrowblk, col0, alpha, beta, (int)h->opt_xcd, (const unsigned char *)h->d_skip, adj, T);
-        };
-        const int n16 = N / 16;
-        if (n16 > 0) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 16, true>, 0, n16); else go(sx::spmm_csr_colwise<false, 16, true>, 0, n16); }
-        if (N % 16) { if (h->opt_exact) go(sx::spmm_csr_colwise<true, 8, true>, n16 * 16, 1); else go(sx::spmm_csr_colwise<false, 8, true>, n16 * 16, 1); }
-        h->last_kernel = "spmm_csr_colwise_rowmajor";
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    if (mode >= 0) {
-        Prof p(h, &h->ev_kernel, s);
-        const int ntiles = (N + 15) / 16, last_cols = N % 16 ? 8 : 16;
-        const sextans_engine::PanelState &P = mode ? h->psc : h->ps;
-        if (int rc = chains_fork()) return rc;
-        const bool split = mode == 0 && h->ps.plan_mixed;   // mixed plan: dictionary blocks here, the other blocks' rows on the gather kernel
-        if (int rc = launch_panel_v2<1>(h, d_B, d_C_in, ldc_in, d_C_out, ldc, ntiles, alpha, beta, s, 0, 0, P.plan_nblk, 0, mode, last_cols, ldb, split)) return rc;
-        if (split) {
-            int col = 0;
-            if (N / 32) { launch_rowgroup<8>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, d_B, d_C_in, ldc_in, d_C_out, ldc, 0, h->M, N / 32, alpha, beta, s, ldb, false, h->ps.d_rg_groups, h->ps.rg_ngroups); col = N / 32 * 32; }
-            if ((N - col) / 16) { launch_rowgroup<4>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, d_B + col, d_C_in + col, ldc_in, d_C_out + col, ldc, 0, h->M, 1, alpha, beta, s, ldb, false, h->ps.d_rg_groups, h->ps.rg_ngroups); col += 16; }
-            if (N - col) launch_rowgroup<2>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, d_B + col, d_C_in + col, ldc_in, d_C_out + col, ldc, 0, h->M, 1, alpha, beta, s, ldb, false, h->ps.d_rg_groups, h->ps.rg_ngroups);
-        }
-        if (int rc = long_rows_join()) return rc;
-        h->last_kernel = mode == 2 ? (hubs || chains ? "spmm_csr_panel_v2_rowmajor_clustered+long_rows" : "spmm_csr_panel_v2_rowmajor_clustered")
-                                   : (hubs || chains ? "spmm_csr_panel_v2_rowmajor+long_rows" : "spmm_csr_panel_v2_rowmajor");
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    // The gather kernel on a matrix without rows on the piece / chain / dense-tile paths: a row of row-major B IS what its lanes fetch
-    // per non-zero (the 4 * LPR floats of a panel row), and a lane's 4 accumulators are 16 bytes of its C row -- no repack, no passes.
-    if (!use_panel && !use_window && !(colwise && !hubs && !chains) && aligned && long_ok && (h->opt_kernel == 0 || h->opt_kernel == 1) && (h->dense_W == 0 && h->rb_n == 0) && h->m_nnz > 0) {
-        Prof p(h, &h->ev_kernel, s);
-        std::vector<Seg> segs = plan;
-        if (N == 8) segs.assign(1, Seg{8, 0, 1});   // (the plan above was made for 16 columns)
-        if (int rc = chains_fork()) return rc;
-        for (const Seg &g : segs) {
-#define SX_SEG(L) launch_rowgroup<L>(h, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->d_skip, d_B + g.col0, d_C_in + g.col0, ldc_in, d_C_out + g.col0, ldc, 0, \
-                                     h->M, g.ntiles, alpha, beta, s, ldb)
-            switch (g.width) {
-                case 32: SX_SEG(8); break;
-                case 16: SX_SEG(4); break;
-                default: SX_SEG(2); break;
-            }
-#undef SX_SEG
-        }
-        if (int rc = long_rows_join()) return rc;
-        h->last_kernel = hubs || chains ? "spmm_csr_rowgroup_rowmajor+long_rows" : "spmm_csr_rowgroup_rowmajor";
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    // Everything else (lane-per-row / window kernels, mixed plans, rows on the piece and chain paths, dense tiles, unaligned operands):
-    // through column-major copies in the engine's workspaces -- two transposes in front, one behind.
-    // (workspaces of their own -- not the host-buffer entry points' d_B / d_Cin / d_Cout, which are filled on another stream; C_in and
-    // C_out may alias, so one C buffer)
-    h->lean_prepare = false;
-    const size_t nB = (size_t)h->K * (size_t)N, nC = (size_t)h->M * (size_t)N;
-    if (int rc = ensure(&h->d_rmB, &h->rmB_cap, nB)) return rc;
-    if (int rc = ensure(&h->d_rmC, &h->rmC_cap, nC)) return rc;
-    {
-        Prof p(h, &h->ev_repack, s);
-        if (aligned) {
-            launch_transpose_skinny(true, d_B, h->d_rmB, ldb, h->K, h->K, N, s);
-            launch_transpose_skinny(true, d_C_in, h->d_rmC, ldc_in, h->M, h->M, N, s);
-        } else {
-            launch_transpose(d_B, ldb, h->d_rmB, h->K, h->K, N, s);
-            launch_transpose(d_C_in, ldc_in, h->d_rmC, h->M, h->M, N, s);
-        }
-    }
-    if (int rc = sextans_spmm_device_rows(h, N, alpha, h->d_rmB, h->K, beta, h->d_rmC, h->M, h->d_rmC, h->M, 0, h->M, 0, stream)) return rc;
-    {
-        Prof p(h, &h->ev_post, s);
-        if (aligned) launch_transpose_skinny(false, h->d_rmC, d_C_out, ldc, h->M, h->M, N, s);
-        else launch_transpose(h->d_rmC, h->M, d_C_out, ldc, N, h->M, s);
-    }
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
 }
 
 }  // extern "C"
@@ -1720,10 +1741,7 @@ int sextans_spmm_host(sextans_handle_t h, int N, float alpha, const float *B, fl
     if (int rc = ensure(&h->d_Cout, &h->C_cap, nC)) return rc;
     SX_HIP(hipMemcpy(h->d_B, B, nB * sizeof(float), hipMemcpyHostToDevice));
     SX_HIP(hipMemcpy(h->d_Cin, C, nC * sizeof(float), hipMemcpyHostToDevice));
-    {   // allocations and the one-time packing of A stay outside the timed region
-        std::vector<Seg> plan; int W = 0; bool up = false, uw = false;
-        if (int rc = prepare(h, N, plan, W, up, uw)) return rc;
-    }
+    if (int rc = prepare(h, N)) return rc;   // allocations and the one-time packing of A stay outside the timed region
     double ns = 0.0;
     if (int rc = run_repeats(h, N, alpha, beta, rp_time, nullptr, nullptr, &ns)) return rc;
     if (elapsed_ns) *elapsed_ns = ns;
@@ -1788,10 +1806,7 @@ int sextans_invoke(sextans_handle_t h, const int32_t *edge_list_ptr, const uint6
         SX_HIP(hipMemcpy(h->d_chC + (size_t)c * c_len, mat_C_ch_in[c], sizeof(float) * (size_t)c_used,
                          hipMemcpyHostToDevice));
     }
-    {
-        std::vector<Seg> plan; int W = 0; bool up = false, uw = false;
-        if (int rc = prepare(h, N, plan, W, up, uw)) return rc;
-    }
+    if (int rc = prepare(h, N)) return rc;
     const float pad = alpha * 0.0f + beta * 0.0f;    // what the accelerator writes into rows M .. colsize-1
     auto pre = [&](hipStream_t cs) {
         if (K > 0)

@@ -196,10 +196,7 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     if (nchunks > 1) {
         st = cc_prepare(h, N, &want_cc);
     } else if (h->M > 0) {   // (whole-slab calls: the plan is built here, not inside the first launch)
-        std::vector<Seg> plan;
-        int W = 0;
-        bool up = false, uw = false;
-        st = prepare(h, N, plan, W, up, uw, true);
+        st = prepare(h, N);
     }
     if (want_cc && h->psc.plan_nblk < nchunks) want_cc = false;
     // Chunk c of rank g = local rows [cuts[g][c], cuts[g][c+1]).  Every rank snaps its OWN interior cuts to the
@@ -315,12 +312,8 @@ int setup_rm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     if (st && !(force && comm)) return st;
     if (!st && world > 1 && h->opt_row_offset != p.row0) st = sextans_set_option(h, "row_offset", p.row0);
     if (int rc = exchange_nnz(h, r, comm, world, rank, row_ranges, force, st, s, &exchanged)) return rc;
-    if (force && h->M > 0) {   // (the lazy form leaves the plan to sextans_spmm_device_rm, which builds it the same way)
-        std::vector<Seg> plan;
-        int W = 0;
-        bool up = false, uw = false;
-        st = rm_plan(h, N, plan, W, up, uw, s);
-    }
+    if (force && h->M > 0)   // (the lazy form leaves the plan to sextans_spmm_device_rm, which builds it the same way)
+        st = rm_plan(h, N, s);
     if (!st && packed && comm) {
         st = ensure(&h->d_stage, &h->stage_cap, (size_t)p.M_total * (size_t)N);
         h->dist_meta_at = nullptr;   // (the column-major form keeps its row tables behind its staging area)

@@ -1060,7 +1060,7 @@ static int ensure_split_rows(sextans_engine *h) {
 // Everything that may allocate or run host-side preprocessing for an N-column SpMM: B-panel workspace,
 // N-tile plan, and (for kernel != 1) the packed row-bucketed form of A.  Idempotent; called by
 // sextans_spmm_device2 and, ahead of the timed region, by sextans_spmm_host.
-int prepare(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_panel, bool &use_window, bool whole) {
+int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
     if (int rc = ensure_col_range(h)) return rc;
     if (int rc = ensure_dense(h)) return rc;   // first the dense tiles leave (when the caller routes them to MFMA) ...
     if (int rc = ensure_split(h)) return rc;   // ... then the long rows; the packed forms below are built from what remains
@@ -1075,14 +1075,10 @@ int prepare(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
     }
     if (h->nhub > 0)   // (16-column granularity: N = 16 t + 8 may run its tail as a half-empty 16-column tile)
         if (int rc = ensure(&h->d_P, &h->P_cap, (size_t)h->split_nv * (size_t)((N + 15) / 16 * 16))) return rc;
-    if (h->nchain > 0 || (N >= 32 && h->opt_pipeline_tiles != 0)) {
-        if (!h->ev_pipe[0])
-            for (hipEvent_t &e : h->ev_pipe) SX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (!h->aux_stream) {
-            SX_HIP(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));   // (a high-priority stream was measured: no difference)
-            SX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            SX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
-        }
+    if (h->nchain > 0 && !h->aux_stream) {
+        SX_HIP(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));   // (a high-priority stream was measured: no difference)
+        SX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+        SX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
     const size_t n16 = (size_t)((N + 15) / 16) * 16;   // (N = 16 t + 8: room for the tail as a zero-padded 16-column tile)
     if (!h->lean_prepare && (h->Bp_cap < (size_t)h->K * n16 || !h->d_Bp)) h->bp_layout = 0;   // new workspace: nothing to reuse
@@ -1102,25 +1098,24 @@ int prepare(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
     bool n8_wide = N == 8 && !h->opt_lpr && h->opt_kernel == 0 && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && h->nhub == 0 && h->nchain == 0 &&
                    h->dense_W == 0 && (size_t)h->K * 8 * sizeof(float) > ((size_t)16 << 20) && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
                    h->M > 0 && h->m_nnz / h->M >= 48;   // (shorter rows: measured a loss -- 2-D 9-point x 2 dof 0.48 -> 0.37 of the roofline per step, 43-entry mesh rows 0.38 -> 0.33)
+    Tiling t;
     auto tiles = [&]() {
         while (lpr > 2 && 4 * lpr > N && !(n8_wide && lpr == 4)) lpr /= 2;
-        W = 4 * lpr;
-        plan.clear();
+        t.W = 4 * lpr;
+        t.segs.clear();
         int col = 0;
-        for (int w : {W, 16, 8}) {
-            if (w > W) continue;
+        for (int w : {t.W, 16, 8}) {
+            if (w > t.W) continue;
             const int nt = (N - col) / w;
-            if (nt > 0) { plan.push_back({w, col, nt}); col += nt * w; }
+            if (nt > 0) { t.segs.push_back({w, col, nt}); col += nt * w; }
         }
     };
     tiles();
     // Kernel choice: "kernel" 1 = row-group gather, 2 = LDS panel, 0 = auto (panel when at least half
     // of the non-zeros sit in row blocks whose B rows are reused -- "only where a tile has reuse").
-    use_panel = false;
     if ((h->opt_kernel == 0 || h->opt_kernel == 4) && h->m_nnz > 0)
         if (int rc = ensure_colwise(h)) return rc;
-    const bool colwise = h->opt_kernel == 4 || (h->opt_kernel == 0 && h->colwise_state == 1);
-    if (h->opt_kernel != 1 && h->opt_kernel != 4 && h->m_nnz > 0 && !(colwise && h->nhub == 0 && h->nchain == 0 && h->dense_W == 0)) {
+    if (h->opt_kernel != 1 && h->opt_kernel != 4 && h->m_nnz > 0 && !(colwise_wanted(h) && h->nhub == 0 && h->nchain == 0 && h->dense_W == 0)) {
         if (int rc = ensure_plan(h, lpr, h->opt_kernel == 2)) return rc;
         // (here, not at launch time: prepare() runs before a hipGraph capture starts, and the builders copy to the host and
         // allocate.  Only for whole-matrix calls: engines that serve row ranges -- the chunks of the multi-GPU pipeline -- never
@@ -1130,39 +1125,39 @@ int prepare(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_
             if (h->cluster_state == 2 && h->cluster_cm_pays && (N >= 16 || n8_wide) && !h->lean_prepare)   // row-major C staging of the reordered form: ceil(N / 16) tiles of M x 16
                 if (int rc = ensure(&h->d_Cs, &h->Cs_cap, (n16 / 16) * (size_t)h->M * 16)) return rc;
         }
-        use_panel = h->ps.plan_built && ((h->opt_kernel == 2) || (h->ps.plan_panel_frac >= 0.5 && (N >= 32 || h->ps.plan_narrow_frac >= 0.5)));
+        t.panel = h->ps.plan_built && ((h->opt_kernel == 2) || (h->ps.plan_panel_frac >= 0.5 && (N >= 32 || h->ps.plan_narrow_frac >= 0.5)));
         // whole-matrix calls on a mixed plan that has its split form: from kSplitMinFrac on (FEM rows + 3 x / 6 x as many uniformly random
         // rows, panel share 0.40 / 0.25: measured against the gather kernel alone, profiles/r05_mixed_plan_split.txt)
-        if (!use_panel && whole && lpr == 4 && h->opt_kernel == 0 && h->ps.plan_built && h->ps.plan_mixed && h->ps.d_rg_skip && h->opt_split_mixed != 0 &&
+        if (!t.panel && whole && lpr == 4 && h->opt_kernel == 0 && h->ps.plan_built && h->ps.plan_mixed && h->ps.d_rg_skip && h->opt_split_mixed != 0 &&
             h->opt_panel_v2 != 0 && h->ps.plan_max_dict <= sx::kWideMaxDict && h->ps.plan_panel_frac >= kSplitMinFrac &&
             (N >= 32 || h->ps.plan_narrow_frac >= kSplitMinFrac))
-            use_panel = true;
+            t.panel = true;
         // (a matrix that runs in the reordered form needs no natural-order plan for that: a randomly numbered mesh without any reuse between
         // consecutive rows has none -- its N = 8 calls fell to the gather kernel, 0.06 against 0.37 at N = 16 on the holdout class)
         const bool reorder8 = whole && h->cluster_state == 2 && h->cluster_cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3;
-        if (n8_wide && !reorder8 && !(use_panel && !h->ps.plan_mixed && h->ps.plan_max_dict <= sx::kWideMaxDict)) {   // not a case for the wide kernel after all
+        if (n8_wide && !reorder8 && !(t.panel && !h->ps.plan_mixed && h->ps.plan_max_dict <= sx::kWideMaxDict)) {   // not a case for the wide kernel after all
             n8_wide = false;
             lpr = 4;
             tiles();
             if (int rc = ensure_plan(h, lpr, h->opt_kernel == 2)) return rc;
-            use_panel = h->ps.plan_built && ((h->opt_kernel == 2) || (h->ps.plan_panel_frac >= 0.5 && h->ps.plan_narrow_frac >= 0.5));
+            t.panel = h->ps.plan_built && ((h->opt_kernel == 2) || (h->ps.plan_panel_frac >= 0.5 && h->ps.plan_narrow_frac >= 0.5));
         }
     }
     // (the reordered form of a graph-clustered matrix runs 16-column tiles whether or not a natural-order plan exists)
     // (a lean prepare -- on behalf of a row-major call -- also keeps 16-column tiles for a clustered plan that is kept for row-major calls
     // only: sextans_spmm_device_rm needs W == 16 to use it, and at N >= 32 the switch to 8 lanes per row below took it to the gather kernel)
     const bool reorder = whole && h->cluster_state == 2 && (h->cluster_cm_pays || h->lean_prepare) && h->opt_kernel != 1 && h->opt_kernel != 3 && lpr == 4;
-    if (!h->opt_lpr && !use_panel && !reorder && N >= 32 && lpr != 8) { lpr = 8; tiles(); }
+    if (!h->opt_lpr && !t.panel && !reorder && N >= 32 && lpr != 8) { lpr = 8; tiles(); }
     // "kernel" 3 = K-windowed accumulator-resident kernel; auto picks it for matrices without B-row reuse
     // whose B does not fit the L2s when the traffic model says the sweep moves fewer bytes than the gather.
-    use_window = false;
-    if (h->m_nnz > 0 && (h->opt_kernel == 3 || (h->opt_kernel == 0 && !use_panel))) {
+    if (h->m_nnz > 0 && (h->opt_kernel == 3 || (h->opt_kernel == 0 && !t.panel))) {
         const bool force = h->opt_kernel == 3;
         if (force || (h->win_state >= 0 && window_pays(h, N, h->win_state == 1 ? h->win_padded : h->m_nnz))) {
             if (int rc = ensure_window(h, force)) return rc;
-            use_window = h->win_state == 1 && (force || window_pays(h, N, h->win_padded));
+            t.window = h->win_state == 1 && (force || window_pays(h, N, h->win_padded));
         }
     }
+    if (out) *out = std::move(t);
     return SEXTANS_OK;
 }
 

@@ -41,6 +41,12 @@ constexpr int kRowsNoFuseB = 0x100;   // internal flag of sextans_spmm_device_ro
 constexpr int kPanelFloats = 9216;    // at most 36 KiB of LDS for the B panel (576 rows at N-tile 16)
 struct Seg { int width, col0, ntiles; int last_cols = 0; };   // N is covered by segments of equally wide tiles; last_cols != 0: valid columns of the
                                                                // segment's LAST tile (8: the tail of N = 16 t + 8 merged into the 16-column segment)
+struct Tiling {                  // what prepare() decided for an N-column call
+    std::vector<Seg> segs;       // N in segments of equally wide tiles
+    int W = 0;                   // main tile width: the packed plan is built for it
+    bool panel = false;          // the LDS-panel plan serves the main rows
+    bool window = false;         // ... or the K-window kernel
+};
 }  // namespace sxe
 
 struct sextans_engine {
@@ -203,7 +209,6 @@ struct sextans_engine {
     int64_t chain_built_opt = -2;
     hipStream_t aux_stream = nullptr;         // the chain kernels need one or two wavefronts for ~1 ms: they run beside the main kernel
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_pipe[4] = {nullptr, nullptr, nullptr, nullptr};   // tile-group pipelining (engine.hip): fork / second-group passes done / first kernel done / side stream done
     std::vector<int> h_split_rows;            // ascending: rows cut into more than one piece
     int nhub = 0;                             // long rows (bucketed + split)
     int split_nv = 0;                         // pieces of all long rows
@@ -258,10 +263,6 @@ struct sextans_engine {
     int64_t opt_row_offset = -1;        // this engine's matrix is the row slab [row_offset, row_offset + M) of a K x K matrix (set by sextans_dist_spmm): lets the
                                         // graph clustering run on a rank's slab (edges to other ranks' rows ignored); -1 = unknown (only square matrices cluster)
     int64_t opt_row_sets = 2;           // clustered grid plan of a short-row matrix (rows <= 32 entries): 128-row bricks = two 64-slot row sets per block and panel; 2 = 3-D grids, 3 = 2-D grids too, 1 = never
-    int64_t opt_pipeline_tiles = 0;     // N >= 32 on spmm_csr_panel_v2: 1 = the 16-column tiles run as two groups and the layout passes of the second
-                                        // group go to the side stream under the first group's kernel.  Built and measured: the second
-                                        // pass over the packed A stream costs more than the hidden repack saves (FEM 4M, N = 128: 3.94 -> 4.09 ms
-                                        // per step, N = 32: 1.12 -> 1.52 ms), so the default is 0 = one launch over all tiles
     int64_t opt_small_v2 = 1;           // measurement switch: 0 = small matrices keep the full-capacity, 4-deep form of spmm_csr_panel_v2
     int64_t opt_panel_v2 = -1;          // 16-column tiles on the register-resident form (spmm_csr_panel_v2<1>: row entries
                                         // loaded once per block, panels by LDS-DMA, tile loop inside the workgroup, C stored
@@ -346,7 +347,11 @@ int ensure_window(sextans_engine *h, bool force);
 bool window_pays(const sextans_engine *h, int N, int64_t padded);
 int ensure_split(sextans_engine *h);
 int ensure_dense(sextans_engine *h);                       // engine_bell.hip
-int prepare(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_panel, bool &use_window, bool whole = true);
+int prepare(sextans_engine *h, int N, bool whole = true, Tiling *out = nullptr);
+// the lane-per-row kernel (spmm_colwise_kernel.h) is asked for ("kernel" = 4) or chosen for this matrix
+inline bool colwise_wanted(const sextans_engine *h) { return h->opt_kernel == 4 || (h->opt_kernel == 0 && h->colwise_state == 1); }
+// every row of the main matrix is on the CSR kernels: no dense tiles on the matrix cores, no routed row blocks
+inline bool csr_only(const sextans_engine *h) { return h->dense_W == 0 && h->rb_n == 0; }
 // dense 32x32 tiles on the matrix cores (engine_bell.hip): C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block rows
 int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
                        int64_t ldc_in, float *d_C_out, int64_t ldc, hipStream_t s);
@@ -356,7 +361,7 @@ int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const floa
 int mark_rowblock_skip(sextans_engine *h);   // after ensure_split: the routed rows join the rows the CSR kernels never write
 
 // clustered-order chunks of sextans_dist_spmm (engine.hip)
-int rm_plan(sextans_engine *h, int N, std::vector<Seg> &plan, int &W, bool &use_panel, bool &use_window, hipStream_t s);   // planning half of sextans_spmm_device_rm
+int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out = nullptr);   // planning half of sextans_spmm_device_rm
 int cc_prepare(sextans_engine *h, int N, bool *ok);
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s);
 void cc_pre(sextans_engine *h, int N, const float *d_B, int64_t ldb, const float *d_C_in_slab, int64_t ldc_in, hipStream_t s);

@@ -8,7 +8,6 @@ FEM=110x110x110x3; FEM1=160x160x160x1; S9x2=synth:stencil2d:1400:1400:9:2; S9=sy
 SHORT="$FEM1 $S9x2 $S9 synth:mesh3d:159:1:random"
 opts() { local spec=$1 n=$2 it=$3; shift 3; echo "== $spec N=$n"; python tools/ab_opts.py $spec $n $it "$@" 2>&1 | grep round; }
 case "$1" in
-  pipelining)      for N in 32 128; do opts $FEM $N 10 pipeline_tiles=0 pipeline_tiles=1; done ;;                                   # r04a
   fma)             for N in 64 128 256; do opts $FEM $N 6 exact=1 exact=0; done
                    for M in $FEM1 $S9x2; do for N in 64 128; do opts $M $N 6 exact=1 exact=0; done; done ;;                       # r04a
   brick_shapes)    for N in 16 128; do opts $FEM $N 8 cluster_shape=0 cluster_shape=320201 cluster_shape=320102 cluster_shape=160401; done   # r04a, r04h
