@@ -506,6 +506,44 @@ int sextans_spmm_t_device_rm(sextans_handle_t h, int N, float alpha, const float
 int sextans_sddmm_device_rm(sextans_handle_t h, int N, float alpha, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, float beta,
                             const float *d_vals_in, float *d_vals_out, void *stream);
 
+/* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
+ *
+ * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or
+ * bf16 (uint16_t *).  A's values, every product and every sum stay fp32.  ld are in ELEMENTS, ldb, ldc_in, ldc >= N, N % 8 == 0; C_in may
+ * alias C_out (same dtype).  With b32 = B widened to fp32 (exact: 16 zero bits appended) and c32 = C_in widened (or itself):
+ *   the fp32 result is BIT FOR BIT what sextans_spmm_device_rm(h, N, alpha, b32, ..., beta, c32, ...) writes on the same engine with the
+ *   same options -- in SEXTANS_MODE_STRICT bit-identical to cpu_spmm_CSR on b32, in SEXTANS_MODE_FAST inside that mode's stated bound;
+ *   a bf16 C_out is that fp32 result rounded to nearest even (a NaN stays a NaN).
+ * Route: the decision of sextans_spmm_device_rm for the call is taken unchanged.
+ *   NATIVE   where it is the gather kernel (sextans_last_kernel "spmm_csr_rowgroup_rowmajor[+long_rows]" on the fp32 entry), no row is an
+ *            exact chain (stat "exact_chain_rows" == 0) and the operands allow 16-byte accesses (16-byte aligned pointers, ldb % 8 == 0,
+ *            C's ld % 4 == 0 for fp32 / % 8 == 0 for bf16; B below 4 GB: K * ldb * 2 < 2^32): the bf16 kernels (spmm_bf16_kernels.h) run on the caller's buffers -- one
+ *            16-byte request per non-zero brings 8 columns instead of 4; no workspace, no extra pass, no allocation, no host
+ *            synchronisation (after sextans_prepare_rm_bf16 the call can be captured into a hipGraph).  sextans_last_kernel =
+ *            "spmm_csr_rowgroup_rowmajor_bf16" / "spmm_csr_rowgroup_rowmajor_bf16+long_rows" (bucketed long rows; split hub rows in
+ *            SEXTANS_MODE_FAST).
+ *   CONVERTED  everything else (LDS-panel and lane-per-row routes, exact chains, mixed plans, dense tiles, unaligned operands): B (and a
+ *            bf16 C_in) are widened into fp32 workspaces of the engine, the fp32 row-major path runs, a bf16 C_out is rounded back.
+ *            Correct for every matrix the fp32 entry accepts; sextans_last_kernel names the fp32 kernel that ran.  The workspaces
+ *            (4 * K * N bytes, + 4 * M * N for a bf16 C) count in stat "device_bytes" and are dropped with the matrix.
+ * Stats "bf16_native_calls" / "bf16_converted_calls": calls served either way since sextans_set_matrix_* (transposed calls included).
+ * sextans_update_values* needs nothing more: the native kernels read the arrays a value refresh rewrites.
+ * SEXTANS_ERR_INVALID: h / pointers NULL, N % 8, an ld < N, c_dtype unknown, an address that is not a multiple of its element size;
+ * SEXTANS_ERR_STATE: no CSR matrix set.
+ *   sextans_spmm_t_device_rm_bf16  the same for A^T (B is M x N, C is K x N), served by the companion engine of sextans_spmm_t_device_rm
+ *       with this engine's options and value refreshes.
+ *   sextans_prepare_rm_bf16  everything a later bf16 call for (N, c_dtype) would build or allocate, built now: the row-major plans of
+ *       sextans_prepare(SEXTANS_LAYOUT_ROWMAJOR) -- transposed != 0: those of SEXTANS_LAYOUT_ROWMAJOR_T -- and, where a call with aligned
+ *       operands converts, the fp32 workspaces.  (A call with UNALIGNED operands on a matrix whose aligned calls are native sizes its
+ *       workspaces itself, at the call.) */
+#define SEXTANS_DTYPE_F32 0
+#define SEXTANS_DTYPE_BF16 1
+int sextans_spmm_device_rm_bf16(sextans_handle_t h, int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const void *d_C_in,
+                                int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, void *stream);
+int sextans_spmm_t_device_rm_bf16(sextans_handle_t h, int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const void *d_C_in,
+                                  int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, void *stream);
+int sextans_prepare_rm_bf16(sextans_handle_t h, int N, int c_dtype, int transposed, void *stream);
+
 /* Row-range form: computes rows [row_begin, row_end) only.  d_C_in / d_C_out address row_begin as
  * their row 0 (ldc_in, ldc_out >= row_end - row_begin).  Used to pipeline a rank's slab in chunks so the
  * all-gather of chunk i overlaps the SpMM of chunk i+1.  flags: SEXTANS_ROWS_REUSE_B_PANELS = the B

@@ -69,7 +69,10 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_export_row_order", "sextans_mtx_read_cached", "sextans_matrix_save", "sextans_matrix_load",
     "sextans_prepare", "sextans_dist_prepare", "sextans_dist_bind_library", "sextans_device_alloc", "sextans_device_copy",
     "sextans_csr_transpose_device", "sextans_spmm_t_device_rm", "sextans_sddmm_device_rm",
-    "sextans_update_values", "sextans_update_values_device"))
+    "sextans_update_values", "sextans_update_values_device",
+    "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16"))
+
+DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 
 
 class _Optional:
@@ -257,6 +260,9 @@ def lib():
                                            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_sddmm_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float,
                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sextans_spmm_device_rm_bf16.argtypes = L.sextans_spmm_t_device_rm_bf16.argtypes = [
+        C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    L.sextans_prepare_rm_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -730,6 +736,22 @@ class Engine:
         this engine's options (sextans_spmm_t_device_rm)."""
         _check(lib().sextans_spmm_t_device_rm(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream),
                "spmm_t_device_rm")
+
+    def spmm_device_rm_bf16(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype=DTYPE_F32, stream=None):
+        """ROW-major operands with B in bf16 and C_in / C_out both fp32 (DTYPE_F32) or bf16 (DTYPE_BF16); ld in elements.  The fp32
+        result has the bits of spmm_device_rm on the widened operands; native on the gather path, through fp32 copies elsewhere
+        (sextans_spmm_device_rm_bf16; stats "bf16_native_calls" / "bf16_converted_calls")."""
+        _check(lib().sextans_spmm_device_rm_bf16(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype, stream),
+               "spmm_device_rm_bf16")
+
+    def spmm_t_device_rm_bf16(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype=DTYPE_F32, stream=None):
+        """The same for A^T (B is M x N, C is K x N), on the companion engine of spmm_t_device_rm (sextans_spmm_t_device_rm_bf16)."""
+        _check(lib().sextans_spmm_t_device_rm_bf16(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype, stream),
+               "spmm_t_device_rm_bf16")
+
+    def prepare_rm_bf16(self, N, c_dtype, transposed=False, stream=None):
+        """Everything a later bf16 call for (N, c_dtype) would build or allocate, built now (sextans_prepare_rm_bf16)."""
+        _check(lib().sextans_prepare_rm_bf16(self._h, N, c_dtype, 1 if transposed else 0, stream), "prepare_rm_bf16")
 
     def sddmm_device_rm(self, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream=None):
         """vals_out[e] = alpha * sum_n X[r, n] * Y[c, n] (+ beta * vals_in[e]) for every entry e = (r, c) of A, in CSR order, with the

@@ -19,6 +19,7 @@
 #include "engine_state.h"
 #include "reorder_kernels.h"
 #include "spmm_colwise_kernel.h"
+#include "spmm_bf16_kernels.h"
 #include "spmm_csr_kernels.h"
 #include "spmm_panel_v2.h"
 #include "spmm_window_kernel.h"
@@ -843,6 +844,8 @@ int sextans_get_stat(sextans_handle_t h, const char *key, double *value) {
     else if (!strcmp(key, "device_bytes")) *value = (double)device_bytes(h);
     else if (!strcmp(key, "value_refreshes")) *value = (double)h->value_refreshes;                  // sextans_update_values* served on this matrix
     else if (!strcmp(key, "value_refresh_rebuilt")) *value = (double)h->value_refresh_rebuilt;      //   ... that dropped a form for a lazy rebuild
+    else if (!strcmp(key, "bf16_native_calls")) *value = (double)(h->bf16_native_calls + (h->tr ? h->tr->bf16_native_calls : 0));            // bf16 calls (transposed ones included) on the caller's buffers
+    else if (!strcmp(key, "bf16_converted_calls")) *value = (double)(h->bf16_converted_calls + (h->tr ? h->tr->bf16_converted_calls : 0));   //   ... and through fp32 copies
     else if (!strcmp(key, "transpose_build_s")) *value = h->transpose_build_s + (h->tr ? h->tr->plan_build_s : 0.0);
     else if (!strcmp(key, "grid_stride_line")) *value = (double)h->cluster_s2;
     else if (!strcmp(key, "grid_stride_plane")) *value = (double)h->cluster_s3;
@@ -1646,6 +1649,189 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
         case RouteRM::kTranspose: return run_rm_transpose(h, c, r.aligned);
         default: return run_rm_direct(h, c, r);
     }
+}
+
+}  // extern "C"
+
+// ---- bf16 dense operands on the row-major entry (spmm_bf16_kernels.h) --------------------------------------------------------------
+namespace sxe {
+int check_rm_bf16_args(sextans_handle_t h, int N, const uint16_t *d_B, int64_t ldb, const void *d_C_in, int64_t ldc_in, void *d_C_out,
+                       int64_t ldc, int c_dtype) {
+    if (!h || N <= 0 || (N % 8) != 0 || !d_B || !d_C_in || !d_C_out || ldb < N || ldc_in < N || ldc < N) return SEXTANS_ERR_INVALID;
+    if (c_dtype != SEXTANS_DTYPE_F32 && c_dtype != SEXTANS_DTYPE_BF16) return SEXTANS_ERR_INVALID;
+    const uintptr_t cmask = c_dtype == SEXTANS_DTYPE_BF16 ? 1 : 3;   // addresses that cannot hold an element of their type
+    if ((reinterpret_cast<uintptr_t>(d_B) & 1) || ((reinterpret_cast<uintptr_t>(d_C_in) | reinterpret_cast<uintptr_t>(d_C_out)) & cmask)) return SEXTANS_ERR_INVALID;
+    return SEXTANS_OK;
+}
+}  // namespace sxe
+namespace {
+// The bf16 kernels' tiling of N: 64-column tiles (8 lanes per row, a whole 128-byte line of a B row), then at most one 32-, 16- and 8-column tile
+std::vector<Seg> bf16_tiles(int N) {
+    std::vector<Seg> v;
+    int col = 0;
+    if (N / 64) { v.push_back(Seg{64, 0, N / 64}); col = N / 64 * 64; }
+    for (int w : {32, 16, 8})
+        if ((N - col) / w) { v.push_back(Seg{w, col, 1}); col += w; }
+    return v;
+}
+template <class F>
+void by_width_bf16(int width, F f) {   // f(LPR): 8 columns per lane
+    switch (width) {
+        case 64: f(std::integral_constant<int, 8>{}); break;
+        case 32: f(std::integral_constant<int, 4>{}); break;
+        case 16: f(std::integral_constant<int, 2>{}); break;
+        default: f(std::integral_constant<int, 1>{}); break;
+    }
+}
+
+struct CallBf16 {
+    int N; float alpha; const uint16_t *B; int64_t ldb; float beta; const void *C_in; int64_t ldc_in; void *C_out; int64_t ldc; bool cbf16; hipStream_t s;
+};
+
+// The native route: the gather kernel (and the piece path of long rows) on the caller's bf16 buffers.  The very arrays run_rm_direct
+// passes (m_rp / m_ci / m_v, the piece table by_len) -- what a value refresh rewrites.
+int run_rm_bf16_native(sextans_engine *h, const CallBf16 &c) {
+    Prof p(h, &h->ev_kernel, c.s);
+    const size_t esz = c.cbf16 ? 2 : 4;
+    const bool stage = h->opt_stage != 0, exact = h->opt_exact != 0;
+    for (const Seg &g : bf16_tiles(c.N))
+        by_width_bf16(g.width, [&](auto L) {
+            constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR, CH = 2048;
+            const int nrowblk = (h->M + RB - 1) / RB;
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)nrowblk * (unsigned)g.ntiles), dim3(sx::kBlock), 0, c.s, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v,
+                                   c.B + g.col0, c.ldb, (const void *)((const char *)c.C_in + esz * (size_t)g.col0), c.ldc_in,
+                                   (void *)((char *)c.C_out + esz * (size_t)g.col0), c.ldc, h->M, g.ntiles, nrowblk, c.alpha, c.beta, (int)h->opt_xcd,
+                                   (const unsigned char *)h->d_skip);
+            };
+#define SX_BF(EX, ST) (c.cbf16 ? go(sx::spmm_csr_rowgroup_bf16<LPR, CH, EX, ST, true>) : go(sx::spmm_csr_rowgroup_bf16<LPR, CH, EX, ST, false>))
+            if (exact) { if (stage) SX_BF(true, true); else SX_BF(true, false); }
+            else       { if (stage) SX_BF(false, true); else SX_BF(false, false); }
+#undef SX_BF
+        });
+    if (h->nhub > 0) {   // the long rows' pieces (raw fp32 sums into P) and their fold
+        const sextans_engine::PieceTable &pt = h->by_len;
+        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->nhub];
+        for (const Seg &g : bf16_tiles(c.N))
+            by_width_bf16(g.width, [&](auto L) {
+                constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR;
+                const int nblk = (v1 - v0 + RB - 1) / RB;
+                if (nblk <= 0) return;
+                auto go = [&](auto kern) {
+                    hipLaunchKernelGGL(kern, dim3((unsigned)nblk * (unsigned)g.ntiles), dim3(sx::kBlock), 0, c.s, pt.d_vrp, pt.d_vend, h->s_ci, h->s_v,
+                                       c.B + g.col0, c.ldb, h->d_P + (int64_t)g.col0 * h->split_nv, (int64_t)h->split_nv, v0, v1, g.ntiles);
+                };
+                if (exact) go(sx::spmm_csr_pieces_bf16<LPR, true>); else go(sx::spmm_csr_pieces_bf16<LPR, false>);
+            });
+        if (c.cbf16) {
+            const int64_t tot = (int64_t)h->nhub * c.N;
+            auto go = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c.s, pt.d_vfirst, pt.d_row, h->d_P, (int64_t)h->split_nv,
+                                   (const uint16_t *)c.C_in, c.ldc_in, (uint16_t *)c.C_out, c.ldc, h->nhub, c.N, c.alpha, c.beta);
+            };
+            if (exact) go(sx::fold_hub_pieces_bf16<true>); else go(sx::fold_hub_pieces_bf16<false>);
+        } else {
+            launch_fold(h, pt, 0, h->nhub, c.N, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+        }
+    }
+    h->last_kernel = h->nhub > 0 ? "spmm_csr_rowgroup_rowmajor_bf16+long_rows" : "spmm_csr_rowgroup_rowmajor_bf16";
+    SX_HIP(hipGetLastError());
+    ++h->bf16_native_calls;
+    return SEXTANS_OK;
+}
+
+void launch_widen(const uint16_t *src, int64_t lds, float *dst, int64_t ldd, int64_t rows, int cols, hipStream_t s) {
+    if (rows <= 0) return;
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && lds % 8 == 0 && ldd % 4 == 0;
+    const int64_t n = vec ? rows * (cols / 8) : rows * cols;
+    if (vec) hipLaunchKernelGGL(sx::widen_bf16_matrix<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, dst, ldd, rows, cols);
+    else hipLaunchKernelGGL(sx::widen_bf16_matrix<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, dst, ldd, rows, cols);
+}
+void launch_round(const float *src, int64_t lds, uint16_t *dst, int64_t ldd, int64_t rows, int cols, hipStream_t s) {
+    if (rows <= 0) return;
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0 && lds % 4 == 0 && ldd % 8 == 0;
+    const int64_t n = vec ? rows * (cols / 8) : rows * cols;
+    if (vec) hipLaunchKernelGGL(sx::round_bf16_matrix<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, dst, ldd, rows, cols);
+    else hipLaunchKernelGGL(sx::round_bf16_matrix<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, lds, dst, ldd, rows, cols);
+}
+
+// the converting route's fp32 copies: B always, C only when it is bf16
+int ensure_bf16_workspaces(sextans_engine *h, int N, bool cbf16) {
+    if (int rc = ensure(&h->d_bfB, &h->bfB_cap, (size_t)h->K * (size_t)N)) return rc;
+    if (cbf16)
+        if (int rc = ensure(&h->d_bfC, &h->bfC_cap, (size_t)h->M * (size_t)N)) return rc;
+    return SEXTANS_OK;
+}
+
+// Every other route: fp32 copies of B (and of a bf16 C) in the engine's workspaces around the fp32 row-major entry point
+int run_rm_bf16_converted(sextans_engine *h, const CallBf16 &c) {
+    if (int rc = ensure_bf16_workspaces(h, c.N, c.cbf16)) return rc;
+    {
+        Prof p(h, &h->ev_repack, c.s);
+        launch_widen(c.B, c.ldb, h->d_bfB, c.N, h->K, c.N, c.s);
+        if (c.cbf16) launch_widen((const uint16_t *)c.C_in, c.ldc_in, h->d_bfC, c.N, h->M, c.N, c.s);
+    }
+    SX_HIP(hipGetLastError());
+    if (!c.cbf16) {
+        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->d_bfB, c.N, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, (void *)c.s)) return rc;
+    } else {
+        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->d_bfB, c.N, c.beta, h->d_bfC, c.N, h->d_bfC, c.N, (void *)c.s)) return rc;
+        Prof p(h, &h->ev_post, c.s);
+        launch_round(h->d_bfC, c.N, (uint16_t *)c.C_out, c.ldc, h->M, c.N, c.s);
+    }
+    SX_HIP(hipGetLastError());
+    ++h->bf16_converted_calls;
+    return SEXTANS_OK;
+}
+
+// 16-byte accesses on the caller's buffers: aligned bases, whole 16-byte groups per row; 32-bit byte offsets into B
+bool bf16_aligned(const sextans_engine *h, const CallBf16 &c) {
+    const int64_t cm = c.cbf16 ? 8 : 4;
+    return (int64_t)h->K * c.ldb * 2 < ((int64_t)1 << 32) && ((reinterpret_cast<uintptr_t>(c.B) | reinterpret_cast<uintptr_t>(c.C_in) | reinterpret_cast<uintptr_t>(c.C_out)) & 15) == 0 &&
+           c.ldb % 8 == 0 && c.ldc_in % cm == 0 && c.ldc % cm == 0;
+}
+// route_rm's decision for the call, unchanged: native where it is the gather kernel and no row is an exact chain
+// (asked with the caller's leading dimensions; a call that converts asks again inside sextans_spmm_device_rm with ldb = N of the
+// workspace -- route_rm looks at ldb only for alignment and the 32-bit limit of the panel paths, so the two cannot disagree on the gather route)
+bool bf16_native(const sextans_engine *h, const CallBf16 &c, const Tiling &t) {
+    if (!bf16_aligned(h, c) || h->nchain > 0) return false;
+    const Call f{c.N, c.alpha, (const float *)c.B, c.ldb, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, h->M, 0, c.s, true};
+    return route_rm(h, f, t).path == RouteRM::kRowgroup;
+}
+}  // namespace
+extern "C" {
+
+int sextans_spmm_device_rm_bf16(sextans_handle_t h, int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const void *d_C_in,
+                                int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, void *stream) {
+    if (int rc = check_rm_bf16_args(h, N, d_B, ldb, d_C_in, ldc_in, d_C_out, ldc, c_dtype)) return rc;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->M == 0) return SEXTANS_OK;
+    Tiling t;
+    if (int rc = rm_plan(h, N, s, &t)) return rc;
+    const CallBf16 c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, c_dtype == SEXTANS_DTYPE_BF16, s};
+    return bf16_native(h, c, t) ? run_rm_bf16_native(h, c) : run_rm_bf16_converted(h, c);
+}
+
+int sextans_prepare_rm_bf16(sextans_handle_t h, int N, int c_dtype, int transposed, void *stream) {
+    if (!h || N <= 0 || (N % 8) != 0 || (c_dtype != SEXTANS_DTYPE_F32 && c_dtype != SEXTANS_DTYPE_BF16) || (transposed != 0 && transposed != 1))
+        return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (transposed) {
+        if (int rc = prepare_transposed(h, N, s)) return rc;
+        return h->tr ? sextans_prepare_rm_bf16(h->tr, N, c_dtype, 0, stream) : SEXTANS_OK;
+    }
+    if (h->M == 0) return SEXTANS_OK;
+    Tiling t;
+    if (int rc = rm_plan(h, N, s, &t)) return rc;
+    // the route of a call with aligned operands; where that is native nothing more is needed (a call with unaligned operands on such a
+    // matrix converts and sizes the copies itself)
+    const CallBf16 c{N, 1.f, nullptr, N, 0.f, nullptr, N, nullptr, N, c_dtype == SEXTANS_DTYPE_BF16, s};
+    if (bf16_native(h, c, t)) return SEXTANS_OK;
+    return ensure_bf16_workspaces(h, N, c.cbf16);
 }
 
 }  // extern "C"

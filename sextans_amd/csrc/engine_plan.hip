@@ -100,7 +100,7 @@ int64_t device_bytes(const sextans_engine *h) {
     b += (int64_t)h->bell_Bf_cap;
     if (h->tr) b += ((int64_t)h->K + 1) * 4 + h->nnz * 8 + (h->d_tperm ? h->nnz * 4 : 0) + device_bytes(h->tr);   // A^T, its entry permutation, its companion's plans and workspaces
     b += h->sddmm_row0_n * 4;
-    b += 4 * (int64_t)(h->Bp_cap + h->B_cap + (h->d_Cin ? h->C_cap : 0) + h->C_cap + h->P_cap + h->stage_cap + h->chB_cap + h->chC_cap + h->Cs_cap + h->rmB_cap + h->rmC_cap + h->Cfull_cap + h->dist_rows_cap);
+    b += 4 * (int64_t)(h->Bp_cap + h->B_cap + (h->d_Cin ? h->C_cap : 0) + h->C_cap + h->P_cap + h->stage_cap + h->chB_cap + h->chC_cap + h->Cs_cap + h->rmB_cap + h->rmC_cap + h->bfB_cap + h->bfC_cap + h->Cfull_cap + h->dist_rows_cap);
     return b;
 }
 
@@ -165,6 +165,10 @@ void free_matrix(sextans_engine *h) {
     (void)hipFree(h->d_v_upd);
     h->d_v_upd = nullptr;
     h->value_refreshes = h->value_refresh_rebuilt = 0;
+    (void)hipFree(h->d_bfB); (void)hipFree(h->d_bfC);
+    h->d_bfB = h->d_bfC = nullptr;
+    h->bfB_cap = h->bfC_cap = 0;
+    h->bf16_native_calls = h->bf16_converted_calls = 0;
     h->d_rp = h->d_ci = nullptr;
     h->d_v = nullptr;
     h->owns_matrix = false;

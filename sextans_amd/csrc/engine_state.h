@@ -228,6 +228,11 @@ struct sextans_engine {
     std::vector<hipEvent_t> dist_events;
     float *d_rmB = nullptr, *d_rmC = nullptr;   // column-major copies of the row-major entry point's fallback path
     size_t rmB_cap = 0, rmC_cap = 0;
+    // bf16 dense operands (sextans_spmm_device_rm_bf16): fp32 copies of B and of a bf16 C for the routes that have no bf16 kernel
+    // (dropped with the matrix), and which way the calls on the current matrix went (stats "bf16_native_calls" / "bf16_converted_calls")
+    float *d_bfB = nullptr, *d_bfC = nullptr;
+    size_t bfB_cap = 0, bfC_cap = 0;
+    int64_t bf16_native_calls = 0, bf16_converted_calls = 0;
     float *d_Cfull = nullptr;           // clustered-order chunks: row-major staging of the WHOLE C ([N / 16][M_total][16]) the received slabs are scattered into
     size_t Cfull_cap = 0;
     int *d_dist_rows = nullptr;         //   ... and every rank's position -> global row table ([world][longest slab])
@@ -366,6 +371,8 @@ int mark_rowblock_skip(sextans_engine *h);   // after ensure_split: the routed r
 
 // clustered-order chunks of sextans_dist_spmm (engine.hip)
 int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out = nullptr);   // planning half of sextans_spmm_device_rm
+// argument checks of the bf16 row-major entry points (engine.hip): SEXTANS_ERR_INVALID or SEXTANS_OK, nothing touched
+int check_rm_bf16_args(sextans_handle_t h, int N, const uint16_t *d_B, int64_t ldb, const void *d_C_in, int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype);
 int cc_prepare(sextans_engine *h, int N, bool *ok);
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s);
 void cc_pre(sextans_engine *h, int N, const float *d_B, int64_t ldb, const float *d_C_in_slab, int64_t ldc_in, hipStream_t s);

@@ -139,6 +139,20 @@ int sextans_spmm_t_device_rm(sextans_handle_t h, int N, float alpha, const float
     return rc;
 }
 
+int sextans_spmm_t_device_rm_bf16(sextans_handle_t h, int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const void *d_C_in,
+                                  int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, void *stream) {
+    if (int rc = check_rm_bf16_args(h, N, d_B, ldb, d_C_in, ldc_in, d_C_out, ldc, c_dtype)) return rc;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    SX_HIP(hipSetDevice(h->device));
+    if (h->K == 0) return SEXTANS_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_transpose(h, s)) return rc;
+    const int rc = sextans_spmm_device_rm_bf16(h->tr, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, c_dtype, stream);
+    h->last_kernel_buf = h->tr->last_kernel;
+    h->last_kernel = h->last_kernel_buf.c_str();
+    return rc;
+}
+
 int sextans_sddmm_device_rm(sextans_handle_t h, int N, float alpha, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, float beta,
                             const float *d_vals_in, float *d_vals_out, void *stream) {
     if (!h || N <= 0 || (N % 8) != 0 || !d_X || !d_Y || !d_vals_out || ldx < N || ldy < N || (ldx % 4) != 0 || (ldy % 4) != 0)

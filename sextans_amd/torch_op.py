@@ -152,35 +152,49 @@ def refresh(A, fast=False):
     _engine_for_parts(A.crow_indices(), A.col_indices(), A.values(), tuple(A.shape), A.device.index or 0, fast, force_refresh=True)
 
 
-def _rowmajor(t, rows, cols, colsp):
-    """fp32, unit column stride, 16-byte aligned base and row stride: the tensor itself when it qualifies, else a padded copy"""
-    if (t.dtype == torch.float32 and cols == colsp and t.stride(1) == 1 and t.stride(0) >= cols and t.stride(0) % 4 == 0 and
-            t.data_ptr() % 16 == 0):
+def _qualifies(t, cols, colsp, dtype):
+    """dtype, unit column stride, 16-byte aligned base and row stride (4 fp32 / 8 bf16 elements): the engine reads or writes it where it lies"""
+    per16 = 4 if dtype == torch.float32 else 8
+    return (t.dtype == dtype and cols == colsp and t.stride(1) == 1 and t.stride(0) >= cols and t.stride(0) % per16 == 0 and
+            t.data_ptr() % 16 == 0)
+
+
+def _rowmajor(t, rows, cols, colsp, dtype=torch.float32):
+    """the tensor itself when it qualifies, else a padded copy in `dtype`"""
+    if _qualifies(t, cols, colsp, dtype):
         return t
-    out = torch.zeros((rows, colsp), dtype=torch.float32, device=t.device)
+    out = torch.zeros((rows, colsp), dtype=dtype, device=t.device)
     out[:, :cols] = t
     return out
 
 
-def spmm(A, B, alpha=1.0, beta=0.0, C=None, out=None, fast=False, transpose_a=False):
-    """out (optional): an (M, N) fp32 row-major tensor that receives the result (N % 8 == 0); may be C itself (in place).
+def spmm(A, B, alpha=1.0, beta=0.0, C=None, out=None, fast=False, transpose_a=False, out_dtype=None):
+    """out (optional): an (M, N) row-major tensor of the result's dtype that receives the result (N % 8 == 0); may be C itself (in place).
     fast (round 6): the engine's documented in-tolerance mode (include/sextans_amd.h, SEXTANS_MODE_FAST) instead of bit identity with the
     reference's cpu_spmm_CSR; a matrix used in both modes keeps one engine per mode.
     transpose_a: alpha * A^T * B + beta * C with B (M, N) and C (K, N) (sextans_spmm_t_device_rm).
+    bf16: a bf16 B that the engine can read where it lies (unit column stride, 16-byte aligned, N % 8 == 0, row stride % 8 == 0) goes to
+    the bf16 entry point (sextans_spmm_device_rm_bf16) without an fp32 copy; the result is still fp32 with the bits of spmm(A, B.float()),
+    since widening is exact.  out_dtype (None = torch.float32, or torch.bfloat16): with torch.bfloat16 the result (and out=) is bf16: the fp32
+    result rounded to nearest even, once, whatever the dtypes and alignment of B and C (a bf16 C is widened exactly and, with a bf16 B, read
+    by the engine as it is; an fp32 C is never rounded; with an fp32 B or an fp32 C: the fp32 result and one rounding pass).
     Differentiable: with grad mode on and A (its values), B or C requiring grad the call is an autograd node (_SpmmFunction) whose
     backward runs on the engine -- dB through the transposed (or, for transpose_a, the forward) product, dA through the SDDMM kernel on
-    A's pattern, dC = beta * G; out= is refused then, as by torch's own out= ops."""
+    A's pattern, dC = beta * G; out= is refused then, as by torch's own out= ops.  A bf16 upstream gradient feeds the dB product through
+    the bf16 entry point, and dB is written in bf16 directly when B is bf16."""
     if A.layout != torch.sparse_csr or not A.is_cuda or not B.is_cuda:
         raise TypeError("spmm expects a CUDA/HIP torch.sparse_csr matrix and a CUDA/HIP dense B")
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise TypeError("out_dtype must be None, torch.float32 or torch.bfloat16")
     if torch.is_grad_enabled() and (A.requires_grad or B.requires_grad or (C is not None and C.requires_grad)):
         if out is not None:
             raise RuntimeError("spmm(): functions with out=... arguments don't support automatic differentiation, but one of the "
                                "arguments requires grad")
-        return _SpmmFunction.apply(A, B, C, float(alpha), float(beta), bool(fast), bool(transpose_a))
-    return _forward(A, B, alpha, beta, C, out, fast, transpose_a)
+        return _SpmmFunction.apply(A, B, C, float(alpha), float(beta), bool(fast), bool(transpose_a), out_dtype)
+    return _forward(A, B, alpha, beta, C, out, fast, transpose_a, out_dtype)
 
 
-def _forward(A, B, alpha, beta, C, out, fast, transpose_a):
+def _forward(A, B, alpha, beta, C, out, fast, transpose_a, out_dtype=None):
     M, K = A.shape
     rows_b, rows_c = (M, K) if transpose_a else (K, M)
     if B.dim() != 2 or B.shape[0] != rows_b:
@@ -189,26 +203,44 @@ def _forward(A, B, alpha, beta, C, out, fast, transpose_a):
     Np = api.round_up_n(N)
     dev = A.device.index or 0
     eng = _engine_for(A, dev, fast)
-    Brm = _rowmajor(B, rows_b, N, Np)
-    if C is not None and beta != 0.0:
+    odt = torch.float32 if out_dtype is None else out_dtype
+    b16 = _qualifies(B, N, Np, torch.bfloat16)          # B as it lies, on the bf16 entry point
+    # dtype of the C buffers the engine works on: bf16 only where that rounds nothing but the result -- an fp32 C is never rounded before
+    # the product (it stays fp32 on the bf16 entry and the result is rounded once, below), so the bits do not depend on where B lies
+    c_given = C is not None and beta != 0.0
+    cdt = torch.bfloat16 if b16 and odt == torch.bfloat16 and (not c_given or C.dtype == torch.bfloat16) else torch.float32
+    Brm = B if b16 else _rowmajor(B, rows_b, N, Np)
+    if c_given:
         if tuple(C.shape) != (rows_c, N):
             raise ValueError("shape mismatch")
-        Cin = _rowmajor(C, rows_c, N, Np)
+        Cin = _rowmajor(C, rows_c, N, Np, cdt)
     else:
         Cin = None
-    if out is not None and (tuple(out.shape) != (rows_c, N) or _rowmajor(out, rows_c, N, Np) is not out):
-        raise ValueError("out must be an (M, N) fp32 row-major tensor with N % 8 == 0, 16-byte aligned")
-    Cout = out if out is not None else (Cin if (Cin is not None and Cin is not C) else None)
+    if out is not None and (tuple(out.shape) != (rows_c, N) or not _qualifies(out, N, Np, odt)):
+        raise ValueError("out must be an (M, N) %s row-major tensor with N %% 8 == 0, 16-byte aligned" % ("fp32" if odt == torch.float32 else "bf16"))
+    eng_out = out if cdt == odt else None               # (fp32 B or fp32 C with a bf16 out: the engine writes fp32, the rounding pass fills out)
+    Cout = eng_out if eng_out is not None else (Cin if (Cin is not None and Cin is not C) else None)
     if Cout is None:       # beta * C_in with C_in = 0 when no C is given: zeros, also for beta == 0 (0 * NaN would not be 0)
-        Cout = torch.zeros((rows_c, Np), dtype=torch.float32, device=B.device) if Cin is None else torch.empty((rows_c, Np), dtype=torch.float32, device=B.device)
+        Cout = torch.zeros((rows_c, Np), dtype=cdt, device=B.device) if Cin is None else torch.empty((rows_c, Np), dtype=cdt, device=B.device)
     if Cin is None:
-        if out is not None:
-            out.zero_()
+        if eng_out is not None:
+            eng_out.zero_()
         Cin = Cout
     stream = torch.cuda.current_stream(B.device).cuda_stream
-    call = eng.spmm_t_device_rm if transpose_a else eng.spmm_device_rm
-    call(Np, float(alpha), Brm.data_ptr(), Brm.stride(0), float(beta), Cin.data_ptr(), Cin.stride(0), Cout.data_ptr(), Cout.stride(0), stream)
-    return Cout if Np == N else Cout[:, :N]
+    if b16:
+        call = eng.spmm_t_device_rm_bf16 if transpose_a else eng.spmm_device_rm_bf16
+        call(Np, float(alpha), Brm.data_ptr(), Brm.stride(0), float(beta), Cin.data_ptr(), Cin.stride(0), Cout.data_ptr(), Cout.stride(0),
+             api.DTYPE_BF16 if cdt == torch.bfloat16 else api.DTYPE_F32, stream)
+    else:
+        call = eng.spmm_t_device_rm if transpose_a else eng.spmm_device_rm
+        call(Np, float(alpha), Brm.data_ptr(), Brm.stride(0), float(beta), Cin.data_ptr(), Cin.stride(0), Cout.data_ptr(), Cout.stride(0), stream)
+    res = Cout if Np == N else Cout[:, :N]
+    if cdt != odt:
+        if out is None:
+            return res.to(odt)
+        out.copy_(res)
+        return out
+    return res
 
 
 class _SpmmFunction(torch.autograd.Function):
@@ -220,8 +252,8 @@ class _SpmmFunction(torch.autograd.Function):
     and backward raises torch's version error.  Not twice differentiable."""
 
     @staticmethod
-    def forward(ctx, A, B, C, alpha, beta, fast, transpose_a):
-        out = _forward(A, B, alpha, beta, C, None, fast, transpose_a)
+    def forward(ctx, A, B, C, alpha, beta, fast, transpose_a, out_dtype=None):
+        out = _forward(A, B, alpha, beta, C, None, fast, transpose_a, out_dtype)
         ctx.save_for_backward(A.crow_indices(), A.col_indices(), A.values(), B)
         ctx.shape, ctx.alpha, ctx.beta, ctx.fast, ctx.transpose_a = tuple(A.shape), alpha, beta, fast, transpose_a
         ctx.dev = A.device.index or 0
@@ -237,14 +269,22 @@ class _SpmmFunction(torch.autograd.Function):
         eng = _engine_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast)
         stream = torch.cuda.current_stream(G.device).cuda_stream
         rows_b, rows_g = (M, K) if ctx.transpose_a else (K, M)
-        Grm = _rowmajor(G, rows_g, N, Np)      # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
         gA = gB = gC = None
         if ctx.needs_input_grad[1]:
-            out = torch.zeros((rows_b, Np), dtype=torch.float32, device=G.device)
-            call = eng.spmm_device_rm if ctx.transpose_a else eng.spmm_t_device_rm
-            call(Np, ctx.alpha, Grm.data_ptr(), Grm.stride(0), 0.0, out.data_ptr(), Np, out.data_ptr(), Np, stream)
+            if _qualifies(G, N, Np, torch.bfloat16):   # bf16 upstream gradient as it lies; dB in bf16 directly when B is bf16
+                odt = torch.bfloat16 if B.dtype == torch.bfloat16 else torch.float32
+                out = torch.zeros((rows_b, Np), dtype=odt, device=G.device)
+                call = eng.spmm_device_rm_bf16 if ctx.transpose_a else eng.spmm_t_device_rm_bf16
+                call(Np, ctx.alpha, G.data_ptr(), G.stride(0), 0.0, out.data_ptr(), Np, out.data_ptr(), Np,
+                     api.DTYPE_BF16 if odt == torch.bfloat16 else api.DTYPE_F32, stream)
+            else:
+                Grm = _rowmajor(G, rows_g, N, Np)      # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
+                out = torch.zeros((rows_b, Np), dtype=torch.float32, device=G.device)
+                call = eng.spmm_device_rm if ctx.transpose_a else eng.spmm_t_device_rm
+                call(Np, ctx.alpha, Grm.data_ptr(), Grm.stride(0), 0.0, out.data_ptr(), Np, out.data_ptr(), Np, stream)
             gB = (out if Np == N else out[:, :N]).to(B.dtype)
         if ctx.needs_input_grad[0]:
+            Grm = _rowmajor(G, rows_g, N, Np)          # (the SDDMM kernel reads fp32)
             Brm = _rowmajor(B, rows_b, N, Np)  # (zero padding adds +0 products: +0 + +0 keeps every sum's bits)
             X, Y = (Brm, Grm) if ctx.transpose_a else (Grm, Brm)
             vals = torch.empty((val.numel(),), dtype=torch.float32, device=G.device)
@@ -253,4 +293,4 @@ class _SpmmFunction(torch.autograd.Function):
             gA = torch.sparse_csr_tensor(crow, col, vals.to(val.dtype), size=(M, K))
         if ctx.needs_input_grad[2]:
             gC = G * ctx.beta if ctx.beta != 0.0 else torch.zeros_like(G)
-        return gA, gB, gC, None, None, None, None
+        return gA, gB, gC, None, None, None, None, None
