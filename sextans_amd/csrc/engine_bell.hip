@@ -7,6 +7,7 @@
 #include <thread>
 
 #include "bell_kernels.h"
+#include "dispatch.h"
 #include "engine_state.h"
 #include "rowblock_mfma_kernel.h"
 
@@ -201,18 +202,16 @@ int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const floa
         const float *bp = h->d_Bp + (size_t)h->K * (size_t)g.col0;
         const float *cin = d_C_in + (int64_t)g.col0 * ldc_in;
         float *cout = d_C_out + (int64_t)g.col0 * ldc;
-        auto go = [&](auto kern, int NT) {
+        auto go = [&](auto T) {
+            constexpr int NT = decltype(T)::value;
             const int tgs = (tiles16 + NT - 1) / NT;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((h->sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, s, h->d_rb_row0, h->d_rb_gptr, h->d_sb_uptr,
+            hipLaunchKernelGGL(sx::spmm_rowblock_mfma_f32<NT>, dim3((unsigned)((h->sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, s, h->d_rb_row0, h->d_rb_gptr, h->d_sb_uptr,
                                (const int2 *)h->d_sb_ucol, h->d_rb_A, bp, (int64_t)h->K * g.width, g.width, h->K, cin, ldc_in, cout, ldc, h->rb_n, h->sb_n,
                                tgs, ncols_panel, ncols, row_begin, row_end, alpha, beta);
         };
         // (a wavefront owns 64 rows x 16 NT columns of C: 16 NT accumulator registers.  NT = 2 = 4 wavefronts per SIMD measured 2 - 4 % ahead of
         // NT = 4 = 2 per SIMD on the dense-block matrix at N = 64 .. 256 -- occupancy over B-fragment reuse; "rowblock_tiles" forces 1 / 4)
-        if (tiles16 >= 4 && h->opt_rb_tiles == 4) go(sx::spmm_rowblock_mfma_f32<4>, 4);
-        else if (h->opt_rb_tiles == 1) go(sx::spmm_rowblock_mfma_f32<1>, 1);
-        else if (tiles16 >= 2) go(sx::spmm_rowblock_mfma_f32<2>, 2);
-        else go(sx::spmm_rowblock_mfma_f32<1>, 1);
+        with_value<4, 2, 1>(tiles16 >= 4 && h->opt_rb_tiles == 4 ? 4 : h->opt_rb_tiles != 1 && tiles16 >= 2 ? 2 : 1, go);
     }
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
@@ -379,6 +378,16 @@ int ensure_dense(sextans_engine *h) {
     return SEXTANS_OK;
 }
 
+// One wavefront per block row and group of NSUB column tiles: as many tiles per wavefront (4, 2 or 1) as divide their number
+static void launch_bell_mfma(const int *col, const sx::bf16x8 *Af, const sx::bf16x8 *Bf, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, int mblocks,
+                      int W, int ntiles, float alpha, float beta, hipStream_t s) {
+    with_value<4, 2, 1>(ntiles % 4 == 0 ? 4 : ntiles % 2 == 0 ? 2 : 1, [&](auto NS) {
+        constexpr int NSUB = decltype(NS)::value;
+        const int64_t waves = (int64_t)mblocks * (ntiles / NSUB);
+        hipLaunchKernelGGL((sx::spmm_bell_mfma<NSUB>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, W, ntiles, alpha, beta);
+    });
+}
+
 int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
                        int64_t ldc_in, float *d_C_out, int64_t ldc, hipStream_t s) {
         const int kblocks = (h->K + 31) / 32, ntiles = N / 32;
@@ -387,12 +396,6 @@ int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, 
                            (sx::u32x4 *)h->d_bell_Bf, kblocks, ntiles);
         const auto *Af = (const sx::bf16x8 *)h->d_dense_Af;
         const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf;
-#define SX_BELL(NSUB)                                                                                               \
-    {                                                                                                               \
-        const int64_t waves = (int64_t)h->dense_mb * (ntiles / NSUB);                                               \
-        hipLaunchKernelGGL((sx::spmm_bell_mfma<NSUB>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, h->d_dense_col, \
-                           Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense_mb, h->dense_W, ntiles, alpha, beta);            \
-    }
         const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->dense_W <= sx::kShMaxRowCols &&
                             h->dense_max_union <= sx::kShMaxUnion && (h->opt_bell_shared == 1 || h->dense_share >= 1.5);
         if (shared) {
@@ -402,8 +405,9 @@ int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, 
             hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((h->dense_mb + sx::kShRows - 1) / sx::kShRows)),
                                dim3(sx::kShThreads), lds, s, h->d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense_mb, h->dense_W,
                                alpha, beta, 0);
-        } else if (ntiles % 4 == 0) SX_BELL(4) else if (ntiles % 2 == 0) SX_BELL(2) else SX_BELL(1)
-#undef SX_BELL
+        } else {
+            launch_bell_mfma(h->d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense_mb, h->dense_W, ntiles, alpha, beta, s);
+        }
         const int row0 = h->dense_mb * 32;
         if (row0 < h->M) {
             const int64_t tot = (int64_t)(h->M - row0) * N;
@@ -502,13 +506,6 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
         Prof p(h, &h->ev_kernel, s);
         const auto *Af = (const sx::bf16x8 *)h->d_bell_Af;
         const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf;
-#define SX_BELL(NSUB)                                                                                  \
-    {                                                                                                  \
-        const int64_t waves = (int64_t)mblocks * (ntiles / NSUB);                                      \
-        hipLaunchKernelGGL((sx::spmm_bell_mfma<NSUB>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, \
-                           h->d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell_W, ntiles,    \
-                           alpha, beta);                                                                      \
-    }
         const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->bell_W <= sx::kShMaxRowCols &&
                             h->bell_max_union <= sx::kShMaxUnion &&
                             (h->opt_bell_shared == 1 || h->bell_share >= 1.5);
@@ -530,8 +527,9 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
                 hipLaunchKernelGGL(sx::spmm_bell_mfma_n256, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->d_bell_col, Af,
                                    Bf, d_C_in, ldc_in, d_C_out, ldc, std::min(mblocks, b0 + nb), h->bell_W, alpha, beta, b0);
             }
-        } else if (ntiles % 4 == 0) SX_BELL(4) else if (ntiles % 2 == 0) SX_BELL(2) else SX_BELL(1)
-#undef SX_BELL
+        } else {
+            launch_bell_mfma(h->d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell_W, ntiles, alpha, beta, s);
+        }
         h->last_kernel = "spmm_bell_mfma";
     }
     SX_HIP(hipGetLastError());

@@ -10,9 +10,65 @@
 #include <cstring>
 #include <mutex>
 
-#include "engine_state.h"
+#include "engine_launch.h"
 
 using namespace sxe;
+
+namespace sxe {
+// ---- clustered-order chunks of the row-partitioned SpMM (sextans_dist_spmm with nchunks > 1) ------------------------------------
+// A rank whose slab runs on a graph-clustered plan used to lose it as soon as the slab was cut into chunks for the all-gather
+// pipeline: a row-range call needs consecutive rows, and the clustered plan has none.  Here a chunk is a range of the plan's ROW
+// BLOCKS; its rows are the positions [p0, p1) of the clustered order, and everything the chunk moves is addressed by position:
+//   cc_pre      (first chunk) B into the permuted panels, the slab of C_in into the natural row-major staging buffer (streaming passes);
+//   cc_chunk    C_in rows of the chunk gathered, 64 bytes each, into the chunk's packed slab [tile][position][16] -- which IS the
+//               rank's slot of the all-gather buffer -- then spmm_csr_panel_v2<..., CROW> over the chunk's blocks, in place;
+//   cc_scatter  (every rank, behind the all-gather) rows of a received slab to their places in a row-major staging buffer of the
+//               WHOLE C through the sender's position -> row table (launch_slab_rows);
+//   cc_finish   one streaming pass staging -> column-major C (launch_tiles_to_colmajor).
+namespace {
+__global__ __launch_bounds__(256) void position_rows(int nblk, int RB, const int *__restrict__ blk_row, const int *__restrict__ slot_row, int row0, int *__restrict__ out) {
+    const int b = blockIdx.x, s = threadIdx.x;
+    if (b >= nblk || s >= RB) return;
+    const int p0 = blk_row[b], n = blk_row[b + 1] - p0;
+    if (s < n) out[p0 + s] = slot_row[(int64_t)b * RB + s] + row0;
+}
+}  // namespace
+
+static bool cc_usable(sextans_engine *h, int N, const Tiling &t) {
+    return h->cluster_state == 2 && h->cluster_cm_pays && t.W == 16 && N % 16 == 0 && t.segs.size() == 1 && t.segs[0].width == 16 && h->nhub == 0 &&
+           h->nchain == 0 && csr_only(h) && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->d_Cs && h->d_slot_row &&
+           h->Cs_cap >= (size_t)(N / 16) * (size_t)h->M * 16 && h->Bp_cap >= (size_t)h->K * (size_t)N && h->psc.plan_sets == 1 &&
+           (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)) && (int)h->psc.h_blk_row.size() == h->psc.plan_nblk + 1;
+}
+void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s) {
+    const int slots = kBlock / 4 * std::max(1, h->psc.plan_sets);   // (grid-brick plans of short-row matrices: two row sets per block)
+    hipLaunchKernelGGL(position_rows, dim3((unsigned)h->psc.plan_nblk), dim3((unsigned)slots), 0, s, h->psc.plan_nblk, slots, h->psc.d_blk_row, h->d_slot_row, row0, d_out);
+}
+static void cc_pre(sextans_engine *h, int N, const float *d_B, int64_t ldb, const float *d_C_in_slab, int64_t ldc_in, hipStream_t s) {
+    Prof p(h, &h->ev_repack, s);
+    if (h->d_colpos) launch_repack_perm(h, d_B, ldb, h->d_Bp, 0, N / 16, N, s);
+    else launch_repack(16, d_B, ldb, h->d_Bp, h->K, 0, N / 16, s, h->col_lo, h->col_hi, -1, h->d_touched);
+    launch_repack(16, d_C_in_slab, ldc_in, h->d_Cs, h->M, 0, N / 16, s);
+    h->bp_layout = -16;
+}
+static int cc_chunk(sextans_engine *h, int N, float alpha, float beta, int b0, int b1, const int *d_rows, int row0, float *slab, int64_t lmax, hipStream_t s) {
+    const int p0 = h->psc.h_blk_row[(size_t)b0], p1 = h->psc.h_blk_row[(size_t)b1];
+    if (p1 <= p0) return SEXTANS_OK;
+    Prof p(h, &h->ev_kernel, s);
+    launch_slab_rows(false, h->d_Cs, (int64_t)h->M * 16, d_rows + p0, row0, p1 - p0, slab, lmax * 16, N / 16, s);
+    float *base = slab - (int64_t)p0 * 16;     // position p of the clustered order -> slab row p - p0
+    if (int rc = launch_panel_v2(h, 1, h->d_Bp, base, lmax * 16, base, lmax * 16, N / 16, alpha, beta, s, 0, b0, b1, 0, 3)) return rc;
+    h->last_kernel = "spmm_csr_panel_v2_reordered";
+    return SEXTANS_OK;
+}
+static int cc_prepare(sextans_engine *h, int N, bool *ok) {
+    Tiling t;
+    *ok = false;
+    if (int rc = prepare(h, N, true, &t)) return rc;
+    *ok = cc_usable(h, N, t);
+    return SEXTANS_OK;
+}
+}  // namespace sxe
 
 namespace {
 struct Id128 { char b[128]; };   // ncclUniqueId, passed to ncclCommInitRank BY VALUE
@@ -191,7 +247,7 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     if (nchunks > 16) nchunks = 16;
     if (int rc = exchange_nnz(h, r, comm, world, rank, row_ranges, force, st, s, &exchanged)) return rc;
     // Clustered-order chunks (round 5): when this rank's slab runs on a graph-clustered plan, chunks are ranges of the plan's row
-    // BLOCKS and every chunk keeps the reordered form (engine.hip: cc_*) -- if every rank of the partition can do the same.
+    // BLOCKS and every chunk keeps the reordered form (cc_* above) -- if every rank of the partition can do the same.
     bool want_cc = false;
     if (nchunks > 1) {
         st = cc_prepare(h, N, &want_cc);
@@ -476,16 +532,16 @@ int sextans_dist_spmm(sextans_handle_t h, void *comm, int world, int rank, const
                                                  h->comm_stream), "ncclAllGather"))
                 return rc;
         if (cc) {   // slabs hold rows in the senders' clustered order: 64-byte rows to their places in the staging buffer of the whole C
-            for (int g = 0; g < world; ++g)
-                cc_scatter(S + (size_t)g * N * lmax[(size_t)c], lmax[(size_t)c], h->d_dist_rows + (size_t)g * m_max + cut(g, c), cut(g, c + 1) - cut(g, c),
-                           h->d_Cfull, M_total * 16, N, h->comm_stream);
+            for (int g = 0; g < world; ++g)   // cc_scatter
+                launch_slab_rows(true, h->d_Cfull, M_total * 16, h->d_dist_rows + (size_t)g * m_max + cut(g, c), 0, cut(g, c + 1) - cut(g, c),
+                                 S + (size_t)g * N * lmax[(size_t)c], lmax[(size_t)c] * 16, N / 16, h->comm_stream);
             continue;
         }
         const unsigned gx = (unsigned)((lmax[(size_t)c] + 255) / 256);
         hipLaunchKernelGGL(dist_unpack_slabs, dim3(gx, (unsigned)N, (unsigned)world), dim3(256), 0, h->comm_stream, S,
                            lmax[(size_t)c], N, reinterpret_cast<const int2 *>(d_meta) + (size_t)c * world, d_C_out, ldc);
     }
-    if (cc) cc_finish(h->d_Cfull, d_C_out, ldc, (int)M_total, N, h->comm_stream);
+    if (cc) launch_tiles_to_colmajor(h->d_Cfull, d_C_out, ldc, (int)M_total, 0, N / 16, N, h->comm_stream);   // cc_finish
     SX_HIP(hipEventRecord(h->dist_events[(size_t)nchunks], h->comm_stream));
     SX_HIP(hipStreamWaitEvent(s, h->dist_events[(size_t)nchunks], 0));
     SX_HIP(hipGetLastError());

@@ -368,7 +368,7 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
     h->ps.plan_pad_row = cap;
     h->ps.plan_built = true;
     if (lpr == 4) h->plan_total_dict = dp.total_dict;
-    if (h->ps.plan_mixed && lpr == 4 && h->ps.plan_nblk > 0) {   // the split form of a mixed plan (engine.hip: split_mixed)
+    if (h->ps.plan_mixed && lpr == 4 && h->ps.plan_nblk > 0) {   // the split form of a mixed plan (engine_spmm.hip: kSplitMixed)
         (void)hipFree(h->ps.d_rg_skip); h->ps.d_rg_skip = nullptr;
         if (hipMalloc((void **)&h->ps.d_rg_skip, (size_t)std::max(h->M, 1)) == hipSuccess) {
             hipLaunchKernelGGL(mixed_row_flags, dim3((unsigned)h->ps.plan_nblk), dim3(256), 0, nullptr, h->ps.plan_nblk, h->ps.d_blk_row, h->ps.d_dict_ptr,

@@ -1,10 +1,14 @@
 // engine_state.h -- the engine object behind the C ABI (include/sextans_amd.h) and what its translation units share:
-//   engine.hip        handles, options, matrices, the SpMM dispatcher (sextans_spmm_device_rows), host-buffer entry points
-//   engine_plan.hip   everything prepared once per matrix, outside every timed region: long-row split, packed panel plans
-//                     (natural / clustered / reordered), window stream -- the analogue of the reference's host-side scheduling
-//                     and packing (sextans-host.cpp:114-148)
-//   engine_bell.hip   blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
-//   engine_dist.hip   native multi-GPU entry (RCCL all-gather of C slabs)
+//   engine.hip          handles, the option table, matrices, stats, plan / row-order export, profiling reads, sextans_device_*
+//   engine_spmm.hip     the column-major SpMM entry (sextans_spmm_device_rows): route_cm decides, run_* launch
+//   engine_rowmajor.hip the row-major entries (sextans_spmm_device_rm, its bf16 form), sextans_prepare and rm_plan
+//   engine_host.hip     host-buffer and reference-shaped entry points (sextans_spmm_host, sextans_invoke, sextans_spmm_csr)
+//   engine_launch.hip   every launch of an SpMM kernel (engine_launch.h): the only unit that instantiates them (dispatch.h)
+//   engine_plan.hip     everything prepared once per matrix, outside every timed region: long-row split, packed panel plans
+//                       (natural / clustered / reordered), window stream -- the analogue of the reference's host-side scheduling
+//                       and packing (sextans-host.cpp:114-148)
+//   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
+//   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
 // Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +50,11 @@ struct Tiling {                  // what prepare() decided for an N-column call
     int W = 0;                   // main tile width: the packed plan is built for it
     bool panel = false;          // the LDS-panel plan serves the main rows
     bool window = false;         // ... or the K-window kernel
+};
+// One SpMM as the caller asked for it: operands, row range [row_begin, row_end) (whole: all of the matrix), flags, stream
+struct Call {
+    int N; float alpha; const float *B; int64_t ldb; float beta; const float *C_in; int64_t ldc_in; float *C_out; int64_t ldc;
+    int row_begin, row_end, flags; hipStream_t s; bool whole;
 };
 }  // namespace sxe
 
@@ -369,16 +378,13 @@ int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const floa
                      int row_end, float alpha, float beta, hipStream_t s);
 int mark_rowblock_skip(sextans_engine *h);   // after ensure_split: the routed rows join the rows the CSR kernels never write
 
-// clustered-order chunks of sextans_dist_spmm (engine.hip)
-int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out = nullptr);   // planning half of sextans_spmm_device_rm
-// argument checks of the bf16 row-major entry points (engine.hip): SEXTANS_ERR_INVALID or SEXTANS_OK, nothing touched
+int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out = nullptr);   // engine_rowmajor.hip: planning half of sextans_spmm_device_rm
+// argument checks of the bf16 row-major entry points (engine_rowmajor.hip): SEXTANS_ERR_INVALID or SEXTANS_OK, nothing touched
 int check_rm_bf16_args(sextans_handle_t h, int N, const uint16_t *d_B, int64_t ldb, const void *d_C_in, int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype);
-int cc_prepare(sextans_engine *h, int N, bool *ok);
+// engine_spmm.hip: the exact chains [ch0, ch1) of a call on the engine's side stream, beside its main kernel (rm: from the caller's row-major B)
+int fork_chains(sextans_engine *h, const Call &c, const std::vector<Seg> &segs, int ch0, int ch1, bool rm);
+// engine_dist.hip: position -> row table of the clustered plan (+ row0), also what sextans_export_row_order reads
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s);
-void cc_pre(sextans_engine *h, int N, const float *d_B, int64_t ldb, const float *d_C_in_slab, int64_t ldc_in, hipStream_t s);
-int cc_chunk(sextans_engine *h, int N, float alpha, float beta, int b0, int b1, const int *d_rows, int row0, float *slab, int64_t lmax, hipStream_t s);
-void cc_scatter(const float *slab, int64_t lmax, const int *d_rows, int n, float *tiles, int64_t tile_stride, int N, hipStream_t s);
-void cc_finish(const float *tiles, float *C, int64_t ldc, int M_total, int N, hipStream_t s);
 
 template <class T>
 int upload(T **dst, const std::vector<T> &src) {

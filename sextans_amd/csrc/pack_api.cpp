@@ -15,7 +15,7 @@ template <class T> T *dup(const std::vector<T> &v) {
     if (p && !v.empty()) memcpy(p, v.data(), sizeof(T) * v.size());
     return p;
 }
-constexpr int kPanelBytes = 36 * 1024;   // must match kPanelFloats * 4 in engine.hip
+constexpr int kPanelBytes = 36 * 1024;   // must match kPanelFloats * 4 in engine_state.h
 }  // namespace
 
 extern "C" {

@@ -2,7 +2,7 @@
 //
 // hipMemcpy / hipMemset wait on the process-wide legacy stream, and HIP fails them -- in EVERY host thread -- while ANY stream of the
 // device is being captured into a hipGraph ("operation would make the legacy stream depend on a capturing blocking stream"), and
-// invalidates that capture on top.  The host-buffer entry points capture their rp_time loop (engine.hip: run_repeats), the one-time
+// invalidates that capture on top.  The host-buffer entry points capture their rp_time loop (engine_host.hip: run_repeats), the one-time
 // plan builders copy small tables back and forth: two engines used by two host threads (re-entrant per handle; the
 // thread-per-GPU model of examples/dist_spmm.cpp) broke each other.  Found by tests/test_concurrency_gpu.py in round 5;
 // tools/capture_race.py reproduces it.  Inside the library a "synchronous" copy is therefore an asynchronous copy on the calling

@@ -1,7 +1,7 @@
 """Registers / scratch / occupancy of every kernel of one translation unit, from hipcc's own resource-usage remarks
 (the same figures the code-object notes carry):
 
-    python tools/kernel_resources.py sextans_amd/csrc/engine.hip [--spills] [--grep panel_v2] > profiles/r05_kernel_resources_engine.txt
+    python tools/kernel_resources.py sextans_amd/csrc/engine_launch.hip [--spills] [--grep panel_v2] > profiles/r05_kernel_resources_engine.txt
 
 Compiles for gfx950 with the flags of sextans_amd/build.py (no GPU needed)."""
 import re
