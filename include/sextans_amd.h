@@ -437,7 +437,7 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
 #define SEXTANS_LAYOUT_COLMAJOR 0
 #define SEXTANS_LAYOUT_ROWMAJOR 1
 /* SEXTANS_LAYOUT_ROWMAJOR_T: the backward-pass forms -- A^T (sextans_csr_transpose_device) and everything the row-major calls of
- * sextans_spmm_t_device_rm build (plans, workspaces) on the companion engine, and the row table of sextans_sddmm_device_rm.  After it, a transposed call for N and an SDDMM call allocate nothing
+ * sextans_spmm_t_device_rm build (plans, workspaces) on the companion engine, the row table of sextans_sddmm_device_rm and the tables of sextans_row_softmax_device.  After it, a transposed call for N, an SDDMM call and a row-softmax call allocate nothing
  * and do not synchronise with the host: they may be captured into a hipGraph.  (Layout 2 is unused.) */
 #define SEXTANS_LAYOUT_ROWMAJOR_T 3
 int sextans_prepare(sextans_handle_t h, int N, int layout, void *stream);
@@ -505,6 +505,36 @@ int sextans_spmm_t_device_rm(sextans_handle_t h, int N, float alpha, const float
  * sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) builds it ahead, with the transposed form. */
 int sextans_sddmm_device_rm(sextans_handle_t h, int N, float alpha, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, float beta,
                             const float *d_vals_in, float *d_vals_out, void *stream);
+
+/* ---- Row softmax on A's pattern (the step between the SDDMM and the SpMM of attention over a fixed sparsity pattern: graph attention,
+ * sparse / sliding-window attention).  Closest thing in the reference: none -- its PEs only multiply and accumulate.
+ *
+ * For the CSR matrix set on h, for every row r with stored entries e in [row_ptr[r], row_ptr[r + 1]), in the entry order it was set with:
+ *     forward    s_e = scale * x_e;   m = max_e s_e;   t_e = exp(s_e - m);   Z = sum_e t_e;   p_e = t_e / Z
+ *     backward   d = sum_e p_e * g_e;   dx_e = scale * p_e * (g_e - d)
+ * in fp32: every product and difference rounded once, exp as exp2 of a rounded product, the sums as fixed trees (at most 32 consecutive
+ * adds per lane, then cross-lane butterflies; long rows: per-chunk partial results combined in a fixed order), p_e = t_e * (1 / Z).  The
+ * same arithmetic in SEXTANS_MODE_STRICT and SEXTANS_MODE_FAST; no float atomics: the same call gives the same bits on every run and
+ * every stream.  Special values as torch.softmax over the row's stored entries: a -inf entry beside finite ones gives exactly +0.0f; a
+ * row of only -inf, a +inf or a NaN gives NaN for the whole row; an empty row does nothing; a row of one finite entry gives exactly
+ * 1.0f (backward: dx = +-0).  A's VALUES are not read: only its pattern.
+ * d_x, d_p, d_g, d_dx: nnz floats each in the CSR entry order of the matrix as set -- the order sextans_sddmm_device_rm writes and
+ * sextans_update_values_device reads, so SDDMM -> softmax -> value refresh -> SpMM chain without a permutation.  16-byte aligned.
+ * Aliasing: d_p may be d_x (in place); d_dx may be d_g or d_p; any other overlap is undefined.
+ * Work is split by non-zeros (a wavefront owns whole rows of about 256 entries in all; a row stays in registers between the max, the
+ * sum and the normalisation: 8 bytes of traffic per non-zero forward, 12 backward); rows longer than 2048 entries take a long-row path
+ * (2048-entry chunks on a wavefront each, partial results in a workspace, one more read of those rows).  The first call on a matrix
+ * validates it (matrices set with sextans_set_matrix_csr_device), builds the tables (nnz / 64 bytes + 24 bytes per long-row chunk, in
+ * stat "device_bytes") and synchronises; sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) builds them ahead.  After either, a
+ * call allocates nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.  The tables depend on the
+ * pattern alone: sextans_update_values* leaves them, sextans_set_matrix_* drops them.  Calls on one handle share the long-row
+ * workspace: run them on one stream, or order them.
+ * sextans_last_kernel: "row_softmax" / "row_softmax_backward", "+long_rows" appended when the long-row path ran; stat
+ * "softmax_long_rows": rows on it (0 before the tables exist).
+ * SEXTANS_ERR_INVALID: h == NULL, a misaligned pointer, a NULL pointer with nnz > 0; SEXTANS_ERR_STATE: no CSR matrix set (the
+ * blocked-ELL bf16 matrix is not covered); nnz == 0 or M == 0: OK, nothing to do. */
+int sextans_row_softmax_device(sextans_handle_t h, float scale, const float *d_x, float *d_p, void *stream);
+int sextans_row_softmax_backward_device(sextans_handle_t h, float scale, const float *d_p, const float *d_g, float *d_dx, void *stream);
 
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *

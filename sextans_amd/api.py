@@ -70,7 +70,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_prepare", "sextans_dist_prepare", "sextans_dist_bind_library", "sextans_device_alloc", "sextans_device_copy",
     "sextans_csr_transpose_device", "sextans_spmm_t_device_rm", "sextans_sddmm_device_rm",
     "sextans_update_values", "sextans_update_values_device",
-    "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16"))
+    "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16",
+    "sextans_row_softmax_device", "sextans_row_softmax_backward_device"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 
@@ -263,6 +264,8 @@ def lib():
     L.sextans_spmm_device_rm_bf16.argtypes = L.sextans_spmm_t_device_rm_bf16.argtypes = [
         C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.sextans_prepare_rm_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.sextans_row_softmax_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sextans_row_softmax_backward_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -758,6 +761,15 @@ class Engine:
         reference's rounding (sextans_sddmm_device_rm); d_vals_in may be None."""
         _check(lib().sextans_sddmm_device_rm(self._h, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream),
                "sddmm_device_rm")
+
+    def row_softmax_device(self, scale, d_x, d_p, stream=None):
+        """p = softmax(scale * x) over the stored entries of every row of A (sextans_row_softmax_device): nnz floats each, in CSR entry
+        order -- what sddmm_device_rm writes and update_values_device reads; d_p may be d_x."""
+        _check(lib().sextans_row_softmax_device(self._h, scale, d_x, d_p, stream), "row_softmax_device")
+
+    def row_softmax_backward_device(self, scale, d_p, d_g, d_dx, stream=None):
+        """dx = scale * p * (g - sum_row p g) (sextans_row_softmax_backward_device); d_dx may be d_g or d_p."""
+        _check(lib().sextans_row_softmax_backward_device(self._h, scale, d_p, d_g, d_dx, stream), "row_softmax_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -387,6 +387,7 @@ int sextans_get_stat(sextans_handle_t h, const char *key, double *value) {
     else if (!strcmp(key, "row_coherence")) *value = h->row_coherence;
     else if (!strcmp(key, "panel_blocks_clustered")) *value = (double)h->psc.plan_nblk;
     else if (!strcmp(key, "device_bytes")) *value = (double)device_bytes(h);
+    else if (!strcmp(key, "softmax_long_rows")) *value = (double)h->sm_long_rows;                  // rows on the long-row path of sextans_row_softmax*_device
     else if (!strcmp(key, "value_refreshes")) *value = (double)h->value_refreshes;                  // sextans_update_values* served on this matrix
     else if (!strcmp(key, "value_refresh_rebuilt")) *value = (double)h->value_refresh_rebuilt;      //   ... that dropped a form for a lazy rebuild
     else if (!strcmp(key, "bf16_native_calls")) *value = (double)(h->bf16_native_calls + (h->tr ? h->tr->bf16_native_calls : 0));            // bf16 calls (transposed ones included) on the caller's buffers

@@ -100,6 +100,7 @@ int64_t device_bytes(const sextans_engine *h) {
     b += (int64_t)h->bell_Bf_cap;
     if (h->tr) b += ((int64_t)h->K + 1) * 4 + h->nnz * 8 + (h->d_tperm ? h->nnz * 4 : 0) + device_bytes(h->tr);   // A^T, its entry permutation, its companion's plans and workspaces
     b += h->sddmm_row0_n * 4;
+    b += h->sm_wrow_n * 4 + (int64_t)h->sm_nchunks * 24;   // row softmax: wavefront rows, long-row chunk table + partials + per-row results
     b += 4 * (int64_t)(h->Bp_cap + h->B_cap + (h->d_Cin ? h->C_cap : 0) + h->C_cap + h->P_cap + h->stage_cap + h->chB_cap + h->chC_cap + h->Cs_cap + h->rmB_cap + h->rmC_cap + h->bfB_cap + h->bfC_cap + h->Cfull_cap + h->dist_rows_cap);
     return b;
 }

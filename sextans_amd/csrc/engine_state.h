@@ -7,6 +7,7 @@
 //   engine_plan.hip     everything prepared once per matrix, outside every timed region: long-row split, packed panel plans
 //                       (natural / clustered / reordered), window stream -- the analogue of the reference's host-side scheduling
 //                       and packing (sextans-host.cpp:114-148)
+//   engine_softmax.hip  row softmax on A's pattern, forward and backward (sextans_row_softmax_device, ..._backward_device)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
 // Not a public header.
@@ -334,6 +335,12 @@ struct sextans_engine {
     double transpose_build_s = 0.0;     // seconds spent transposing A (the companion's plans: its own plan_build_s)
     int *d_sddmm_row0 = nullptr;        // sextans_sddmm_device_rm: row of the first entry of every 256-entry wavefront range (+ M - 1 at the end)
     int64_t sddmm_row0_n = 0;           // ints in it
+    // row softmax on the pattern (engine_softmax.hip, row_softmax_kernels.h): built once per matrix from row_ptr alone, dropped with the matrix
+    int *d_sm_wrow = nullptr;           // first row of every wavefront (+ M at the end)
+    int64_t sm_wrow_n = 0;              // ints in it (0 = not built)
+    int2 *d_sm_tab = nullptr;           // long rows: {row, chunk of the row} per 2048-entry chunk
+    float2 *d_sm_part = nullptr;        //   ... and the workspace of per-chunk partial results
+    int sm_nchunks = 0, sm_long_rows = 0;
 };
 
 namespace sxe {
@@ -350,6 +357,9 @@ void free_split(sextans_engine *h);
 void free_dense(sextans_engine *h);
 void free_matrix(sextans_engine *h);
 void free_backward(sextans_engine *h);                     // engine_transpose.hip: A^T, its companion and the SDDMM row table
+int validate_matrix(sextans_engine *h);                    // engine_transpose.hip: row_ptr / columns of a caller-provided device matrix, once
+void free_softmax(sextans_engine *h);                      // engine_softmax.hip: the row-softmax tables and workspace
+int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)
 int transposed_options(sextans_engine *h, const char *key, int64_t value);   // engine.hip: one option (nullptr: all) onto the companion
 int ensure(float **p, size_t *cap, size_t need);

@@ -26,9 +26,8 @@ void free_backward(sextans_engine *h) {
     (void)hipFree(h->d_sddmm_row0);
     h->d_sddmm_row0 = nullptr;
     h->sddmm_row0_n = 0;
+    free_softmax(h);
 }
-
-namespace {
 
 int validate_matrix(sextans_engine *h) {   // a device matrix nobody has looked at yet: its indices address X / Y rows and A^T's row pointer
     if (h->owns_matrix || h->device_matrix_checked || h->M == 0) return SEXTANS_OK;
@@ -39,6 +38,8 @@ int validate_matrix(sextans_engine *h) {   // a device matrix nobody has looked 
     h->device_matrix_checked = true;
     return SEXTANS_OK;
 }
+
+namespace {
 
 // A^T and its companion engine, once per matrix (the values are those of this moment; sextans_update_values* brings newer ones through d_tperm)
 int ensure_transpose(sextans_engine *h, hipStream_t s) {
@@ -95,6 +96,7 @@ int ensure_sddmm_rows(sextans_engine *h, hipStream_t s) {
 
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s) {
     if (int rc = ensure_sddmm_rows(h, s)) return rc;
+    if (int rc = ensure_softmax_tables(h, s)) return rc;
     SX_HIP(hipStreamSynchronize(s));
     if (h->K == 0) return SEXTANS_OK;
     if (int rc = ensure_transpose(h, s)) return rc;

@@ -11,8 +11,19 @@ over C per call.)  N that is not a multiple of 8 is padded up internally (the re
 sparsity pattern (keyed on the index tensors' addresses, their contents re-checked when their version counters move; the entry pins the tensors, at most 8 kept, clear_cache()
 drops them); new VALUES on a cached pattern are a refresh of the engine's copies, not a new engine (refresh(), cache_info()); not part
 of the reference, whose only front end is the CLI.
+
+Attention over a fixed sparsity pattern (graph attention, sparse / sliding-window attention) on the same cached engine:
+
+    S = sddmm(A, X, Y, alpha=1.0, beta=0.0)        S_e = alpha * <X[r, :], Y[c, :]> + beta * A_e on A's pattern
+    P = row_softmax(S, scale=1.0)                  softmax over every row's stored entries
+    O = sparse_attention(A, Q, K, V, scale=None, bias=False)  = spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V)
+
+S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
+other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
 """
 import collections
+import math
+import weakref
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -78,8 +89,29 @@ def cache_info():
     return {"engines_built": _counters["engines_built"], "value_refreshes": _counters["value_refreshes"], "entries": len(_cache)}
 
 
+_carried = {}   # id(T) -> (weak reference to T, A's crow, A's col, T's index version counters): sparse results of the ops below
+
+
+def _carry(T, crow, col):
+    """Remember that the sparse tensor T was built on (crow, col), the index tensors a cache entry remembers.  The index members of a
+    newly built sparse tensor have version counters of their own, which say nothing to the cache: it would fall back to the
+    fingerprint (a read-back) on every call of a pipeline.  The ops look the remembered tensors up by T's identity instead."""
+    key = id(T)
+    _carried[key] = (weakref.ref(T, lambda _, key=key: _carried.pop(key, None)), crow, col, (_ver(T.crow_indices()), _ver(T.col_indices())))
+    return T
+
+
+def _index_tensors(A):
+    """A's index tensors -- for a result of sddmm() / row_softmax() that nobody has written to since, the ones it was built on."""
+    c = _carried.get(id(A))
+    if c is not None and c[0]() is A and None not in c[3] and (_ver(A.crow_indices()), _ver(A.col_indices())) == c[3]:
+        return c[1], c[2]
+    return A.crow_indices(), A.col_indices()
+
+
 def _engine_for(A, dev, fast=False):
-    return _engine_for_parts(A.crow_indices(), A.col_indices(), A.values(), tuple(A.shape), dev, fast)
+    crow, col = _index_tensors(A)
+    return _engine_for_parts(crow, col, A.values(), tuple(A.shape), dev, fast)
 
 
 def _refresh_entry(ent, val):
@@ -91,6 +123,10 @@ def _refresh_entry(ent, val):
 
 
 def _engine_for_parts(crow, col, val, shape, dev, fast=False, force_refresh=False):
+    return _entry_for_parts(crow, col, val, shape, dev, fast, force_refresh).eng
+
+
+def _entry_for_parts(crow, col, val, shape, dev, fast=False, force_refresh=False, values_needed=True):
     """One engine per sparsity PATTERN, at most _MAX_ENGINES of them (LRU: every entry pins an engine with its device workspaces).
     The key holds the addresses of A's INDEX tensors, the shape, nnz, device and mode -- not the values: what is expensive to build
     (block dictionaries, clustering, the sort behind A^T) depends on the pattern alone.  The entry keeps A's index tensors alive: as
@@ -103,7 +139,8 @@ def _engine_for_parts(crow, col, val, shape, dev, fast=False, force_refresh=Fals
       The entry remembers the value tensor it last served (address + version).  A call that finds other values -- an optimizer step in
     place, another value tensor on the same pattern, values without a version counter (every call) -- refreshes the engine's copies on
     the current stream (sextans_update_values_device) instead of building an engine.  What the counters cannot see is a change made
-    through ANOTHER alias of the value storage (the dense tensor A was built from): refresh(A) is for that."""
+    through ANOTHER alias of the value storage (the dense tensor A was built from): refresh(A) is for that.
+      values_needed=False (row_softmax: the pattern alone matters) leaves the values of a cached engine as they are."""
     M, K = shape
     key = (dev, crow.data_ptr(), col.data_ptr(), M, K, val.numel(), bool(fast))
     ivers = (_ver(crow), _ver(col))
@@ -118,9 +155,9 @@ def _engine_for_parts(crow, col, val, shape, dev, fast=False, force_refresh=Fals
     if ent is not None:
         _cache.move_to_end(key)
         vv = _ver(val)
-        if force_refresh or vv is None or vv != ent.val_ver or val.data_ptr() != ent.val_ptr:
+        if values_needed and (force_refresh or vv is None or vv != ent.val_ver or val.data_ptr() != ent.val_ptr):
             _refresh_entry(ent, val)
-        return ent.eng
+        return ent
     ent = _Entry()
     ent.crow32, ent.col32 = crow.to(torch.int32).contiguous(), col.to(torch.int32).contiguous()
     ent.val32 = val.to(torch.float32).contiguous()
@@ -134,7 +171,7 @@ def _engine_for_parts(crow, col, val, shape, dev, fast=False, force_refresh=Fals
     _cache[key] = ent
     while len(_cache) > _MAX_ENGINES:
         _evict(next(iter(_cache)))
-    return eng
+    return ent
 
 
 def refresh(A, fast=False):
@@ -254,7 +291,7 @@ class _SpmmFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, A, B, C, alpha, beta, fast, transpose_a, out_dtype=None):
         out = _forward(A, B, alpha, beta, C, None, fast, transpose_a, out_dtype)
-        ctx.save_for_backward(A.crow_indices(), A.col_indices(), A.values(), B)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B)
         ctx.shape, ctx.alpha, ctx.beta, ctx.fast, ctx.transpose_a = tuple(A.shape), alpha, beta, fast, transpose_a
         ctx.dev = A.device.index or 0
         return out
@@ -294,3 +331,155 @@ class _SpmmFunction(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             gC = G * ctx.beta if ctx.beta != 0.0 else torch.zeros_like(G)
         return gA, gB, gC, None, None, None, None, None
+
+
+def _vals32(v):
+    """fp32, contiguous, 16-byte aligned: v itself where it is all that"""
+    v = v.detach().to(torch.float32).contiguous()
+    return v if v.data_ptr() % 16 == 0 else v.clone()
+
+
+def _grad_values(G, crow, col, nnz):
+    """The values of a gradient on A's pattern, in A's entry order: a CSR gradient built on the pattern (what every backward here and
+    torch's own sparse ops return), or a dense one, gathered."""
+    if G.layout == torch.sparse_csr:
+        if G.values().numel() != nnz:
+            raise ValueError("gradient on another sparsity pattern")
+        return _vals32(G.values())
+    rows = torch.repeat_interleave(torch.arange(crow.numel() - 1, device=crow.device), (crow[1:] - crow[:-1]).long(), output_size=nnz)
+    return _vals32(G[rows, col.long()])
+
+
+def _check_sparse(A, name):
+    if not isinstance(A, torch.Tensor) or A.layout != torch.sparse_csr or not A.is_cuda:
+        raise TypeError("%s expects a CUDA/HIP torch.sparse_csr matrix" % name)
+    if A.dim() != 2:
+        raise ValueError("%s expects a 2-D sparse_csr matrix" % name)
+
+
+class _SddmmFunction(torch.autograd.Function):
+    """S = alpha * (X Y^T on A's pattern) + beta * A.  With upstream gradient G_S (on the pattern):
+         dX = alpha * G_S * Y      the forward product of the cached engine, G_S's values refreshed onto it
+         dY = alpha * G_S^T * X    its transposed product
+         dA = beta * G_S"""
+
+    @staticmethod
+    def forward(ctx, A, X, Y, alpha, beta, fast):
+        M, K = A.shape
+        N = X.shape[1]
+        Np = api.round_up_n(N)
+        dev = A.device.index or 0
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, K), dev, fast, values_needed=False)
+        Xr, Yr = _rowmajor(X.detach(), M, N, Np), _rowmajor(Y.detach(), K, N, Np)   # (zero padding adds +0 products: the sums keep their bits)
+        out = torch.empty((val.numel(),), dtype=torch.float32, device=A.device)
+        if out.numel():
+            vin = _vals32(val) if beta != 0.0 else None
+            ent.eng.sddmm_device_rm(Np, alpha, Xr.data_ptr(), Xr.stride(0), Yr.data_ptr(), Yr.stride(0), beta,
+                                    vin.data_ptr() if vin is not None else None, out.data_ptr(), torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, X, Y)
+        ctx.shape, ctx.alpha, ctx.beta, ctx.fast, ctx.dev, ctx.vdtype = (M, K), alpha, beta, fast, dev, val.dtype
+        return torch.sparse_csr_tensor(crow, col, out, size=(M, K))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, X, Y = ctx.saved_tensors
+        M, K = ctx.shape
+        N = X.shape[1]
+        Np = api.round_up_n(N)
+        gX = gY = gA = None
+        if not any(ctx.needs_input_grad[:3]):
+            return None, None, None, None, None, None
+        nnz = int(col.numel())
+        g = _grad_values(G, crow, col, nnz)
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            eng = _entry_for_parts(crow, col, g, ctx.shape, ctx.dev, ctx.fast).eng   # the engine of the pattern, on G_S's values
+            if ctx.needs_input_grad[1]:
+                Yr = _rowmajor(Y.detach(), K, N, Np)
+                out = torch.zeros((M, Np), dtype=torch.float32, device=g.device)
+                eng.spmm_device_rm(Np, ctx.alpha, Yr.data_ptr(), Yr.stride(0), 0.0, out.data_ptr(), Np, out.data_ptr(), Np, stream)
+                gX = (out if Np == N else out[:, :N]).to(X.dtype)
+            if ctx.needs_input_grad[2]:
+                Xr = _rowmajor(X.detach(), M, N, Np)
+                out = torch.zeros((K, Np), dtype=torch.float32, device=g.device)
+                eng.spmm_t_device_rm(Np, ctx.alpha, Xr.data_ptr(), Xr.stride(0), 0.0, out.data_ptr(), Np, out.data_ptr(), Np, stream)
+                gY = (out if Np == N else out[:, :N]).to(Y.dtype)
+        if ctx.needs_input_grad[0]:
+            gA = torch.sparse_csr_tensor(crow, col, (g * ctx.beta).to(ctx.vdtype), size=(M, K))
+        return gA, gX, gY, None, None, None
+
+
+class _RowSoftmaxFunction(torch.autograd.Function):
+    """P = softmax(scale * S) over every row's stored entries; dS = scale * P * (G - sum_row P G): both on the engine of the pattern
+    (sextans_row_softmax_device, sextans_row_softmax_backward_device)."""
+
+    @staticmethod
+    def forward(ctx, S, scale, fast):
+        M, K = S.shape
+        dev = S.device.index or 0
+        crow, col = _index_tensors(S)
+        val = S.values()
+        ent = _entry_for_parts(crow, col, val, (M, K), dev, fast, values_needed=False)
+        x = _vals32(val)
+        p = torch.empty_like(x)
+        if x.numel():
+            ent.eng.row_softmax_device(scale, x.data_ptr(), p.data_ptr(), torch.cuda.current_stream(S.device).cuda_stream)
+        ctx.save_for_backward(crow, col, p)
+        ctx.shape, ctx.scale, ctx.fast, ctx.dev, ctx.vdtype = (M, K), scale, fast, dev, val.dtype
+        return torch.sparse_csr_tensor(crow, col, p.to(val.dtype), size=(M, K))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, p = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        g = _grad_values(G, crow, col, int(p.numel()))
+        dx = torch.empty_like(p)
+        if p.numel():
+            ent = _entry_for_parts(crow, col, p, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+            ent.eng.row_softmax_backward_device(ctx.scale, p.data_ptr(), g.data_ptr(), dx.data_ptr(), torch.cuda.current_stream(p.device).cuda_stream)
+        return torch.sparse_csr_tensor(crow, col, dx.to(ctx.vdtype), size=ctx.shape), None, None
+
+
+def sddmm(A, X, Y, alpha=1.0, beta=0.0, fast=False):
+    """S on A's pattern, S_e = alpha * <X[r, :], Y[c, :]> + beta * A_e for every stored entry e = (r, c): a sparse_csr tensor with A's own
+    index tensors and fp32 values, the bits of sextans_sddmm_device_rm (every product and sum rounded in column order).  X is (M, N),
+    Y is (K, N); operands the kernel cannot read where they lie (N % 8 != 0, strides, dtype) are copied as spmm() copies them.
+    Differentiable in X, Y and (beta != 0) A; the backward products run on the cached engine with the gradient's values."""
+    _check_sparse(A, "sddmm")
+    if not (isinstance(X, torch.Tensor) and isinstance(Y, torch.Tensor) and X.is_cuda and Y.is_cuda):
+        raise TypeError("sddmm expects CUDA/HIP dense X and Y")
+    M, K = A.shape
+    if X.dim() != 2 or Y.dim() != 2 or X.shape[0] != M or Y.shape[0] != K or X.shape[1] != Y.shape[1] or X.shape[1] == 0:
+        raise ValueError("shape mismatch")
+    crow, col = _index_tensors(A)
+    return _carry(_SddmmFunction.apply(A, X, Y, float(alpha), float(beta), bool(fast)), crow, col)
+
+
+def row_softmax(S, scale=1.0, fast=False):
+    """P on S's pattern: softmax(scale * S) over the stored entries of every row (torch.softmax's special values: -inf beside finite
+    entries gives 0, an empty row nothing), a sparse_csr tensor with S's index tensors.  Computed in fp32; other value dtypes are
+    converted and the result converted back.  Differentiable."""
+    _check_sparse(S, "row_softmax")
+    crow, col = _index_tensors(S)
+    return _carry(_RowSoftmaxFunction.apply(S, float(scale), bool(fast)), crow, col)
+
+
+def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False):
+    """softmax(scale * (Q K^T [+ A]) restricted to A's pattern) V:  spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V).
+    A (M x Kk) gives the pattern -- and, with bias=True, an additive bias / mask through its values; Q is (M, d), K (Kk, d), V (Kk, dv);
+    scale=None means 1 / sqrt(d).  Differentiable in Q, K, V and (bias=True) A.  A composition of the three ops on one cached engine,
+    not a fused kernel: S and P are materialised (the backward needs P)."""
+    _check_sparse(A, "sparse_attention")
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (Q, K, V)):
+        raise TypeError("sparse_attention expects CUDA/HIP dense Q, K and V")
+    if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or V.shape[0] != A.shape[1]:
+        raise ValueError("shape mismatch")
+    if scale is None:
+        scale = 1.0 / math.sqrt(Q.shape[1])
+    S = sddmm(A, Q, K, 1.0, 1.0 if bias else 0.0, fast)
+    return spmm(row_softmax(S, scale, fast), V, fast=fast)
