@@ -375,7 +375,7 @@ int sextans_export_row_order(sextans_handle_t h, int *order, int *clustered);
  * "window_state" (0 not evaluated, 1 built, -1 rejected), "panel_fraction", "panel_blocks", "piece_path_rows",
  * "reassociated_rows", "bucket_threshold", "split_threshold", "dense_tiles", "dense_tile_fraction",
  * "dense_tiles_on_mfma", "row_cluster" and the other clustering figures listed with that option, "device_bytes" (bytes of
- * device memory the engine holds right now: matrix copies, packed plans, workspaces), "col_range_lo" / "col_range_hi" (the rows
+ * device memory the engine has asked the runtime for and holds right now: matrix copies, packed plans, tables, workspaces), "col_range_lo" / "col_range_hi" (the rows
  * of B the matrix has columns in: only those are repacked -- a rank of a row-partitioned SpMM over a banded matrix touches
  * 1 / world of B plus a halo), "cluster_decline" (why the graph clustering was not used: 1 not square and "row_similarity" = 0, 2 long-row paths,
  * 3 offsets, 4 natural blocks full, 5 no shared neighbourhoods, 6..9 a builder failed, 10..12 plan unusable / no gain,

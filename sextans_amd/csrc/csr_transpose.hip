@@ -26,18 +26,9 @@ namespace {
         if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return 2; }       \
     } while (0)
 
-struct Scratch {   // device allocations freed on every exit path
-    std::vector<void *> p;
-    hipStream_t s = nullptr;
-    ~Scratch() {
-        if (!p.empty()) (void)hipStreamSynchronize(s);   // (nothing enqueued may still read them)
-        for (void *q : p) (void)hipFree(q);
-    }
-    template <class T> hipError_t alloc(T **out, size_t n) {
-        hipError_t e = hipMalloc((void **)out, sizeof(T) * (n ? n : 1));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
+struct SyncOnExit {   // declared behind the scratch buffers of a function: nothing enqueued may still read them when they are freed
+    hipStream_t s;
+    ~SyncOnExit() { (void)hipStreamSynchronize(s); }
 };
 
 inline unsigned blocks_for(long long n, int per) { return (unsigned)((n + per - 1) / per); }
@@ -81,29 +72,27 @@ int csr_transpose_device(int M, int K, int64_t nnz, const int *d_rp, const int *
         TR_HIP(hipStreamSynchronize(s));
         return 0;
     }
-    Scratch tmp;
-    tmp.s = s;
-    int *rows = nullptr, *scols = nullptr;
-    TR_HIP(tmp.alloc(&rows, (size_t)nnz));
-    TR_HIP(tmp.alloc(&scols, (size_t)nnz));
+    DevBuf<int> rows, scols, eid, seid_own;
+    DevBuf<char> sort_tmp;
+    SyncOnExit sync{s};
+    TR_HIP(rows.alloc((size_t)nnz));
+    TR_HIP(scols.alloc((size_t)nnz));
     hipLaunchKernelGGL(expand_row_ids, dim3(blocks_for(M, 4)), dim3(256), 0, s, M, d_rp, rows);
     int bits = 1;
     while (bits < 32 && (1LL << bits) < (long long)K) ++bits;
-    void *sort_tmp = nullptr;
     size_t bytes = 0;
     if (!d_v) {   // the pattern alone (the row-similarity graph): the row ids travel through the sort straight into t_ci
-        TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_ci, scols, rows, t_ci, (int)nnz, 0, bits, s));
-        TR_HIP(tmp.alloc((char **)&sort_tmp, bytes));
-        TR_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, d_ci, scols, rows, t_ci, (int)nnz, 0, bits, s));   // stable: rows ascending per column
+        TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_ci, scols.get(), rows.get(), t_ci, (int)nnz, 0, bits, s));
+        TR_HIP(sort_tmp.alloc(bytes));
+        TR_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, d_ci, scols.get(), rows.get(), t_ci, (int)nnz, 0, bits, s));   // stable: rows ascending per column
     } else {      // values too: the entry index travels through the sort, row id and value are gathered behind it
-        int *eid = nullptr, *seid = nullptr;
-        TR_HIP(tmp.alloc(&eid, (size_t)nnz));
-        if (t_perm) seid = t_perm;   // the caller keeps the sorted entry indices: t_v[i] = d_v[t_perm[i]] for every later set of values
-        else TR_HIP(tmp.alloc(&seid, (size_t)nnz));
+        TR_HIP(eid.alloc((size_t)nnz));
+        if (!t_perm) TR_HIP(seid_own.alloc((size_t)nnz));
+        int *seid = t_perm ? t_perm : seid_own.get();   // the caller keeps the sorted entry indices: t_v[i] = d_v[t_perm[i]] for every later set of values
         hipLaunchKernelGGL(iota, dim3(blocks_for(nnz, 256)), dim3(256), 0, s, (long long)nnz, eid);
-        TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_ci, scols, eid, seid, (int)nnz, 0, bits, s));
-        TR_HIP(tmp.alloc((char **)&sort_tmp, bytes));
-        TR_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, d_ci, scols, eid, seid, (int)nnz, 0, bits, s));   // stable: CSR order per column
+        TR_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, d_ci, scols.get(), eid.get(), seid, (int)nnz, 0, bits, s));
+        TR_HIP(sort_tmp.alloc(bytes));
+        TR_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, d_ci, scols.get(), eid.get(), seid, (int)nnz, 0, bits, s));   // stable: CSR order per column
         hipLaunchKernelGGL(gather_entries, dim3(blocks_for(nnz, 256)), dim3(256), 0, s, (long long)nnz, seid, rows, d_v, t_ci, t_v);
     }
     segment_starts_device(K, nnz, scols, t_rp, s);
@@ -128,12 +117,13 @@ extern "C" int sextans_csr_transpose_device(int device, int M, int K, int64_t nn
         if (M > 0 && sx::validate_csr_device(M, K, nnz, d_row_ptr, d_col_idx, &bad, err)) return SEXTANS_ERR_HIP;
         if (bad) return (bad & 1) ? SEXTANS_ERR_INVALID : SEXTANS_ERR_INDEX;
     }
+    // (the arrays are the caller's from here on, to be released with sextans_device_free: raw memory like sextans_device_alloc's)
     int *trp = nullptr, *tci = nullptr;
     float *tv = nullptr;
-    auto fail = [&](int rc) { (void)hipFree(trp); (void)hipFree(tci); (void)hipFree(tv); return rc; };
-    if (hipMalloc((void **)&trp, sizeof(int) * ((size_t)K + 1)) != hipSuccess ||
-        hipMalloc((void **)&tci, sizeof(int) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess ||
-        hipMalloc((void **)&tv, sizeof(float) * (size_t)std::max<int64_t>(nnz, 1)) != hipSuccess)
+    auto fail = [&](int rc) { (void)sextans_device_free(device, trp); (void)sextans_device_free(device, tci); (void)sextans_device_free(device, tv); return rc; };
+    if (sextans_device_alloc(device, sizeof(int) * ((size_t)K + 1), (void **)&trp) != SEXTANS_OK ||
+        sextans_device_alloc(device, sizeof(int) * (size_t)std::max<int64_t>(nnz, 1), (void **)&tci) != SEXTANS_OK ||
+        sextans_device_alloc(device, sizeof(float) * (size_t)std::max<int64_t>(nnz, 1), (void **)&tv) != SEXTANS_OK)
         return fail(SEXTANS_ERR_ALLOC);
     if (sx::csr_transpose_device(M, K, nnz, d_row_ptr, d_col_idx, d_val, trp, tci, tv, (hipStream_t)stream, err)) return fail(SEXTANS_ERR_HIP);
     *o_row_ptr = trp; *o_col_idx = tci; *o_val = tv;

@@ -138,21 +138,14 @@ int sextans_destroy(sextans_handle_t h) {
     (void)hipSetDevice(h->device);
     free_matrix(h);
     free_bell(h);
-    (void)hipFree(h->d_bell_Bf);
-    (void)hipFree(h->d_Bp); (void)hipFree(h->d_B); (void)hipFree(h->d_Cin); (void)hipFree(h->d_Cout); (void)hipFree(h->d_Cs);
     sextans_profile_reset(h);
-    (void)hipFree(h->d_P);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-    (void)hipFree(h->d_dbg);
-    (void)hipFree(h->d_chB); (void)hipFree(h->d_chC);
-    (void)hipFree(h->d_stage);
-    (void)hipFree(h->d_Cfull); (void)hipFree(h->d_dist_rows); (void)hipFree(h->d_rmB); (void)hipFree(h->d_rmC);
     for (hipEvent_t e : h->dist_events) (void)hipEventDestroy(e);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     if (h->host_stream) (void)hipStreamDestroy(h->host_stream);
-    delete h;
+    delete h;   // (the workspaces go with it: on h->device, set above)
     return SEXTANS_OK;
 }
 
@@ -194,7 +187,7 @@ int sextans_set_option(sextans_handle_t h, const char *key, int64_t value) {
             case kWindowStream: free_window(h); break;
             case kClusterPlan: free_cluster_plan(h); h->cluster_rm_tried = false; break;
             case kPackedPlans: free_plan(h); break;
-            case kColwiseVerdict: h->colwise_state = 0; break;
+            case kColwiseVerdict: h->cluster.colwise_state = 0; break;
             case kNothing: break;
         }
         h->dist_cut_key.clear();   // chunk cuts are aligned to the packed forms the options select (all ranks of a partition must change
@@ -203,9 +196,9 @@ int sextans_set_option(sextans_handle_t h, const char *key, int64_t value) {
     *slot = value;
     if (slot == &h->opt_phase_timing) {
         (void)hipSetDevice(h->device);
-        if (value && !h->d_dbg && hipMalloc((void **)&h->d_dbg, 64) != hipSuccess) return SEXTANS_ERR_HIP;
+        if (value && h->d_dbg.reserve(8) != hipSuccess) return SEXTANS_ERR_HIP;
         if (h->d_dbg) (void)hipMemset(h->d_dbg, 0, 64);
-        if (!value && h->d_dbg) { (void)hipFree(h->d_dbg); h->d_dbg = nullptr; }
+        if (!value) h->d_dbg.reset();
     }
     return h->tr ? transposed_options(h, key, value) : SEXTANS_OK;
 }
@@ -248,18 +241,18 @@ int sextans_set_matrix_csr(sextans_handle_t h, int M, int K, int64_t nnz, const 
     }
     SX_HIP(hipSetDevice(h->device));
     free_matrix(h);
-    int *rp = nullptr, *ci = nullptr;
-    float *v = nullptr;
-    SX_HIP(hipMalloc((void **)&rp, sizeof(int) * ((size_t)M + 1)));
-    SX_HIP(hipMalloc((void **)&ci, sizeof(int) * (size_t)(nnz ? nnz : 1)));
-    SX_HIP(hipMalloc((void **)&v, sizeof(float) * (size_t)(nnz ? nnz : 1)));
+    DevBuf<int> rp, ci;
+    DevBuf<float> v;
+    SX_HIP(rp.alloc((size_t)M + 1));
+    SX_HIP(ci.alloc((size_t)nnz));
+    SX_HIP(v.alloc((size_t)nnz));
     SX_HIP(hipMemcpy(rp, row_ptr, sizeof(int) * ((size_t)M + 1), hipMemcpyHostToDevice));
     if (nnz) {
         SX_HIP(hipMemcpy(ci, col_idx, sizeof(int) * (size_t)nnz, hipMemcpyHostToDevice));
         SX_HIP(hipMemcpy(v, val, sizeof(float) * (size_t)nnz, hipMemcpyHostToDevice));
     }
-    h->d_rp = rp; h->d_ci = ci; h->d_v = v;
-    h->owns_matrix = true;
+    h->mat.d_rp_own = std::move(rp); h->mat.d_ci_own = std::move(ci); h->mat.d_v_own = std::move(v);
+    h->d_rp = h->mat.d_rp_own; h->d_ci = h->mat.d_ci_own; h->d_v = h->mat.d_v_own;
     h->M = M; h->K = K; h->nnz = nnz;
     free_dense(h);   // source = main = the matrix itself until the dense-tile and long-row tests have run
     return SEXTANS_OK;
@@ -272,7 +265,6 @@ int sextans_set_matrix_csr_device(sextans_handle_t h, int M, int K, int64_t nnz,
     SX_HIP(hipSetDevice(h->device));
     free_matrix(h);
     h->d_rp = d_row_ptr; h->d_ci = d_col_idx; h->d_v = d_val;
-    h->owns_matrix = false;
     h->M = M; h->K = K; h->nnz = nnz;
     free_dense(h);
     return SEXTANS_OK;
@@ -310,14 +302,14 @@ __global__ __launch_bounds__(64) void dict_overlap(const int *__restrict__ dict_
 // such runs could be written to column-major C as 64-byte pieces straight from the SpMM kernel instead of through the staging buffer.
 int run16_stat(sextans_engine *h, double *value) {
     *value = 0.0;
-    if (h->cluster_state <= 0 || !h->d_slot_row || h->psc.plan_nblk <= 0) return SEXTANS_OK;
-    const int RB = kBlock / 4 * std::max(1, h->psc.plan_sets);
-    std::vector<int> sr((size_t)h->psc.plan_nblk * RB);
-    SX_HIP(hipMemcpy(sr.data(), h->d_slot_row, sizeof(int) * sr.size(), hipMemcpyDeviceToHost));
-    const std::vector<int> &br = h->psc.h_blk_row;
-    if ((int)br.size() != h->psc.plan_nblk + 1) return SEXTANS_OK;
+    if (h->cluster.state <= 0 || !h->cluster.d_slot_row || h->cluster.psc.plan_nblk <= 0) return SEXTANS_OK;
+    const int RB = kBlock / 4 * std::max(1, h->cluster.psc.plan_sets);
+    std::vector<int> sr((size_t)h->cluster.psc.plan_nblk * RB);
+    SX_HIP(hipMemcpy(sr.data(), h->cluster.d_slot_row, sizeof(int) * sr.size(), hipMemcpyDeviceToHost));
+    const std::vector<int> &br = h->cluster.psc.h_blk_row;
+    if ((int)br.size() != h->cluster.psc.plan_nblk + 1) return SEXTANS_OK;
     int64_t in_runs = 0, slots = 0;
-    for (int b = 0; b < h->psc.plan_nblk; ++b) {
+    for (int b = 0; b < h->cluster.psc.plan_nblk; ++b) {
         const int n = br[(size_t)b + 1] - br[(size_t)b];
         const int *r = sr.data() + (size_t)b * RB;
         slots += n;
@@ -332,16 +324,15 @@ int run16_stat(sextans_engine *h, double *value) {
     return SEXTANS_OK;
 }
 int dict_overlap_stat(sextans_engine *h, double *value) {
-    const sextans_engine::PanelState &P = h->cluster_state > 0 ? h->psc : h->ps;
+    const sextans_engine::PanelState &P = h->cluster.state > 0 ? h->cluster.psc : h->ps;
     *value = 0.0;
     if (!P.plan_built || P.plan_nblk < 2 || !P.d_dict || !P.d_dict_ptr) return SEXTANS_OK;
-    unsigned long long *d = nullptr, hv[2] = {0, 0};
-    SX_HIP(hipMalloc((void **)&d, sizeof hv));
+    DevBuf<unsigned long long> d;
+    unsigned long long hv[2] = {0, 0};
+    SX_HIP(d.alloc(2));
     SX_HIP(hipMemset(d, 0, sizeof hv));
     hipLaunchKernelGGL(dict_overlap, dim3((unsigned)P.plan_nblk - 1), dim3(64), 0, hipStreamPerThread, P.d_dict_ptr, P.d_dict, P.plan_dict_stride, P.plan_nblk, d);
-    const hipError_t e = hipMemcpy(hv, d, sizeof hv, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    SX_HIP(e);
+    SX_HIP(hipMemcpy(hv, d, sizeof hv, hipMemcpyDeviceToHost));
     *value = hv[1] ? (double)hv[0] / (double)hv[1] : 0.0;
     return SEXTANS_OK;
 }
@@ -355,52 +346,52 @@ int sextans_get_stat(sextans_handle_t h, const char *key, double *value) {
         if (int rc = ensure_dense(h)) return rc;
         if (int rc = ensure_split(h)) return rc;
     }
-    if (!strcmp(key, "plan_build_s")) *value = h->plan_build_s;
-    else if (!strcmp(key, "window_padded_entries")) *value = (double)h->win_padded;
-    else if (!strcmp(key, "window_state")) *value = (double)h->win_state;
-    else if (!strcmp(key, "reassociated_rows")) *value = (double)h->h_split_rows.size();
-    else if (!strcmp(key, "piece_path_rows")) *value = (double)(h->nhub + h->nchain);
-    else if (!strcmp(key, "exact_chain_rows")) *value = (double)h->nchain;
-    else if (!strcmp(key, "chain_threshold")) *value = (double)h->chain_T;
-    else if (!strcmp(key, "split_threshold")) *value = (double)h->split_T;
-    else if (!strcmp(key, "bucket_threshold")) *value = (double)h->bucket_L0;
-    else if (!strcmp(key, "dense_tiles")) *value = (double)h->dense_tiles;
-    else if (!strcmp(key, "dense_tile_fraction")) *value = h->nnz > 0 ? (double)h->dense_nnz / (double)h->nnz : 0.0;
-    else if (!strcmp(key, "dense_tiles_on_mfma")) *value = h->dense_W > 0 ? 1.0 : 0.0;
+    if (!strcmp(key, "plan_build_s")) *value = h->mat.plan_build_s;
+    else if (!strcmp(key, "window_padded_entries")) *value = (double)h->win.padded;
+    else if (!strcmp(key, "window_state")) *value = (double)h->win.state;
+    else if (!strcmp(key, "reassociated_rows")) *value = (double)h->split.h_split_rows.size();
+    else if (!strcmp(key, "piece_path_rows")) *value = (double)(h->split.nhub + h->split.nchain);
+    else if (!strcmp(key, "exact_chain_rows")) *value = (double)h->split.nchain;
+    else if (!strcmp(key, "chain_threshold")) *value = (double)h->split.chain_T;
+    else if (!strcmp(key, "split_threshold")) *value = (double)h->split.T;
+    else if (!strcmp(key, "bucket_threshold")) *value = (double)h->split.bucket_L0;
+    else if (!strcmp(key, "dense_tiles")) *value = (double)h->dense.tiles;
+    else if (!strcmp(key, "dense_tile_fraction")) *value = h->nnz > 0 ? (double)h->dense.nnz / (double)h->nnz : 0.0;
+    else if (!strcmp(key, "dense_tiles_on_mfma")) *value = h->dense.W > 0 ? 1.0 : 0.0;
     else if (!strcmp(key, "bell_share")) *value = h->bell_share;
-    else if (!strcmp(key, "row_cluster")) *value = (double)h->cluster_state;          // 1 grid bricks / 2 graph clustering in use, -1 declined, 0 not evaluated yet
-    else if (!strcmp(key, "cluster_shared_fraction")) *value = h->cluster_shared;
-    else if (!strcmp(key, "cluster_decline")) *value = (double)h->cluster_decline;
+    else if (!strcmp(key, "row_cluster")) *value = (double)h->cluster.state;          // 1 grid bricks / 2 graph clustering in use, -1 declined, 0 not evaluated yet
+    else if (!strcmp(key, "cluster_shared_fraction")) *value = h->cluster.shared;
+    else if (!strcmp(key, "cluster_decline")) *value = (double)h->cluster.decline;
     else if (!strcmp(key, "graph_fallbacks")) *value = (double)h->graph_fallbacks;   // rp_time loops launched one by one because their hipGraph capture was invalidated from outside
     else if (!strcmp(key, "cluster_run16_fraction")) return run16_stat(h, value);   // share of the clustered plan's slots in runs of >= 16 consecutive rows of their block
     else if (!strcmp(key, "dict_overlap_consecutive")) return dict_overlap_stat(h, value);   // share of a block's dictionary rows the previous block of the walk holds too (the plan whole-matrix calls use)
     else if (!strcmp(key, "dist_setup_exchanges")) *value = (double)h->dist_exchanges;   // control collectives + host syncs of the dist entry points so far (0 new ones after sextans_dist_prepare)
-    else if (!strcmp(key, "cluster_graph_kind")) *value = (double)h->cluster_graph_kind;
-    else if (!strcmp(key, "cluster_runs")) *value = h->cluster_runs ? 1.0 : 0.0;
-    else if (!strcmp(key, "pattern_symmetry")) *value = h->pattern_symmetry;
+    else if (!strcmp(key, "cluster_graph_kind")) *value = (double)h->cluster.graph_kind;
+    else if (!strcmp(key, "cluster_runs")) *value = h->cluster.runs ? 1.0 : 0.0;
+    else if (!strcmp(key, "pattern_symmetry")) *value = h->cluster.pattern_symmetry;
     else if (!strcmp(key, "col_range_lo")) *value = (double)h->col_lo;
     else if (!strcmp(key, "col_range_hi")) *value = (double)h->col_hi;
-    else if (!strcmp(key, "b_rows_repacked")) *value = h->d_touched ? (double)h->touched_segments * 64.0 : (double)(h->col_hi - h->col_lo);
-    else if (!strcmp(key, "colwise")) *value = (double)h->colwise_state;
+    else if (!strcmp(key, "b_rows_repacked")) *value = h->mat.d_touched ? (double)h->mat.touched_segments * 64.0 : (double)(h->col_hi - h->col_lo);
+    else if (!strcmp(key, "colwise")) *value = (double)h->cluster.colwise_state;
     else if (!strcmp(key, "mixed_plan")) *value = h->ps.plan_built && h->ps.plan_mixed ? (h->ps.d_rg_skip && h->opt_split_mixed != 0 ? 2.0 : 1.0) : 0.0;   // 2: runs in its split form
-    else if (!strcmp(key, "row_sets")) *value = (double)(h->cluster_state > 0 ? h->psc.plan_sets : h->ps.plan_sets);
-    else if (!strcmp(key, "row_coherence")) *value = h->row_coherence;
-    else if (!strcmp(key, "panel_blocks_clustered")) *value = (double)h->psc.plan_nblk;
+    else if (!strcmp(key, "row_sets")) *value = (double)(h->cluster.state > 0 ? h->cluster.psc.plan_sets : h->ps.plan_sets);
+    else if (!strcmp(key, "row_coherence")) *value = h->cluster.row_coherence;
+    else if (!strcmp(key, "panel_blocks_clustered")) *value = (double)h->cluster.psc.plan_nblk;
     else if (!strcmp(key, "device_bytes")) *value = (double)device_bytes(h);
-    else if (!strcmp(key, "softmax_long_rows")) *value = (double)h->sm_long_rows;                  // rows on the long-row path of sextans_row_softmax*_device
-    else if (!strcmp(key, "value_refreshes")) *value = (double)h->value_refreshes;                  // sextans_update_values* served on this matrix
-    else if (!strcmp(key, "value_refresh_rebuilt")) *value = (double)h->value_refresh_rebuilt;      //   ... that dropped a form for a lazy rebuild
-    else if (!strcmp(key, "bf16_native_calls")) *value = (double)(h->bf16_native_calls + (h->tr ? h->tr->bf16_native_calls : 0));            // bf16 calls (transposed ones included) on the caller's buffers
-    else if (!strcmp(key, "bf16_converted_calls")) *value = (double)(h->bf16_converted_calls + (h->tr ? h->tr->bf16_converted_calls : 0));   //   ... and through fp32 copies
-    else if (!strcmp(key, "transpose_build_s")) *value = h->transpose_build_s + (h->tr ? h->tr->plan_build_s : 0.0);
+    else if (!strcmp(key, "softmax_long_rows")) *value = (double)h->softmax.long_rows;                  // rows on the long-row path of sextans_row_softmax*_device
+    else if (!strcmp(key, "value_refreshes")) *value = (double)h->mat.value_refreshes;                  // sextans_update_values* served on this matrix
+    else if (!strcmp(key, "value_refresh_rebuilt")) *value = (double)h->mat.value_refresh_rebuilt;      //   ... that dropped a form for a lazy rebuild
+    else if (!strcmp(key, "bf16_native_calls")) *value = (double)(h->mat.bf16_native_calls + (h->tr ? h->tr->mat.bf16_native_calls : 0));            // bf16 calls (transposed ones included) on the caller's buffers
+    else if (!strcmp(key, "bf16_converted_calls")) *value = (double)(h->mat.bf16_converted_calls + (h->tr ? h->tr->mat.bf16_converted_calls : 0));   //   ... and through fp32 copies
+    else if (!strcmp(key, "transpose_build_s")) *value = h->at.build_s + (h->tr ? h->tr->mat.plan_build_s : 0.0);
     else if (!strcmp(key, "grid_stride_line")) *value = (double)h->cluster_s2;
     else if (!strcmp(key, "grid_stride_plane")) *value = (double)h->cluster_s3;
     else if (!strcmp(key, "panel_rows_natural")) *value = (double)h->plan_total_dict;  // B rows copied into LDS per N tile, natural order
-    else if (!strcmp(key, "panel_rows_clustered")) *value = (double)h->cluster_total_dict;
+    else if (!strcmp(key, "panel_rows_clustered")) *value = (double)h->cluster.total_dict;
     else if (!strcmp(key, "panel_fraction")) *value = h->ps.plan_panel_frac;
     else if (!strcmp(key, "panel_blocks")) *value = (double)h->ps.plan_nblk;
-    else if (!strcmp(key, "index_stream_entries")) *value = (double)(h->cluster_state > 0 ? h->psc.plan_idx_len : h->ps.plan_idx_len);
-    else if (!strcmp(key, "value_stream_entries")) *value = (double)(h->cluster_state > 0 ? h->psc.plan_stream_len : h->ps.plan_stream_len);
+    else if (!strcmp(key, "index_stream_entries")) *value = (double)(h->cluster.state > 0 ? h->cluster.psc.plan_idx_len : h->ps.plan_idx_len);
+    else if (!strcmp(key, "value_stream_entries")) *value = (double)(h->cluster.state > 0 ? h->cluster.psc.plan_stream_len : h->ps.plan_stream_len);
     else return SEXTANS_ERR_INVALID;
     return SEXTANS_OK;
 }
@@ -482,8 +473,8 @@ int sextans_reassociated_rows(sextans_handle_t h, int *rows, int capacity, int *
     SX_HIP(hipSetDevice(h->device));
     if (int rc = ensure_dense(h)) return rc;
     if (int rc = ensure_split(h)) return rc;
-    *count = (int)h->h_split_rows.size();
-    for (int i = 0; i < *count && i < capacity; ++i) rows[i] = h->h_split_rows[(size_t)i];
+    *count = (int)h->split.h_split_rows.size();
+    for (int i = 0; i < *count && i < capacity; ++i) rows[i] = h->split.h_split_rows[(size_t)i];
     return SEXTANS_OK;
 }
 
@@ -498,18 +489,16 @@ int sextans_export_row_order(sextans_handle_t h, int *order, int *clustered) {
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     SX_HIP(hipSetDevice(h->device));
     if (int rc = prepare(h, 16)) return rc;
-    const bool have = h->cluster_state > 0 && h->d_slot_row && h->psc.plan_built && h->nhub == 0 && h->nchain == 0;
-    if (clustered) *clustered = have ? h->cluster_state : 0;
+    const bool have = h->cluster.state > 0 && h->cluster.d_slot_row && h->cluster.psc.plan_built && h->split.nhub == 0 && h->split.nchain == 0;
+    if (clustered) *clustered = have ? h->cluster.state : 0;
     if (!have) {
         for (int i = 0; i < h->M; ++i) order[i] = i;
         return SEXTANS_OK;
     }
-    int *d_tab = nullptr;
-    SX_HIP(hipMalloc((void **)&d_tab, sizeof(int) * (size_t)std::max(h->M, 1)));
+    DevBuf<int> d_tab;
+    SX_HIP(d_tab.alloc((size_t)std::max(h->M, 1)));
     cc_table(h, 0, d_tab, nullptr);
-    const hipError_t e = hipMemcpy(order, d_tab, sizeof(int) * (size_t)h->M, hipMemcpyDeviceToHost);
-    (void)hipFree(d_tab);
-    SX_HIP(e);
+    SX_HIP(hipMemcpy(order, d_tab, sizeof(int) * (size_t)h->M, hipMemcpyDeviceToHost));
     return SEXTANS_OK;
 }
 

@@ -14,9 +14,7 @@
 namespace sxe {
 
 void free_bell(sextans_engine *h) {
-    (void)hipFree(h->d_bell_col_owned); (void)hipFree(h->d_bell_Af);
-    h->d_bell_col_owned = nullptr; h->d_bell_col = nullptr; h->d_bell_Af = nullptr;
-    h->bell_M = h->bell_K = h->bell_W = 0;
+    h->bell = {};
 }
 
 // "MFMA only where a tile is actually dense" (north_star).  Counts the 32x32 tiles of the main matrix whose fill
@@ -86,8 +84,8 @@ int build_rowblocks(sextans_engine *h) {
             gptr.push_back((int)total);
             routed_nnz += (int64_t)rp[(size_t)16 * b + 16] - rp[(size_t)16 * b];
         }
-    h->dense_tiles = (int64_t)row0.size();
-    h->dense_nnz = routed_nnz;
+    h->dense.tiles = (int64_t)row0.size();
+    h->dense.nnz = routed_nnz;
     if (row0.empty()) return SEXTANS_OK;
     std::vector<int> gcol((size_t)total);
     {
@@ -103,9 +101,9 @@ int build_rowblocks(sextans_engine *h) {
             });
         for (auto &t : ts) t.join();
     }
-    if (int rc = upload(&h->d_rb_row0, row0)) return rc;
-    if (int rc = upload(&h->d_rb_gptr, gptr)) return rc;
-    if (int rc = upload(&h->d_rb_gcol, gcol)) return rc;
+    if (int rc = upload(h->dense.d_rb_row0, row0)) return rc;
+    if (int rc = upload(h->dense.d_rb_gptr, gptr)) return rc;
+    if (int rc = upload(h->dense.d_rb_gcol, gcol)) return rc;
     {   // super blocks of 4 routed blocks: the ascending union of their groups + who owns each (the kernel loads a B fragment once per entry)
         const int nrb = (int)row0.size(), nsb = (nrb + 3) / 4;
         std::vector<int> ucount((size_t)nsb, 0);
@@ -145,15 +143,15 @@ int build_rowblocks(sextans_engine *h) {
         parallel_sb([&](int sb) { merge4(sb, ucol.data() + uptr[(size_t)sb], umask.data() + uptr[(size_t)sb]); });
         std::vector<int> uent(2 * ucol.size());   // {column group, owner mask} pairs: one 8-byte scalar load per entry
         for (size_t k = 0; k < ucol.size(); ++k) { uent[2 * k] = ucol[k]; uent[2 * k + 1] = umask[k]; }
-        if (int rc = upload(&h->d_sb_uptr, uptr)) return rc;
-        if (int rc = upload(&h->d_sb_ucol, uent)) return rc;
-        h->sb_n = nsb;
-        h->sb_entries = uptr[(size_t)nsb];
+        if (int rc = upload(h->dense.d_sb_uptr, uptr)) return rc;
+        if (int rc = upload(h->dense.d_sb_ucol, uent)) return rc;
+        h->dense.sb_n = nsb;
+        h->dense.sb_entries = uptr[(size_t)nsb];
     }
-    SX_HIP(hipMalloc((void **)&h->d_rb_A, sizeof(float) * 64 * (size_t)total));
-    SX_HIP(hipMemsetAsync(h->d_rb_A, 0, sizeof(float) * 64 * (size_t)total, hipStreamPerThread));
-    hipLaunchKernelGGL(sx::rowblock_fill_fragments, dim3((unsigned)((row0.size() + 3) / 4)), dim3(256), 0, hipStreamPerThread, h->d_rp, h->d_ci, h->d_v, h->d_rb_row0,
-                       h->d_rb_gptr, h->d_rb_gcol, h->d_rb_A, (int)row0.size());
+    SX_HIP(h->dense.d_rb_A.alloc(64 * (size_t)total));
+    SX_HIP(hipMemsetAsync(h->dense.d_rb_A, 0, sizeof(float) * 64 * (size_t)total, hipStreamPerThread));
+    hipLaunchKernelGGL(sx::rowblock_fill_fragments, dim3((unsigned)((row0.size() + 3) / 4)), dim3(256), 0, hipStreamPerThread, h->d_rp, h->d_ci, h->d_v, h->dense.d_rb_row0,
+                       h->dense.d_rb_gptr, h->dense.d_rb_gcol, h->dense.d_rb_A, (int)row0.size());
     SX_HIP(hipStreamSynchronize(hipStreamPerThread));
     // the remainder: routed rows emptied, as the source matrix of the long-row split
     std::vector<int> mrp((size_t)h->M + 1, 0);
@@ -171,22 +169,22 @@ int build_rowblocks(sextans_engine *h) {
         mrp[(size_t)r + 1] = (int)w;
     }
     ci.resize(w ? w : 1); va.resize(w ? w : 1);
-    if (int rc = upload(&h->d_srp, mrp)) return rc;
-    if (int rc = upload(&h->d_sci, ci)) return rc;
-    if (int rc = upload(&h->d_sv, va)) return rc;
-    h->s_rp = h->d_srp; h->s_ci = h->d_sci; h->s_v = h->d_sv; h->s_nnz = (int64_t)w;
+    if (int rc = upload(h->dense.d_srp, mrp)) return rc;
+    if (int rc = upload(h->dense.d_sci, ci)) return rc;
+    if (int rc = upload(h->dense.d_sv, va)) return rc;
+    h->s_rp = h->dense.d_srp; h->s_ci = h->dense.d_sci; h->s_v = h->dense.d_sv; h->s_nnz = (int64_t)w;
     h->m_rp = h->s_rp; h->m_ci = h->s_ci; h->m_v = h->s_v; h->m_nnz = h->s_nnz;
-    h->rb_n = (int)row0.size();
-    h->rb_groups = total;
+    h->dense.rb_n = (int)row0.size();
+    h->dense.rb_groups = total;
     return SEXTANS_OK;
 }
 
 int mark_rowblock_skip(sextans_engine *h) {
-    if (!h->d_skip) {
-        SX_HIP(hipMalloc((void **)&h->d_skip, (size_t)std::max(h->M, 1)));
-        SX_HIP(hipMemsetAsync(h->d_skip, 0, (size_t)std::max(h->M, 1), hipStreamPerThread));
+    if (!h->split.d_skip) {
+        SX_HIP(h->split.d_skip.alloc((size_t)std::max(h->M, 1)));
+        SX_HIP(hipMemsetAsync(h->split.d_skip, 0, (size_t)std::max(h->M, 1), hipStreamPerThread));
     }
-    hipLaunchKernelGGL(sx::rowblock_mark_skip, dim3((unsigned)(((int64_t)h->rb_n * 16 + 255) / 256)), dim3(256), 0, hipStreamPerThread, h->d_rb_row0, h->rb_n, h->d_skip);
+    hipLaunchKernelGGL(sx::rowblock_mark_skip, dim3((unsigned)(((int64_t)h->dense.rb_n * 16 + 255) / 256)), dim3(256), 0, hipStreamPerThread, h->dense.d_rb_row0, h->dense.rb_n, h->split.d_skip);
     SX_HIP(hipStreamSynchronize(hipStreamPerThread));
     return SEXTANS_OK;
 }
@@ -205,8 +203,8 @@ int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const floa
         auto go = [&](auto T) {
             constexpr int NT = decltype(T)::value;
             const int tgs = (tiles16 + NT - 1) / NT;
-            hipLaunchKernelGGL(sx::spmm_rowblock_mfma_f32<NT>, dim3((unsigned)((h->sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, s, h->d_rb_row0, h->d_rb_gptr, h->d_sb_uptr,
-                               (const int2 *)h->d_sb_ucol, h->d_rb_A, bp, (int64_t)h->K * g.width, g.width, h->K, cin, ldc_in, cout, ldc, h->rb_n, h->sb_n,
+            hipLaunchKernelGGL(sx::spmm_rowblock_mfma_f32<NT>, dim3((unsigned)((h->dense.sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, s, h->dense.d_rb_row0, h->dense.d_rb_gptr, h->dense.d_sb_uptr,
+                               (const int2 *)h->dense.d_sb_ucol.get(), h->dense.d_rb_A, bp, (int64_t)h->K * g.width, g.width, h->K, cin, ldc_in, cout, ldc, h->dense.rb_n, h->dense.sb_n,
                                tgs, ncols_panel, ncols, row_begin, row_end, alpha, beta);
         };
         // (a wavefront owns 64 rows x 16 NT columns of C: 16 NT accumulator registers.  NT = 2 = 4 wavefronts per SIMD measured 2 - 4 % ahead of
@@ -218,16 +216,16 @@ int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const floa
 }
 
 int ensure_dense(sextans_engine *h) {
-    if (h->dense_built_mfma == h->opt_mfma_dense && h->dense_built_fill == h->opt_dense_fill_x100) return SEXTANS_OK;
-    if (h->dense_W > 0 || h->rb_n > 0 || h->opt_mfma_dense) {   // the source matrix may change: everything downstream starts again
+    if (h->dense.built_mfma == h->opt_mfma_dense && h->dense.built_fill == h->opt_dense_fill_x100) return SEXTANS_OK;
+    if (h->dense.W > 0 || h->dense.rb_n > 0 || h->opt_mfma_dense) {   // the source matrix may change: everything downstream starts again
         free_plan(h);
         free_window(h);
     }
-    const bool had_tiles = h->dense_W > 0 || h->rb_n > 0;
+    const bool had_tiles = h->dense.W > 0 || h->dense.rb_n > 0;
     if (had_tiles || h->opt_mfma_dense) free_dense(h);
-    else { h->dense_tiles = h->dense_nnz = 0; }
-    h->dense_built_mfma = h->opt_mfma_dense;
-    h->dense_built_fill = h->opt_dense_fill_x100;
+    else { h->dense.tiles = h->dense.nnz = 0; }
+    h->dense.built_mfma = h->opt_mfma_dense;
+    h->dense.built_fill = h->opt_dense_fill_x100;
     if (h->opt_mfma_dense == 2) return build_rowblocks(h);
     const int mb = h->M / 32;
     if (mb == 0 || h->nnz == 0) return SEXTANS_OK;
@@ -267,8 +265,8 @@ int ensure_dense(sextans_engine *h) {
             }
         }
         // scaled to the whole matrix
-        h->dense_nnz = tot ? (int64_t)((double)in_dense / (double)tot * (double)h->nnz) : 0;
-        h->dense_tiles = (int64_t)((double)tiles * (double)mb / (double)nsample);
+        h->dense.nnz = tot ? (int64_t)((double)in_dense / (double)tot * (double)h->nnz) : 0;
+        h->dense.tiles = (int64_t)((double)tiles * (double)mb / (double)nsample);
         return SEXTANS_OK;
     }
     if (int rc = read_back_entries(h, ci, va, 0)) return rc;
@@ -287,11 +285,11 @@ int ensure_dense(sextans_engine *h) {
             while (b < cols.size() && cols[b] == cols[a]) ++b;
             if ((int64_t)(b - a) >= thr && dense[(size_t)br].size() < 256) {
                 dense[(size_t)br].push_back(cols[a]);
-                h->dense_nnz += (int64_t)(b - a);
+                h->dense.nnz += (int64_t)(b - a);
             }
             a = b;
         }
-        h->dense_tiles += (int64_t)dense[(size_t)br].size();
+        h->dense.tiles += (int64_t)dense[(size_t)br].size();
         W = std::max(W, (int)dense[(size_t)br].size());
     }
     if (W == 0) return SEXTANS_OK;   // nothing to route
@@ -344,34 +342,33 @@ int ensure_dense(sextans_engine *h) {
     std::vector<float>().swap(blk);
     ci.resize(w ? w : 1); va.resize(w ? w : 1);
     // the remainder becomes the source matrix of the long-row split (which has not run yet for this source)
-    if (int rc = upload(&h->d_srp, mrp)) return rc;
-    if (int rc = upload(&h->d_sci, ci)) return rc;
-    if (int rc = upload(&h->d_sv, va)) return rc;
-    h->s_rp = h->d_srp; h->s_ci = h->d_sci; h->s_v = h->d_sv; h->s_nnz = (int64_t)w;
+    if (int rc = upload(h->dense.d_srp, mrp)) return rc;
+    if (int rc = upload(h->dense.d_sci, ci)) return rc;
+    if (int rc = upload(h->dense.d_sv, va)) return rc;
+    h->s_rp = h->dense.d_srp; h->s_ci = h->dense.d_sci; h->s_v = h->dense.d_sv; h->s_nnz = (int64_t)w;
     h->m_rp = h->s_rp; h->m_ci = h->s_ci; h->m_v = h->s_v; h->m_nnz = h->s_nnz;
-    if (int rc = upload(&h->d_dense_col, bcol)) return rc;
-    uint16_t *d_val = nullptr;
-    SX_HIP(hipMalloc((void **)&d_val, bval.size() * 2));
+    if (int rc = upload(h->dense.d_dense_col, bcol)) return rc;
+    DevBuf<uint16_t> d_val;
+    SX_HIP(d_val.alloc(bval.size()));
     SX_HIP(hipMemcpy(d_val, bval.data(), bval.size() * 2, hipMemcpyHostToDevice));
     const int64_t nslots = (int64_t)mb * W;
-    SX_HIP(hipMalloc(&h->d_dense_Af, (size_t)nslots * 2048));
+    SX_HIP(h->dense.d_dense_Af.alloc((size_t)nslots * 2048));
     hipLaunchKernelGGL(sx::bell_repack_a, dim3((unsigned)((nslots * 128 + 255) / 256)), dim3(256), 0, nullptr, d_val,
-                       (sx::u32x4 *)h->d_dense_Af, nslots);
+                       (sx::u32x4 *)h->dense.d_dense_Af.get(), nslots);
     SX_HIP(hipDeviceSynchronize());
-    (void)hipFree(d_val);
-    h->dense_mb = mb;
-    h->dense_W = W;
+    d_val.reset();
+    h->dense.mb = mb;
+    h->dense.W = W;
     {   // do neighbouring block rows share tile columns (block-diagonal / banded dense structure)?  Then N = 256 runs the
         // LDS-shared MFMA kernel
-        unsigned long long *d_cnt = nullptr, h_cnt[4] = {0, 0, 0, 0};
-        SX_HIP(hipMalloc((void **)&d_cnt, 4 * sizeof(unsigned long long)));
+        DevBuf<unsigned long long> d_cnt;
+        unsigned long long h_cnt[4] = {0, 0, 0, 0};
+        SX_HIP(d_cnt.alloc(4));
         SX_HIP(hipMemset(d_cnt, 0, 4 * sizeof(unsigned long long)));
         const int groups = (mb + sx::kShRows - 1) / sx::kShRows;
-        hipLaunchKernelGGL(sx::bell_union_count, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, nullptr, h->d_dense_col, mb, W,
+        hipLaunchKernelGGL(sx::bell_union_count, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, nullptr, h->dense.d_dense_col, mb, W,
                            d_cnt, d_cnt + 1, d_cnt + 2, d_cnt + 3);
-        const hipError_t e = hipMemcpy(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost);
-        (void)hipFree(d_cnt);
-        SX_HIP(e);
+        SX_HIP(hipMemcpy(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost));
         h->dense_share = h_cnt[0] ? (double)h_cnt[1] / (double)h_cnt[0] : 0.0;
         h->dense_max_union = h_cnt[3] ? 0x7fffffff : (int)h_cnt[2];
     }
@@ -393,22 +390,22 @@ int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, 
         const int kblocks = (h->K + 31) / 32, ntiles = N / 32;
         const int64_t threads = (int64_t)kblocks * ntiles * 128;
         hipLaunchKernelGGL(sx::bell_repack_b_f32, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_B, ldb, h->K,
-                           (sx::u32x4 *)h->d_bell_Bf, kblocks, ntiles);
-        const auto *Af = (const sx::bf16x8 *)h->d_dense_Af;
-        const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf;
-        const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->dense_W <= sx::kShMaxRowCols &&
+                           (sx::u32x4 *)h->d_bell_Bf.get(), kblocks, ntiles);
+        const auto *Af = (const sx::bf16x8 *)h->dense.d_dense_Af.get();
+        const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf.get();
+        const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->dense.W <= sx::kShMaxRowCols &&
                             h->dense_max_union <= sx::kShMaxUnion && (h->opt_bell_shared == 1 || h->dense_share >= 1.5);
         if (shared) {
             constexpr size_t lds = (size_t)sx::kShRing * sx::kShTileBytes + (size_t)(sx::kShMaxUnion + 8) * (sizeof(int) + sx::kShRows * sizeof(short)) +
                                    (size_t)sx::kShMaxRowCols * sizeof(int);
             if (int rc = allow_big_lds(h, reinterpret_cast<const void *>(sx::spmm_bell_mfma_shared), (int)lds)) return rc;
-            hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((h->dense_mb + sx::kShRows - 1) / sx::kShRows)),
-                               dim3(sx::kShThreads), lds, s, h->d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense_mb, h->dense_W,
+            hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((h->dense.mb + sx::kShRows - 1) / sx::kShRows)),
+                               dim3(sx::kShThreads), lds, s, h->dense.d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense.mb, h->dense.W,
                                alpha, beta, 0);
         } else {
-            launch_bell_mfma(h->d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense_mb, h->dense_W, ntiles, alpha, beta, s);
+            launch_bell_mfma(h->dense.d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense.mb, h->dense.W, ntiles, alpha, beta, s);
         }
-        const int row0 = h->dense_mb * 32;
+        const int row0 = h->dense.mb * 32;
         if (row0 < h->M) {
             const int64_t tot = (int64_t)(h->M - row0) * N;
             hipLaunchKernelGGL(sx::scale_tail_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, d_C_in, ldc_in,
@@ -430,24 +427,23 @@ int sextans_set_matrix_bell_device(sextans_handle_t h, int M, int K, int ell_wid
     SX_HIP(hipSetDevice(h->device));
     free_bell(h);
     const int64_t nslots = (int64_t)(M / 32) * ell_width;
-    SX_HIP(hipMalloc(&h->d_bell_Af, (size_t)nslots * 2048));
+    SX_HIP(h->bell.d_bell_Af.alloc((size_t)nslots * 2048));
     const int64_t threads = nslots * 128;
     hipLaunchKernelGGL(sx::bell_repack_a, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, nullptr,
-                       d_block_val, (sx::u32x4 *)h->d_bell_Af, nslots);
+                       d_block_val, (sx::u32x4 *)h->bell.d_bell_Af.get(), nslots);
     SX_HIP(hipDeviceSynchronize());
-    h->d_bell_col = d_block_col;
-    h->bell_M = M; h->bell_K = K; h->bell_W = ell_width;
+    h->bell.d_bell_col = d_block_col;
+    h->bell.M = M; h->bell.K = K; h->bell.W = ell_width;
     {   // do the block rows of a workgroup share block columns?  (decides between the per-wavefront kernels and the
         // LDS-shared one, "MFMA only where a tile is actually dense" + reuse)
-        unsigned long long *d_cnt = nullptr, h_cnt[4] = {0, 0, 0, 0};
-        SX_HIP(hipMalloc((void **)&d_cnt, 4 * sizeof(unsigned long long)));
+        DevBuf<unsigned long long> d_cnt;
+        unsigned long long h_cnt[4] = {0, 0, 0, 0};
+        SX_HIP(d_cnt.alloc(4));
         SX_HIP(hipMemset(d_cnt, 0, 4 * sizeof(unsigned long long)));
         const int groups = (M / 32 + sx::kShRows - 1) / sx::kShRows;
         hipLaunchKernelGGL(sx::bell_union_count, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, nullptr, d_block_col, M / 32,
                            ell_width, d_cnt, d_cnt + 1, d_cnt + 2, d_cnt + 3);
-        const hipError_t e = hipMemcpy(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost);
-        (void)hipFree(d_cnt);
-        SX_HIP(e);
+        SX_HIP(hipMemcpy(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost));
         h->bell_share = h_cnt[0] ? (double)h_cnt[1] / (double)h_cnt[0] : 0.0;
         h->bell_max_union = h_cnt[3] ? 0x7fffffff : (int)h_cnt[2];   // duplicate / unsorted block columns: never the shared kernel
         if (h_cnt[3]) h->bell_share = 0.0;
@@ -461,16 +457,15 @@ int sextans_set_matrix_bell(sextans_handle_t h, int M, int K, int ell_width, con
         return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
     const size_t nslots = (size_t)(M / 32) * (size_t)ell_width;
-    int *d_col = nullptr;
-    uint16_t *d_val = nullptr;
-    SX_HIP(hipMalloc((void **)&d_col, nslots * sizeof(int)));
-    SX_HIP(hipMalloc((void **)&d_val, nslots * 2048));
+    DevBuf<int> d_col;
+    DevBuf<uint16_t> d_val;
+    SX_HIP(d_col.alloc(nslots));
+    SX_HIP(d_val.alloc(nslots * 1024));
     SX_HIP(hipMemcpy(d_col, block_col, nslots * sizeof(int), hipMemcpyHostToDevice));
     SX_HIP(hipMemcpy(d_val, block_val, nslots * 2048, hipMemcpyHostToDevice));
     int rc = sextans_set_matrix_bell_device(h, M, K, ell_width, d_col, d_val);
-    (void)hipFree(d_val);
-    if (rc) { (void)hipFree(d_col); return rc; }
-    h->d_bell_col_owned = d_col;
+    if (rc) return rc;
+    h->bell.d_bell_col_owned = std::move(d_col);   // (d_bell_col points here)
     return SEXTANS_OK;
 }
 
@@ -484,29 +479,24 @@ int sextans_spmm_bell_device(sextans_handle_t h, int N, float alpha, const uint1
 int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const float *d_C_in,
                               int64_t ldc_in, float *d_C_out, int64_t ldc, void *stream) {
     if (!h || N <= 0 || (N % 32) || !d_B || !d_C_in || !d_C_out) return SEXTANS_ERR_INVALID;
-    if (!h->d_bell_Af) return SEXTANS_ERR_STATE;
-    if (ldb < h->bell_K || (ldb % 8) || ldc < h->bell_M || ldc_in < h->bell_M) return SEXTANS_ERR_INVALID;
+    if (!h->bell.d_bell_Af) return SEXTANS_ERR_STATE;
+    if (ldb < h->bell.K || (ldb % 8) || ldc < h->bell.M || ldc_in < h->bell.M) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    const int kblocks = h->bell_K / 32, mblocks = h->bell_M / 32, ntiles = N / 32;
-    const size_t need = (size_t)h->bell_K * (size_t)N * 2;
-    if (h->bell_Bf_cap < need) {
-        if (h->d_bell_Bf) SX_HIP(hipFree(h->d_bell_Bf));
-        h->d_bell_Bf = nullptr; h->bell_Bf_cap = 0;
-        SX_HIP(hipMalloc(&h->d_bell_Bf, need));
-        h->bell_Bf_cap = need;
-    }
+    const int kblocks = h->bell.K / 32, mblocks = h->bell.M / 32, ntiles = N / 32;
+    const size_t need = (size_t)h->bell.K * (size_t)N * 2;
+    SX_HIP(h->d_bell_Bf.reserve(need));
     {
         Prof p(h, &h->ev_repack, s);
         const int64_t threads = (int64_t)kblocks * ntiles * 128;
         hipLaunchKernelGGL(sx::bell_repack_b, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_B,
-                           ldb, (sx::u32x4 *)h->d_bell_Bf, kblocks, ntiles);
+                           ldb, (sx::u32x4 *)h->d_bell_Bf.get(), kblocks, ntiles);
     }
     {
         Prof p(h, &h->ev_kernel, s);
-        const auto *Af = (const sx::bf16x8 *)h->d_bell_Af;
-        const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf;
-        const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->bell_W <= sx::kShMaxRowCols &&
+        const auto *Af = (const sx::bf16x8 *)h->bell.d_bell_Af.get();
+        const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf.get();
+        const bool shared = ntiles == 8 && h->opt_bell_shared != 0 && sx::kShRows * h->bell.W <= sx::kShMaxRowCols &&
                             h->bell_max_union <= sx::kShMaxUnion &&
                             (h->opt_bell_shared == 1 || h->bell_share >= 1.5);
         if (shared) {
@@ -514,7 +504,7 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
                                   (size_t)sx::kShMaxRowCols * sizeof(int);
             if (int rc = allow_big_lds(h, reinterpret_cast<const void *>(sx::spmm_bell_mfma_shared), (int)lds)) return rc;
             hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((mblocks + sx::kShRows - 1) / sx::kShRows)), dim3(sx::kShThreads), lds,
-                               s, h->d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell_W, alpha, beta, (int)h->opt_bell_debug);
+                               s, h->bell.d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell.W, alpha, beta, (int)h->opt_bell_debug);
             h->last_kernel = "spmm_bell_mfma_shared";
             SX_HIP(hipGetLastError());
             return SEXTANS_OK;
@@ -524,11 +514,11 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
             const int G = h->opt_bell_gen > 0 ? (int)h->opt_bell_gen : mblocks;
             for (int b0 = 0; b0 < mblocks; b0 += G) {
                 const int nb = std::min(G, mblocks - b0);
-                hipLaunchKernelGGL(sx::spmm_bell_mfma_n256, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->d_bell_col, Af,
-                                   Bf, d_C_in, ldc_in, d_C_out, ldc, std::min(mblocks, b0 + nb), h->bell_W, alpha, beta, b0);
+                hipLaunchKernelGGL(sx::spmm_bell_mfma_n256, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->bell.d_bell_col, Af,
+                                   Bf, d_C_in, ldc_in, d_C_out, ldc, std::min(mblocks, b0 + nb), h->bell.W, alpha, beta, b0);
             }
         } else {
-            launch_bell_mfma(h->d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell_W, ntiles, alpha, beta, s);
+            launch_bell_mfma(h->bell.d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell.W, ntiles, alpha, beta, s);
         }
         h->last_kernel = "spmm_bell_mfma";
     }

@@ -35,24 +35,24 @@ __global__ __launch_bounds__(256) void position_rows(int nblk, int RB, const int
 }  // namespace
 
 static bool cc_usable(sextans_engine *h, int N, const Tiling &t) {
-    return h->cluster_state == 2 && h->cluster_cm_pays && t.W == 16 && N % 16 == 0 && t.segs.size() == 1 && t.segs[0].width == 16 && h->nhub == 0 &&
-           h->nchain == 0 && csr_only(h) && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->d_Cs && h->d_slot_row &&
-           h->Cs_cap >= (size_t)(N / 16) * (size_t)h->M * 16 && h->Bp_cap >= (size_t)h->K * (size_t)N && h->psc.plan_sets == 1 &&
-           (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)) && (int)h->psc.h_blk_row.size() == h->psc.plan_nblk + 1;
+    return h->cluster.state == 2 && h->cluster.cm_pays && t.W == 16 && N % 16 == 0 && t.segs.size() == 1 && t.segs[0].width == 16 && h->split.nhub == 0 &&
+           h->split.nchain == 0 && csr_only(h) && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->d_Cs && h->cluster.d_slot_row &&
+           h->d_Cs.size() >= (size_t)(N / 16) * (size_t)h->M * 16 && h->d_Bp.size() >= (size_t)h->K * (size_t)N && h->cluster.psc.plan_sets == 1 &&
+           (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)) && (int)h->cluster.psc.h_blk_row.size() == h->cluster.psc.plan_nblk + 1;
 }
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s) {
-    const int slots = kBlock / 4 * std::max(1, h->psc.plan_sets);   // (grid-brick plans of short-row matrices: two row sets per block)
-    hipLaunchKernelGGL(position_rows, dim3((unsigned)h->psc.plan_nblk), dim3((unsigned)slots), 0, s, h->psc.plan_nblk, slots, h->psc.d_blk_row, h->d_slot_row, row0, d_out);
+    const int slots = kBlock / 4 * std::max(1, h->cluster.psc.plan_sets);   // (grid-brick plans of short-row matrices: two row sets per block)
+    hipLaunchKernelGGL(position_rows, dim3((unsigned)h->cluster.psc.plan_nblk), dim3((unsigned)slots), 0, s, h->cluster.psc.plan_nblk, slots, h->cluster.psc.d_blk_row, h->cluster.d_slot_row, row0, d_out);
 }
 static void cc_pre(sextans_engine *h, int N, const float *d_B, int64_t ldb, const float *d_C_in_slab, int64_t ldc_in, hipStream_t s) {
     Prof p(h, &h->ev_repack, s);
-    if (h->d_colpos) launch_repack_perm(h, d_B, ldb, h->d_Bp, 0, N / 16, N, s);
-    else launch_repack(16, d_B, ldb, h->d_Bp, h->K, 0, N / 16, s, h->col_lo, h->col_hi, -1, h->d_touched);
+    if (h->cluster.d_colpos) launch_repack_perm(h, d_B, ldb, h->d_Bp, 0, N / 16, N, s);
+    else launch_repack(16, d_B, ldb, h->d_Bp, h->K, 0, N / 16, s, h->col_lo, h->col_hi, -1, h->mat.d_touched);
     launch_repack(16, d_C_in_slab, ldc_in, h->d_Cs, h->M, 0, N / 16, s);
     h->bp_layout = -16;
 }
 static int cc_chunk(sextans_engine *h, int N, float alpha, float beta, int b0, int b1, const int *d_rows, int row0, float *slab, int64_t lmax, hipStream_t s) {
-    const int p0 = h->psc.h_blk_row[(size_t)b0], p1 = h->psc.h_blk_row[(size_t)b1];
+    const int p0 = h->cluster.psc.h_blk_row[(size_t)b0], p1 = h->cluster.psc.h_blk_row[(size_t)b1];
     if (p1 <= p0) return SEXTANS_OK;
     Prof p(h, &h->ev_kernel, s);
     launch_slab_rows(false, h->d_Cs, (int64_t)h->M * 16, d_rows + p0, row0, p1 - p0, slab, lmax * 16, N / 16, s);
@@ -153,13 +153,13 @@ int exchange(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     std::vector<int> me(per, 0), buf(per * (size_t)world, 0);
     for (int i = 0; i < n; ++i) me[(size_t)i] = status ? 0 : mine[i];
     me[(size_t)n] = status;
-    int *d = nullptr;
-    SX_HIP(hipMalloc((void **)&d, sizeof(int) * buf.size()));
+    DevBuf<int> d;
+    SX_HIP(d.alloc(buf.size()));
     hipError_t e0 = hipMemcpyAsync(d + per * (size_t)rank, me.data(), sizeof(int) * per, hipMemcpyHostToDevice, s);
     const int rc = e0 != hipSuccess ? SEXTANS_OK : rccl_check(r->AllGather(d + per * (size_t)rank, d, per, 2 /* ncclInt32 */, comm, s), what);
     hipError_t e1 = (rc || e0 != hipSuccess) ? hipSuccess : hipMemcpyAsync(buf.data(), d, sizeof(int) * buf.size(), hipMemcpyDeviceToHost, s);
     hipError_t e2 = hipStreamSynchronize(s);
-    (void)hipFree(d);
+    d.reset();
     if (rc) return rc;
     SX_HIP(e0);
     SX_HIP(e1);
@@ -254,7 +254,7 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     } else if (h->M > 0) {   // (whole-slab calls: the plan is built here, not inside the first launch)
         st = prepare(h, N);
     }
-    if (want_cc && h->psc.plan_nblk < nchunks) want_cc = false;
+    if (want_cc && h->cluster.psc.plan_nblk < nchunks) want_cc = false;
     // Chunk c of rank g = local rows [cuts[g][c], cuts[g][c+1]).  Every rank snaps its OWN interior cuts to the
     // boundaries its kernels want (sextans_align_row: row blocks of the LDS-panel plan, wavefronts of the window kernel,
     // so every chunk keeps the whole-matrix kernel) and the cut positions are exchanged once per (partition, N, chunk
@@ -264,11 +264,8 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     if (force || h->dist_cut_key != key || st) {
         h->dist_cut_key.clear();
         const size_t need = (size_t)world * (size_t)p.m_max;
-        if (!st && want_cc && h->dist_rows_cap < need) {   // every rank's position -> global row table: [world][m_max] ints (allocated before the flag exchange carries the status)
-            (void)hipFree(h->d_dist_rows);
-            h->d_dist_rows = nullptr; h->dist_rows_cap = 0;
-            if (hipMalloc((void **)&h->d_dist_rows, sizeof(int) * std::max<size_t>(need, 1)) != hipSuccess) { (void)hipGetLastError(); st = SEXTANS_ERR_HIP; g_last_error = "hipMalloc(row tables) failed"; }
-            else h->dist_rows_cap = need;
+        if (!st && want_cc && h->d_dist_rows.size() < need) {   // every rank's position -> global row table: [world][m_max] ints (allocated before the flag exchange carries the status)
+            if (h->d_dist_rows.alloc(need) != hipSuccess) { (void)hipGetLastError(); st = SEXTANS_ERR_HIP; g_last_error = "hipMalloc(row tables) failed"; }
         }
         bool all_cc = want_cc && !st;
         if (comm) {   // does every rank want clustered-order chunks?  (one int per rank)
@@ -294,7 +291,7 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
         mine[(size_t)nchunks] = p.m_loc;
         for (int c = 1; c < nchunks && !st; ++c) {
             if (all_cc) {   // positions of the clustered order at block boundaries
-                mine[(size_t)c] = h->psc.h_blk_row[(size_t)((int64_t)h->psc.plan_nblk * c / nchunks)];
+                mine[(size_t)c] = h->cluster.psc.h_blk_row[(size_t)((int64_t)h->cluster.psc.plan_nblk * c / nchunks)];
                 continue;
             }
             int a = (int)((int64_t)p.m_loc * c / nchunks);
@@ -328,8 +325,8 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
         }
         // staging + per-chunk {row0, len} tables (ints, kept behind the float staging area)
         const size_t meta_floats = (size_t)nchunks * (size_t)world * 2;
-        if (h->stage_cap < (size_t)out.off[(size_t)nchunks] + meta_floats) h->dist_meta_at = nullptr;   // new buffer: tables gone
-        if (int rc = ensure(&h->d_stage, &h->stage_cap, (size_t)out.off[(size_t)nchunks] + meta_floats)) return rc;
+        if (h->d_stage.size() < (size_t)out.off[(size_t)nchunks] + meta_floats) h->dist_meta_at = nullptr;   // new buffer: tables gone
+        if (int rc = reserve(h->d_stage, (size_t)out.off[(size_t)nchunks] + meta_floats)) return rc;
         if (!h->comm_stream) SX_HIP(hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
         while (h->dist_events.size() < (size_t)nchunks + 1) {
             hipEvent_t e;
@@ -352,7 +349,7 @@ int setup_cm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
         }
         out.cc = h->dist_cc;
         if (out.cc)   // row-major staging of the whole C: received slabs are scattered into it, one streaming pass writes column-major C at the end
-            if (int rc = ensure(&h->d_Cfull, &h->Cfull_cap, (size_t)p.M_total * (size_t)N)) return rc;
+            if (int rc = reserve(h->d_Cfull, (size_t)p.M_total * (size_t)N)) return rc;
         return SEXTANS_OK;
     };
     if (!st) st = workspaces();
@@ -371,7 +368,7 @@ int setup_rm(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const 
     if (force && h->M > 0)   // (the lazy form leaves the plan to sextans_spmm_device_rm, which builds it the same way)
         st = rm_plan(h, N, s);
     if (!st && packed && comm) {
-        st = ensure(&h->d_stage, &h->stage_cap, (size_t)p.M_total * (size_t)N);
+        st = reserve(h->d_stage, (size_t)p.M_total * (size_t)N);
         h->dist_meta_at = nullptr;   // (the column-major form keeps its row tables behind its staging area)
     }
     return settle(h, r, comm, world, rank, st, exchanged || (force && comm), s);
@@ -387,15 +384,15 @@ struct BellSetup {
 int setup_bell(sextans_engine *h, Rccl *r, void *comm, int world, int rank, const int *row_ranges, int N, hipStream_t s, bool force, BellSetup &out) {
     int st = read_partition(world, rank, row_ranges, 32, out.p);
     const Partition &p = out.p;
-    if (!st && p.m_loc != h->bell_M) st = SEXTANS_ERR_INVALID;
-    if (!st && !h->d_bell_Af) st = SEXTANS_ERR_STATE;
+    if (!st && p.m_loc != h->bell.M) st = SEXTANS_ERR_INVALID;
+    if (!st && !h->bell.d_bell_Af) st = SEXTANS_ERR_STATE;
     if (st && !(force && comm)) return st;
     auto workspaces = [&]() -> int {
         out.lmax = std::max<int64_t>(1, p.m_max);
         out.slab = (size_t)N * (size_t)out.lmax;
         const size_t meta_floats = (size_t)world * 2;
-        if (h->stage_cap < (size_t)world * out.slab + meta_floats) h->dist_meta_at = nullptr;
-        if (int rc = ensure(&h->d_stage, &h->stage_cap, (size_t)world * out.slab + meta_floats)) return rc;
+        if (h->d_stage.size() < (size_t)world * out.slab + meta_floats) h->dist_meta_at = nullptr;
+        if (int rc = reserve(h->d_stage, (size_t)world * out.slab + meta_floats)) return rc;
         std::vector<int> meta(meta_floats);
         for (int g = 0; g < world; ++g) { meta[2 * (size_t)g] = row_ranges[2 * g]; meta[2 * (size_t)g + 1] = row_ranges[2 * g + 1] - row_ranges[2 * g]; }
         out.d_meta = reinterpret_cast<int *>(h->d_stage + (size_t)world * out.slab);
@@ -514,7 +511,7 @@ int sextans_dist_spmm(sextans_handle_t h, void *comm, int world, int rank, const
         if (cc) {
             if (first) cc_pre(h, N, d_B, ldb, d_C_in + row0, ldc_in, s);
             first = false;
-            const int b0 = (int)((int64_t)h->psc.plan_nblk * c / nchunks), b1 = c + 1 == nchunks ? h->psc.plan_nblk : (int)((int64_t)h->psc.plan_nblk * (c + 1) / nchunks);
+            const int b0 = (int)((int64_t)h->cluster.psc.plan_nblk * c / nchunks), b1 = c + 1 == nchunks ? h->cluster.psc.plan_nblk : (int)((int64_t)h->cluster.psc.plan_nblk * (c + 1) / nchunks);
             if (int rc = cc_chunk(h, N, alpha, beta, b0, b1, h->d_dist_rows + (size_t)rank * m_max, row0, mine, lmax[(size_t)c], s)) return rc;
         } else if (c1 > c0) {
             if (int rc = sextans_spmm_device_rows(h, N, alpha, d_B, ldb, beta, d_C_in + row0 + c0, ldc_in, mine,
@@ -622,7 +619,7 @@ int sextans_dist_spmm_rm(sextans_handle_t h, void *comm, int world, int rank, co
 int sextans_dist_spmm_bell(sextans_handle_t h, void *comm, int world, int rank, const int *row_ranges, int N, float alpha, const uint16_t *d_B,
                            int64_t ldb, float beta, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, void *stream) {
     if (!dist_args_ok(h, comm, world, rank, row_ranges) || N <= 0 || (N % 32) || !d_B || !d_C_in || !d_C_out) return SEXTANS_ERR_INVALID;
-    if (!h->d_bell_Af) return SEXTANS_ERR_STATE;
+    if (!h->bell.d_bell_Af) return SEXTANS_ERR_STATE;
     Rccl *r = comm ? rccl() : nullptr;
     if (comm && !r) return SEXTANS_ERR_STATE;
     SX_HIP(hipSetDevice(h->device));

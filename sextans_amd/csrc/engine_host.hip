@@ -85,12 +85,11 @@ int run_repeats(sextans_engine *h, int N, float alpha, float beta, int rp_time, 
     *ns = (double)ms * 1e6;
     return SEXTANS_OK;
 }
-// column-major B, C_in and C_out of the host-buffer entry points (C_in and C_out share one capacity)
+// column-major B, C_in and C_out of the host-buffer entry points
 int ensure_staging(sextans_engine *h, size_t nB, size_t nC) {
-    if (int rc = ensure(&h->d_B, &h->B_cap, nB)) return rc;
-    size_t ccap = h->C_cap;
-    if (int rc = ensure(&h->d_Cin, &ccap, nC)) return rc;
-    return ensure(&h->d_Cout, &h->C_cap, nC);
+    if (int rc = reserve(h->d_B, nB)) return rc;
+    if (int rc = reserve(h->d_Cin, nC)) return rc;
+    return reserve(h->d_Cout, nC);
 }
 }  // namespace
 extern "C" {
@@ -150,8 +149,8 @@ int sextans_invoke(sextans_handle_t h, const int32_t *edge_list_ptr, const uint6
     const int64_t c_cs = sextans_chan_c_colsize(M), c_len = sextans_chan_c_len(M, N);
     const int64_t b_used = b_cs * (N / 8), c_used = c_cs * (N / 8);
     const size_t nB = (size_t)K * (size_t)N, nC = (size_t)M * (size_t)N;
-    if (int rc = ensure(&h->d_chB, &h->chB_cap, (size_t)b_len * num_ch_b)) return rc;
-    if (int rc = ensure(&h->d_chC, &h->chC_cap, (size_t)c_len * 8)) return rc;
+    if (int rc = reserve(h->d_chB, (size_t)b_len * num_ch_b)) return rc;
+    if (int rc = reserve(h->d_chC, (size_t)c_len * 8)) return rc;
     if (int rc = ensure_staging(h, nB, nC)) return rc;
     for (int c = 0; c < num_ch_b; ++c) {
         if (!mat_B_ch[c]) return SEXTANS_ERR_INVALID;

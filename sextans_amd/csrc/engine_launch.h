@@ -16,7 +16,7 @@ void preload_device_code();   // sextans_create: loads the code object now inste
 // B (column-major, ldb) -> N-tile panels of `width` columns.  ncols < ntiles * width: the last panel is zero-filled past them
 void launch_repack(int width, const float *dB, int64_t ldb, float *dBp, int K, int col_base, int ntiles, hipStream_t s, int k_begin = 0,
                    int k_end = -1, int ncols = -1, const unsigned char *touched = nullptr);
-// ... -> 16-column panels in the column order of the graph-clustered plan (h->d_colpos), rows [col_lo, col_hi) of B
+// ... -> 16-column panels in the column order of the graph-clustered plan (h->cluster.d_colpos), rows [col_lo, col_hi) of B
 void launch_repack_perm(sextans_engine *h, const float *dB, int64_t ldb, float *dBp, int col_base, int ntiles, int ncols, hipStream_t s);
 // row-major 16-column tiles ([tile][M][16]) -> column-major C, columns [col0, col0 + ncols)
 void launch_tiles_to_colmajor(const float *tiles, float *C, int64_t ldc, int M, int col0, int ntiles, int ncols, hipStream_t s);

@@ -87,7 +87,7 @@ void launch_repack(int width, const float *dB, int64_t ldb, float *dBp, int K, i
 
 void launch_repack_perm(sextans_engine *h, const float *dB, int64_t ldb, float *dBp, int col_base, int ntiles, int ncols, hipStream_t s) {
     hipLaunchKernelGGL(sx::repack_b_panels_perm, dim3((unsigned)((h->col_hi - h->col_lo + sx::kBlock - 1) / sx::kBlock), (unsigned)ntiles), dim3(sx::kBlock), 0, s,
-                       dB, ldb, dBp, h->K, col_base, h->d_colpos, h->col_lo, h->col_hi, ncols, h->d_touched);
+                       dB, ldb, dBp, h->K, col_base, h->cluster.d_colpos, h->col_lo, h->col_hi, ncols, h->mat.d_touched);
 }
 
 void launch_tiles_to_colmajor(const float *tiles, float *C, int64_t ldc, int M, int col0, int ntiles, int ncols, hipStream_t s) {
@@ -130,10 +130,10 @@ int launch_panel(sextans_engine *h, int width, const float *dBp, const float *dC
         const int tile_floats = NT * (RB + 1);   // the C tile reuses the panel bytes
         const size_t lds = (size_t)(panel_floats > tile_floats ? panel_floats : tile_floats) * sizeof(int);
         auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(nwg), dim3(sx::kBlock), lds, s, (const int2 *)h->ps.d_row_off, h->ps.d_lidx,
+            hipLaunchKernelGGL(kern, dim3(nwg), dim3(sx::kBlock), lds, s, (const int2 *)h->ps.d_row_off.get(), h->ps.d_lidx,
                                h->ps.d_pcol32, h->ps.d_pval, h->ps.d_blk_row, h->ps.d_dict_ptr, h->ps.d_dict, h->ps.plan_dict_stride, dBp,
                                pstride, dCin, ldc_in, dCout, ldc, ntiles, nblk, alpha, beta, xcd, panel_floats,
-                               (long long *)h->d_dbg, blk_begin, row_base, (const unsigned char *)h->d_skip, (const int2 *)h->ps.d_ioff, pad_rows);
+                               (long long *)h->d_dbg.get(), blk_begin, row_base, (const unsigned char *)h->split.d_skip.get(), (const int2 *)h->ps.d_ioff.get(), pad_rows);
         };
         with_bool(h->opt_exact, [&](auto EX) {
             constexpr bool E = decltype(EX)::value;
@@ -168,9 +168,9 @@ struct V2Launch {   // everything decided for one launch
 
 V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_in, int64_t ldc, int64_t bcol_ld, int nblk, int mode, int64_t rm_ldb) {
     V2Launch d{};
-    const sextans_engine::PanelState &P = mode ? h->psc : h->ps;
-    d.slot_row = (mode == 1 || mode == 2) ? h->d_slot_row : nullptr;
-    d.skip = mode == 3 ? nullptr : (const unsigned char *)h->d_skip;   // rows on the piece path: never written by this kernel (mode 2: their staging rows keep C_in)
+    const sextans_engine::PanelState &P = mode ? h->cluster.psc : h->ps;
+    d.slot_row = (mode == 1 || mode == 2) ? h->cluster.d_slot_row : nullptr;
+    d.skip = mode == 3 ? nullptr : (const unsigned char *)h->split.d_skip.get();   // rows on the piece path: never written by this kernel (mode 2: their staging rows keep C_in)
     const bool crow = mode == 2 || mode == 3;
     // register-resident batches (16 entries each) per row: from the mean row length of the main matrix, so that matrices
     // with short rows (1-dof stencils: 27 entries) do not fetch six batches per row
@@ -204,7 +204,7 @@ V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_i
     d.ngrp = (nsuper + d.tpw - 1) / d.tpw;
     const bool rm = rm_ldb > 0;
     d.pstride = rm ? rm_ldb : bcol_ld > 0 ? bcol_ld : (int64_t)h->K * 16;
-    d.dict = (rm && crow && h->d_dict_nat) ? h->d_dict_nat : P.d_dict;
+    d.dict = (rm && crow && h->cluster.d_dict_nat) ? h->cluster.d_dict_nat : P.d_dict;
     // LDS = the panel: plan capacity + the +1.0f row.  A clustered plan of a short-row matrix is packed for a 320-row panel
     // (engine_plan.hip: small_panel): 20.5 KB instead of 36.9 KB per workgroup, so the CU holds as many workgroups as the registers
     // allow (5 at <= 96 registers) instead of the 4 the full panel permits -- these launches are latency-bound
@@ -286,13 +286,13 @@ int launch_panel_v2(sextans_engine *h, int H, const float *dBp, const float *dCi
     // dict_blocks_only (mixed plan, split form): the launch walks P.d_dict_blocks instead of [blk_begin, blk_end)
     // rm_ldb > 0 (sextans_spmm_device_rm): dBp is the caller's ROW-major B with that leading dimension, dCin / dCout its row-major C
     // (ldc_in / ldc = row strides); mode 2 then reads B through the plan's dictionaries translated back to the caller's column
-    // numbers (h->d_dict_nat) instead of permuted panels.
+    // numbers (h->cluster.d_dict_nat) instead of permuted panels.
     // mode 1 (grid bricks): the plan over the rows in brick order, whole-matrix calls only; its slot -> row table addresses C.
     // mode 2 (graph clustering, the reordered form): dBp = permuted panels, dCin == dCout == the row-major staging buffer,
     // ldc_in == ldc == floats per tile; the same slot -> row table addresses the staging rows.
     // mode 3 (clustered-order chunks of sextans_dist_spmm): the graph-clustered plan with C addressed BY POSITION in the clustered order
     // (no slot -> row table): dCin == dCout == a packed slab [tile][position][16] of the chunk, ldc_in == ldc == floats per tile.
-    const sextans_engine::PanelState &P = mode ? h->psc : h->ps;
+    const sextans_engine::PanelState &P = mode ? h->cluster.psc : h->ps;
     const int nblk = dict_blocks_only ? P.n_dict_blocks : blk_end - blk_begin;
     if (nblk <= 0 || nsuper <= 0) return SEXTANS_OK;
     if (mode == 0)
@@ -300,9 +300,9 @@ int launch_panel_v2(sextans_engine *h, int H, const float *dBp, const float *dCi
     const V2Launch d = plan_panel_v2(h, H, nsuper, ldc_in, ldc, bcol_ld, nblk, mode, rm_ldb);
     auto go = [&](auto kern) -> int {
         if (int rc = allow_big_lds(h, reinterpret_cast<const void *>(kern), (int)d.lds)) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk * (unsigned)d.ngrp), dim3(sx::kBlock), d.lds, s, (const int2 *)P.d_row_off,
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk * (unsigned)d.ngrp), dim3(sx::kBlock), d.lds, s, (const int2 *)P.d_row_off.get(),
                            P.d_lidx, P.d_pval, P.d_blk_row, P.d_dict_ptr, d.dict, P.plan_dict_stride, dBp, d.pstride, dCin, ldc_in, dCout, ldc, nsuper, d.tpw, nblk, alpha, beta, d.xcd,
-                           P.plan_pad_row, blk_begin, row_base, d.skip, (long long *)h->d_dbg, d.slot_row, (const int2 *)P.d_ioff, last_cols, dict_blocks_only ? (const int *)P.d_dict_blocks : (const int *)nullptr);
+                           P.plan_pad_row, blk_begin, row_base, d.skip, (long long *)h->d_dbg.get(), d.slot_row, (const int2 *)P.d_ioff.get(), last_cols, dict_blocks_only ? (const int *)P.d_dict_blocks.get() : (const int *)nullptr);
         return SEXTANS_OK;
     };
     return PanelV2Kernels::launch(d.v, h->opt_exact != 0, go);
@@ -330,11 +330,11 @@ void launch_window(sextans_engine *h, const float *dBp8, const float *dCin, int6
                    int wave_begin, int wave_end, int row_base, float alpha, float beta, hipStream_t s) {
     const int nwg = (wave_end - wave_begin + sx::kWinWaves - 1) / sx::kWinWaves;
     if (nwg <= 0) return;
-    const size_t lds = (size_t)sx::kWinWaves * (size_t)(h->win_rw + 1) * sx::kWinNT * sizeof(float);
+    const size_t lds = (size_t)sx::kWinWaves * (size_t)(h->win.rw + 1) * sx::kWinNT * sizeof(float);
     with_bool(h->opt_exact, [&](auto EX) { with_value<4, 8>((int)h->opt_win_unroll, [&](auto U) {
         hipLaunchKernelGGL((sx::spmm_csr_window<decltype(EX)::value, decltype(U)::value>), dim3((unsigned)nwg * (unsigned)ntiles), dim3(sx::kWinWaves * 64), lds, s,
-                           (const sx::u32x2 *)h->d_wstream, (const int *)h->d_wstep0, dBp8, (int64_t)h->K * sx::kWinNT, dCin,
-                           ldc_in, dCout, ldc, h->M, h->win_rw, wave_begin, wave_end, nwg, row_base, alpha, beta, (const unsigned char *)h->d_skip);
+                           (const sx::u32x2 *)h->win.d_wstream.get(), (const int *)h->win.d_wstep0.get(), dBp8, (int64_t)h->K * sx::kWinNT, dCin,
+                           ldc_in, dCout, ldc, h->M, h->win.rw, wave_begin, wave_end, nwg, row_base, alpha, beta, (const unsigned char *)h->split.d_skip.get());
     }); });
 }
 
@@ -363,7 +363,7 @@ void launch_colwise(sextans_engine *h, bool rm, int N, const float *B, int64_t l
         const dim3 grid = adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)(ntiles / T));
         with_bool(h->opt_exact, [&](auto EX) { with_value<16, 8>(width, [&](auto W) { with_bool(rm, [&](auto RM) {
             hipLaunchKernelGGL((sx::spmm_csr_colwise<decltype(EX)::value, decltype(W)::value, decltype(RM)::value>), grid, dim3(sx::kBlock), 0, s, h->m_rp, h->m_ci,
-                               h->m_v, B, ldb, dCin, ldc_in, dCout, ldc, row_begin, row_end, nrowblk, col0, alpha, beta, (int)h->opt_xcd, (const unsigned char *)h->d_skip, adj, T);
+                               h->m_v, B, ldb, dCin, ldc_in, dCout, ldc, row_begin, row_end, nrowblk, col0, alpha, beta, (int)h->opt_xcd, (const unsigned char *)h->split.d_skip.get(), adj, T);
         }); }); });
     };
     const int n16 = N / 16;
@@ -395,9 +395,9 @@ void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const float 
             constexpr int lds = sx::chain_fused_lds_bytes(decltype(W)::value), threads = sx::chain_fused_threads(decltype(W)::value);
             const auto kern = sx::chain_fused<decltype(W)::value, decltype(EX)::value>;
             (void)allow_big_lds(h, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)(c1 - c0) * (unsigned)ntiles), dim3((unsigned)threads), (size_t)lds, s, h->d_chain_row,
-                               perm ? h->d_chain_beg_c : h->d_chain_beg, h->d_chain_off, (c0 == 0 && c1 == h->nchain) ? h->d_chain_perm : (const int *)nullptr,
-                               perm ? (const int *)h->d_chain_ci_perm : h->s_ci, perm ? (const float *)h->d_chain_v_c : h->s_v, bp, rm_B ? (int64_t)0 : (int64_t)h->K * g.width,
+            hipLaunchKernelGGL(kern, dim3((unsigned)(c1 - c0) * (unsigned)ntiles), dim3((unsigned)threads), (size_t)lds, s, h->split.d_chain_row,
+                               perm ? h->cluster.d_chain_beg_c : h->split.d_chain_beg, h->split.d_chain_off, (c0 == 0 && c1 == h->split.nchain) ? h->split.d_chain_perm : (const int *)nullptr,
+                               perm ? (const int *)h->cluster.d_chain_ci_perm : h->s_ci, perm ? (const float *)h->cluster.d_chain_v_c : h->s_v, bp, rm_B ? (int64_t)0 : (int64_t)h->K * g.width,
                                rm_B ? (int)rm_ldb : g.width, dCin, ldc_in, dCout, ldc, g.col0, ntiles, c0, row_base, alpha, beta, rm_B ? 1 : 0);
         }); });
     }
@@ -405,14 +405,14 @@ void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const float 
 
 void launch_hub_pieces(sextans_engine *h, int width, const sextans_engine::PieceTable &t, const float *dBp, int ntiles, int col0, int v0,
                        int v1, hipStream_t s, const int *colpos, int64_t rm_ldb) {
-    float *P = h->d_P + (int64_t)col0 * h->split_nv;
+    float *P = h->d_P + (int64_t)col0 * h->split.nv;
     by_width(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR;
         const int nblk = (v1 - v0 + RB - 1) / RB;
         if (nblk <= 0) return;
         with_bool(h->opt_exact, [&](auto EX) { with_bool(rm_ldb > 0, [&](auto RM) {
             hipLaunchKernelGGL((sx::spmm_csr_pieces<LPR, decltype(EX)::value, decltype(RM)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, s, t.d_vrp,
-                               t.d_vend, h->s_ci, h->s_v, dBp, rm_ldb > 0 ? rm_ldb : (int64_t)h->K * 4 * LPR, P, (int64_t)h->split_nv, v0, v1, ntiles, colpos);
+                               t.d_vend, h->s_ci, h->s_v, dBp, rm_ldb > 0 ? rm_ldb : (int64_t)h->K * 4 * LPR, P, (int64_t)h->split.nv, v0, v1, ntiles, colpos);
         }); });
     });
 }
@@ -422,7 +422,7 @@ void launch_fold(sextans_engine *h, const sextans_engine::PieceTable &t, int hub
     const int64_t tot = (int64_t)(hub1 - hub0) * N;
     with_bool(h->opt_exact, [&](auto EX) {
         hipLaunchKernelGGL(sx::fold_hub_pieces<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t.d_vfirst, t.d_row, h->d_P,
-                           (int64_t)h->split_nv, dCin, ldc_in, dCout, ldc, hub0, hub1 - hub0, N, row_base, alpha, beta, rm ? 1 : 0);
+                           (int64_t)h->split.nv, dCin, ldc_in, dCout, ldc, hub0, hub1 - hub0, N, row_base, alpha, beta, rm ? 1 : 0);
     });
 }
 
@@ -449,7 +449,7 @@ void launch_rowgroup_bf16(sextans_engine *h, int width, const uint16_t *B, int64
         with_bool(h->opt_exact, [&](auto EX) { with_bool(h->opt_stage, [&](auto ST) { with_bool(cbf16, [&](auto CB) {
             hipLaunchKernelGGL((sx::spmm_csr_rowgroup_bf16<LPR, CH, decltype(EX)::value, decltype(ST)::value, decltype(CB)::value>), dim3((unsigned)nrowblk * (unsigned)ntiles),
                                dim3(sx::kBlock), 0, s, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, B, ldb, dCin, ldc_in, dCout, ldc, h->M, ntiles, nrowblk, alpha, beta,
-                               (int)h->opt_xcd, (const unsigned char *)h->d_skip);
+                               (int)h->opt_xcd, (const unsigned char *)h->split.d_skip.get());
         }); }); });
     });
 }
@@ -461,17 +461,17 @@ void launch_hub_pieces_bf16(sextans_engine *h, int width, const sextans_engine::
         if (nblk <= 0) return;
         with_bool(h->opt_exact, [&](auto EX) {
             hipLaunchKernelGGL((sx::spmm_csr_pieces_bf16<LPR, decltype(EX)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, s, t.d_vrp, t.d_vend,
-                               h->s_ci, h->s_v, B, ldb, h->d_P + (int64_t)col0 * h->split_nv, (int64_t)h->split_nv, v0, v1, ntiles);
+                               h->s_ci, h->s_v, B, ldb, h->d_P + (int64_t)col0 * h->split.nv, (int64_t)h->split.nv, v0, v1, ntiles);
         });
     });
 }
 
 void launch_fold_bf16(sextans_engine *h, const sextans_engine::PieceTable &t, int N, const uint16_t *dCin, int64_t ldc_in, uint16_t *dCout,
                       int64_t ldc, float alpha, float beta, hipStream_t s) {
-    const int64_t tot = (int64_t)h->nhub * N;
+    const int64_t tot = (int64_t)h->split.nhub * N;
     with_bool(h->opt_exact, [&](auto EX) {
         hipLaunchKernelGGL(sx::fold_hub_pieces_bf16<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t.d_vfirst, t.d_row, h->d_P,
-                           (int64_t)h->split_nv, dCin, ldc_in, dCout, ldc, h->nhub, N, alpha, beta);
+                           (int64_t)h->split.nv, dCin, ldc_in, dCout, ldc, h->split.nhub, N, alpha, beta);
     });
 }
 

@@ -41,113 +41,38 @@ __global__ __launch_bounds__(256) void mixed_group_list(int M, const unsigned ch
 }
 }  // namespace
 
-void free_panel_state(sextans_engine::PanelState &p) {
-    (void)hipFree(p.d_dict_ptr); (void)hipFree(p.d_dict); (void)hipFree(p.d_lidx); (void)hipFree(p.d_blk_row);
-    (void)hipFree(p.d_row_off); (void)hipFree(p.d_pcol32); (void)hipFree(p.d_pval); (void)hipFree(p.d_ioff); (void)hipFree(p.d_rg_skip); (void)hipFree(p.d_rg_groups); (void)hipFree(p.d_dict_blocks);
-    p = sextans_engine::PanelState();
-}
-
 void free_cluster_plan(sextans_engine *h) {   // the clustered-order plan and its tables; it is reconsidered at the next whole-matrix call
-    free_panel_state(h->psc);
-    (void)hipFree(h->d_slot_row); (void)hipFree(h->d_colpos); (void)hipFree(h->d_dict_nat);
-    h->d_slot_row = h->d_colpos = h->d_dict_nat = nullptr;
-    h->cluster_cm_pays = true;
-    h->cluster_runs = false;
-    (void)hipFree(h->d_chain_ci_perm); (void)hipFree(h->d_chain_beg_c); (void)hipFree(h->d_chain_v_c);
-    h->d_chain_ci_perm = h->d_chain_beg_c = nullptr; h->d_chain_v_c = nullptr;
-    h->cluster_state = 0;
-    h->colwise_state = 0;
-    h->row_coherence = 0.0;
-    h->cluster_decline = 0;
-    h->cluster_total_dict = 0;
-    h->cluster_shared = 0.0;
-    h->cluster_graph_kind = 0;
-    h->pattern_symmetry = 1.0;
+    h->cluster = {};
 }
 
 void free_plan(sextans_engine *h) {   // every packed form of the current main matrix
     h->cluster_rm_tried = false;
-    free_panel_state(h->ps);
-    for (auto &p : h->plan_stash) free_panel_state(p);
+    h->ps = {};
+    for (auto &p : h->plan_stash) p = {};
     free_cluster_plan(h);
     h->cluster_s2 = h->cluster_s3 = 0;
-    h->plan_total_dict = h->cluster_total_dict = 0;
+    h->plan_total_dict = 0;
 }
 
 int64_t device_bytes(const sextans_engine *h) {
-    auto plan_bytes = [](const sextans_engine::PanelState &p) -> int64_t {
-        if (!p.plan_built || !p.plan_lpr) return 0;
-        const int64_t rb = (int64_t)(sx::kBlock / p.plan_lpr) * p.plan_sets;
-        return (int64_t)p.plan_nblk * (4 * (2 + p.plan_dict_stride + 2 * rb)) +
-               (p.stream_released ? 0 : p.plan_stream_len * 4 + p.plan_idx_len * 2 + (p.d_ioff ? (int64_t)p.plan_nblk * rb * 8 : 0) +
-                                            (p.plan_mixed ? p.plan_stream_len * 4 : 4));
-    };
-    int64_t b = 0;
-    const int64_t rows = (int64_t)h->M + 1;
-    if (h->owns_matrix) b += rows * 4 + h->nnz * 8;
-    if (h->d_v_upd) b += h->nnz * 4;
-    if (h->d_srp) b += rows * 4 + h->s_nnz * 8;
-    if (h->d_mrp) b += rows * 4 + h->m_nnz * 8 + h->M;
-    b += ((int64_t)h->split_nv * 8 + (int64_t)h->nhub * 8) * 2 + (int64_t)h->nchain * 24;
-    b += plan_bytes(h->ps) + plan_bytes(h->psc);
-    for (const auto &p : h->plan_stash) b += plan_bytes(p);
-    if (h->d_slot_row) b += (int64_t)h->psc.plan_nblk * 64 * h->psc.plan_sets * 4;
-    if (h->d_colpos) b += (int64_t)h->K * 4;
-    if (h->d_chain_ci_perm && !h->h_chain_off.empty()) b += (int64_t)h->h_chain_off.back() * 8 + (int64_t)h->nchain * 4;
-    if (h->d_wstream) b += h->win_padded * 8 + (int64_t)h->win_nwaves * 4;
-    if (h->d_dense_Af) b += (int64_t)h->dense_mb * h->dense_W * (2048 + 4);
-    if (h->d_bell_Af) b += (int64_t)(h->bell_M / 32) * h->bell_W * (2048 + (h->d_bell_col_owned ? 4 : 0));
-    b += (int64_t)h->bell_Bf_cap;
-    if (h->tr) b += ((int64_t)h->K + 1) * 4 + h->nnz * 8 + (h->d_tperm ? h->nnz * 4 : 0) + device_bytes(h->tr);   // A^T, its entry permutation, its companion's plans and workspaces
-    b += h->sddmm_row0_n * 4;
-    b += h->sm_wrow_n * 4 + (int64_t)h->sm_nchunks * 24;   // row softmax: wavefront rows, long-row chunk table + partials + per-row results
-    b += 4 * (int64_t)(h->Bp_cap + h->B_cap + (h->d_Cin ? h->C_cap : 0) + h->C_cap + h->P_cap + h->stage_cap + h->chB_cap + h->chC_cap + h->Cs_cap + h->rmB_cap + h->rmC_cap + h->bfB_cap + h->bfC_cap + h->Cfull_cap + h->dist_rows_cap);
+    int64_t b = h->mat.bytes() + h->ps.bytes() + h->cluster.bytes() + h->win.bytes() + h->dense.bytes() + h->bell.bytes() + h->split.bytes() + h->at.bytes() +
+                h->d_sddmm_row0.bytes() + h->softmax.bytes() + h->workspace_bytes();
+    for (const auto &p : h->plan_stash) b += p.bytes();
+    if (h->tr) b += device_bytes(h->tr);   // the companion's plans and workspaces (A^T itself is this engine's)
     return b;
 }
 
 void free_window(sextans_engine *h) {
-    (void)hipFree(h->d_wstream); (void)hipFree(h->d_wstep0);
-    h->d_wstream = nullptr; h->d_wstep0 = nullptr;
-    h->win_nwaves = h->win_rw = 0;
-    h->win_padded = 0;
-    h->win_state = 0;
-    h->win_built_rows = h->win_built_cols = -1;
+    h->win = {};
 }
 
 void free_split(sextans_engine *h) {   // long-row state: main matrix, skip flags, piece tables (built from the source)
-    for (auto *t : {&h->by_len, &h->by_row}) {
-        (void)hipFree(t->d_vrp); (void)hipFree(t->d_vend); (void)hipFree(t->d_vfirst); (void)hipFree(t->d_row);
-        *t = sextans_engine::PieceTable();
-    }
-    (void)hipFree(h->d_chain_row); (void)hipFree(h->d_chain_beg); (void)hipFree(h->d_chain_off); (void)hipFree(h->d_chain_perm);
-    h->d_chain_row = h->d_chain_beg = h->d_chain_perm = nullptr; h->d_chain_off = nullptr;
-    h->nchain = 0; h->h_chain_row.clear(); h->h_chain_off.clear(); h->chain_T = 0; h->chain_built_opt = -2;
-    (void)hipFree(h->d_mrp); (void)hipFree(h->d_mci); (void)hipFree(h->d_mv); (void)hipFree(h->d_skip);
-    h->d_mrp = h->d_mci = nullptr;
-    h->d_mv = nullptr;
-    h->d_skip = nullptr;
-    h->h_split_rows.clear();
-    h->nhub = h->split_nv = 0;
-    h->split_T = h->bucket_L0 = 0;
-    h->split_built_opt = h->bucket_built_opt = h->split_built_gnnz = -2;
+    h->split = {};
     h->m_rp = h->s_rp; h->m_ci = h->s_ci; h->m_v = h->s_v; h->m_nnz = h->s_nnz;
 }
 
 void free_dense(sextans_engine *h) {   // dense-tile state and everything downstream of the source matrix
-    (void)hipFree(h->d_dense_col); (void)hipFree(h->d_dense_Af);
-    h->d_dense_col = nullptr; h->d_dense_Af = nullptr;
-    h->dense_mb = h->dense_W = 0;
-    h->dense_tiles = h->dense_nnz = 0;
-    (void)hipFree(h->d_rb_row0); (void)hipFree(h->d_rb_gptr); (void)hipFree(h->d_rb_gcol); (void)hipFree(h->d_rb_A);
-    h->d_rb_row0 = h->d_rb_gptr = h->d_rb_gcol = nullptr; h->d_rb_A = nullptr;
-    h->rb_n = 0; h->rb_groups = 0;
-    (void)hipFree(h->d_sb_uptr); (void)hipFree(h->d_sb_ucol); (void)hipFree(h->d_sb_umask);
-    h->d_sb_uptr = h->d_sb_ucol = nullptr; h->d_sb_umask = nullptr;
-    h->sb_n = 0; h->sb_entries = 0;
-    h->dense_built_mfma = h->dense_built_fill = -2;
-    (void)hipFree(h->d_srp); (void)hipFree(h->d_sci); (void)hipFree(h->d_sv);
-    h->d_srp = h->d_sci = nullptr;
-    h->d_sv = nullptr;
+    h->dense = {};
     h->s_rp = h->d_rp; h->s_ci = h->d_ci; h->s_v = h->d_v; h->s_nnz = h->nnz;
     free_split(h);
 }
@@ -157,38 +82,12 @@ void free_matrix(sextans_engine *h) {
     free_plan(h);
     free_dense(h);
     free_window(h);
-    h->plan_build_s = 0.0;
-    if (h->owns_matrix) {
-        (void)hipFree((void *)h->d_rp);
-        (void)hipFree((void *)h->d_ci);
-        (void)hipFree((void *)h->d_v);
-    }
-    (void)hipFree(h->d_v_upd);
-    h->d_v_upd = nullptr;
-    h->value_refreshes = h->value_refresh_rebuilt = 0;
-    (void)hipFree(h->d_bfB); (void)hipFree(h->d_bfC);
-    h->d_bfB = h->d_bfC = nullptr;
-    h->bfB_cap = h->bfC_cap = 0;
-    h->bf16_native_calls = h->bf16_converted_calls = 0;
+    h->mat = {};
     h->d_rp = h->d_ci = nullptr;
     h->d_v = nullptr;
-    h->owns_matrix = false;
-    h->device_matrix_checked = false;
-    h->col_range_known = false;
-    (void)hipFree(h->d_touched);
-    h->d_touched = nullptr; h->touched_segments = 0;
     h->m_rp = h->m_ci = h->s_rp = h->s_ci = nullptr; h->m_v = h->s_v = nullptr; h->m_nnz = h->s_nnz = 0;
     h->dist_cut_key.clear();   // chunk cuts are aligned to the packed forms of one matrix
     h->bp_layout = 0;          // B panels belong to one (K, B)
-}
-
-int ensure(float **p, size_t *cap, size_t need) {
-    if (*cap >= need && *p) return SEXTANS_OK;
-    if (*p) SX_HIP(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    SX_HIP(hipMalloc((void **)p, (need ? need : 1) * sizeof(float)));
-    *cap = need;
-    return SEXTANS_OK;
 }
 
 // Device copy of the CSR arrays -> host, validated: the host-side plan builders index arrays of size K with
@@ -235,8 +134,8 @@ void adopt_device_plan(sextans_engine::PanelState &c, sx::DevicePlan &dp, const 
     c.plan_nblk = dp.nblk;
     c.plan_dict_stride = dp.dict_stride;
     c.plan_mixed = dp.mixed;
-    c.d_blk_row = dp.d_blk_row; c.d_dict_ptr = dp.d_dict_cnt; c.d_dict = dp.d_dict; c.d_row_off = dp.d_slot_info;
-    c.d_lidx = dp.d_idx16; c.d_pcol32 = dp.d_col32; c.d_pval = dp.d_val; c.d_ioff = dp.d_ioff;
+    c.d_blk_row = std::move(dp.d_blk_row); c.d_dict_ptr = std::move(dp.d_dict_cnt); c.d_dict = std::move(dp.d_dict); c.d_row_off = std::move(dp.d_slot_info);
+    c.d_lidx = std::move(dp.d_idx16); c.d_pcol32 = std::move(dp.d_col32); c.d_pval = std::move(dp.d_val); c.d_ioff = std::move(dp.d_ioff);
     c.plan_idx_len = dp.idx_len;
     c.h_blk_row.swap(dp.h_blk_row);
     c.plan_stream_len = dp.stream_len;
@@ -245,7 +144,6 @@ void adopt_device_plan(sextans_engine::PanelState &c, sx::DevicePlan &dp, const 
     c.plan_max_row = dp.max_row_len;
     c.plan_pad_row = cap;
     c.plan_built = true;
-    dp = sx::DevicePlan();
 }
 
 int sample_reuse(sextans_engine *h, int RB, int max_unique, double min_reuse, double min_reuse2, double *frac, double *frac2) {
@@ -291,21 +189,21 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
         if (h->ps.plan_lpr != lpr) std::swap(h->ps, h->plan_stash[idx(lpr)]);
         if (h->ps.plan_lpr && h->ps.plan_lpr != lpr) {   // displaced a third form: park it in its own slot
             std::swap(h->ps, h->plan_stash[idx(h->ps.plan_lpr)]);
-            free_panel_state(h->ps);
+            h->ps = {};
         }
         if (h->ps.plan_lpr == lpr && h->ps.plan_min_reuse == plan_key(h) && (h->ps.plan_built || !force))
             return SEXTANS_OK;
     }
-    free_panel_state(h->ps);
+    h->ps = {};
     PlanTimer timer(h);
     // A matrix handed over with sextans_set_matrix_csr_device has not been looked at by anybody yet: the kernels gather B
     // rows by column index and the builders trust row_ptr to be monotone, so it is validated once, on the device.
-    if (!h->owns_matrix && !h->device_matrix_checked) {
+    if (!h->owns_matrix() && !h->mat.device_matrix_checked) {
         int bad = 0;
         std::string verr;
         if (sx::validate_csr_device(h->M, h->K, h->nnz, h->d_rp, h->d_ci, &bad, verr)) { g_last_error = verr; return SEXTANS_ERR_HIP; }
         if (bad) return (bad & 1) ? SEXTANS_ERR_INVALID : SEXTANS_ERR_INDEX;
-        h->device_matrix_checked = true;
+        h->mat.device_matrix_checked = true;
     }
     const int RB = sx::kBlock / lpr;
     // two thresholds: "panel_min_reuse_x100" decides for N <= 16, "panel_min_reuse_wide_x100" for N >= 32 (prepare()); the plan
@@ -334,7 +232,7 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
     const int cap = kPanelFloats / (4 * lpr);
     const int brc = sx::build_panel_plan_device(h->M, h->K, h->m_rp, h->m_ci, h->m_v, lpr, cap, min_reuse, dp, err, nullptr,
                                                 lpr == 4 && h->opt_share_index != 0);
-    if (brc == 2) { g_last_error = err; sx::free_device_plan(dp); return SEXTANS_ERR_HIP; }
+    if (brc == 2) { g_last_error = err; return SEXTANS_ERR_HIP; }
     h->ps.plan_lpr = lpr;
     h->ps.plan_min_reuse = plan_key(h);
     h->ps.plan_narrow_frac = narrow_frac;
@@ -350,15 +248,15 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
     if (brc == 0 && dp.mixed && lpr == 4 && h->m_nnz > 0 && (double)dp.nnz_in_panel_blocks >= 0.98 * (double)h->m_nnz) {
         sx::DevicePlan all;
         const int rc2 = sx::build_panel_plan_device(h->M, h->K, h->m_rp, h->m_ci, h->m_v, lpr, cap, 0.0, all, err, nullptr, h->opt_share_index != 0);
-        if (rc2 == 0 && !all.mixed && all.dict_stride <= 9 * RB) { sx::free_device_plan(dp); dp = all; all = sx::DevicePlan(); h->ps.plan_all_dict = true; }
-        else { sx::free_device_plan(all); if (rc2 == 2) (void)hipGetLastError(); }
+        if (rc2 == 0 && !all.mixed && all.dict_stride <= 9 * RB) { dp = std::move(all); h->ps.plan_all_dict = true; }
+        else if (rc2 == 2) (void)hipGetLastError();
     }
-    if (dp.dict_stride > 9 * RB) { sx::free_device_plan(dp); return SEXTANS_ERR_STATE; }   // capacity = 9 * RB by construction
+    if (dp.dict_stride > 9 * RB) return SEXTANS_ERR_STATE;   // capacity = 9 * RB by construction
     h->ps.plan_nblk = dp.nblk;
     h->ps.plan_dict_stride = dp.dict_stride;
     h->ps.plan_mixed = dp.mixed;
-    h->ps.d_blk_row = dp.d_blk_row; h->ps.d_dict_ptr = dp.d_dict_cnt; h->ps.d_dict = dp.d_dict; h->ps.d_row_off = dp.d_slot_info;
-    h->ps.d_lidx = dp.d_idx16; h->ps.d_pcol32 = dp.d_col32; h->ps.d_pval = dp.d_val; h->ps.d_ioff = dp.d_ioff;
+    h->ps.d_blk_row = std::move(dp.d_blk_row); h->ps.d_dict_ptr = std::move(dp.d_dict_cnt); h->ps.d_dict = std::move(dp.d_dict); h->ps.d_row_off = std::move(dp.d_slot_info);
+    h->ps.d_lidx = std::move(dp.d_idx16); h->ps.d_pcol32 = std::move(dp.d_col32); h->ps.d_pval = std::move(dp.d_val); h->ps.d_ioff = std::move(dp.d_ioff);
     h->ps.plan_idx_len = dp.idx_len;
     h->ps.h_blk_row.swap(dp.h_blk_row);
     h->ps.plan_stream_len = dp.stream_len;
@@ -370,19 +268,18 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
     h->ps.plan_built = true;
     if (lpr == 4) h->plan_total_dict = dp.total_dict;
     if (h->ps.plan_mixed && lpr == 4 && h->ps.plan_nblk > 0) {   // the split form of a mixed plan (engine_spmm.hip: kSplitMixed)
-        (void)hipFree(h->ps.d_rg_skip); h->ps.d_rg_skip = nullptr;
-        if (hipMalloc((void **)&h->ps.d_rg_skip, (size_t)std::max(h->M, 1)) == hipSuccess) {
+        if (h->ps.d_rg_skip.alloc((size_t)std::max(h->M, 1)) == hipSuccess) {
             hipLaunchKernelGGL(mixed_row_flags, dim3((unsigned)h->ps.plan_nblk), dim3(256), 0, nullptr, h->ps.plan_nblk, h->ps.d_blk_row, h->ps.d_dict_ptr,
-                               (const unsigned char *)h->d_skip, h->ps.d_rg_skip);
+                               h->split.d_skip.get(), h->ps.d_rg_skip);
             const int ng = (h->M + 127) / 128;
-            (void)hipFree(h->ps.d_rg_groups); h->ps.d_rg_groups = nullptr; h->ps.rg_ngroups = 0;
-            if (hipMalloc((void **)&h->ps.d_rg_groups, sizeof(int) * ((size_t)ng + 1)) == hipSuccess) {
+            h->ps.rg_ngroups = 0;
+            if (h->ps.d_rg_groups.alloc((size_t)ng + 1) == hipSuccess) {
                 SX_HIP(hipMemsetAsync(h->ps.d_rg_groups + ng, 0, sizeof(int), nullptr));
                 hipLaunchKernelGGL(mixed_group_list, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, nullptr, h->M, h->ps.d_rg_skip, h->ps.d_rg_groups, h->ps.d_rg_groups + ng);
                 SX_HIP(hipMemcpy(&h->ps.rg_ngroups, h->ps.d_rg_groups + ng, sizeof(int), hipMemcpyDeviceToHost));
             } else {
                 (void)hipGetLastError();
-                (void)hipFree(h->ps.d_rg_skip); h->ps.d_rg_skip = nullptr;
+                h->ps.d_rg_skip.reset();
             }
             SX_HIP(hipDeviceSynchronize());
             // the blocks with a dictionary, in order (the register-resident kernel walks this list: every workgroup of its launch works,
@@ -391,13 +288,13 @@ int ensure_plan(sextans_engine *h, int lpr, bool force) {
             SX_HIP(hipMemcpy(cnt.data(), h->ps.d_dict_ptr, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
             for (int b = 0; b < h->ps.plan_nblk; ++b)
                 if (cnt[(size_t)b] > 0) list.push_back(b);
-            (void)hipFree(h->ps.d_dict_blocks); h->ps.d_dict_blocks = nullptr; h->ps.n_dict_blocks = 0;
-            if (h->ps.d_rg_skip && !list.empty() && hipMalloc((void **)&h->ps.d_dict_blocks, sizeof(int) * list.size()) == hipSuccess) {
+            h->ps.d_dict_blocks.reset(); h->ps.n_dict_blocks = 0;
+            if (h->ps.d_rg_skip && !list.empty() && h->ps.d_dict_blocks.alloc(list.size()) == hipSuccess) {
                 SX_HIP(hipMemcpy(h->ps.d_dict_blocks, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice));
                 h->ps.n_dict_blocks = (int)list.size();
             } else {
                 (void)hipGetLastError();
-                (void)hipFree(h->ps.d_rg_skip); h->ps.d_rg_skip = nullptr;   // (no split form)
+                h->ps.d_rg_skip.reset();   // (no split form)
             }
         } else {
             (void)hipGetLastError();   // (without the table the mixed kernel runs)
@@ -462,21 +359,19 @@ int cluster_grid(sextans_engine *h) {   // 0 = in use, 1 = declined
         if (run_rows < 1 || b2 < 1 || b3 < 1) return 1;
     }
     std::string err;
-    int *d_perm = nullptr, *prp = nullptr, *pci = nullptr;
-    unsigned char *d_cut = nullptr;
-    float *pv = nullptr;
+    DevBuf<int> d_perm, prp, pci;
+    DevBuf<unsigned char> d_cut;
+    DevBuf<float> pv;
     sx::DevicePlan dp;
-    auto drop = [&]() { (void)hipFree(d_perm); (void)hipFree(d_cut); (void)hipFree(prp); (void)hipFree(pci); (void)hipFree(pv); sx::free_device_plan(dp); return 1; };
     const int lpr = 4, RB = sx::kBlock / lpr, cap = kPanelFloats / (4 * lpr);
     const double min_reuse = std::min((double)h->opt_min_reuse_x100, (double)h->opt_min_reuse_wide_x100) / 100.0;
     int brc = 1, cap_used = cap;
     for (; sets >= 1; --sets) {
-        (void)hipFree(d_perm); (void)hipFree(d_cut); (void)hipFree(prp); (void)hipFree(pci); (void)hipFree(pv);
-        d_perm = prp = pci = nullptr; d_cut = nullptr; pv = nullptr;
-        sx::free_device_plan(dp);
+        d_perm.reset(); d_cut.reset(); prp.reset(); pci.reset(); pv.reset();
+        dp = sx::DevicePlan();
         const int l2 = sets == 2 && h->opt_cluster_shape == 0 ? (gs.s3 > 0 ? 4 : 8) : b2, l3 = sets == 2 && h->opt_cluster_shape == 0 ? (gs.s3 > 0 ? 2 : 1) : b3;   // (a measurement shape + row_sets = 3: that shape as two row sets)
-        if (sx::build_brick_order_device(h->M, gs, run_rows, l2, l3, (int)h->opt_cluster_group, &d_perm, &d_cut, err)) return drop();
-        if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_perm, &prp, &pci, &pv, err)) return drop();
+        if (sx::build_brick_order_device(h->M, gs, run_rows, l2, l3, (int)h->opt_cluster_group, d_perm, d_cut, err)) return 1;
+        if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_perm, prp, pci, pv, err)) return 1;
         cap_used = cap;
         brc = sx::build_panel_plan_device(h->M, h->K, prp, pci, pv, lpr, cap, min_reuse, dp, err, d_cut, h->opt_share_index != 0, sets);
         if (sets == 2 && (brc != 0 || dp.mixed || dp.max_dict > sx::kWideMaxDict || dp.dict_stride > 9 * RB)) continue;   // 128-row bricks do not fit the panel
@@ -484,24 +379,22 @@ int cluster_grid(sextans_engine *h) {   // 0 = in use, 1 = declined
         // 128-row brick comes back as uneven pieces, not as an error -- then 64-row bricks
         if (sets == 2 && dp.capacity_cuts > 0) continue;
         if (brc == 0 && sets == 1 && small_panel_fits(h, dp)) {   // short rows, small dictionaries: packed again for a 320-row panel (same blocks, less LDS)
-            sx::free_device_plan(dp);
             cap_used = 5 * RB;
             brc = sx::build_panel_plan_device(h->M, h->K, prp, pci, pv, lpr, cap_used, min_reuse, dp, err, d_cut, h->opt_share_index != 0);
         }
         break;
     }
     if (sets < 1) sets = 1;
-    (void)hipFree(prp); (void)hipFree(pci); (void)hipFree(pv); (void)hipFree(d_cut);
-    prp = pci = nullptr; pv = nullptr; d_cut = nullptr;
-    if (brc != 0) return drop();
-    h->cluster_total_dict = dp.total_dict;
+    prp.reset(); pci.reset(); pv.reset(); d_cut.reset();
+    if (brc != 0) return 1;
+    h->cluster.total_dict = dp.total_dict;
     const bool gain = (double)dp.total_dict <= 0.85 * (double)h->plan_total_dict;
-    if (dp.mixed || dp.dict_stride > 9 * RB || dp.max_dict > sx::kWideMaxDict || (h->opt_row_cluster < 0 && !gain)) return drop();
-    if (sx::build_slot_rows_device(dp.nblk, RB * dp.sets, dp.d_blk_row, d_perm, &h->d_slot_row, err)) return drop();
-    (void)hipFree(d_perm);
-    adopt_device_plan(h->psc, dp, h, lpr, cap_used);
-    h->psc.plan_panel_frac = h->ps.plan_panel_frac;
-    h->psc.plan_narrow_frac = h->ps.plan_narrow_frac;
+    if (dp.mixed || dp.dict_stride > 9 * RB || dp.max_dict > sx::kWideMaxDict || (h->opt_row_cluster < 0 && !gain)) return 1;
+    if (sx::build_slot_rows_device(dp.nblk, RB * dp.sets, dp.d_blk_row, d_perm, h->cluster.d_slot_row, err)) return 1;
+    d_perm.reset();
+    adopt_device_plan(h->cluster.psc, dp, h, lpr, cap_used);
+    h->cluster.psc.plan_panel_frac = h->ps.plan_panel_frac;
+    h->cluster.psc.plan_narrow_frac = h->ps.plan_narrow_frac;
     return 0;
 }
 
@@ -512,36 +405,34 @@ int cluster_grid(sextans_engine *h) {   // 0 = in use, 1 = declined
 // form's passes (decline 12); this form has no passes.  Uses the grid-brick machinery (slot -> row table, cluster_state 1).
 int cluster_runs(sextans_engine *h) {   // 0 = in use, 1 = declined
     if (!h->ps.plan_built || h->ps.plan_lpr != 4 || h->ps.plan_mixed || h->M != h->K || h->M < 65536 || h->ps.plan_nblk <= 0) return 1;
-    if ((double)h->M / h->ps.plan_nblk >= 56.0 || h->dense_W > 0) return 1;               // natural blocks (nearly) full: nothing to gain
+    if ((double)h->M / h->ps.plan_nblk >= 56.0 || h->dense.W > 0) return 1;               // natural blocks (nearly) full: nothing to gain
     const int lpr = 4, RB = sx::kBlock / lpr, cap = kPanelFloats / (4 * lpr), run = 16;
     std::string err;
-    int *g_rp = nullptr, *g_ci = nullptr, *s_rp = nullptr, *s_ci = nullptr, *d_order_r = nullptr, *d_order = nullptr, *prp = nullptr, *pci = nullptr;
-    unsigned char *d_cut = nullptr, *g_w = nullptr, *s_w = nullptr;
-    float *pv = nullptr;
+    DevBuf<int> g_rp, g_ci, s_rp, s_ci, d_order_r, d_order, prp, pci;
+    DevBuf<unsigned char> d_cut, g_w, s_w;
+    DevBuf<float> pv;
     sx::DevicePlan dp;
-    auto drop = [&]() { for (void *q : {(void *)g_rp, (void *)g_ci, (void *)s_rp, (void *)s_ci, (void *)d_order_r, (void *)d_order, (void *)prp, (void *)pci, (void *)d_cut, (void *)pv, (void *)g_w, (void *)s_w}) (void)hipFree(q);
-                        sx::free_device_plan(dp); (void)hipGetLastError(); return 1; };
+    auto drop = [&]() { (void)hipGetLastError(); return 1; };
     int64_t g_nnz = 0, s_nnz = 0;
     int Mr = 0;
-    if (sx::run_graph_device(h->M, run, h->m_rp, h->m_ci, &g_rp, &g_ci, &g_w, &g_nnz, &Mr, err)) return drop();
-    if (sx::symmetrize_graph_device(Mr, g_nnz, g_rp, g_ci, g_w, &s_rp, &s_ci, &s_w, &s_nnz, err)) return drop();   // (the matching needs symmetric weights)
+    if (sx::run_graph_device(h->M, run, h->m_rp, h->m_ci, g_rp, g_ci, g_w, &g_nnz, &Mr, err)) return drop();
+    if (sx::symmetrize_graph_device(Mr, g_nnz, g_rp, g_ci, g_w, s_rp, s_ci, s_w, &s_nnz, err)) return drop();   // (the matching needs symmetric weights)
     // (blocks = the clusters of the level at which they hold up to 4 runs: cutting the final order every 4 runs would straddle them)
-    int *d_group = nullptr;
-    if (sx::cluster_rows_graph_device(Mr, Mr, s_nnz, s_rp, s_ci, (int)std::min<int64_t>(h->opt_cluster_top, 0x40000000), &d_order_r, err, s_w, RB / run, &d_group)) return drop();
-    const int erc = sx::expand_run_order_device(h->M, Mr, run, RB / run, d_order_r, d_group, &d_order, &d_cut, err);
-    (void)hipFree(d_group);
+    DevBuf<int> d_group;
+    if (sx::cluster_rows_graph_device(Mr, Mr, s_nnz, s_rp, s_ci, (int)std::min<int64_t>(h->opt_cluster_top, 0x40000000), d_order_r, err, s_w, RB / run, &d_group)) return drop();
+    const int erc = sx::expand_run_order_device(h->M, Mr, run, RB / run, d_order_r, d_group, d_order, d_cut, err);
+    d_group.reset();
     if (erc) return drop();
-    if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_order, &prp, &pci, &pv, err)) return drop();
+    if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_order, prp, pci, pv, err)) return drop();
     const double min_reuse = std::min((double)h->opt_min_reuse_x100, (double)h->opt_min_reuse_wide_x100) / 100.0;
     if (sx::build_panel_plan_device(h->M, h->K, prp, pci, pv, lpr, cap, min_reuse, dp, err, d_cut, h->opt_share_index != 0) != 0) return drop();
     if (dp.mixed || dp.dict_stride > 9 * RB || dp.max_dict > sx::kWideMaxDict) return drop();
-    h->cluster_total_dict = dp.total_dict;
+    h->cluster.total_dict = dp.total_dict;
     if (h->opt_run_cluster < 2 && (double)dp.total_dict > 0.9 * (double)h->plan_total_dict) return drop();   // (>= 10 % fewer panel rows; "run_cluster" = 2 keeps it regardless: measurements)
-    if (sx::build_slot_rows_device(dp.nblk, RB, dp.d_blk_row, d_order, &h->d_slot_row, err)) return drop();
-    adopt_device_plan(h->psc, dp, h, lpr, cap);
-    h->psc.plan_panel_frac = h->ps.plan_panel_frac;
-    h->psc.plan_narrow_frac = h->ps.plan_narrow_frac;
-    for (void *q : {(void *)g_rp, (void *)g_ci, (void *)s_rp, (void *)s_ci, (void *)d_order_r, (void *)d_order, (void *)prp, (void *)pci, (void *)d_cut, (void *)pv, (void *)g_w, (void *)s_w}) (void)hipFree(q);
+    if (sx::build_slot_rows_device(dp.nblk, RB, dp.d_blk_row, d_order, h->cluster.d_slot_row, err)) return drop();
+    adopt_device_plan(h->cluster.psc, dp, h, lpr, cap);
+    h->cluster.psc.plan_panel_frac = h->ps.plan_panel_frac;
+    h->cluster.psc.plan_narrow_frac = h->ps.plan_narrow_frac;
     return 0;
 }
 
@@ -558,47 +449,46 @@ int cluster_graph(sextans_engine *h) {   // 0 = in use, else declined: the reaso
     const bool slab = h->M != h->K && h->opt_row_offset >= 0 && h->opt_row_offset + h->M <= h->K;
     const bool rect = h->M != h->K && !slab;
     if (h->m_nnz <= 0 || (rect && h->opt_row_similarity == 0)) return 1;                 // 1: not square (and the row-similarity graph switched off)
-    if (h->dense_W > 0) return 2;                                                       // 2: dense tiles on the MFMA path (rows on the piece / chain paths are fine: they are empty here)
+    if (h->dense.W > 0) return 2;                                                       // 2: dense tiles on the MFMA path (rows on the piece / chain paths are fine: they are empty here)
     if ((int64_t)h->K * 64 >= ((int64_t)1 << 32)) return 3;   // 3: 32-bit byte offsets into a K x 16 panel
     const int lpr = 4, RB = sx::kBlock / lpr, cap = kPanelFloats / (4 * lpr);
     std::string err;
-    int *g_rp_own = nullptr, *g_ci_own = nullptr;      // the graph the rows are clustered over
-    unsigned char *g_w_own = nullptr;                  // ... and its weights, when it brings its own
+    DevBuf<int> g_rp_own, g_ci_own;                    // the graph the rows are clustered over
+    DevBuf<unsigned char> g_w_own;                     // ... and its weights, when it brings its own
     const int *g_rp = h->m_rp, *g_ci = h->m_ci;
     int64_t g_nnz = h->m_nnz;
-    struct FreeGraph { int *&a, *&b; unsigned char *&c; ~FreeGraph() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); } } free_graph{g_rp_own, g_ci_own, g_w_own};
     // worth trying?  Not when the natural-order plan already fills its blocks (numberings with locality: the grid path or nothing)
     if (h->opt_row_cluster < 0 && h->ps.plan_built && !h->ps.plan_mixed && h->ps.plan_nblk > 0 && (double)h->M / h->ps.plan_nblk >= 50.0) return 4;   // 4: natural blocks are full
     if (slab) {
-        if (sx::local_square_pattern_device(h->M, h->m_rp, h->m_ci, (int)h->opt_row_offset, &g_rp_own, &g_ci_own, &g_nnz, err)) return 6;
+        if (sx::local_square_pattern_device(h->M, h->m_rp, h->m_ci, (int)h->opt_row_offset, g_rp_own, g_ci_own, &g_nnz, err)) return 6;
         g_rp = g_rp_own; g_ci = g_ci_own;
     }
     double shared = 0.0, near = 0.0, sym = 1.0;
     bool rowsim = rect || h->opt_row_similarity > 0;
     if (!rowsim) {
         if (sx::probe_shared_neighbourhood_device(h->M, g_rp, g_ci, 256, &shared, &near, err, &sym)) return 5;
-        h->pattern_symmetry = sym;
+        h->cluster.pattern_symmetry = sym;
     }
-    auto adopt = [&](int *rp, int *ci, unsigned char *w, int64_t n) {   // replaces the graph owned so far
-        (void)hipFree(g_rp_own); (void)hipFree(g_ci_own); (void)hipFree(g_w_own);
-        g_rp_own = rp; g_ci_own = ci; g_w_own = w; g_rp = rp; g_ci = ci; g_nnz = n;
+    auto adopt = [&](DevBuf<int> &rp, DevBuf<int> &ci, DevBuf<unsigned char> &w, int64_t n) {   // replaces the graph owned so far
+        g_rp_own = std::move(rp); g_ci_own = std::move(ci); g_w_own = std::move(w);
+        g_rp = g_rp_own; g_ci = g_ci_own; g_nnz = n;
     };
     if (rowsim) {
-        int *rp = nullptr, *ci = nullptr;
-        unsigned char *w = nullptr;
+        DevBuf<int> rp, ci;
+        DevBuf<unsigned char> w;
         int64_t n = 0;
-        if (sx::row_similarity_graph_device(h->M, h->K, h->m_nnz, h->m_rp, h->m_ci, &rp, &ci, &w, &n, &shared, &near, err)) return 6;
+        if (sx::row_similarity_graph_device(h->M, h->K, h->m_nnz, h->m_rp, h->m_ci, rp, ci, w, &n, &shared, &near, err)) return 6;
         adopt(rp, ci, w, n);
     }
     if (rowsim || sym < 0.98) {   // the matching needs symmetric weights: G + G^T (the kNN lists of the row-similarity graph are not mutual either)
-        int *rp = nullptr, *ci = nullptr;
-        unsigned char *w = nullptr;
+        DevBuf<int> rp, ci;
+        DevBuf<unsigned char> w;
         int64_t n = 0;
-        if (sx::symmetrize_graph_device(h->M, g_nnz, g_rp, g_ci, g_w_own, &rp, &ci, g_w_own ? &w : nullptr, &n, err)) return 6;
+        if (sx::symmetrize_graph_device(h->M, g_nnz, g_rp, g_ci, g_w_own, rp, ci, w, &n, err)) return 6;
         adopt(rp, ci, w, n);
     }
-    h->cluster_graph_kind = rowsim ? 2 : sym < 0.98 ? 3 : slab ? 1 : 0;
-    h->cluster_shared = shared;
+    h->cluster.graph_kind = rowsim ? 2 : sym < 0.98 ? 3 : slab ? 1 : 0;
+    h->cluster.shared = shared;
     if (h->opt_row_cluster < 0) {
         // ... and not when neighbouring rows do not share neighbourhoods (random columns: there is nothing to find)
         if (shared < 0.2) return 5;                                                                                               // 5: no shared neighbourhoods
@@ -607,52 +497,48 @@ int cluster_graph(sextans_engine *h) {   // 0 = in use, else declined: the reaso
         // or slower per step); without locality in the numbering the reordered form wins even there (1-dof mesh, random order: 1.7x)
         if (h->m_nnz / h->M < 20 && near >= 0.5) return 13;
     }
-    int *d_order = nullptr, *d_colpos = nullptr, *prp = nullptr, *pci = nullptr;
-    float *pv = nullptr;
-    unsigned char *d_cut = nullptr;
+    DevBuf<int> d_order, d_colpos, prp, pci;
+    DevBuf<float> pv;
+    DevBuf<unsigned char> d_cut;
     sx::DevicePlan dp;
-    auto drop = [&](int why) { (void)hipFree(d_order); (void)hipFree(d_colpos); (void)hipFree(d_cut); (void)hipFree(prp); (void)hipFree(pci); (void)hipFree(pv);
-                               sx::free_device_plan(dp); return why; };
-    if (sx::cluster_rows_graph_device(h->M, h->M, g_nnz, g_rp, g_ci, (int)std::min<int64_t>(h->opt_cluster_top, 0x40000000), &d_order, err, g_w_own)) return drop(6);   // 6 .. 9: a builder failed
+    if (sx::cluster_rows_graph_device(h->M, h->M, g_nnz, g_rp, g_ci, (int)std::min<int64_t>(h->opt_cluster_top, 0x40000000), d_order, err, g_w_own)) return 6;   // 6 .. 9: a builder failed
     if (h->opt_refine_sweeps > 0)   // boundary rows to the block that holds more of their neighbours (blocks of 62 rows, room for 2 more each)
-        if (sx::refine_blocks_device(h->M, g_rp, g_ci, d_order, (int)std::min<int64_t>(RB, std::max<int64_t>(32, h->opt_refine_rows)), RB, (int)h->opt_refine_sweeps, &d_cut, err) == 2) return drop(6);
+        if (sx::refine_blocks_device(h->M, g_rp, g_ci, d_order, (int)std::min<int64_t>(RB, std::max<int64_t>(32, h->opt_refine_rows)), RB, (int)h->opt_refine_sweeps, d_cut, err) == 2) return 6;
     const bool relabel = h->opt_relabel_columns != 0;
-    if (relabel && sx::column_first_touch_order_device(h->M, h->K, h->m_rp, h->m_ci, d_order, &d_colpos, err)) return drop(7);
-    if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_order, &prp, &pci, &pv, err)) return drop(8);
-    if (relabel && sx::relabel_columns_device(h->m_nnz, pci, d_colpos, err)) return drop(8);
+    if (relabel && sx::column_first_touch_order_device(h->M, h->K, h->m_rp, h->m_ci, d_order, d_colpos, err)) return 7;
+    if (sx::permute_csr_rows_device(h->M, h->m_nnz, h->m_rp, h->m_ci, h->m_v, d_order, prp, pci, pv, err)) return 8;
+    if (relabel && sx::relabel_columns_device(h->m_nnz, pci, d_colpos, err)) return 8;
     // Every block that fits gets a dictionary (threshold 0): the tail of the order holds the rows nothing wanted to merge with, and
     // ONE block of such rows without reuse would make the whole plan "mixed".  The reuse test is made on the plan as a whole below.
     const double min_reuse = std::min((double)h->opt_min_reuse_x100, (double)h->opt_min_reuse_wide_x100) / 100.0;
     int brc = sx::build_panel_plan_device(h->M, h->K, prp, pci, pv, lpr, cap, 0.0, dp, err, d_cut, h->opt_share_index != 0);
     int cap_used = cap;
     if (brc == 0 && small_panel_fits(h, dp)) {
-        sx::free_device_plan(dp);
         cap_used = 5 * RB;
         brc = sx::build_panel_plan_device(h->M, h->K, prp, pci, pv, lpr, cap_used, 0.0, dp, err, d_cut, h->opt_share_index != 0);
     }
-    (void)hipFree(prp); (void)hipFree(pci); (void)hipFree(pv); (void)hipFree(d_cut);
-    prp = pci = nullptr; pv = nullptr; d_cut = nullptr;
-    if (brc != 0) return drop(9);
-    h->cluster_total_dict = dp.total_dict;
+    prp.reset(); pci.reset(); pv.reset(); d_cut.reset();
+    if (brc != 0) return 9;
+    h->cluster.total_dict = dp.total_dict;
     // 10: a row wider than the panel / limits of the 32-bit offsets; 11: the reordered plan has no reuse either; 12: not enough gain
-    if (dp.mixed || dp.dict_stride > 9 * RB || dp.max_dict > sx::kWideMaxDict || (int64_t)h->M * 64 >= ((int64_t)1 << 32)) return drop(10);
-    if ((double)h->m_nnz < min_reuse * (double)dp.total_dict) return drop(11);
+    if (dp.mixed || dp.dict_stride > 9 * RB || dp.max_dict > sx::kWideMaxDict || (int64_t)h->M * 64 >= ((int64_t)1 << 32)) return 10;
+    if ((double)h->m_nnz < min_reuse * (double)dp.total_dict) return 11;
     {   // automatic: worth the two extra passes over C only if it copies >= 40 % fewer B rows than what would run otherwise -- the
         // natural-order plan, or the grid-brick plan when the grid path built one first (ensure_cluster_plan)
         // Row-major calls (sextans_spmm_device_rm) pay no pass for it: there a plan that copies >= 25 % fewer B rows is kept (measured on
         // the holdout class: 36 % fewer panel rows = kernel 686 -> 593 us), for those calls only ("cluster_cm_pays").
         const int64_t ref = h->cluster_ref_dict > 0 ? h->cluster_ref_dict : (h->ps.plan_built ? h->plan_total_dict : 0);
         const bool auto_ref = h->opt_row_cluster < 0 && ref > 0;
-        if (auto_ref && (double)dp.total_dict > (h->cluster_for_rm ? 0.75 : 0.6) * (double)ref) return drop(12);
-        h->cluster_cm_pays = !(auto_ref && (double)dp.total_dict > 0.6 * (double)ref);
+        if (auto_ref && (double)dp.total_dict > (h->cluster_for_rm ? 0.75 : 0.6) * (double)ref) return 12;
+        h->cluster.cm_pays = !(auto_ref && (double)dp.total_dict > 0.6 * (double)ref);
     }
-    if (sx::build_slot_rows_device(dp.nblk, RB, dp.d_blk_row, d_order, &h->d_slot_row, err)) return drop(9);
-    (void)hipFree(d_order);
+    if (sx::build_slot_rows_device(dp.nblk, RB, dp.d_blk_row, d_order, h->cluster.d_slot_row, err)) return 9;
+    d_order.reset();
     const double covered = h->m_nnz ? (double)dp.nnz_in_panel_blocks / (double)h->m_nnz : 0.0;
-    adopt_device_plan(h->psc, dp, h, lpr, cap_used);
-    h->psc.plan_panel_frac = covered;
-    h->psc.plan_narrow_frac = h->psc.plan_panel_frac;
-    h->d_colpos = d_colpos;
+    adopt_device_plan(h->cluster.psc, dp, h, lpr, cap_used);
+    h->cluster.psc.plan_panel_frac = covered;
+    h->cluster.psc.plan_narrow_frac = h->cluster.psc.plan_panel_frac;
+    h->cluster.d_colpos = std::move(d_colpos);
     return 0;
 }
 }  // namespace
@@ -661,16 +547,16 @@ int cluster_graph(sextans_engine *h) {   // 0 = in use, else declined: the reaso
 // row-partitioned SpMM over a banded / mesh matrix touches 1 / world of B plus a halo, and the replicated repack was what capped
 // the compute phase of the FEM class at 4.2 x on 8 ranks (profiles/r04_rank_slab_times.json).  Rounded outwards to 64 rows.
 int ensure_col_range(sextans_engine *h) {
-    if (h->col_range_known) return SEXTANS_OK;
+    if (h->mat.col_range_known) return SEXTANS_OK;
     h->col_lo = 0; h->col_hi = h->K;
-    h->col_range_known = true;
+    h->mat.col_range_known = true;
     if (h->nnz <= 0 || !h->d_ci) return SEXTANS_OK;
-    if (!h->owns_matrix && !h->device_matrix_checked) {   // a device matrix nobody has validated yet: its indices are not trusted here
+    if (!h->owns_matrix() && !h->mat.device_matrix_checked) {   // a device matrix nobody has validated yet: its indices are not trusted here
         int bad = 0;
         std::string verr;
         if (sx::validate_csr_device(h->M, h->K, h->nnz, h->d_rp, h->d_ci, &bad, verr)) { g_last_error = verr; return SEXTANS_ERR_HIP; }
         if (bad) return (bad & 1) ? SEXTANS_ERR_INVALID : SEXTANS_ERR_INDEX;
-        h->device_matrix_checked = true;
+        h->mat.device_matrix_checked = true;
     }
     int lo = 0, hi = -1;
     std::string err;
@@ -683,12 +569,11 @@ int ensure_col_range(sextans_engine *h) {
     // mesh reaches a handful of far-away columns, which stretched [col_lo, col_hi) over all of B -- 85 us of repack per rank at 8
     // ranks against 17 us for its share (profiles/r05_rank_slab_times.json).  Kept only when it skips at least an eighth.
     {
-        unsigned char *f = nullptr;
+        DevBuf<unsigned char> f;
         int64_t touched = 0;
-        if (sx::column_touch_flags_device(h->K, h->nnz, h->d_ci, &f, &touched, err) == 0) {
+        if (sx::column_touch_flags_device(h->K, h->nnz, h->d_ci, f, &touched, err) == 0) {
             const int64_t in_range = (h->col_hi - h->col_lo + 63) / 64;
-            if (touched * 8 <= in_range * 7) { h->d_touched = f; h->touched_segments = touched; }
-            else (void)hipFree(f);
+            if (touched * 8 <= in_range * 7) { h->mat.d_touched = std::move(f); h->mat.touched_segments = touched; }
         } else (void)hipGetLastError();
     }
     return SEXTANS_OK;
@@ -696,14 +581,14 @@ int ensure_col_range(sextans_engine *h) {
 
 // Short rows in a numbering with locality: the lane-per-row kernel on the caller's column-major B (spmm_colwise_kernel.h).
 int ensure_colwise(sextans_engine *h) {
-    if (h->colwise_state != 0) return SEXTANS_OK;
-    h->colwise_state = -1;
+    if (h->cluster.colwise_state != 0) return SEXTANS_OK;
+    h->cluster.colwise_state = -1;
     if (h->M < 2 || h->m_nnz <= 0 || h->m_nnz / h->M > h->opt_colwise_max_len) return SEXTANS_OK;
     std::string err;
     double close = 0.0;
     if (sx::probe_row_coherence_device(h->M, h->m_rp, h->m_ci, 4096, &close, err)) { (void)hipGetLastError(); return SEXTANS_OK; }
-    h->row_coherence = close;
-    if (close >= 0.7) h->colwise_state = 1;
+    h->cluster.row_coherence = close;
+    if (close >= 0.7) h->cluster.colwise_state = 1;
     return SEXTANS_OK;
 }
 
@@ -717,8 +602,7 @@ void release_plan_streams(sextans_engine *h) {
     sextans_engine::PanelState &p = h->ps;
     if (!p.plan_built || p.stream_released || p.plan_lpr != 4) return;
     if ((size_t)h->K * 16 * sizeof(float) <= ((size_t)16 << 20)) return;   // column-major staging may still pick the natural-order plan
-    (void)hipFree(p.d_lidx); (void)hipFree(p.d_pval); (void)hipFree(p.d_pcol32); (void)hipFree(p.d_ioff);
-    p.d_lidx = nullptr; p.d_pval = nullptr; p.d_pcol32 = nullptr; p.d_ioff = nullptr;
+    p.d_lidx.reset(); p.d_pval.reset(); p.d_pcol32.reset(); p.d_ioff.reset();
     p.stream_released = true;
 }
 
@@ -733,14 +617,11 @@ int restore_plan_streams(sextans_engine *h) {
     const int brc = sx::build_panel_plan_device(h->M, h->K, h->m_rp, h->m_ci, h->m_v, lpr, cap, p.plan_all_dict ? 0.0 : min_reuse, dp, err, nullptr,
                                                 lpr == 4 && h->opt_share_index != 0);
     if (brc != 0 || dp.nblk != p.plan_nblk || dp.stream_len != p.plan_stream_len) {
-        sx::free_device_plan(dp);
         if (brc == 2) g_last_error = err;
         return brc == 2 ? SEXTANS_ERR_HIP : SEXTANS_ERR_STATE;
     }
-    p.d_lidx = dp.d_idx16; p.d_pval = dp.d_val; p.d_pcol32 = dp.d_col32; p.d_ioff = dp.d_ioff;
+    p.d_lidx = std::move(dp.d_idx16); p.d_pval = std::move(dp.d_val); p.d_pcol32 = std::move(dp.d_col32); p.d_ioff = std::move(dp.d_ioff);
     p.plan_idx_len = dp.idx_len;
-    dp.d_idx16 = nullptr; dp.d_val = nullptr; dp.d_col32 = nullptr; dp.d_ioff = nullptr;
-    sx::free_device_plan(dp);
     p.stream_released = false;
     return SEXTANS_OK;
 }
@@ -755,68 +636,63 @@ __global__ __launch_bounds__(256) void compact_chain_entries(const int *__restri
 }
 
 int ensure_cluster_plan(sextans_engine *h) {
-    if (h->cluster_state != 0) return SEXTANS_OK;
-    h->cluster_state = -1;
+    if (h->cluster.state != 0) return SEXTANS_OK;
+    h->cluster.state = -1;
     if (h->opt_row_cluster == 0 || h->M < 4096) return SEXTANS_OK;
     PlanTimer timer(h);
     h->cluster_ref_dict = 0;
     if (h->opt_row_cluster != 2 && cluster_grid(h) == 0) {
-        h->cluster_state = 1;
+        h->cluster.state = 1;
         // A grid whose rows reach into several far-apart column ranges (DOF-MAJOR numbering: all x unknowns, then y, then z -- a row of
         // the 3-dof FEM matrix has its 81 columns in three blocks of the matrix) gets bricks of one unknown each, whose dictionaries are
         // three times the node-major ones: blocks of ~28 rows, 20 dictionary rows per matrix row.  The graph clustering puts the rows of
         // a node back together whatever the numbering: measured on the 3M-row matrix 860 us per step with the bricks, 720 reordered
         // (node-major order: 530).  So when the brick plan's blocks are cut short by the dictionary, the graph plan is built as well and
         // kept if it copies >= 40 % fewer B rows than the bricks.
-        const double rows_per_block = (double)h->M / std::max(1, h->psc.plan_nblk);
-        if (h->opt_row_cluster < 0 && rows_per_block < 40.0 * h->psc.plan_sets) {
-            sextans_engine::PanelState grid = std::move(h->psc);
-            int *grid_slot_row = h->d_slot_row;
-            const int64_t grid_dict = h->cluster_total_dict;
-            h->psc = sextans_engine::PanelState();
-            h->d_slot_row = nullptr;
+        const double rows_per_block = (double)h->M / std::max(1, h->cluster.psc.plan_nblk);
+        if (h->opt_row_cluster < 0 && rows_per_block < 40.0 * h->cluster.psc.plan_sets) {
+            sextans_engine::PanelState grid = std::move(h->cluster.psc);
+            DevBuf<int> grid_slot_row = std::move(h->cluster.d_slot_row);
+            const int64_t grid_dict = h->cluster.total_dict;
+            h->cluster.psc = {};
             h->cluster_ref_dict = grid_dict;
             const int why = cluster_graph(h);
             (void)hipGetLastError();
-            if (why == 0) {
-                free_panel_state(grid);
-                (void)hipFree(grid_slot_row);
-                h->cluster_state = 2;
+            if (why == 0) {   // (the bricks go when `grid` and `grid_slot_row` leave scope)
+                h->cluster.state = 2;
             } else {   // keep the bricks
-                free_panel_state(h->psc);
-                (void)hipFree(h->d_slot_row); (void)hipFree(h->d_colpos);
-                h->d_colpos = nullptr;
-                h->psc = std::move(grid);
-                h->d_slot_row = grid_slot_row;
-                h->cluster_total_dict = grid_dict;
-                h->cluster_decline = why;
+                h->cluster.d_colpos.reset();
+                h->cluster.psc = std::move(grid);
+                h->cluster.d_slot_row = std::move(grid_slot_row);
+                h->cluster.total_dict = grid_dict;
+                h->cluster.decline = why;
             }
         }
-    } else if ((h->cluster_decline = cluster_graph(h)) == 0) h->cluster_state = 2;
-    else if (h->cluster_decline == 12 && h->opt_row_cluster < 0 && h->opt_run_cluster != 0 && cluster_runs(h) == 0) {
-        h->cluster_state = 1;     // the slot -> row machinery of the grid bricks; the graph plan stays declined (12) for column-major calls
-        h->cluster_runs = true;
+    } else if ((h->cluster.decline = cluster_graph(h)) == 0) h->cluster.state = 2;
+    else if (h->cluster.decline == 12 && h->opt_row_cluster < 0 && h->opt_run_cluster != 0 && cluster_runs(h) == 0) {
+        h->cluster.state = 1;     // the slot -> row machinery of the grid bricks; the graph plan stays declined (12) for column-major calls
+        h->cluster.runs = true;
     }
-    if (h->cluster_state == 2 && h->nchain > 0 && h->d_colpos) {
+    if (h->cluster.state == 2 && h->split.nchain > 0 && h->cluster.d_colpos) {
         // the exact-chain kernels read B rows by column index: for the permuted panels of the reordered form they get the chain rows'
         // entries once more, compact, with relabelled columns (a few thousand entries)
-        const long long total = h->h_chain_off.empty() ? 0 : h->h_chain_off.back();
-        std::vector<int> beg((size_t)h->nchain);
-        for (int i = 0; i < h->nchain; ++i) beg[(size_t)i] = (int)h->h_chain_off[(size_t)i];
-        bool ok = total > 0 && total < 0x7fffffffLL && hipMalloc((void **)&h->d_chain_ci_perm, sizeof(int) * (size_t)total) == hipSuccess &&
-                  hipMalloc((void **)&h->d_chain_v_c, sizeof(float) * (size_t)total) == hipSuccess && upload(&h->d_chain_beg_c, beg) == SEXTANS_OK;
+        const long long total = h->split.h_chain_off.empty() ? 0 : h->split.h_chain_off.back();
+        std::vector<int> beg((size_t)h->split.nchain);
+        for (int i = 0; i < h->split.nchain; ++i) beg[(size_t)i] = (int)h->split.h_chain_off[(size_t)i];
+        bool ok = total > 0 && total < 0x7fffffffLL && h->cluster.d_chain_ci_perm.alloc((size_t)total) == hipSuccess &&
+                  h->cluster.d_chain_v_c.alloc((size_t)total) == hipSuccess && upload(h->cluster.d_chain_beg_c, beg) == SEXTANS_OK;
         if (ok) {
-            hipLaunchKernelGGL(compact_chain_entries, dim3((unsigned)h->nchain), dim3(256), 0, nullptr, h->d_chain_beg, h->d_chain_off, h->s_ci, h->s_v,
-                               h->d_colpos, h->d_chain_ci_perm, h->d_chain_v_c);
+            hipLaunchKernelGGL(compact_chain_entries, dim3((unsigned)h->split.nchain), dim3(256), 0, nullptr, h->split.d_chain_beg, h->split.d_chain_off, h->s_ci, h->s_v,
+                               h->cluster.d_colpos, h->cluster.d_chain_ci_perm, h->cluster.d_chain_v_c);
             ok = hipDeviceSynchronize() == hipSuccess;
         }
         if (!ok) {   // (declined like every other failure in here)
             free_cluster_plan(h);
-            h->cluster_state = -1;
-            h->cluster_decline = 9;
+            h->cluster.state = -1;
+            h->cluster.decline = 9;
         }
     }
-    if (h->cluster_state == 1 || (h->cluster_state == 2 && h->cluster_cm_pays)) release_plan_streams(h);
+    if (h->cluster.state == 1 || (h->cluster.state == 2 && h->cluster.cm_pays)) release_plan_streams(h);
     (void)hipGetLastError();   // a failure in here (out of memory for the sort buffers, ...) only declines the clustered plan
     return SEXTANS_OK;
 }
@@ -856,14 +732,14 @@ bool window_pays(const sextans_engine *h, int N, int64_t padded) {
 
 // Build (or reuse) the K-windowed stream of A.  force: "kernel" = 3 (no pay-off / skew test).
 int ensure_window(sextans_engine *h, bool force) {
-    if (h->win_state != 0 && h->win_built_rows == h->opt_win_rows && h->win_built_cols == h->opt_win_cols &&
-        (h->win_state == 1 || !force))
+    if (h->win.state != 0 && h->win.built_rows == h->opt_win_rows && h->win.built_cols == h->opt_win_cols &&
+        (h->win.state == 1 || !force))
         return SEXTANS_OK;
     free_window(h);
     PlanTimer timer(h);
-    h->win_built_rows = h->opt_win_rows;
-    h->win_built_cols = h->opt_win_cols;
-    h->win_state = -1;
+    h->win.built_rows = h->opt_win_rows;
+    h->win.built_cols = h->opt_win_cols;
+    h->win.state = -1;
     const int RW = (int)h->opt_win_rows;
     if (RW < 1 || RW > sx::kWinMaxRowsPerWave || h->opt_win_cols < 1 || h->opt_win_cols > 0x7fffffff ||
         (int64_t)h->K > ((int64_t)1 << sx::kWinColBits) || h->m_nnz == 0)
@@ -879,13 +755,13 @@ int ensure_window(sextans_engine *h, bool force) {
         return SEXTANS_OK;
     if (!force && (double)plan.padded > 1.35 * (double)h->m_nnz) return SEXTANS_OK;
     static_assert(sizeof(sx::WinEntry) == sizeof(uint2), "stream entries are loaded as uint2");
-    SX_HIP(hipMalloc((void **)&h->d_wstream, sizeof(uint2) * plan.stream.size()));
-    SX_HIP(hipMemcpy(h->d_wstream, plan.stream.data(), sizeof(uint2) * plan.stream.size(), hipMemcpyHostToDevice));
-    if (int rc = upload(&h->d_wstep0, plan.wave_step0)) return rc;
-    h->win_nwaves = plan.nwaves;
-    h->win_rw = RW;
-    h->win_padded = plan.padded;
-    h->win_state = 1;
+    SX_HIP(h->win.d_wstream.alloc(plan.stream.size()));
+    SX_HIP(hipMemcpy(h->win.d_wstream, plan.stream.data(), sizeof(uint2) * plan.stream.size(), hipMemcpyHostToDevice));
+    if (int rc = upload(h->win.d_wstep0, plan.wave_step0)) return rc;
+    h->win.nwaves = plan.nwaves;
+    h->win.rw = RW;
+    h->win.padded = plan.padded;
+    h->win.state = 1;
     return SEXTANS_OK;
 }
 
@@ -903,23 +779,23 @@ int ensure_window(sextans_engine *h, bool force) {
 
 static int ensure_split_rows(sextans_engine *h);
 int ensure_split(sextans_engine *h) {
-    const bool fresh = !(h->split_built_opt == h->opt_split_rows && h->bucket_built_opt == h->opt_bucket_rows &&
-                         h->split_built_gnnz == h->opt_global_nnz && h->chain_built_opt == h->opt_exact_chain);
+    const bool fresh = !(h->split.built_opt == h->opt_split_rows && h->split.bucket_built_opt == h->opt_bucket_rows &&
+                         h->split.built_gnnz == h->opt_global_nnz && h->split.chain_built_opt == h->opt_exact_chain);
     if (int rc = ensure_split_rows(h)) return rc;
-    if (fresh && h->rb_n > 0) return mark_rowblock_skip(h);   // rows of blocks routed to the fp32 matrix cores: never written by the CSR kernels
+    if (fresh && h->dense.rb_n > 0) return mark_rowblock_skip(h);   // rows of blocks routed to the fp32 matrix cores: never written by the CSR kernels
     return SEXTANS_OK;
 }
 static int ensure_split_rows(sextans_engine *h) {
-    if (h->split_built_opt == h->opt_split_rows && h->bucket_built_opt == h->opt_bucket_rows &&
-        h->split_built_gnnz == h->opt_global_nnz && h->chain_built_opt == h->opt_exact_chain)
+    if (h->split.built_opt == h->opt_split_rows && h->split.bucket_built_opt == h->opt_bucket_rows &&
+        h->split.built_gnnz == h->opt_global_nnz && h->split.chain_built_opt == h->opt_exact_chain)
         return SEXTANS_OK;
     free_split(h);
     free_plan(h);      // the packed forms are built from the main matrix
     free_window(h);
-    h->split_built_opt = h->opt_split_rows;
-    h->bucket_built_opt = h->opt_bucket_rows;
-    h->split_built_gnnz = h->opt_global_nnz;
-    h->chain_built_opt = h->opt_exact_chain;
+    h->split.built_opt = h->opt_split_rows;
+    h->split.bucket_built_opt = h->opt_bucket_rows;
+    h->split.built_gnnz = h->opt_global_nnz;
+    h->split.chain_built_opt = h->opt_exact_chain;
     if (h->M == 0 || h->s_nnz == 0) return SEXTANS_OK;
     int64_t T = h->opt_split_rows, L0 = h->opt_bucket_rows;
     // strict order: rows above the automatic threshold become exact chains instead of one-piece rows
@@ -990,19 +866,19 @@ static int ensure_split_rows(sextans_engine *h) {
             beg.push_back(rp[(size_t)r]);
             off.push_back(off.back() + len);
         }
-        if (int rc = upload(&h->d_chain_row, chain_rows)) return rc;
-        if (int rc = upload(&h->d_chain_beg, beg)) return rc;
-        if (int rc = upload(&h->d_chain_off, off)) return rc;
+        if (int rc = upload(h->split.d_chain_row, chain_rows)) return rc;
+        if (int rc = upload(h->split.d_chain_beg, beg)) return rc;
+        if (int rc = upload(h->split.d_chain_off, off)) return rc;
         {   // launch order of whole-matrix calls: longest chain first (a workgroup lives as long as its row is; one per CU)
             std::vector<int> perm(chain_rows.size());
             for (size_t i = 0; i < perm.size(); ++i) perm[i] = (int)i;
             std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return off[(size_t)a + 1] - off[(size_t)a] > off[(size_t)b + 1] - off[(size_t)b]; });
-            if (int rc = upload(&h->d_chain_perm, perm)) return rc;
+            if (int rc = upload(h->split.d_chain_perm, perm)) return rc;
         }
-        h->h_chain_row = chain_rows;
-        h->h_chain_off = off;
-        h->nchain = (int)chain_rows.size();
-        h->chain_T = Tc_rows;
+        h->split.h_chain_row = chain_rows;
+        h->split.h_chain_off = off;
+        h->split.nchain = (int)chain_rows.size();
+        h->split.chain_T = Tc_rows;
     }
     std::vector<int> ci;
     std::vector<float> va;
@@ -1017,10 +893,10 @@ static int ensure_split_rows(sextans_engine *h) {
             for (int64_t j = j0; j < j1; j += step) { vrp.push_back((int)j); vend.push_back((int)std::min(j + step, j1)); }
         }
         vfirst.push_back((int)vrp.size());
-        if (int rc = upload(&t.d_vrp, vrp)) return rc;
-        if (int rc = upload(&t.d_vend, vend)) return rc;
-        if (int rc = upload(&t.d_vfirst, vfirst)) return rc;
-        if (int rc = upload(&t.d_row, order)) return rc;
+        if (int rc = upload(t.d_vrp, vrp)) return rc;
+        if (int rc = upload(t.d_vend, vend)) return rc;
+        if (int rc = upload(t.d_vfirst, vfirst)) return rc;
+        if (int rc = upload(t.d_row, order)) return rc;
         t.h_row = order;
         t.h_vfirst = vfirst;
         return SEXTANS_OK;
@@ -1029,8 +905,8 @@ static int ensure_split_rows(sextans_engine *h) {
     std::stable_sort(by_len.begin(), by_len.end(), [&](int a, int b) {
         return rp[(size_t)a + 1] - rp[(size_t)a] > rp[(size_t)b + 1] - rp[(size_t)b];
     });
-    if (int rc = build(by_len, h->by_len)) return rc;
-    if (int rc = build(piece_rows, h->by_row)) return rc;
+    if (int rc = build(by_len, h->split.by_len)) return rc;
+    if (int rc = build(piece_rows, h->split.by_row)) return rc;
     // main matrix: long rows emptied; skip flags
     std::vector<int> mrp((size_t)h->M + 1, 0);
     std::vector<unsigned char> skip((size_t)h->M, 0);
@@ -1040,7 +916,7 @@ static int ensure_split_rows(sextans_engine *h) {
             const int j0 = rp[(size_t)r], j1 = rp[(size_t)r + 1];
             if (k < rows.size() && rows[k] == r) {
                 skip[(size_t)r] = 1;
-                if ((int64_t)j1 - j0 > T) h->h_split_rows.push_back(r);
+                if ((int64_t)j1 - j0 > T) h->split.h_split_rows.push_back(r);
                 ++k;
             } else {
                 if (w != (size_t)j0) {
@@ -1054,15 +930,15 @@ static int ensure_split_rows(sextans_engine *h) {
         ci.resize(w ? w : 1); va.resize(w ? w : 1);
         h->m_nnz = (int64_t)w;
     }
-    if (int rc = upload(&h->d_mrp, mrp)) return rc;
-    if (int rc = upload(&h->d_mci, ci)) return rc;
-    if (int rc = upload(&h->d_mv, va)) return rc;
-    if (int rc = upload(&h->d_skip, skip)) return rc;
-    h->m_rp = h->d_mrp; h->m_ci = h->d_mci; h->m_v = h->d_mv;
-    h->nhub = (int)piece_rows.size();
-    h->split_nv = h->by_len.h_vfirst.back();
-    h->split_T = T == INT64_MAX ? 0 : T;
-    h->bucket_L0 = L0;
+    if (int rc = upload(h->split.d_mrp, mrp)) return rc;
+    if (int rc = upload(h->split.d_mci, ci)) return rc;
+    if (int rc = upload(h->split.d_mv, va)) return rc;
+    if (int rc = upload(h->split.d_skip, skip)) return rc;
+    h->m_rp = h->split.d_mrp; h->m_ci = h->split.d_mci; h->m_v = h->split.d_mv;
+    h->split.nhub = (int)piece_rows.size();
+    h->split.nv = h->split.by_len.h_vfirst.back();
+    h->split.T = T == INT64_MAX ? 0 : T;
+    h->split.bucket_L0 = L0;
     return SEXTANS_OK;
 }
 
@@ -1073,26 +949,21 @@ int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
     if (int rc = ensure_col_range(h)) return rc;
     if (int rc = ensure_dense(h)) return rc;   // first the dense tiles leave (when the caller routes them to MFMA) ...
     if (int rc = ensure_split(h)) return rc;   // ... then the long rows; the packed forms below are built from what remains
-    if (h->dense_W > 0 && N % 32 == 0) {
+    if (h->dense.W > 0 && N % 32 == 0) {
         const size_t need = (size_t)((h->K + 31) / 32) * 32 * (size_t)N * 2;
-        if (h->bell_Bf_cap < need) {
-            if (h->d_bell_Bf) SX_HIP(hipFree(h->d_bell_Bf));
-            h->d_bell_Bf = nullptr; h->bell_Bf_cap = 0;
-            SX_HIP(hipMalloc(&h->d_bell_Bf, need));
-            h->bell_Bf_cap = need;
-        }
+        SX_HIP(h->d_bell_Bf.reserve(need));
     }
-    if (h->nhub > 0)   // (16-column granularity: N = 16 t + 8 may run its tail as a half-empty 16-column tile)
-        if (int rc = ensure(&h->d_P, &h->P_cap, (size_t)h->split_nv * (size_t)((N + 15) / 16 * 16))) return rc;
-    if (h->nchain > 0 && !h->aux_stream) {
+    if (h->split.nhub > 0)   // (16-column granularity: N = 16 t + 8 may run its tail as a half-empty 16-column tile)
+        if (int rc = reserve(h->d_P, (size_t)h->split.nv * (size_t)((N + 15) / 16 * 16))) return rc;
+    if (h->split.nchain > 0 && !h->aux_stream) {
         SX_HIP(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));   // (a high-priority stream was measured: no difference)
         SX_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         SX_HIP(hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
     }
     const size_t n16 = (size_t)((N + 15) / 16) * 16;   // (N = 16 t + 8: room for the tail as a zero-padded 16-column tile)
-    if (!h->lean_prepare && (h->Bp_cap < (size_t)h->K * n16 || !h->d_Bp)) h->bp_layout = 0;   // new workspace: nothing to reuse
+    if (!h->lean_prepare && (h->d_Bp.size() < (size_t)h->K * n16 || !h->d_Bp)) h->bp_layout = 0;   // new workspace: nothing to reuse
     if (!h->lean_prepare)
-        if (int rc = ensure(&h->d_Bp, &h->Bp_cap, (size_t)h->K * n16)) return rc;
+        if (int rc = reserve(h->d_Bp, (size_t)h->K * n16)) return rc;
     // main tile width: 4*lanes_per_row, but never wider than N itself (N = 8 -> 2 lanes per row); then
     // 16- and 8-wide tiles for the remainder (N is a multiple of 8, the reference's N-tile
     // granularity: sextans.cpp:57-60).
@@ -1104,8 +975,8 @@ int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
     // N = 8 (the reference's own N tile) on a large matrix without long rows: the 16-column plan and the register-resident kernel
     // with a half-empty tile (spmm_panel_v2.h: last_cols) beat the 8-column panel kernel (4M-row FEM: 733 -> ~620 us per step) and
     // save the second packed plan; small B (column-major staging) and matrices with rows on the piece / chain paths keep 2 lanes per row
-    bool n8_wide = N == 8 && !h->opt_lpr && h->opt_kernel == 0 && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && h->nhub == 0 && h->nchain == 0 &&
-                   h->dense_W == 0 && (size_t)h->K * 8 * sizeof(float) > ((size_t)16 << 20) && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
+    bool n8_wide = N == 8 && !h->opt_lpr && h->opt_kernel == 0 && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && h->split.nhub == 0 && h->split.nchain == 0 &&
+                   h->dense.W == 0 && (size_t)h->K * 8 * sizeof(float) > ((size_t)16 << 20) && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
                    h->M > 0 && h->m_nnz / h->M >= 48;   // (shorter rows: measured a loss -- 2-D 9-point x 2 dof 0.48 -> 0.37 of the roofline per step, 43-entry mesh rows 0.38 -> 0.33)
     Tiling t;
     auto tiles = [&]() {
@@ -1124,15 +995,15 @@ int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
     // of the non-zeros sit in row blocks whose B rows are reused -- "only where a tile has reuse").
     if ((h->opt_kernel == 0 || h->opt_kernel == 4) && h->m_nnz > 0)
         if (int rc = ensure_colwise(h)) return rc;
-    if (h->opt_kernel != 1 && h->opt_kernel != 4 && h->m_nnz > 0 && !(colwise_wanted(h) && h->nhub == 0 && h->nchain == 0 && h->dense_W == 0)) {
+    if (h->opt_kernel != 1 && h->opt_kernel != 4 && h->m_nnz > 0 && !(colwise_wanted(h) && h->split.nhub == 0 && h->split.nchain == 0 && h->dense.W == 0)) {
         if (int rc = ensure_plan(h, lpr, h->opt_kernel == 2)) return rc;
         // (here, not at launch time: prepare() runs before a hipGraph capture starts, and the builders copy to the host and
         // allocate.  Only for whole-matrix calls: engines that serve row ranges -- the chunks of the multi-GPU pipeline -- never
         // use the clustered plan and do not pay for it.)
         if (lpr == 4 && whole && h->opt_kernel != 3) {
             if (int rc = ensure_cluster_plan(h)) return rc;
-            if (h->cluster_state == 2 && h->cluster_cm_pays && (N >= 16 || n8_wide) && !h->lean_prepare)   // row-major C staging of the reordered form: ceil(N / 16) tiles of M x 16
-                if (int rc = ensure(&h->d_Cs, &h->Cs_cap, (n16 / 16) * (size_t)h->M * 16)) return rc;
+            if (h->cluster.state == 2 && h->cluster.cm_pays && (N >= 16 || n8_wide) && !h->lean_prepare)   // row-major C staging of the reordered form: ceil(N / 16) tiles of M x 16
+                if (int rc = reserve(h->d_Cs, (n16 / 16) * (size_t)h->M * 16)) return rc;
         }
         t.panel = h->ps.plan_built && ((h->opt_kernel == 2) || (h->ps.plan_panel_frac >= 0.5 && (N >= 32 || h->ps.plan_narrow_frac >= 0.5)));
         // whole-matrix calls on a mixed plan that has its split form: from kSplitMinFrac on (FEM rows + 3 x / 6 x as many uniformly random
@@ -1143,7 +1014,7 @@ int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
             t.panel = true;
         // (a matrix that runs in the reordered form needs no natural-order plan for that: a randomly numbered mesh without any reuse between
         // consecutive rows has none -- its N = 8 calls fell to the gather kernel, 0.06 against 0.37 at N = 16 on the holdout class)
-        const bool reorder8 = whole && h->cluster_state == 2 && h->cluster_cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3;
+        const bool reorder8 = whole && h->cluster.state == 2 && h->cluster.cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3;
         if (n8_wide && !reorder8 && !(t.panel && !h->ps.plan_mixed && h->ps.plan_max_dict <= sx::kWideMaxDict)) {   // not a case for the wide kernel after all
             n8_wide = false;
             lpr = 4;
@@ -1155,15 +1026,15 @@ int prepare(sextans_engine *h, int N, bool whole, Tiling *out) {
     // (the reordered form of a graph-clustered matrix runs 16-column tiles whether or not a natural-order plan exists)
     // (a lean prepare -- on behalf of a row-major call -- also keeps 16-column tiles for a clustered plan that is kept for row-major calls
     // only: sextans_spmm_device_rm needs W == 16 to use it, and at N >= 32 the switch to 8 lanes per row below took it to the gather kernel)
-    const bool reorder = whole && h->cluster_state == 2 && (h->cluster_cm_pays || h->lean_prepare) && h->opt_kernel != 1 && h->opt_kernel != 3 && lpr == 4;
+    const bool reorder = whole && h->cluster.state == 2 && (h->cluster.cm_pays || h->lean_prepare) && h->opt_kernel != 1 && h->opt_kernel != 3 && lpr == 4;
     if (!h->opt_lpr && !t.panel && !reorder && N >= 32 && lpr != 8) { lpr = 8; tiles(); }
     // "kernel" 3 = K-windowed accumulator-resident kernel; auto picks it for matrices without B-row reuse
     // whose B does not fit the L2s when the traffic model says the sweep moves fewer bytes than the gather.
     if (h->m_nnz > 0 && (h->opt_kernel == 3 || (h->opt_kernel == 0 && !t.panel))) {
         const bool force = h->opt_kernel == 3;
-        if (force || (h->win_state >= 0 && window_pays(h, N, h->win_state == 1 ? h->win_padded : h->m_nnz))) {
+        if (force || (h->win.state >= 0 && window_pays(h, N, h->win.state == 1 ? h->win.padded : h->m_nnz))) {
             if (int rc = ensure_window(h, force)) return rc;
-            t.window = h->win_state == 1 && (force || window_pays(h, N, h->win_padded));
+            t.window = h->win.state == 1 && (force || window_pays(h, N, h->win.padded));
         }
     }
     if (out) *out = std::move(t);

@@ -24,38 +24,38 @@ void refresh_plan(const sextans_engine *h, const sextans_engine::PanelState &p, 
     if (!p.plan_built || p.stream_released || !p.d_pval || !p.plan_lpr || p.plan_nblk <= 0) return;
     const int slots = (sx::kBlock / p.plan_lpr) * p.plan_sets;
     hipLaunchKernelGGL(sx::refresh_packed_stream, dim3((unsigned)p.plan_nblk), dim3(256), 0, s, p.plan_nblk, slots, p.plan_lpr, p.d_blk_row, slot_row,
-                       (const int2 *)p.d_row_off, h->m_rp, (const unsigned *)h->m_v, (unsigned *)p.d_pval);
+                       (const int2 *)p.d_row_off.get(), h->m_rp, (const unsigned *)h->m_v, (unsigned *)p.d_pval.get());
 }
 
 int refresh_forms(sextans_engine *h, hipStream_t s) {
     bool rebuilt = false;
-    if (h->d_wstream) { free_window(h); rebuilt = true; }
-    if (h->d_sv || h->dense_W > 0 || h->rb_n > 0) {   // dense tiles / row blocks were cut out: the source is an owned copy, the side matrices hold values
+    if (h->win.d_wstream) { free_window(h); rebuilt = true; }
+    if (h->dense.d_sv || h->dense.W > 0 || h->dense.rb_n > 0) {   // dense tiles / row blocks were cut out: the source is an owned copy, the side matrices hold values
         free_plan(h);
         free_window(h);
         free_dense(h);
         rebuilt = true;
     }
     // the stages that alias the matrix as set follow its value array
-    if (!h->d_sv) h->s_v = h->d_v;
-    if (!h->d_mv) h->m_v = h->s_v;
-    if (h->d_mv && h->d_skip && h->M > 0)
+    if (!h->dense.d_sv) h->s_v = h->d_v;
+    if (!h->split.d_mv) h->m_v = h->s_v;
+    if (h->split.d_mv && h->split.d_skip && h->M > 0)
         hipLaunchKernelGGL(sx::refresh_main_values, dim3((unsigned)((h->M + 3) / 4)), dim3(256), 0, s, h->M, h->s_rp, (const unsigned *)h->s_v,
-                           (const unsigned char *)h->d_skip, (const int *)h->d_mrp, (unsigned *)h->d_mv);
+                           (const unsigned char *)h->split.d_skip.get(), (const int *)h->split.d_mrp.get(), (unsigned *)h->split.d_mv.get());
     refresh_plan(h, h->ps, nullptr, s);
     for (const auto &p : h->plan_stash) refresh_plan(h, p, nullptr, s);
-    refresh_plan(h, h->psc, h->d_slot_row, s);
-    if (h->d_chain_v_c && h->nchain > 0)
-        hipLaunchKernelGGL(sx::refresh_chain_values, dim3((unsigned)h->nchain), dim3(256), 0, s, h->d_chain_beg, h->d_chain_off, (const unsigned *)h->s_v,
-                           (unsigned *)h->d_chain_v_c);
+    refresh_plan(h, h->cluster.psc, h->cluster.d_slot_row, s);
+    if (h->cluster.d_chain_v_c && h->split.nchain > 0)
+        hipLaunchKernelGGL(sx::refresh_chain_values, dim3((unsigned)h->split.nchain), dim3(256), 0, s, h->split.d_chain_beg, h->split.d_chain_off, (const unsigned *)h->s_v,
+                           (unsigned *)h->cluster.d_chain_v_c.get());
     if (h->tr) {   // (ensure_transpose allocates the entry permutation together with A^T)
-        hipLaunchKernelGGL(sx::refresh_transposed, dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, s, (long long)h->nnz, h->d_tperm,
-                           (const unsigned *)h->d_v, (unsigned *)h->d_tv);
-        if (int rc = sextans_update_values_device(h->tr, h->d_tv, s)) return rc;
+        hipLaunchKernelGGL(sx::refresh_transposed, dim3((unsigned)((h->nnz + 255) / 256)), dim3(256), 0, s, (long long)h->nnz, h->at.d_tperm,
+                           (const unsigned *)h->d_v, (unsigned *)h->at.d_tv.get());
+        if (int rc = sextans_update_values_device(h->tr, h->at.d_tv, s)) return rc;
     }
     SX_HIP(hipGetLastError());
-    ++h->value_refreshes;
-    if (rebuilt) ++h->value_refresh_rebuilt;
+    ++h->mat.value_refreshes;
+    if (rebuilt) ++h->mat.value_refresh_rebuilt;
     return SEXTANS_OK;
 }
 
@@ -73,7 +73,7 @@ int sextans_update_values_device(sextans_handle_t h, const float *d_val, void *s
     if (!d_val) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
-    if (h->owns_matrix) {   // the engine's own array keeps the values
+    if (h->owns_matrix()) {   // the engine's own array keeps the values
         if (d_val != h->d_v) SX_HIP(hipMemcpyAsync((void *)h->d_v, d_val, sizeof(float) * (size_t)h->nnz, hipMemcpyDeviceToDevice, s));
     } else {
         h->d_v = d_val;     // not copied, not owned (may be the array as before, changed in place)
@@ -87,9 +87,9 @@ int sextans_update_values(sextans_handle_t h, const float *val) {
     if (h->nnz == 0) return SEXTANS_OK;
     if (!val) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
-    if (!h->owns_matrix) {   // a caller-provided device matrix: the uploaded values live in an array of the engine's (until the next update)
-        if (!h->d_v_upd) SX_HIP(hipMalloc((void **)&h->d_v_upd, sizeof(float) * (size_t)h->nnz));
-        h->d_v = h->d_v_upd;
+    if (!h->owns_matrix()) {   // a caller-provided device matrix: the uploaded values live in an array of the engine's (until the next update)
+        if (!h->mat.d_v_upd) SX_HIP(h->mat.d_v_upd.alloc((size_t)h->nnz));
+        h->d_v = h->mat.d_v_upd;
     }
     SX_HIP(hipDeviceSynchronize());   // nothing enqueued earlier may still read the values (synchronous, like sextans_set_matrix_csr)
     SX_HIP(hipMemcpy((void *)h->d_v, val, sizeof(float) * (size_t)h->nnz, hipMemcpyHostToDevice));

@@ -34,7 +34,7 @@ int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out) {
     if (int rc = prepare(h, Nplan, true, &t)) return rc;
     // A clustered plan that was declined only because the column-major form has to pay two passes over C for it (decline 12) is
     // reconsidered for this layout, where it costs nothing: built once, used by row-major calls only unless it pays for both.
-    if ((h->cluster_state == -1 || h->cluster_runs) && h->cluster_decline == 12 && !h->cluster_rm_tried && t.W == 16 && h->opt_row_cluster < 0) {
+    if ((h->cluster.state == -1 || h->cluster.runs) && h->cluster.decline == 12 && !h->cluster_rm_tried && t.W == 16 && h->opt_row_cluster < 0) {
         h->cluster_rm_tried = true;
         free_cluster_plan(h);
         h->cluster_for_rm = true;
@@ -42,20 +42,17 @@ int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out) {
         h->cluster_for_rm = false;
         if (rc) return rc;
     }
-    if (t.W == 16 && h->cluster_state == 2 && h->d_colpos && !h->d_dict_nat) {   // the plan's dictionaries hold relabelled columns: translate them back once
-        const long long n = (long long)h->psc.plan_nblk * h->psc.plan_dict_stride;
-        int *colinv = nullptr;
-        if (hipMalloc((void **)&colinv, sizeof(int) * (size_t)std::max(h->K, 1)) != hipSuccess ||
-            hipMalloc((void **)&h->d_dict_nat, sizeof(int) * (size_t)std::max<long long>(n, 1)) != hipSuccess) {
-            (void)hipFree(colinv); (void)hipFree(h->d_dict_nat); h->d_dict_nat = nullptr; (void)hipGetLastError();
+    if (t.W == 16 && h->cluster.state == 2 && h->cluster.d_colpos && !h->cluster.d_dict_nat) {   // the plan's dictionaries hold relabelled columns: translate them back once
+        const long long n = (long long)h->cluster.psc.plan_nblk * h->cluster.psc.plan_dict_stride;
+        DevBuf<int> colinv;
+        if (colinv.alloc((size_t)std::max(h->K, 1)) != hipSuccess || h->cluster.d_dict_nat.alloc((size_t)std::max<long long>(n, 1)) != hipSuccess) {
+            (void)hipGetLastError();
             g_last_error = "row-major plan: out of device memory for the translated block dictionaries";
             return SEXTANS_ERR_HIP;
         }
-        hipLaunchKernelGGL(invert_positions, dim3((unsigned)((h->K + 255) / 256)), dim3(256), 0, s, h->K, h->d_colpos, colinv);
-        hipLaunchKernelGGL(translate_dict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, h->K, h->psc.d_dict, colinv, h->d_dict_nat);
-        const hipError_t se = hipStreamSynchronize(s);
-        (void)hipFree(colinv);
-        SX_HIP(se);
+        hipLaunchKernelGGL(invert_positions, dim3((unsigned)((h->K + 255) / 256)), dim3(256), 0, s, h->K, h->cluster.d_colpos, colinv);
+        hipLaunchKernelGGL(translate_dict, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, h->K, h->cluster.psc.d_dict, colinv, h->cluster.d_dict_nat);
+        SX_HIP(hipStreamSynchronize(s));
     }
     if (out) *out = std::move(t);
     return SEXTANS_OK;
@@ -89,7 +86,7 @@ RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
     // 16-byte gathers and the chain producers' LDS-DMA read B rows ldb floats apart instead of panel rows, the fold and the chain
     // consumer write C[r * ldc + n].  The main kernels skip those rows (d_skip), so the order between the launches does not matter;
     // the chains run beside the main kernel on the engine's side stream, as in the column-major form.
-    const bool hubs = h->nhub > 0, chains = h->nchain > 0;
+    const bool hubs = h->split.nhub > 0, chains = h->split.nchain > 0;
     const bool long_ok = (!hubs && !chains) || (r.aligned && (!chains || (h->aux_stream && h->ev_fork && h->ev_join && c.ldb < ((int64_t)1 << 31))));
     if (colwise && r.aligned && !hubs && !chains && csr_only(h) && h->m_nnz > 0) {   // short rows in a local numbering: lane per row, 16-byte accesses
         r.path = RouteRM::kColwise;
@@ -97,11 +94,11 @@ RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
     }
     if (t.W == 16 && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && csr_only(h) &&
         !(colwise && !hubs && !chains) && r.aligned && fits && long_ok && h->m_nnz > 0) {
-        if (h->cluster_state == 2) r.mode = 2;
-        else if (h->cluster_state == 1) r.mode = 1;
+        if (h->cluster.state == 2) r.mode = 2;
+        else if (h->cluster.state == 1) r.mode = 1;
         else if (t.panel && (!h->ps.plan_mixed || (h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_kernel == 0)) && h->ps.plan_max_dict <= kWideMaxDict) r.mode = 0;
     }
-    if (r.mode == 2 && h->d_colpos && !h->d_dict_nat) r.mode = -1;   // (cannot happen after rm_plan; kept as a guard)
+    if (r.mode == 2 && h->cluster.d_colpos && !h->cluster.d_dict_nat) r.mode = -1;   // (cannot happen after rm_plan; kept as a guard)
     if (r.mode >= 0) {
         r.path = RouteRM::kPanelV2;
         r.split = r.mode == 0 && h->ps.plan_mixed;
@@ -131,12 +128,12 @@ int run_rm_colwise(sextans_engine *h, const Call &c) {
 // The paths on the caller's row-major operands (kPanelV2, kRowgroup), rows on the long-row paths included
 int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
     Prof p(h, &h->ev_kernel, c.s);
-    const bool long_rows = h->nhub > 0 || h->nchain > 0;
-    if (h->nchain > 0) {
+    const bool long_rows = h->split.nhub > 0 || h->split.nchain > 0;
+    if (h->split.nchain > 0) {
         std::vector<Seg> segs;   // tiles of the chain kernel: 16-column tiles and an 8-column tail (never past column N of a B row)
         if (c.N / 16) segs.push_back(Seg{16, 0, c.N / 16});
         if (c.N % 16) segs.push_back(Seg{8, c.N / 16 * 16, 1});
-        if (int rc = fork_chains(h, c, segs, 0, h->nchain, true)) return rc;
+        if (int rc = fork_chains(h, c, segs, 0, h->split.nchain, true)) return rc;
     }
     // the gather kernel: over the rows of the blocks without a dictionary (split form of a mixed plan), or over all rows
     auto rowgroups = [&](const std::vector<Seg> &segs, const unsigned char *skip, const int *groups, int ngroups) {
@@ -146,20 +143,20 @@ int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
     };
     if (r.path == RouteRM::kPanelV2) {
         const int ntiles = (c.N + 15) / 16, last_cols = c.N % 16 ? 8 : 16;
-        const sextans_engine::PanelState &P = r.mode ? h->psc : h->ps;
+        const sextans_engine::PanelState &P = r.mode ? h->cluster.psc : h->ps;
         if (int rc = launch_panel_v2(h, 1, c.B, c.C_in, c.ldc_in, c.C_out, c.ldc, ntiles, c.alpha, c.beta, c.s, 0, 0, P.plan_nblk, 0, r.mode, last_cols, c.ldb, r.split))
             return rc;
         if (r.split) rowgroups(wide_first(c.N), h->ps.d_rg_skip, h->ps.d_rg_groups, h->ps.rg_ngroups);
     } else {
-        rowgroups(r.segs, h->d_skip, nullptr, 0);
+        rowgroups(r.segs, h->split.d_skip, nullptr, 0);
     }
-    if (h->nhub > 0) {   // the long rows' pieces and their fold
-        const sextans_engine::PieceTable &pt = h->by_len;
-        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->nhub];
+    if (h->split.nhub > 0) {   // the long rows' pieces and their fold
+        const sextans_engine::PieceTable &pt = h->split.by_len;
+        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->split.nhub];
         for (const Seg &g : wide_first(c.N)) launch_hub_pieces(h, g.width, pt, c.B + g.col0, g.ntiles, g.col0, v0, v1, c.s, nullptr, c.ldb);
-        launch_fold(h, pt, 0, h->nhub, c.N, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+        launch_fold(h, pt, 0, h->split.nhub, c.N, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
     }
-    if (h->nchain > 0) SX_HIP(hipStreamWaitEvent(c.s, h->ev_join, 0));
+    if (h->split.nchain > 0) SX_HIP(hipStreamWaitEvent(c.s, h->ev_join, 0));
     h->last_kernel = r.path == RouteRM::kRowgroup ? (long_rows ? "spmm_csr_rowgroup_rowmajor+long_rows" : "spmm_csr_rowgroup_rowmajor")
                      : r.mode == 2 ? (long_rows ? "spmm_csr_panel_v2_rowmajor_clustered+long_rows" : "spmm_csr_panel_v2_rowmajor_clustered")
                                    : (long_rows ? "spmm_csr_panel_v2_rowmajor+long_rows" : "spmm_csr_panel_v2_rowmajor");
@@ -174,8 +171,8 @@ int run_rm_transpose(sextans_engine *h, const Call &c, bool aligned) {
     const int N = c.N;
     h->lean_prepare = false;
     const size_t nB = (size_t)h->K * (size_t)N, nC = (size_t)h->M * (size_t)N;
-    if (int rc = ensure(&h->d_rmB, &h->rmB_cap, nB)) return rc;
-    if (int rc = ensure(&h->d_rmC, &h->rmC_cap, nC)) return rc;
+    if (int rc = reserve(h->d_rmB, nB)) return rc;
+    if (int rc = reserve(h->d_rmC, nC)) return rc;
     {
         Prof p(h, &h->ev_repack, c.s);
         launch_transpose(aligned, true, c.B, h->d_rmB, c.ldb, h->K, h->K, N, c.s);
@@ -203,24 +200,24 @@ int run_rm_bf16_native(sextans_engine *h, const CallBf16 &c) {
     for (const Seg &g : bf16_tiles(c.N))
         launch_rowgroup_bf16(h, g.width, c.B + g.col0, c.ldb, (const char *)c.C_in + esz * (size_t)g.col0, c.ldc_in, (char *)c.C_out + esz * (size_t)g.col0, c.ldc,
                              g.ntiles, c.alpha, c.beta, c.cbf16, c.s);
-    if (h->nhub > 0) {   // the long rows' pieces (raw fp32 sums into P) and their fold
-        const sextans_engine::PieceTable &pt = h->by_len;
-        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->nhub];
+    if (h->split.nhub > 0) {   // the long rows' pieces (raw fp32 sums into P) and their fold
+        const sextans_engine::PieceTable &pt = h->split.by_len;
+        const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->split.nhub];
         for (const Seg &g : bf16_tiles(c.N)) launch_hub_pieces_bf16(h, g.width, pt, c.B + g.col0, c.ldb, g.ntiles, g.col0, v0, v1, c.s);
         if (c.cbf16) launch_fold_bf16(h, pt, c.N, (const uint16_t *)c.C_in, c.ldc_in, (uint16_t *)c.C_out, c.ldc, c.alpha, c.beta, c.s);
-        else launch_fold(h, pt, 0, h->nhub, c.N, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+        else launch_fold(h, pt, 0, h->split.nhub, c.N, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
     }
-    h->last_kernel = h->nhub > 0 ? "spmm_csr_rowgroup_rowmajor_bf16+long_rows" : "spmm_csr_rowgroup_rowmajor_bf16";
+    h->last_kernel = h->split.nhub > 0 ? "spmm_csr_rowgroup_rowmajor_bf16+long_rows" : "spmm_csr_rowgroup_rowmajor_bf16";
     SX_HIP(hipGetLastError());
-    ++h->bf16_native_calls;
+    ++h->mat.bf16_native_calls;
     return SEXTANS_OK;
 }
 
 // the converting route's fp32 copies: B always, C only when it is bf16
 int ensure_bf16_workspaces(sextans_engine *h, int N, bool cbf16) {
-    if (int rc = ensure(&h->d_bfB, &h->bfB_cap, (size_t)h->K * (size_t)N)) return rc;
+    if (int rc = reserve(h->mat.d_bfB, (size_t)h->K * (size_t)N)) return rc;
     if (cbf16)
-        if (int rc = ensure(&h->d_bfC, &h->bfC_cap, (size_t)h->M * (size_t)N)) return rc;
+        if (int rc = reserve(h->mat.d_bfC, (size_t)h->M * (size_t)N)) return rc;
     return SEXTANS_OK;
 }
 
@@ -229,19 +226,19 @@ int run_rm_bf16_converted(sextans_engine *h, const CallBf16 &c) {
     if (int rc = ensure_bf16_workspaces(h, c.N, c.cbf16)) return rc;
     {
         Prof p(h, &h->ev_repack, c.s);
-        launch_widen(c.B, c.ldb, h->d_bfB, c.N, h->K, c.N, c.s);
-        if (c.cbf16) launch_widen((const uint16_t *)c.C_in, c.ldc_in, h->d_bfC, c.N, h->M, c.N, c.s);
+        launch_widen(c.B, c.ldb, h->mat.d_bfB, c.N, h->K, c.N, c.s);
+        if (c.cbf16) launch_widen((const uint16_t *)c.C_in, c.ldc_in, h->mat.d_bfC, c.N, h->M, c.N, c.s);
     }
     SX_HIP(hipGetLastError());
     if (!c.cbf16) {
-        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->d_bfB, c.N, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, (void *)c.s)) return rc;
+        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->mat.d_bfB, c.N, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, (void *)c.s)) return rc;
     } else {
-        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->d_bfB, c.N, c.beta, h->d_bfC, c.N, h->d_bfC, c.N, (void *)c.s)) return rc;
+        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->mat.d_bfB, c.N, c.beta, h->mat.d_bfC, c.N, h->mat.d_bfC, c.N, (void *)c.s)) return rc;
         Prof p(h, &h->ev_post, c.s);
-        launch_round(h->d_bfC, c.N, (uint16_t *)c.C_out, c.ldc, h->M, c.N, c.s);
+        launch_round(h->mat.d_bfC, c.N, (uint16_t *)c.C_out, c.ldc, h->M, c.N, c.s);
     }
     SX_HIP(hipGetLastError());
-    ++h->bf16_converted_calls;
+    ++h->mat.bf16_converted_calls;
     return SEXTANS_OK;
 }
 
@@ -255,7 +252,7 @@ bool bf16_aligned(const sextans_engine *h, const CallBf16 &c) {
 // (asked with the caller's leading dimensions; a call that converts asks again inside sextans_spmm_device_rm with ldb = N of the
 // workspace -- route_rm looks at ldb only for alignment and the 32-bit limit of the panel paths, so the two cannot disagree on the gather route)
 bool bf16_native(const sextans_engine *h, const CallBf16 &c, const Tiling &t) {
-    if (!bf16_aligned(h, c) || h->nchain > 0) return false;
+    if (!bf16_aligned(h, c) || h->split.nchain > 0) return false;
     const Call f{c.N, c.alpha, (const float *)c.B, c.ldb, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, h->M, 0, c.s, true};
     return route_rm(h, f, t).path == RouteRM::kRowgroup;
 }

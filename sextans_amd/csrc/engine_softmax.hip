@@ -9,24 +9,20 @@
 namespace sxe {
 
 void free_softmax(sextans_engine *h) {
-    (void)hipFree(h->d_sm_wrow); (void)hipFree(h->d_sm_tab); (void)hipFree(h->d_sm_part);
-    h->d_sm_wrow = nullptr; h->d_sm_tab = nullptr; h->d_sm_part = nullptr;
-    h->sm_wrow_n = 0;
-    h->sm_nchunks = h->sm_long_rows = 0;
+    h->softmax = {};
 }
 
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s) {
-    if (h->d_sm_wrow || h->nnz == 0 || h->M == 0) return SEXTANS_OK;
+    if (h->softmax.d_sm_wrow || h->nnz == 0 || h->M == 0) return SEXTANS_OK;
     if (int rc = validate_matrix(h)) return rc;
     const int64_t nw = (h->nnz + sx::kSoftmaxWaveEntries - 1) / sx::kSoftmaxWaveEntries;
-    int *d_wrow = nullptr, *d_cnt = nullptr;   // d_cnt: long rows, their chunks, the fill cursor
+    DevBuf<int> d_wrow, d_cnt;   // d_cnt: long rows, their chunks, the fill cursor
     auto fail = [&](int rc, const char *what) {
         if (what) { g_last_error = what; (void)hipGetLastError(); }
-        (void)hipFree(d_wrow); (void)hipFree(d_cnt);
         free_softmax(h);
         return rc;
     };
-    if (hipMalloc((void **)&d_wrow, sizeof(int) * (size_t)(nw + 1)) != hipSuccess || hipMalloc((void **)&d_cnt, sizeof(int) * 4) != hipSuccess)
+    if (d_wrow.alloc((size_t)(nw + 1)) != hipSuccess || d_cnt.alloc(4) != hipSuccess)
         return fail(SEXTANS_ERR_ALLOC, "row softmax: out of device memory for the wavefront table");
     int cnt[4] = {0, 0, 0, 0};
     const dim3 rows_grid((unsigned)(((int64_t)h->M + 255) / 256));
@@ -38,17 +34,16 @@ int ensure_softmax_tables(sextans_engine *h, hipStream_t s) {
     if (hipMemcpyAsync(cnt, d_cnt, sizeof(int) * 2, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
         return fail(SEXTANS_ERR_HIP, "row softmax: counting the long rows failed");
     if (cnt[1] > 0) {
-        if (hipMalloc((void **)&h->d_sm_tab, sizeof(int2) * (size_t)cnt[1]) != hipSuccess ||
-            hipMalloc((void **)&h->d_sm_part, sizeof(float2) * 2 * (size_t)cnt[1]) != hipSuccess)   // partials + per-row results
+        if (h->softmax.d_sm_tab.alloc((size_t)cnt[1]) != hipSuccess ||
+            h->softmax.d_sm_part.alloc(2 * (size_t)cnt[1]) != hipSuccess)   // partials + per-row results
             return fail(SEXTANS_ERR_ALLOC, "row softmax: out of device memory for the long-row tables");
-        hipLaunchKernelGGL(sx::softmax_fill_long, rows_grid, dim3(256), 0, s, h->M, h->d_rp, d_cnt + 2, cnt[1], h->d_sm_tab);
+        hipLaunchKernelGGL(sx::softmax_fill_long, rows_grid, dim3(256), 0, s, h->M, h->d_rp, d_cnt + 2, cnt[1], h->softmax.d_sm_tab);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail(SEXTANS_ERR_HIP, "row softmax: building the long-row table failed");
     }
-    (void)hipFree(d_cnt);
-    h->d_sm_wrow = d_wrow;
-    h->sm_wrow_n = nw + 1;
-    h->sm_long_rows = cnt[0];
-    h->sm_nchunks = cnt[1];
+    d_cnt.reset();
+    h->softmax.d_sm_wrow = std::move(d_wrow);
+    h->softmax.long_rows = cnt[0];
+    h->softmax.nchunks = cnt[1];
     return SEXTANS_OK;
 }
 
@@ -67,20 +62,20 @@ int run(sextans_engine *h, float scale, const float *x, const float *g, float *o
     SX_HIP(hipSetDevice(h->device));
     if (h->nnz == 0 || h->M == 0) return SEXTANS_OK;
     if (int rc = ensure_softmax_tables(h, s)) return rc;
-    const long long nw = h->sm_wrow_n - 1;
+    const long long nw = (long long)h->softmax.d_sm_wrow.size() - 1;
     const int nnz = (int)h->nnz;
-    hipLaunchKernelGGL((sx::row_softmax_rows<BWD>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, nnz, h->d_rp, h->d_sm_wrow, nw, scale, x, g, out);
+    hipLaunchKernelGGL((sx::row_softmax_rows<BWD>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, nnz, h->d_rp, h->softmax.d_sm_wrow, nw, scale, x, g, out);
     SX_HIP(hipGetLastError());
-    if (h->sm_nchunks > 0) {
-        const dim3 grid((unsigned)((h->sm_nchunks + 3) / 4));
-        float2 *part = h->d_sm_part, *res = h->d_sm_part + h->sm_nchunks;
-        hipLaunchKernelGGL((sx::softmax_long_partial<BWD>), grid, dim3(256), 0, s, nnz, h->d_rp, h->d_sm_tab, h->sm_nchunks, scale, x, g, part);
-        hipLaunchKernelGGL((sx::softmax_long_combine<BWD>), grid, dim3(256), 0, s, h->d_rp, h->d_sm_tab, h->sm_nchunks, part, res);
-        hipLaunchKernelGGL((sx::softmax_long_finish<BWD>), grid, dim3(256), 0, s, nnz, h->d_rp, h->d_sm_tab, h->sm_nchunks, scale, x, g, res, out);
+    if (h->softmax.nchunks > 0) {
+        const dim3 grid((unsigned)((h->softmax.nchunks + 3) / 4));
+        float2 *part = h->softmax.d_sm_part, *res = h->softmax.d_sm_part + h->softmax.nchunks;
+        hipLaunchKernelGGL((sx::softmax_long_partial<BWD>), grid, dim3(256), 0, s, nnz, h->d_rp, h->softmax.d_sm_tab, h->softmax.nchunks, scale, x, g, part);
+        hipLaunchKernelGGL((sx::softmax_long_combine<BWD>), grid, dim3(256), 0, s, h->d_rp, h->softmax.d_sm_tab, h->softmax.nchunks, part, res);
+        hipLaunchKernelGGL((sx::softmax_long_finish<BWD>), grid, dim3(256), 0, s, nnz, h->d_rp, h->softmax.d_sm_tab, h->softmax.nchunks, scale, x, g, res, out);
         SX_HIP(hipGetLastError());
     }
-    h->last_kernel = BWD ? (h->sm_nchunks > 0 ? "row_softmax_backward+long_rows" : "row_softmax_backward")
-                         : (h->sm_nchunks > 0 ? "row_softmax+long_rows" : "row_softmax");
+    h->last_kernel = BWD ? (h->softmax.nchunks > 0 ? "row_softmax_backward+long_rows" : "row_softmax_backward")
+                         : (h->softmax.nchunks > 0 ? "row_softmax+long_rows" : "row_softmax");
     return SEXTANS_OK;
 }
 

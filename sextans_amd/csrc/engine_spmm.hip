@@ -83,13 +83,13 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
         else { r.blk0 = (int)(i0 - br.begin()); r.blk1 = (int)(i1 - br.begin()); }
     }
     // ... and the window kernel when it starts and ends on wavefront (rows-per-wave) boundaries
-    const bool window = t.window && c.row_begin % h->win_rw == 0 && (c.row_end % h->win_rw == 0 || c.row_end == h->M);
+    const bool window = t.window && c.row_begin % h->win.rw == 0 && (c.row_end % h->win.rw == 0 || c.row_end == h->M);
     // long rows of this range: entries [hub0, hub1) of a piece table, pieces [v0, v1).  Whole-matrix calls walk the
     // table sorted by length (workgroups of equally long pieces), row ranges the one sorted by row.
-    r.pt = c.whole ? &h->by_len : &h->by_row;
-    if (h->nhub > 0) {
+    r.pt = c.whole ? &h->split.by_len : &h->split.by_row;
+    if (h->split.nhub > 0) {
         const auto &rows = r.pt->h_row;
-        if (c.whole) { r.hub1 = h->nhub; }
+        if (c.whole) { r.hub1 = h->split.nhub; }
         else {
             r.hub0 = (int)(std::lower_bound(rows.begin(), rows.end(), c.row_begin) - rows.begin());
             r.hub1 = (int)(std::lower_bound(rows.begin(), rows.end(), c.row_end) - rows.begin());
@@ -97,10 +97,10 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
         r.v0 = r.pt->h_vfirst[(size_t)r.hub0]; r.v1 = r.pt->h_vfirst[(size_t)r.hub1];
     }
     r.hubs = r.hub1 > r.hub0;
-    r.ch1 = h->nchain;
-    if (h->nchain > 0 && !c.whole) {
-        r.ch0 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), c.row_begin) - h->h_chain_row.begin());
-        r.ch1 = (int)(std::lower_bound(h->h_chain_row.begin(), h->h_chain_row.end(), c.row_end) - h->h_chain_row.begin());
+    r.ch1 = h->split.nchain;
+    if (h->split.nchain > 0 && !c.whole) {
+        r.ch0 = (int)(std::lower_bound(h->split.h_chain_row.begin(), h->split.h_chain_row.end(), c.row_begin) - h->split.h_chain_row.begin());
+        r.ch1 = (int)(std::lower_bound(h->split.h_chain_row.begin(), h->split.h_chain_row.end(), c.row_end) - h->split.h_chain_row.begin());
     }
     r.chains = r.ch1 > r.ch0;
     if (window) {
@@ -119,7 +119,7 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
     }
     // Small B (fits the L2s), dictionary-only plan, one N segment: the panel kernel stages straight from the
     // caller's column-major B and the repack launch disappears.
-    r.fuse_b = r.panel && !h->ps.plan_mixed && h->opt_fuse_b && !(c.flags & kRowsNoFuseB) && t.segs.size() == 1 && h->rb_n == 0 &&   // (routed row blocks read the repacked panels)
+    r.fuse_b = r.panel && !h->ps.plan_mixed && h->opt_fuse_b && !(c.flags & kRowsNoFuseB) && t.segs.size() == 1 && h->dense.rb_n == 0 &&   // (routed row blocks read the repacked panels)
                t.segs[0].width == t.W && !r.hubs && !r.chains &&
                (size_t)h->K * (size_t)N * sizeof(float) <= ((size_t)16 << 20) &&
                // (a graph-clustered plan beats the natural-order blocks of a renumbered matrix also while B fits the L2s, once the
@@ -127,18 +127,18 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
                // (... and below that size once the call is large enough: a 13 965-row matrix in a random node order, N = 128,
                // 112 us staged from column-major B on its natural-order plan against 34 us reordered; N = 16: 13.3 against 15.0.
                // Crossover measured at ~24 M non-zero x column products: tools/small_renumbered.py)
-               !(c.whole && h->cluster_state == 2 && h->cluster_cm_pays && (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)));
+               !(c.whole && h->cluster.state == 2 && h->cluster.cm_pays && (h->M >= 65536 || h->m_nnz * (int64_t)N >= ((int64_t)24 << 20)));
     // (Staging from column-major B for LARGE matrices -- no repack launch at all -- was measured in round 4 and loses everywhere: 4M-row
     // 3-dof FEM N = 16 kernel 660 -> 872 us against 83 us of repack saved; 1-dof 27-point 379 -> 577; 2-D 9-point 296 -> 427;
     // 5-point 270 -> 412: 36 four-byte loads per lane and panel through registers instead of nine LDS-DMA requests.)
     // The reordered form (graph-clustered plan, ensure_cluster_plan): whole-matrix calls, 16-column tiles.  Its B panels hold the
     // rows of B in the plan's column order and C goes through the block-major staging buffer (reorder_kernels.h); an 8-column
     // remainder tile keeps the natural-order kernels and panels.  (Layout tag -W: such panels are never reused by a row-range call.)
-    r.reordered = c.whole && h->cluster_state == 2 && h->cluster_cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3 && t.W == 16 && !r.fuse_b &&
-                  (!r.chains || h->d_chain_ci_perm) && csr_only(h) && h->d_Cs &&
+    r.reordered = c.whole && h->cluster.state == 2 && h->cluster.cm_pays && h->opt_kernel != 1 && h->opt_kernel != 3 && t.W == 16 && !r.fuse_b &&
+                  (!r.chains || h->cluster.d_chain_ci_perm) && csr_only(h) && h->d_Cs &&
                   // (the staging buffer is sized by prepare() for the N it saw: a plan that survived a set_option("kernel") and a
                   // larger N since then must not run past its end -- ADVICE r04)
-                  h->Cs_cap >= (size_t)((N + 15) / 16) * (size_t)h->M * 16 && (N >= 16 || (N == 8 && !r.hubs && !r.chains));
+                  h->d_Cs.size() >= (size_t)((N + 15) / 16) * (size_t)h->M * 16 && (N >= 16 || (N == 8 && !r.hubs && !r.chains));
     r.cs_tile = r.reordered ? (int64_t)h->M * 16 : 0;
     // 32-bit byte offsets inside the wide kernels: panels and C columns (wide_fits), and the caller's B when the kernel stages
     // from it (wide_fits_b)
@@ -154,23 +154,23 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
     std::vector<Seg> &plan = r.segs;
     plan = std::move(t.segs);
     if (v2 && t.W == 16 && plan.size() == 2 && plan[0].width == 16 && plan[1].width == 8 && plan[1].ntiles == 1 &&
-        (h->nhub == 0 || h->P_cap >= (size_t)h->split_nv * (size_t)(N + 8)) &&
+        (h->split.nhub == 0 || h->d_P.size() >= (size_t)h->split.nv * (size_t)(N + 8)) &&
         // (with rows on the piece / chain paths only where the main rows are long enough to matter: on the KKT class -- 6 entries per
         // row, arrow borders as chains -- the wider piece / chain work cost more than the gather tail: 1 510 -> 1 687 us at N = 24)
-        ((h->nhub == 0 && h->nchain == 0) || (h->M > 0 && h->m_nnz / h->M >= 16)) &&
-        csr_only(h) && h->Bp_cap >= (size_t)h->K * (size_t)(N + 8) &&
-        (!r.reordered || h->Cs_cap >= (size_t)(N / 16 + 1) * (size_t)h->M * 16)) {
+        ((h->split.nhub == 0 && h->split.nchain == 0) || (h->M > 0 && h->m_nnz / h->M >= 16)) &&
+        csr_only(h) && h->d_Bp.size() >= (size_t)h->K * (size_t)(N + 8) &&
+        (!r.reordered || h->d_Cs.size() >= (size_t)(N / 16 + 1) * (size_t)h->M * 16)) {
         plan[0].ntiles += 1;
         plan[0].last_cols = 8;
         plan.pop_back();
-    } else if (v2 && t.W == 16 && plan.size() == 1 && plan[0].width == 8 && plan[0].ntiles == 1 && h->nhub == 0 && h->nchain == 0 &&
-               csr_only(h) && h->Bp_cap >= (size_t)h->K * 16 && (!r.reordered || h->Cs_cap >= (size_t)h->M * 16)) {
+    } else if (v2 && t.W == 16 && plan.size() == 1 && plan[0].width == 8 && plan[0].ntiles == 1 && h->split.nhub == 0 && h->split.nchain == 0 &&
+               csr_only(h) && h->d_Bp.size() >= (size_t)h->K * 16 && (!r.reordered || h->d_Cs.size() >= (size_t)h->M * 16)) {
         plan[0] = Seg{16, 0, 1, 8};   // N = 8 on the 16-column plan (engine_plan.hip: prepare, n8_wide)
     }
     r.layout = r.reordered ? -t.W : plan[0].last_cols != 0 ? t.W + 100 : t.W;
     r.skip_repack = r.fuse_b || ((c.flags & SEXTANS_ROWS_REUSE_B_PANELS) != 0 && h->bp_layout == r.layout);
     // whole-matrix calls on repacked panels: the plan over the rows in clustered (brick) order when the matrix has one
-    r.clustered = c.whole && !r.fuse_b && h->cluster_state == 1;
+    r.clustered = c.whole && !r.fuse_b && h->cluster.state == 1;
     choose_launches(h, c, t.W, wide_fits_b, r);
     return r;
 }
@@ -181,12 +181,12 @@ int run_window(sextans_engine *h, const Call &c, const RouteCM &r) {
     // B in 8-column panels (the reference's N tile), then one tile-major launch
     if (!r.skip_repack) {
         Prof p(h, &h->ev_repack, s);
-        launch_repack(8, c.B, c.ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->d_touched);
+        launch_repack(8, c.B, c.ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->mat.d_touched);
         h->bp_layout = r.layout;
     }
     {
         Prof p(h, &h->ev_kernel, s);
-        const int w0 = c.row_begin / h->win_rw, w1 = (c.row_end + h->win_rw - 1) / h->win_rw;
+        const int w0 = c.row_begin / h->win.rw, w1 = (c.row_end + h->win.rw - 1) / h->win.rw;
         launch_window(h, h->d_Bp, c.C_in, c.ldc_in, c.C_out, c.ldc, N / 8, w0, w1, c.row_begin, c.alpha, c.beta, s);
         const std::vector<Seg> p8{{8, 0, N / 8}};
         if (r.hubs) {
@@ -194,8 +194,8 @@ int run_window(sextans_engine *h, const Call &c, const RouteCM &r) {
             launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
         }
         if (r.chains) launch_chains(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, r.ch0, r.ch1, c.row_begin, c.alpha, c.beta, s);
-        h->last_kernel = kernel_name(2, r.hubs || r.chains, h->dense_W > 0);
-        if (h->rb_n > 0) {
+        h->last_kernel = kernel_name(2, r.hubs || r.chains, h->dense.W > 0);
+        if (h->dense.rb_n > 0) {
             if (int rc = launch_rowblocks(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
             h->last_kernel = with_rowblocks(h, h->last_kernel);
         }
@@ -223,11 +223,11 @@ int launch_segment(sextans_engine *h, const Call &c, const RouteCM &r, const Seg
     const int *colpos = nullptr;   // of the piece launch at the end
     switch (l) {
         case RouteCM::kReorderedV2:
-            if (int rc = launch_panel_v2(h, 1, bp, h->d_Cs, r.cs_tile, h->d_Cs, r.cs_tile, g.ntiles, c.alpha, c.beta, s, 0, 0, h->psc.plan_nblk, 0, 2))
+            if (int rc = launch_panel_v2(h, 1, bp, h->d_Cs, r.cs_tile, h->d_Cs, r.cs_tile, g.ntiles, c.alpha, c.beta, s, 0, 0, h->cluster.psc.plan_nblk, 0, 2))
                 return rc;   // (a merged tail tile needs no mask here: its staging columns exist, the pass below writes back the valid ones)
             // rows on the piece path: their partial sums from the PERMUTED panels (column c sits at row colpos[c]); folded into C
             // behind the staging -> C pass below, which leaves C_in in their rows
-            colpos = h->d_colpos;
+            colpos = h->cluster.d_colpos;
             break;
         case RouteCM::kV2Wide: {
             const int nsuper = g.ntiles / 2;
@@ -249,14 +249,14 @@ int launch_segment(sextans_engine *h, const Call &c, const RouteCM &r, const Seg
             break;
         case RouteCM::kV2:
             if (int rc = launch_panel_v2(h, 1, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.clustered ? 0 : r.blk0,
-                                         r.clustered ? h->psc.plan_nblk : r.blk1, c.row_begin, r.clustered ? 1 : 0, g.last_cols ? g.last_cols : 16))
+                                         r.clustered ? h->cluster.psc.plan_nblk : r.blk1, c.row_begin, r.clustered ? 1 : 0, g.last_cols ? g.last_cols : 16))
                 return rc;
             break;
         default:   // the panel or the gather kernel, at the segment's width
             if (l == RouteCM::kPanel) {
                 if (int rc = launch_panel(h, g.width, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin)) return rc;
             } else {
-                launch_rowgroup(h, g.width, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->d_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end,
+                launch_rowgroup(h, g.width, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->split.d_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end,
                                 g.ntiles, c.alpha, c.beta, s);
             }
     }
@@ -274,8 +274,8 @@ int run_segments(sextans_engine *h, const Call &c, const RouteCM &r) {
             h->bp_layout = r.layout;
             for (const Seg &g : r.segs) {
                 float *dst = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-                if (r.reordered && g.width == 16 && h->d_colpos) launch_repack_perm(h, c.B, c.ldb, dst, g.col0, g.ntiles, seg_cols(g), s);
-                else launch_repack(g.width, c.B, c.ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, seg_cols(g), h->d_touched);
+                if (r.reordered && g.width == 16 && h->cluster.d_colpos) launch_repack_perm(h, c.B, c.ldb, dst, g.col0, g.ntiles, seg_cols(g), s);
+                else launch_repack(g.width, c.B, c.ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, seg_cols(g), h->mat.d_touched);
             }
         }
         if (r.reordered)
@@ -292,8 +292,8 @@ int run_segments(sextans_engine *h, const Call &c, const RouteCM &r) {
         if (r.hubs && !r.reordered) launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
         if (r.chains && !r.reordered) SX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
         const bool v2_used = std::any_of(r.launch, r.launch + r.segs.size(), [](RouteCM::Launch l) { return l < RouteCM::kPanel; });
-        h->last_kernel = r.reordered ? "spmm_csr_panel_v2_reordered" : kernel_name(v2_used ? 3 : r.panel ? 1 : 0, r.hubs || r.chains, h->dense_W > 0);
-        if (h->rb_n > 0) {   // dense blocks of 16 rows on the fp32 matrix cores, from the same panels (the kernels above skipped their rows)
+        h->last_kernel = r.reordered ? "spmm_csr_panel_v2_reordered" : kernel_name(v2_used ? 3 : r.panel ? 1 : 0, r.hubs || r.chains, h->dense.W > 0);
+        if (h->dense.rb_n > 0) {   // dense blocks of 16 rows on the fp32 matrix cores, from the same panels (the kernels above skipped their rows)
             if (int rc = launch_rowblocks(h, r.segs, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
             h->last_kernel = with_rowblocks(h, h->last_kernel);
         }
@@ -326,7 +326,7 @@ int sextans_align_row(sextans_handle_t h, int N, int row, int *aligned) {
     if (int rc = prepare(h, N, false, &t)) return rc;
     *aligned = row;
     if (row == h->M) return SEXTANS_OK;
-    if (t.window) *aligned = row / h->win_rw * h->win_rw;
+    if (t.window) *aligned = row / h->win.rw * h->win.rw;
     else if (t.panel && !h->ps.h_blk_row.empty())
         *aligned = *(std::upper_bound(h->ps.h_blk_row.begin(), h->ps.h_blk_row.end(), row) - 1);
     return SEXTANS_OK;
@@ -356,7 +356,7 @@ int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float
     if (nrows == 0) return SEXTANS_OK;
     Tiling t;
     if (int rc = prepare(h, N, whole, &t)) return rc;
-    if (h->dense_W > 0) {
+    if (h->dense.W > 0) {
         // Dense tiles first, on the matrix cores: C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block
         // rows (and alpha * 0 + beta * C_in below them); the CSR kernels then add alpha * (A_rest * B) on top
         // (their beta becomes 1, their C_in the partial result): one C pass per kernel, no extra combine launch.

@@ -10,6 +10,10 @@
 //   engine_softmax.hip  row softmax on A's pattern, forward and backward (sextans_row_softmax_device, ..._backward_device)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
+//   engine_transpose.hip  the backward pass: A^T behind a companion engine (sextans_spmm_t_device_rm) and the SDDMM
+//   engine_refresh.hip  new values on the pattern already planned (sextans_update_values[_device])
+// Every device array the engine owns is an sx::DevBuf (device_buffer.h); state that is dropped together sits in one nested struct whose
+// default member initialisers are its reset values, so that the free_* functions assign `{}`; stat "device_bytes" sums the bytes().
 // Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
 #include "sextans_amd.h"
 #include "thread_stream.h"
 
@@ -41,6 +46,7 @@ extern thread_local std::string g_last_error;   // text behind sextans_last_erro
     } while (0)
 
 namespace sxe {
+using sx::DevBuf;
 struct EventPair { hipEvent_t a, b; };
 constexpr int kRowsNoFuseB = 0x100;   // internal flag of sextans_spmm_device_rows: always stage from the repacked panel
 constexpr int kPanelFloats = 9216;    // at most 36 KiB of LDS for the B panel (576 rows at N-tile 16)
@@ -60,6 +66,7 @@ struct Call {
 }  // namespace sxe
 
 struct sextans_engine {
+    template <class T> using DevBuf = sx::DevBuf<T>;
     int device = 0;
     int num_cus = 256;
     // matrix
@@ -67,22 +74,33 @@ struct sextans_engine {
     int64_t nnz = 0;
     const int *d_rp = nullptr, *d_ci = nullptr;
     const float *d_v = nullptr;
-    bool owns_matrix = false;
-    float *d_v_upd = nullptr;             // sextans_update_values (host values) on a caller-provided device matrix: the uploaded values, owned (d_v points here)
-    int64_t value_refreshes = 0;          // sextans_update_values* served on the current matrix (stat "value_refreshes")
-    int64_t value_refresh_rebuilt = 0;    //   ... of which dropped a packed form for a lazy rebuild instead of rewriting it
-    bool device_matrix_checked = false;   // a caller-provided device matrix has been validated (row_ptr monotone, columns < K)
+    struct Matrix {   // what lives exactly as long as the matrix as set (free_matrix)
+        DevBuf<int> d_rp_own, d_ci_own;   // a matrix set from host arrays (sextans_set_matrix_csr): the uploaded copy, owned (d_rp / d_ci / d_v point here)
+        DevBuf<float> d_v_own;
+        DevBuf<float> d_v_upd;                // sextans_update_values (host values) on a caller-provided device matrix: the uploaded values, owned (d_v points here)
+        int64_t value_refreshes = 0;          // sextans_update_values* served on the current matrix (stat "value_refreshes")
+        int64_t value_refresh_rebuilt = 0;    //   ... of which dropped a packed form for a lazy rebuild instead of rewriting it
+        bool device_matrix_checked = false;   // a caller-provided device matrix has been validated (row_ptr monotone, columns < K)
+        bool col_range_known = false;
+        DevBuf<unsigned char> d_touched;      // one byte per 64 rows of B: does the matrix have a column there (null = repack everything in [col_lo, col_hi))
+        int64_t touched_segments = 0;
+        // bf16 dense operands (sextans_spmm_device_rm_bf16): fp32 copies of B and of a bf16 C for the routes that have no bf16 kernel
+        // (dropped with the matrix), and which way the calls on the current matrix went (stats "bf16_native_calls" / "bf16_converted_calls")
+        DevBuf<float> d_bfB, d_bfC;
+        int64_t bf16_native_calls = 0, bf16_converted_calls = 0;
+        double plan_build_s = 0.0;      // host seconds spent building packed forms of A for the current matrix
+        int64_t bytes() const { return d_rp_own.bytes() + d_ci_own.bytes() + d_v_own.bytes() + d_v_upd.bytes() + d_touched.bytes() + d_bfB.bytes() + d_bfC.bytes(); }
+    };
+    Matrix mat;
+    bool owns_matrix() const { return mat.d_rp_own != nullptr; }
     // workspaces
     std::set<const void *> big_lds_kernels;   // kernels whose dynamic-LDS limit has been raised ON THIS ENGINE'S DEVICE (the
                                               // attribute is per device: a process-wide flag breaks the second GPU of a process)
-    float *d_Bp = nullptr;
-    size_t Bp_cap = 0;              // floats
+    DevBuf<float> d_Bp;
     int bp_layout = 0;              // main panel width of the last repack into d_Bp (0 = none)
-    float *d_B = nullptr, *d_Cin = nullptr, *d_Cout = nullptr;   // host-path staging
-    size_t B_cap = 0, C_cap = 0;
+    DevBuf<float> d_B, d_Cin, d_Cout;                            // host-path staging
     hipStream_t host_stream = nullptr;                           // stream of the host-buffer entry points
-    float *d_chB = nullptr, *d_chC = nullptr;                    // accelerator channel layouts (sextans_invoke)
-    size_t chB_cap = 0, chC_cap = 0;
+    DevBuf<float> d_chB, d_chC;                                  // accelerator channel layouts (sextans_invoke)
     // block-dictionary plan for the LDS-panel kernel (built lazily, per lanes_per_row)
     // One packed form per lanes_per_row value (2 / 4 / 8): the active one below, the others parked in plan_stash, so
     // callers that alternate between N classes (N = 8 -> 2 lanes, N >= 16 -> 4) do not rebuild on every switch.
@@ -93,18 +111,18 @@ struct sextans_engine {
         int64_t plan_min_reuse = -1;
         // d_dict_ptr: entries per block dictionary; d_dict: dictionaries at stride plan_dict_stride;
         // d_row_off: {first packed entry, entries} per (block, slot)
-        int *d_dict_ptr = nullptr, *d_dict = nullptr, *d_blk_row = nullptr, *d_row_off = nullptr;
-        int *d_pcol32 = nullptr;
-        float *d_pval = nullptr;
+        DevBuf<int> d_dict_ptr, d_dict, d_blk_row, d_row_off;
+        DevBuf<int> d_pcol32;
+        DevBuf<float> d_pval;
         int plan_nblk = 0;
         std::vector<int> h_blk_row;     // host copy of the plan's block boundaries (row-range calls, sextans_align_row)
-        unsigned short *d_lidx = nullptr;
-        int *d_dict_blocks = nullptr;      // mixed plans, split form: the blocks that have a dictionary, ascending (n_dict_blocks of them)
+        DevBuf<unsigned short> d_lidx;
+        DevBuf<int> d_dict_blocks;         // mixed plans, split form: the blocks that have a dictionary, ascending (n_dict_blocks of them)
         int n_dict_blocks = 0;
-        int *d_rg_groups = nullptr;        // ... and the groups of 128 rows that hold a row of the gather kernel's (rg_ngroups of them)
+        DevBuf<int> d_rg_groups;           // ... and the groups of 128 rows that hold a row of the gather kernel's (rg_ngroups of them)
         int rg_ngroups = 0;
-        unsigned char *d_rg_skip = nullptr;   // mixed plans: 1 = the row is NOT the gather kernel's (it lies in a dictionary block, or on the piece path)
-        int *d_ioff = nullptr;          // per (block, slot): start of the slot's index list in d_lidx when identical lists of consecutive rows are
+        DevBuf<unsigned char> d_rg_skip;      // mixed plans: 1 = the row is NOT the gather kernel's (it lies in a dictionary block, or on the piece path)
+        DevBuf<int> d_ioff;             // per (block, slot): start of the slot's index list in d_lidx when identical lists of consecutive rows are
                                         // stored once (plan_device.hip: share_index_lists); null = at the slot's first packed entry
         int64_t plan_idx_len = 0;       // entries of d_lidx (= plan_stream_len without sharing)
         double plan_panel_frac = 0.0;   // share of non-zeros living in dictionary blocks
@@ -118,71 +136,93 @@ struct sextans_engine {
         bool plan_built = false;        // false: only the sampled verdict exists (no packed stream)
         bool stream_released = false;   // the packed stream (d_lidx / d_pval / d_pcol32: 6 bytes per non-zero) has been handed back while a
                                         // clustered plan serves the whole-matrix calls; restore_plan_streams() rebuilds it (same bytes)
+        int64_t bytes() const {
+            return d_dict_ptr.bytes() + d_dict.bytes() + d_blk_row.bytes() + d_row_off.bytes() + d_pcol32.bytes() + d_pval.bytes() + d_lidx.bytes() +
+                   d_dict_blocks.bytes() + d_rg_groups.bytes() + d_rg_skip.bytes() + d_ioff.bytes();
+        }
     };
     PanelState ps;                      // active
-    // The same plan over the rows in CLUSTERED order (row_cluster.hip: brick by brick for grid-stencil matrices), 4 lanes per row,
-    // used by spmm_csr_panel_v2 for whole-matrix calls; row-range calls and every other kernel keep the natural-order plan above.
-    PanelState psc;
+    struct ClusterPlan {   // the clustered-order plan and its tables; it is reconsidered at the next whole-matrix call (free_cluster_plan)
+        // The same plan over the rows in CLUSTERED order (row_cluster.hip: brick by brick for grid-stencil matrices), 4 lanes per row,
+        // used by spmm_csr_panel_v2 for whole-matrix calls; row-range calls and every other kernel keep the natural-order plan above.
+        PanelState psc;
+        DevBuf<int> d_slot_row;             // psc: row of the main matrix per (block, slot)
+        DevBuf<int> d_dict_nat;             // psc, graph clustering: the block dictionaries in the CALLER's column numbers (row-major calls read B where it lies)
+        bool runs = false;                  // cluster_state 1 by run-level clustering (runs of 16 consecutive rows over the graph of runs), not grid bricks
+        bool cm_pays = true;                // the graph-clustered plan also serves column-major calls (>= 40 % fewer panel rows: it pays two passes over C)
+        DevBuf<int> d_colpos;               // psc, graph clustering: row of the permuted B panels that holds column c (K ints)
+        int colwise_state = 0;              // spmm_csr_colwise for this matrix: 0 not evaluated, 1 short rows in a numbering with locality, -1 no
+        double row_coherence = 0.0;         // sampled share of consecutive rows' entries with neighbouring columns
+        int decline = 0;                    // why the graph clustering was declined (engine_plan.hip: cluster_graph), 0 = it was not
+        double shared = 0.0;                // sampled share of a neighbour row's columns a row has too (graph clustering pre-test)
+        int graph_kind = 0;                 // graph the rows were clustered over: 0 the matrix itself, 1 a slab's own square pattern, 2 row similarity
+        double pattern_symmetry = 1.0;      // sampled share of entries (r, c) of a square matrix whose mirror (c, r) exists
+        int state = 0;                      // 0 not evaluated, 1 grid bricks in use, 2 graph clustering (reordered form) in use, -1 declined
+        int64_t total_dict = 0;             // sum of the block dictionaries: clustered order
+        // the chain rows' entries once more, compact, columns relabelled for the permuted B panels of the reordered form (ensure_cluster_plan)
+        DevBuf<int> d_chain_ci_perm, d_chain_beg_c;
+        DevBuf<float> d_chain_v_c;
+        int64_t bytes() const {
+            return psc.bytes() + d_slot_row.bytes() + d_dict_nat.bytes() + d_colpos.bytes() + d_chain_ci_perm.bytes() + d_chain_beg_c.bytes() + d_chain_v_c.bytes();
+        }
+    };
+    ClusterPlan cluster;
     int64_t cluster_ref_dict = 0;       // panel rows of the grid-brick plan while the graph plan is weighed against it (ensure_cluster_plan)
-    int *d_slot_row = nullptr;          // psc: row of the main matrix per (block, slot)
-    int *d_dict_nat = nullptr;          // psc, graph clustering: the block dictionaries in the CALLER's column numbers (row-major calls read B where it lies)
-    bool cluster_runs = false;          // cluster_state 1 by run-level clustering (runs of 16 consecutive rows over the graph of runs), not grid bricks
     bool cluster_for_rm = false;        // the plan is being (re)considered for row-major calls: no passes over C to pay for
     bool lean_prepare = false;         // prepare() on behalf of a row-major call: no B-panel / C-staging workspaces (nothing is repacked or staged there)
     bool cluster_rm_tried = false;      //   ... once per matrix
-    bool cluster_cm_pays = true;        // the graph-clustered plan also serves column-major calls (>= 40 % fewer panel rows: it pays two passes over C)
-    int *d_colpos = nullptr;            // psc, graph clustering: row of the permuted B panels that holds column c (K ints)
-    float *d_Cs = nullptr;              //   ... and the row-major C staging buffer of the reordered form: [N / 16][M][16] floats
-    size_t Cs_cap = 0;
+    DevBuf<float> d_Cs;                 // graph clustering: the row-major C staging buffer of the reordered form: [N / 16][M][16] floats
     int col_lo = 0, col_hi = 0;         // columns [col_lo, col_hi) the matrix as set has entries in: the only rows of B a call repacks
-    bool col_range_known = false;
-    unsigned char *d_touched = nullptr; // one byte per 64 rows of B: does the matrix have a column there (null = repack everything in [col_lo, col_hi))
-    int64_t touched_segments = 0;
-    int colwise_state = 0;              // spmm_csr_colwise for this matrix: 0 not evaluated, 1 short rows in a numbering with locality, -1 no
-    double row_coherence = 0.0;         // sampled share of consecutive rows' entries with neighbouring columns
-    int cluster_decline = 0;            // why the graph clustering was declined (engine_plan.hip: cluster_graph), 0 = it was not
-    double cluster_shared = 0.0;        // sampled share of a neighbour row's columns a row has too (graph clustering pre-test)
-    int cluster_graph_kind = 0;         // graph the rows were clustered over: 0 the matrix itself, 1 a slab's own square pattern, 2 row similarity
-    double pattern_symmetry = 1.0;      // sampled share of entries (r, c) of a square matrix whose mirror (c, r) exists
-    int cluster_state = 0;              // 0 not evaluated, 1 grid bricks in use, 2 graph clustering (reordered form) in use, -1 declined
     int64_t cluster_s2 = 0, cluster_s3 = 0;
-    int64_t plan_total_dict = 0, cluster_total_dict = 0;   // sum of the block dictionaries: natural order / clustered order
+    int64_t plan_total_dict = 0;        // sum of the block dictionaries: natural order
     PanelState plan_stash[3];           // parked, indexed by lanes_per_row 2 / 4 / 8 -> 0 / 1 / 2
-    // K-windowed accumulator-resident plan (spmm_csr_window; built lazily)
-    uint2 *d_wstream = nullptr;
-    int *d_wstep0 = nullptr;
-    int win_nwaves = 0, win_rw = 0;
-    int64_t win_padded = 0;         // stream entries including padding
-    int win_state = 0;              // 0 = not evaluated, 1 = built, -1 = rejected (skewed rows / K too large)
-    int64_t win_built_rows = -1, win_built_cols = -1;
-    double plan_build_s = 0.0;      // host seconds spent building packed forms of A for the current matrix
+    struct Window {   // K-windowed accumulator-resident plan (spmm_csr_window; built lazily)
+        DevBuf<uint2> d_wstream;
+        DevBuf<int> d_wstep0;
+        int nwaves = 0, rw = 0;
+        int64_t padded = 0;         // stream entries including padding
+        int state = 0;              // 0 = not evaluated, 1 = built, -1 = rejected (skewed rows / K too large)
+        int64_t built_rows = -1, built_cols = -1;
+        int64_t bytes() const { return d_wstream.bytes() + d_wstep0.bytes(); }
+    };
+    Window win;
     // "MFMA only where a tile is actually dense" (options "mfma_dense_tiles" / "dense_tile_fill_x100"): 32x32 tiles of
     // the main matrix whose fill reaches the threshold, as a blocked-ELL bf16 side matrix; the CSR kernels keep the rest
-    int dense_mb = 0, dense_W = 0;  // full block rows, ELL width (0 = no dense tile / not extracted)
+    struct DenseTiles {   // dense-tile state: everything downstream of it is dropped with it (free_dense)
+        int mb = 0, W = 0;          // full block rows, ELL width (0 = no dense tile / not extracted)
+        DevBuf<int> d_dense_col;
+        DevBuf<unsigned char> d_dense_Af;
+        int64_t tiles = 0, nnz = 0;
+        int64_t built_mfma = -2, built_fill = -2;
+        // "mfma_dense_tiles" = 2: dense blocks of 16 rows on the fp32 matrix cores (rowblock_mfma_kernel.h); tiles / nnz then count them
+        int rb_n = 0;                   // routed blocks
+        int64_t rb_groups = 0;          // their 16 x 4 fragments
+        DevBuf<int> d_rb_row0, d_rb_gptr, d_rb_gcol;   // first row, fragment range, column group per fragment
+        DevBuf<float> d_rb_A;           // fragments in MFMA operand order (64 floats each)
+        int sb_n = 0;                   // super blocks of 4 routed blocks: ascending union of their column groups + 4-bit owner masks
+        int64_t sb_entries = 0;
+        DevBuf<int> d_sb_uptr, d_sb_ucol;
+        DevBuf<int> d_srp, d_sci;       // owned copy of the source (exists only when tiles were cut out)
+        DevBuf<float> d_sv;
+        int64_t bytes() const {
+            return d_dense_col.bytes() + d_dense_Af.bytes() + d_rb_row0.bytes() + d_rb_gptr.bytes() + d_rb_gcol.bytes() + d_rb_A.bytes() + d_sb_uptr.bytes() +
+                   d_sb_ucol.bytes() + d_srp.bytes() + d_sci.bytes() + d_sv.bytes();
+        }
+    };
+    DenseTiles dense;
     double dense_share = 0.0;       // blocks per distinct block column in groups of 8 block rows of the dense-tile matrix
     int dense_max_union = 0;
-    int *d_dense_col = nullptr;
-    void *d_dense_Af = nullptr;
-    int64_t dense_tiles = 0, dense_nnz = 0;
-    int64_t dense_built_mfma = -2, dense_built_fill = -2;
-    // "mfma_dense_tiles" = 2: dense blocks of 16 rows on the fp32 matrix cores (rowblock_mfma_kernel.h); dense_tiles / dense_nnz then count them
-    int rb_n = 0;                   // routed blocks
-    int64_t rb_groups = 0;          // their 16 x 4 fragments
-    int *d_rb_row0 = nullptr, *d_rb_gptr = nullptr, *d_rb_gcol = nullptr;   // first row, fragment range, column group per fragment
-    float *d_rb_A = nullptr;        // fragments in MFMA operand order (64 floats each)
-    int sb_n = 0;                   // super blocks of 4 routed blocks: ascending union of their column groups + 4-bit owner masks
-    int64_t sb_entries = 0;
-    int *d_sb_uptr = nullptr, *d_sb_ucol = nullptr;
-    unsigned char *d_sb_umask = nullptr;
-    // blocked-ELL bf16 matrix (MFMA path)
-    int bell_M = 0, bell_K = 0, bell_W = 0;
+    struct Bell {   // blocked-ELL bf16 matrix (MFMA path)
+        int M = 0, K = 0, W = 0;
+        const int *d_bell_col = nullptr;
+        DevBuf<int> d_bell_col_owned;
+        DevBuf<unsigned char> d_bell_Af;   // A blocks in MFMA fragment order (owned)
+        int64_t bytes() const { return d_bell_col_owned.bytes() + d_bell_Af.bytes(); }
+    };
+    Bell bell;
     int bell_max_union = 0;         // largest number of distinct block columns inside a group of 8 block rows
     double bell_share = 0.0;        // blocks per distinct block column inside groups of 8 block rows (1 = no sharing, 8 = identical rows)
-    const int *d_bell_col = nullptr;
-    int *d_bell_col_owned = nullptr;
-    void *d_bell_Af = nullptr;      // A blocks in MFMA fragment order (owned)
-    void *d_bell_Bf = nullptr;      // B in fragment order (workspace)
-    size_t bell_Bf_cap = 0;         // bytes
+    DevBuf<unsigned char> d_bell_Bf;   // B in fragment order (workspace)
     // Long rows leave the "main" matrix -- the CSR arrays every kernel and plan works on, equal to the arrays
     // above when there are none -- and go through the piece path (rows sorted by length, one row group per piece):
     //   bucketed rows (longer than the bucket threshold L0, option "bucket_rows"): ONE piece, summed in order =
@@ -195,64 +235,61 @@ struct sextans_engine {
     const int *s_rp = nullptr, *s_ci = nullptr;
     const float *s_v = nullptr;
     int64_t s_nnz = 0;
-    int *d_srp = nullptr, *d_sci = nullptr;   // owned copy of the source (exists only when tiles were cut out)
-    float *d_sv = nullptr;
     const int *m_rp = nullptr, *m_ci = nullptr;
     const float *m_v = nullptr;
     int64_t m_nnz = 0;
-    int *d_mrp = nullptr, *d_mci = nullptr;   // owned compacted copy (exists only when rows left)
-    float *d_mv = nullptr;
-    unsigned char *d_skip = nullptr;          // 1 = the row's C is written by the piece path, not by the main kernel
     struct PieceTable {                       // pieces [begin, end) in d_ci / d_v, first piece per long row, the rows
-        int *d_vrp = nullptr, *d_vend = nullptr, *d_vfirst = nullptr, *d_row = nullptr;
+        DevBuf<int> d_vrp, d_vend, d_vfirst, d_row;
         std::vector<int> h_row, h_vfirst;
+        int64_t bytes() const { return d_vrp.bytes() + d_vend.bytes() + d_vfirst.bytes() + d_row.bytes(); }
     };
-    PieceTable by_len, by_row;                // sorted by length (whole-matrix calls: balanced workgroups) / by row (row ranges)
-    // exact chains (strict order, "exact_chain" = 1): rows longer than the automatic threshold leave the piece tables too
-    // and are summed by chain_fused -- still one serial chain of rounded adds per (row, column), bit-identical
-    int nchain = 0;
-    int *d_chain_row = nullptr, *d_chain_beg = nullptr, *d_chain_perm = nullptr;   // perm: chain rows by length, longest first
-    long long *d_chain_off = nullptr;                   // prefix of the lengths
-    // the chain rows' entries once more, compact, columns relabelled for the permuted B panels of the reordered form (ensure_cluster_plan)
-    int *d_chain_ci_perm = nullptr, *d_chain_beg_c = nullptr;
-    float *d_chain_v_c = nullptr;
-    std::vector<int> h_chain_row;
-    std::vector<long long> h_chain_off;
-    int64_t chain_T = 0;
-    int64_t chain_built_opt = -2;
+    struct LongRows {   // long-row state: main matrix, skip flags, piece tables (built from the source; free_split)
+        DevBuf<int> d_mrp, d_mci;                 // owned compacted copy (exists only when rows left)
+        DevBuf<float> d_mv;
+        DevBuf<unsigned char> d_skip;             // 1 = the row's C is written by the piece path, not by the main kernel
+        PieceTable by_len, by_row;                // sorted by length (whole-matrix calls: balanced workgroups) / by row (row ranges)
+        // exact chains (strict order, "exact_chain" = 1): rows longer than the automatic threshold leave the piece tables too
+        // and are summed by chain_fused -- still one serial chain of rounded adds per (row, column), bit-identical
+        int nchain = 0;
+        DevBuf<int> d_chain_row, d_chain_beg, d_chain_perm;   // perm: chain rows by length, longest first
+        DevBuf<long long> d_chain_off;                      // prefix of the lengths
+        std::vector<int> h_chain_row;
+        std::vector<long long> h_chain_off;
+        int64_t chain_T = 0;
+        int64_t chain_built_opt = -2;
+        std::vector<int> h_split_rows;            // ascending: rows cut into more than one piece
+        int nhub = 0;                             // long rows (bucketed + split)
+        int nv = 0;                               // pieces of all long rows
+        int64_t T = 0, bucket_L0 = 0;             // thresholds in effect (0 = none)
+        int64_t built_opt = -2, bucket_built_opt = -2, built_gnnz = -2;   // option values the state above was built for
+        int64_t bytes() const {
+            return d_mrp.bytes() + d_mci.bytes() + d_mv.bytes() + d_skip.bytes() + by_len.bytes() + by_row.bytes() + d_chain_row.bytes() + d_chain_beg.bytes() +
+                   d_chain_perm.bytes() + d_chain_off.bytes();
+        }
+    };
+    LongRows split;
     hipStream_t aux_stream = nullptr;         // the chain kernels need one or two wavefronts for ~1 ms: they run beside the main kernel
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::vector<int> h_split_rows;            // ascending: rows cut into more than one piece
-    int nhub = 0;                             // long rows (bucketed + split)
-    int split_nv = 0;                         // pieces of all long rows
-    int64_t split_T = 0, bucket_L0 = 0;       // thresholds in effect (0 = none)
-    int64_t split_built_opt = -2, bucket_built_opt = -2, split_built_gnnz = -2;   // option values the state above was built for
-    float *d_P = nullptr;
-    size_t P_cap = 0;
-    long long *d_dbg = nullptr;     // 8 counters for phase timing (option "phase_timing")
+    DevBuf<float> d_P;
+    DevBuf<long long> d_dbg;        // 8 counters for phase timing (option "phase_timing")
     // native multi-GPU form (sextans_dist_spmm): slab staging S[chunk][world][N][lmax_chunk], communication stream
-    float *d_stage = nullptr;
-    size_t stage_cap = 0;
+    DevBuf<float> d_stage;
     int64_t graph_fallbacks = 0;        // host-entry repeat loops whose hipGraph capture failed (another thread touched the legacy stream): launched one by one instead
     hipStream_t comm_stream = nullptr;
     std::vector<hipEvent_t> dist_events;
-    float *d_rmB = nullptr, *d_rmC = nullptr;   // column-major copies of the row-major entry point's fallback path
-    size_t rmB_cap = 0, rmC_cap = 0;
-    // bf16 dense operands (sextans_spmm_device_rm_bf16): fp32 copies of B and of a bf16 C for the routes that have no bf16 kernel
-    // (dropped with the matrix), and which way the calls on the current matrix went (stats "bf16_native_calls" / "bf16_converted_calls")
-    float *d_bfB = nullptr, *d_bfC = nullptr;
-    size_t bfB_cap = 0, bfC_cap = 0;
-    int64_t bf16_native_calls = 0, bf16_converted_calls = 0;
-    float *d_Cfull = nullptr;           // clustered-order chunks: row-major staging of the WHOLE C ([N / 16][M_total][16]) the received slabs are scattered into
-    size_t Cfull_cap = 0;
-    int *d_dist_rows = nullptr;         //   ... and every rank's position -> global row table ([world][longest slab])
-    size_t dist_rows_cap = 0;
+    DevBuf<float> d_rmB, d_rmC;         // column-major copies of the row-major entry point's fallback path
+    DevBuf<float> d_Cfull;              // clustered-order chunks: row-major staging of the WHOLE C ([N / 16][M_total][16]) the received slabs are scattered into
+    DevBuf<int> d_dist_rows;            //   ... and every rank's position -> global row table ([world][longest slab])
     bool dist_cc = false;               //   ... in use for the partition of dist_cut_key (every rank agreed)
     int64_t dist_exchanges = 0;         // control collectives + host synchronisations the dist entry points have performed (stat "dist_setup_exchanges")
     std::vector<int> dist_nnz_key;      // (ranges, rank) the whole matrix's non-zero count was exchanged for
     std::vector<int> dist_cut_key, dist_cuts;   // (ranges, N, nchunks, rank) the chunk cuts of all ranks were exchanged for
     std::vector<int> dist_meta;     // {first row, rows} per (chunk, rank) as last uploaded, and where
     const int *dist_meta_at = nullptr;
+    int64_t workspace_bytes() const {   // the flat workspaces above: they outlive the matrix
+        return d_Bp.bytes() + d_B.bytes() + d_Cin.bytes() + d_Cout.bytes() + d_chB.bytes() + d_chC.bytes() + d_Cs.bytes() + d_bell_Bf.bytes() + d_P.bytes() +
+               d_dbg.bytes() + d_stage.bytes() + d_rmB.bytes() + d_rmC.bytes() + d_Cfull.bytes() + d_dist_rows.bytes();
+    }
     // options
     int64_t opt_share_index = 1;        // plans at 4 lanes per row: consecutive rows with identical 16-bit index lists (dof rows of a mesh node) share one copy
     int64_t opt_refine_rows = 62;       // ... rows per block before the refinement (64 - room for rows that move in)
@@ -312,7 +349,7 @@ struct sextans_engine {
     int64_t opt_bell_shared = -1;       // N = 256: workgroups of 8 block rows share each B tile through an LDS ring
                                         // (spmm_bell_mfma_shared).  1 = always, 0 = never, -1 = when the 8 block rows of a
                                         // workgroup share block columns (blocks per distinct column >= 1.5)
-    int64_t opt_rb_tiles = 0;           // measurements only: tiles of 16 columns per wavefront of the fp32 row-block MFMA kernel (0 = 4 where N allows)
+    int64_t opt_rb_tiles = 0;           // measurements only: tiles of 16 columns per wavefront of the fp32 row-block MFMA kernel (0 = 2 where N allows, 4 only when asked for)
     int64_t opt_mode = 0;               // SEXTANS_MODE_* as last set through option "mode"
     int64_t opt_dist_broadcast_runs = 0;   // measurements / tests only: sextans_dist_spmm_rm exchanges ranges of EQUAL length by grouped broadcasts too
     int64_t opt_bell_debug = 0;         // measurements only (wrong results): ablation bits of spmm_bell_mfma_shared
@@ -329,28 +366,32 @@ struct sextans_engine {
     // transposed form (sextans_spmm_t_device_rm, engine_transpose.hip): A^T in arrays this engine owns, served by a companion engine
     // that carries this engine's options -- A's values as of its build or of the last sextans_update_values*, dropped with the matrix
     sextans_engine *tr = nullptr;
-    int *d_trp = nullptr, *d_tci = nullptr;
-    float *d_tv = nullptr;
-    int *d_tperm = nullptr;             // entry of A behind every entry of A^T (the stable sort's payload): d_tv[i] = d_v[d_tperm[i]]
-    double transpose_build_s = 0.0;     // seconds spent transposing A (the companion's plans: its own plan_build_s)
-    int *d_sddmm_row0 = nullptr;        // sextans_sddmm_device_rm: row of the first entry of every 256-entry wavefront range (+ M - 1 at the end)
-    int64_t sddmm_row0_n = 0;           // ints in it
-    // row softmax on the pattern (engine_softmax.hip, row_softmax_kernels.h): built once per matrix from row_ptr alone, dropped with the matrix
-    int *d_sm_wrow = nullptr;           // first row of every wavefront (+ M at the end)
-    int64_t sm_wrow_n = 0;              // ints in it (0 = not built)
-    int2 *d_sm_tab = nullptr;           // long rows: {row, chunk of the row} per 2048-entry chunk
-    float2 *d_sm_part = nullptr;        //   ... and the workspace of per-chunk partial results
-    int sm_nchunks = 0, sm_long_rows = 0;
+    struct Transposed {
+        DevBuf<int> d_trp, d_tci;
+        DevBuf<float> d_tv;
+        DevBuf<int> d_tperm;                // entry of A behind every entry of A^T (the stable sort's payload): d_tv[i] = d_v[d_tperm[i]]
+        double build_s = 0.0;               // seconds spent transposing A (the companion's plans: its own plan_build_s)
+        int64_t bytes() const { return d_trp.bytes() + d_tci.bytes() + d_tv.bytes() + d_tperm.bytes(); }
+    };
+    Transposed at;
+    DevBuf<int> d_sddmm_row0;           // sextans_sddmm_device_rm: row of the first entry of every 256-entry wavefront range (+ M - 1 at the end)
+    struct Softmax {   // row softmax on the pattern (engine_softmax.hip, row_softmax_kernels.h): built once per matrix from row_ptr alone, dropped with the matrix
+        DevBuf<int> d_sm_wrow;              // first row of every wavefront (+ M at the end); empty = not built
+        DevBuf<int2> d_sm_tab;              // long rows: {row, chunk of the row} per 2048-entry chunk
+        DevBuf<float2> d_sm_part;           //   ... and the workspace of per-chunk partial results
+        int nchunks = 0, long_rows = 0;
+        int64_t bytes() const { return d_sm_wrow.bytes() + d_sm_tab.bytes() + d_sm_part.bytes(); }
+    };
+    Softmax softmax;
 };
 
 namespace sxe {
 
 int check_device(int device);
-void free_panel_state(sextans_engine::PanelState &p);
 void free_plan(sextans_engine *h);
 void free_cluster_plan(sextans_engine *h);
 int64_t plan_key(const sextans_engine *h);
-int64_t device_bytes(const sextans_engine *h);   // what the engine holds in HBM right now (stat "device_bytes")
+int64_t device_bytes(const sextans_engine *h);   // bytes the engine has asked the runtime for and still holds (stat "device_bytes")
 void free_window(sextans_engine *h);
 void free_bell(sextans_engine *h);
 void free_split(sextans_engine *h);
@@ -362,7 +403,6 @@ void free_softmax(sextans_engine *h);                      // engine_softmax.hip
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)
 int transposed_options(sextans_engine *h, const char *key, int64_t value);   // engine.hip: one option (nullptr: all) onto the companion
-int ensure(float **p, size_t *cap, size_t need);
 int allow_big_lds(sextans_engine *h, const void *kern, int bytes);
 int read_back_row_ptr(sextans_engine *h, std::vector<int> &rp, int level = 2);
 int read_back_entries(sextans_engine *h, std::vector<int> &ci, std::vector<float> &va, int level = 2);
@@ -377,9 +417,9 @@ int ensure_split(sextans_engine *h);
 int ensure_dense(sextans_engine *h);                       // engine_bell.hip
 int prepare(sextans_engine *h, int N, bool whole = true, Tiling *out = nullptr);
 // the lane-per-row kernel (spmm_colwise_kernel.h) is asked for ("kernel" = 4) or chosen for this matrix
-inline bool colwise_wanted(const sextans_engine *h) { return h->opt_kernel == 4 || (h->opt_kernel == 0 && h->colwise_state == 1); }
+inline bool colwise_wanted(const sextans_engine *h) { return h->opt_kernel == 4 || (h->opt_kernel == 0 && h->cluster.colwise_state == 1); }
 // every row of the main matrix is on the CSR kernels: no dense tiles on the matrix cores, no routed row blocks
-inline bool csr_only(const sextans_engine *h) { return h->dense_W == 0 && h->rb_n == 0; }
+inline bool csr_only(const sextans_engine *h) { return h->dense.W == 0 && h->dense.rb_n == 0; }
 // dense 32x32 tiles on the matrix cores (engine_bell.hip): C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block rows
 int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
                        int64_t ldc_in, float *d_C_out, int64_t ldc, hipStream_t s);
@@ -397,16 +437,22 @@ int fork_chains(sextans_engine *h, const Call &c, const std::vector<Seg> &segs, 
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s);
 
 template <class T>
-int upload(T **dst, const std::vector<T> &src) {
-    SX_HIP(hipMalloc((void **)dst, sizeof(T) * (src.empty() ? 1 : src.size())));
-    if (!src.empty()) SX_HIP(hipMemcpy(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+int upload(DevBuf<T> &dst, const std::vector<T> &src) {
+    SX_HIP(dst.alloc(src.size()));
+    if (!src.empty()) SX_HIP(hipMemcpy(dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice));
+    return SEXTANS_OK;
+}
+
+template <class T>
+int reserve(DevBuf<T> &buf, size_t n) {   // grow-only workspace of at least n elements
+    SX_HIP(buf.reserve(n));
     return SEXTANS_OK;
 }
 
 struct PlanTimer {   // accumulates host seconds spent packing A (reported by sextans_get_stat "plan_build_s")
     sextans_engine *h; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     explicit PlanTimer(sextans_engine *h_) : h(h_) {}
-    ~PlanTimer() { h->plan_build_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    ~PlanTimer() { h->mat.plan_build_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
 struct Prof {   // HIP events around a launch group on the launch stream (option "profile")

@@ -15,27 +15,22 @@ namespace sxe {
 void free_transpose(sextans_engine *h) {
     if (h->tr) sextans_destroy(h->tr);
     h->tr = nullptr;
-    (void)hipFree(h->d_trp); (void)hipFree(h->d_tci); (void)hipFree(h->d_tv); (void)hipFree(h->d_tperm);
-    h->d_trp = h->d_tci = h->d_tperm = nullptr;
-    h->d_tv = nullptr;
-    h->transpose_build_s = 0.0;
+    h->at = {};
 }
 
 void free_backward(sextans_engine *h) {
     free_transpose(h);
-    (void)hipFree(h->d_sddmm_row0);
-    h->d_sddmm_row0 = nullptr;
-    h->sddmm_row0_n = 0;
+    h->d_sddmm_row0 = {};
     free_softmax(h);
 }
 
 int validate_matrix(sextans_engine *h) {   // a device matrix nobody has looked at yet: its indices address X / Y rows and A^T's row pointer
-    if (h->owns_matrix || h->device_matrix_checked || h->M == 0) return SEXTANS_OK;
+    if (h->owns_matrix() || h->mat.device_matrix_checked || h->M == 0) return SEXTANS_OK;
     int bad = 0;
     std::string verr;
     if (sx::validate_csr_device(h->M, h->K, h->nnz, h->d_rp, h->d_ci, &bad, verr)) { g_last_error = verr; return SEXTANS_ERR_HIP; }
     if (bad) return (bad & 1) ? SEXTANS_ERR_INVALID : SEXTANS_ERR_INDEX;
-    h->device_matrix_checked = true;
+    h->mat.device_matrix_checked = true;
     return SEXTANS_OK;
 }
 
@@ -46,17 +41,16 @@ int ensure_transpose(sextans_engine *h, hipStream_t s) {
     if (h->tr) return SEXTANS_OK;
     const auto t0 = std::chrono::steady_clock::now();
     if (int rc = validate_matrix(h)) return rc;
-    if (hipMalloc((void **)&h->d_trp, sizeof(int) * ((size_t)h->K + 1)) != hipSuccess ||
-        hipMalloc((void **)&h->d_tci, sizeof(int) * (size_t)std::max<int64_t>(h->nnz, 1)) != hipSuccess ||
-        hipMalloc((void **)&h->d_tv, sizeof(float) * (size_t)std::max<int64_t>(h->nnz, 1)) != hipSuccess ||
-        hipMalloc((void **)&h->d_tperm, sizeof(int) * (size_t)std::max<int64_t>(h->nnz, 1)) != hipSuccess) {
+    const size_t entries = (size_t)std::max<int64_t>(h->nnz, 1);
+    if (h->at.d_trp.alloc((size_t)h->K + 1) != hipSuccess || h->at.d_tci.alloc(entries) != hipSuccess || h->at.d_tv.alloc(entries) != hipSuccess ||
+        h->at.d_tperm.alloc(entries) != hipSuccess) {
         g_last_error = "transposed form: out of device memory for A^T";
         (void)hipGetLastError();
         free_transpose(h);   // (whatever was allocated before the failure)
         return SEXTANS_ERR_ALLOC;
     }
     std::string err;
-    if (sx::csr_transpose_device(h->M, h->K, h->nnz, h->d_rp, h->d_ci, h->d_v, h->d_trp, h->d_tci, h->d_tv, s, err, h->d_tperm)) {
+    if (sx::csr_transpose_device(h->M, h->K, h->nnz, h->d_rp, h->d_ci, h->d_v, h->at.d_trp, h->at.d_tci, h->at.d_tv, s, err, h->at.d_tperm)) {
         g_last_error = err;
         free_transpose(h);
         return SEXTANS_ERR_HIP;
@@ -65,10 +59,10 @@ int ensure_transpose(sextans_engine *h, hipStream_t s) {
     if (int rc = sextans_create(&tr, h->device)) { free_transpose(h); return rc; }
     h->tr = tr;
     int rc = transposed_options(h, nullptr, 0);
-    if (!rc) rc = sextans_set_matrix_csr_device(tr, h->K, h->M, h->nnz, h->d_trp, h->d_tci, h->d_tv);
+    if (!rc) rc = sextans_set_matrix_csr_device(tr, h->K, h->M, h->nnz, h->at.d_trp, h->at.d_tci, h->at.d_tv);
     if (rc) { free_transpose(h); return rc; }
-    tr->device_matrix_checked = true;   // (built from a validated matrix)
-    h->transpose_build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    tr->mat.device_matrix_checked = true;   // (built from a validated matrix)
+    h->at.build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return SEXTANS_OK;
 }
 
@@ -79,13 +73,11 @@ int ensure_sddmm_rows(sextans_engine *h, hipStream_t s) {
     if (h->d_sddmm_row0 || h->nnz == 0) return SEXTANS_OK;
     if (int rc = validate_matrix(h)) return rc;
     const int64_t nw = (h->nnz + sx::kSddmmWaveEntries - 1) / sx::kSddmmWaveEntries;
-    if (hipMalloc((void **)&h->d_sddmm_row0, sizeof(int) * (size_t)(nw + 1)) != hipSuccess) {
+    if (h->d_sddmm_row0.alloc((size_t)(nw + 1)) != hipSuccess) {
         (void)hipGetLastError();
-        h->d_sddmm_row0 = nullptr;
         g_last_error = "sddmm: out of device memory for the row table";
         return SEXTANS_ERR_ALLOC;
     }
-    h->sddmm_row0_n = nw + 1;
     hipLaunchKernelGGL(sx::sddmm_wave_rows, dim3((unsigned)((nw + 1 + 255) / 256)), dim3(256), 0, s, h->M, (long long)h->nnz, h->d_rp,
                        (long long)nw, h->d_sddmm_row0);
     SX_HIP(hipGetLastError());

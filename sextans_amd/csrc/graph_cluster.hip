@@ -49,17 +49,6 @@ namespace {
         if (e_ != hipSuccess) { err = std::string(#x) + ": " + hipGetErrorString(e_); return 2; }       \
     } while (0)
 
-struct Scratch {   // device allocations freed on every exit path (keep() hands one over to the caller)
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
-    template <class T> hipError_t alloc(T **out, size_t n) {
-        hipError_t e = hipMalloc((void **)out, sizeof(T) * (n ? n : 1));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    void keep(void *q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
-};
-
 constexpr int kTriMaxLen = 256;   // rows longer than this: unit weights (their neighbourhoods are not compared)
 constexpr int kTriHT = 512;       // hash slots per wavefront for one row's columns (load <= 0.5)
 constexpr int kNbHT = 512;        // hash slots per wavefront for a cluster's neighbouring clusters
@@ -580,9 +569,9 @@ int probe_shared_neighbourhood_device(int M, const int *d_rp, const int *d_ci, i
     *near_fraction = 0.0;
     if (symmetric_fraction) *symmetric_fraction = 1.0;
     if (M < 16 || nsample < 1) return 0;
-    Scratch tmp;
-    unsigned long long *d_acc = nullptr, h_acc[6] = {0, 0, 0, 0, 0, 0};
-    GC_HIP(tmp.alloc(&d_acc, 6));
+    DevBuf<unsigned long long> d_acc;
+    unsigned long long h_acc[6] = {0, 0, 0, 0, 0, 0};
+    GC_HIP(d_acc.alloc(6));
     GC_HIP(hipMemset(d_acc, 0, sizeof h_acc));
     hipLaunchKernelGGL(probe_shared, dim3(blocks_for(nsample, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, nsample, d_acc);
     GC_HIP(hipMemcpy(h_acc, d_acc, sizeof h_acc, hipMemcpyDeviceToHost));
@@ -595,9 +584,9 @@ int probe_shared_neighbourhood_device(int M, const int *d_rp, const int *d_ci, i
 int probe_row_coherence_device(int M, const int *d_rp, const int *d_ci, int nsample, double *close_fraction, std::string &err) {
     *close_fraction = 0.0;
     if (M < 2 || nsample < 1) return 0;
-    Scratch tmp;
-    unsigned long long *d_acc = nullptr, h_acc[2] = {0, 0};
-    GC_HIP(tmp.alloc(&d_acc, 2));
+    DevBuf<unsigned long long> d_acc;
+    unsigned long long h_acc[2] = {0, 0};
+    GC_HIP(d_acc.alloc(2));
     GC_HIP(hipMemset(d_acc, 0, sizeof h_acc));
     hipLaunchKernelGGL(probe_coherence, dim3(blocks_for(nsample, 256)), dim3(256), 0, nullptr, M, d_rp, d_ci, nsample, d_acc);
     GC_HIP(hipMemcpy(h_acc, d_acc, sizeof h_acc, hipMemcpyDeviceToHost));
@@ -612,43 +601,41 @@ __global__ __launch_bounds__(256) void snapshot_clusters(int M, const int2 *__re
 }
 }  // namespace
 
-int cluster_rows_graph_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, int max_cluster_rows, int **d_order,
-                              std::string &err, const unsigned char *d_weights, int snapshot_limit, int **d_snapshot) {
-    *d_order = nullptr;
-    int *snap = nullptr;
+int cluster_rows_graph_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, int max_cluster_rows, DevBuf<int> &d_order,
+                              std::string &err, const unsigned char *d_weights, int snapshot_limit, DevBuf<int> *d_snapshot) {
+    d_order.reset();
+    DevBuf<int> snap;
     bool snapped = false;
-    if (d_snapshot) *d_snapshot = nullptr;
+    if (d_snapshot) d_snapshot->reset();
     if (M != K || M < 2 || nnz <= 0) return 1;
-    Scratch tmp;
-    unsigned char *t = nullptr;
-    int *ord[2] = {nullptr, nullptr}, *cstart[2] = {nullptr, nullptr};
-    int2 *cinfo[2] = {nullptr, nullptr};
-    int *cand = nullptr, *matched = nullptr, *want = nullptr, *mate = nullptr, *is_leader = nullptr, *new_idx = nullptr, *new_size = nullptr,
-        *new_start = nullptr;
-    GC_HIP(tmp.alloc(&t, (size_t)nnz));
-    if (d_snapshot) GC_HIP(tmp.alloc(&snap, (size_t)M));
+    DevBuf<unsigned char> t;
+    DevBuf<int> ord[2], cstart[2];
+    DevBuf<int2> cinfo[2];
+    DevBuf<int> cand, matched, want, mate, is_leader, new_idx, new_size, new_start;
+    GC_HIP(t.alloc((size_t)nnz));
+    if (d_snapshot) GC_HIP(snap.alloc((size_t)M));
     for (int i = 0; i < 2; ++i) {
-        GC_HIP(tmp.alloc(&ord[i], (size_t)M));
-        GC_HIP(tmp.alloc(&cstart[i], (size_t)M + 1));
-        GC_HIP(tmp.alloc(&cinfo[i], (size_t)M));
+        GC_HIP(ord[i].alloc((size_t)M));
+        GC_HIP(cstart[i].alloc((size_t)M + 1));
+        GC_HIP(cinfo[i].alloc((size_t)M));
     }
-    GC_HIP(tmp.alloc(&cand, (size_t)M * kCand));
-    unsigned *candw = nullptr, *W = nullptr;
-    int *flip = nullptr, *d_count = nullptr;
-    GC_HIP(tmp.alloc(&d_count, 1));
-    GC_HIP(tmp.alloc(&candw, (size_t)M * kCand * 4));
-    GC_HIP(tmp.alloc(&flip, (size_t)M));
-    GC_HIP(tmp.alloc(&matched, (size_t)M));
-    GC_HIP(tmp.alloc(&want, (size_t)M));
-    GC_HIP(tmp.alloc(&mate, (size_t)M));
-    GC_HIP(tmp.alloc(&is_leader, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&new_idx, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&new_size, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&new_start, (size_t)M + 1));
-    void *scan_tmp = nullptr;
+    GC_HIP(cand.alloc((size_t)M * kCand));
+    DevBuf<unsigned> candw, W;
+    DevBuf<int> flip, d_count;
+    GC_HIP(d_count.alloc(1));
+    GC_HIP(candw.alloc((size_t)M * kCand * 4));
+    GC_HIP(flip.alloc((size_t)M));
+    GC_HIP(matched.alloc((size_t)M));
+    GC_HIP(want.alloc((size_t)M));
+    GC_HIP(mate.alloc((size_t)M));
+    GC_HIP(is_leader.alloc((size_t)M + 1));
+    GC_HIP(new_idx.alloc((size_t)M + 1));
+    GC_HIP(new_size.alloc((size_t)M + 1));
+    GC_HIP(new_start.alloc((size_t)M + 1));
+    DevBuf<char> scan_tmp;
     size_t scan_bytes = 0;
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, is_leader, new_idx, M + 1, nullptr));
-    GC_HIP(tmp.alloc((char **)&scan_tmp, scan_bytes));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, is_leader.get(), new_idx.get(), M + 1, nullptr));
+    GC_HIP(scan_tmp.alloc(scan_bytes));
 
     if (d_weights) GC_HIP(hipMemcpyAsync(t, d_weights, (size_t)nnz, hipMemcpyDeviceToDevice, nullptr));
     else hipLaunchKernelGGL(tri_weights, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, t);
@@ -667,7 +654,7 @@ int cluster_rows_graph_device(int M, int K, int64_t nnz, const int *d_rp, const 
                 hipLaunchKernelGGL(level_candidates, dim3(blocks_for(nc, 4)), dim3(256), 0, nullptr, nc, M, cstart[cur], ord[cur], cinfo[cur], d_rp,
                                    d_ci, t, (int)limit, salt, matched, cand, candw);
             } else {
-                if (!W) GC_HIP(tmp.alloc(&W, (size_t)kDenseMax * kDenseMax * 4));
+                if (!W) GC_HIP(W.alloc((size_t)kDenseMax * kDenseMax * 4));
                 GC_HIP(hipMemsetAsync(W, 0, sizeof(unsigned) * (size_t)nc * nc * 4, nullptr));
                 hipLaunchKernelGGL(level_dense_accumulate, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, nc, ord[cur], cinfo[cur], d_rp, d_ci, t,
                                    (int)limit, matched, W);
@@ -688,8 +675,8 @@ int cluster_rows_graph_device(int M, int K, int64_t nnz, const int *d_rp, const 
         hipLaunchKernelGGL(level_orient, dim3(blocks_for(nc, 256)), dim3(256), 0, nullptr, nc, mate, cand, candw, flip);
         hipLaunchKernelGGL(level_leaders, dim3(blocks_for((long long)nc + 1, 256)), dim3(256), 0, nullptr, nc, mate, cstart[cur], is_leader,
                            new_size);
-        GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, is_leader, new_idx, nc + 1, nullptr));
-        GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, new_size, new_start, nc + 1, nullptr));
+        GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), scan_bytes, is_leader.get(), new_idx.get(), nc + 1, nullptr));
+        GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), scan_bytes, new_size.get(), new_start.get(), nc + 1, nullptr));
         hipLaunchKernelGGL(level_move, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, nc, ord[cur], cinfo[cur], cstart[cur], mate, flip,
                            new_idx, new_start, ord[cur ^ 1], cinfo[cur ^ 1], cstart[cur ^ 1]);
         int nc_new = 0;
@@ -712,43 +699,41 @@ int cluster_rows_graph_device(int M, int K, int64_t nnz, const int *d_rp, const 
     if (snap && !snapped) hipLaunchKernelGGL(snapshot_clusters, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, cinfo[cur], snap);
     GC_HIP(hipDeviceSynchronize());
     GC_HIP(hipGetLastError());
-    tmp.keep(ord[cur]);
-    *d_order = ord[cur];
-    if (snap) { tmp.keep(snap); *d_snapshot = snap; }
+    d_order = std::move(ord[cur]);
+    if (snap) *d_snapshot = std::move(snap);
     return 0;
 }
 
-int refine_blocks_device(int M, const int *d_rp, const int *d_ci, int *d_order, int per, int cap, int sweeps, unsigned char **d_cut,
+int refine_blocks_device(int M, const int *d_rp, const int *d_ci, int *d_order, int per, int cap, int sweeps, DevBuf<unsigned char> &d_cut,
                          std::string &err) {
-    *d_cut = nullptr;
+    d_cut.reset();
     if (M < 2 || per < 1 || per > cap) return 1;
-    Scratch tmp;
     const int nb = (M + per - 1) / per;
-    int *blk = nullptr, *pos = nullptr, *size[2] = {nullptr, nullptr}, *seg = nullptr, *val = nullptr, *sval = nullptr, *moved = nullptr;
-    unsigned long long *key = nullptr, *skey = nullptr;
-    unsigned char *cut = nullptr;
-    GC_HIP(tmp.alloc(&blk, (size_t)M));
-    GC_HIP(tmp.alloc(&pos, (size_t)M));
-    GC_HIP(tmp.alloc(&size[0], (size_t)nb));
-    GC_HIP(tmp.alloc(&size[1], (size_t)nb));
-    GC_HIP(tmp.alloc(&seg, (size_t)nb));
-    GC_HIP(tmp.alloc(&val, (size_t)M));
-    GC_HIP(tmp.alloc(&sval, (size_t)M));
-    GC_HIP(tmp.alloc(&key, (size_t)M));
-    GC_HIP(tmp.alloc(&skey, (size_t)M));
-    GC_HIP(tmp.alloc(&moved, 1));
-    GC_HIP(tmp.alloc(&cut, (size_t)M));
-    void *sort_tmp = nullptr;
+    DevBuf<int> blk, pos, size[2], seg, val, sval, moved;
+    DevBuf<unsigned long long> key, skey;
+    DevBuf<unsigned char> cut;
+    GC_HIP(blk.alloc((size_t)M));
+    GC_HIP(pos.alloc((size_t)M));
+    GC_HIP(size[0].alloc((size_t)nb));
+    GC_HIP(size[1].alloc((size_t)nb));
+    GC_HIP(seg.alloc((size_t)nb));
+    GC_HIP(val.alloc((size_t)M));
+    GC_HIP(sval.alloc((size_t)M));
+    GC_HIP(key.alloc((size_t)M));
+    GC_HIP(skey.alloc((size_t)M));
+    GC_HIP(moved.alloc(1));
+    GC_HIP(cut.alloc((size_t)M));
+    DevBuf<char> sort_tmp;
     size_t bytes = 0;
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, val, sval, M, 0, 64, nullptr));
-    GC_HIP(tmp.alloc((char **)&sort_tmp, bytes));
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key.get(), skey.get(), val.get(), sval.get(), M, 0, 64, nullptr));
+    GC_HIP(sort_tmp.alloc(bytes));
     hipLaunchKernelGGL(refine_init, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, per, d_order, blk, pos);
     GC_HIP(hipMemsetAsync(size[0], 0, sizeof(int) * (size_t)nb, nullptr));
     hipLaunchKernelGGL(refine_sizes, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, blk, size[0]);
     int cur = 0;
     for (int sweep = 0; sweep < sweeps; ++sweep) {
         hipLaunchKernelGGL(refine_requests, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, blk, sweep, key, val);
-        GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, skey, val, sval, M, 0, 64, nullptr));
+        GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, key.get(), skey.get(), val.get(), sval.get(), M, 0, 64, nullptr));
         GC_HIP(hipMemcpyAsync(size[cur ^ 1], size[cur], sizeof(int) * (size_t)nb, hipMemcpyDeviceToDevice, nullptr));
         GC_HIP(hipMemsetAsync(moved, 0, sizeof(int), nullptr));
         hipLaunchKernelGGL(refine_segments, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, skey, seg);
@@ -760,37 +745,34 @@ int refine_blocks_device(int M, const int *d_rp, const int *d_ci, int *d_order, 
         if ((long long)h_moved * 2000 < M) break;
     }
     hipLaunchKernelGGL(refine_final_keys, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, blk, pos, key, val);
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, skey, val, d_order, M, 0, 64, nullptr));
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, key.get(), skey.get(), val.get(), d_order, M, 0, 64, nullptr));
     hipLaunchKernelGGL(refine_cuts, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, skey, cut);
     GC_HIP(hipDeviceSynchronize());
     GC_HIP(hipGetLastError());
-    tmp.keep(cut);
-    *d_cut = cut;
+    d_cut = std::move(cut);
     return 0;
 }
 
-int column_first_touch_order_device(int M, int K, const int *d_rp, const int *d_ci, const int *d_order, int **d_colpos, std::string &err) {
-    *d_colpos = nullptr;
+int column_first_touch_order_device(int M, int K, const int *d_rp, const int *d_ci, const int *d_order, DevBuf<int> &d_colpos, std::string &err) {
+    d_colpos.reset();
     if (K <= 0) return 1;
-    Scratch tmp;
-    int *first = nullptr, *first_sorted = nullptr, *cols = nullptr, *cols_sorted = nullptr, *pos = nullptr;
-    GC_HIP(tmp.alloc(&first, (size_t)K));
-    GC_HIP(tmp.alloc(&first_sorted, (size_t)K));
-    GC_HIP(tmp.alloc(&cols, (size_t)K));
-    GC_HIP(tmp.alloc(&cols_sorted, (size_t)K));
-    GC_HIP(tmp.alloc(&pos, (size_t)K));
+    DevBuf<int> first, first_sorted, cols, cols_sorted, pos;
+    GC_HIP(first.alloc((size_t)K));
+    GC_HIP(first_sorted.alloc((size_t)K));
+    GC_HIP(cols.alloc((size_t)K));
+    GC_HIP(cols_sorted.alloc((size_t)K));
+    GC_HIP(pos.alloc((size_t)K));
     hipLaunchKernelGGL(iota_fill, dim3(blocks_for(K, 256)), dim3(256), 0, nullptr, K, cols, first, 0x7fffffff);
     if (M > 0) hipLaunchKernelGGL(first_touch, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, d_order, first);
-    void *sort_tmp = nullptr;
+    DevBuf<char> sort_tmp;
     size_t bytes = 0;
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, first, first_sorted, cols, cols_sorted, K, 0, 32, nullptr));
-    GC_HIP(tmp.alloc((char **)&sort_tmp, bytes));
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, first, first_sorted, cols, cols_sorted, K, 0, 32, nullptr));   // stable: ties by column
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, first.get(), first_sorted.get(), cols.get(), cols_sorted.get(), K, 0, 32, nullptr));
+    GC_HIP(sort_tmp.alloc(bytes));
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, first.get(), first_sorted.get(), cols.get(), cols_sorted.get(), K, 0, 32, nullptr));   // stable: ties by column
     hipLaunchKernelGGL(invert_perm, dim3(blocks_for(K, 256)), dim3(256), 0, nullptr, K, cols_sorted, pos);
     GC_HIP(hipDeviceSynchronize());
     GC_HIP(hipGetLastError());
-    tmp.keep(pos);
-    *d_colpos = pos;
+    d_colpos = std::move(pos);
     return 0;
 }
 
@@ -820,29 +802,27 @@ __global__ __launch_bounds__(256) void slab_fill(int M, const int *__restrict__ 
 }
 }  // namespace
 
-int local_square_pattern_device(int M, const int *d_rp, const int *d_ci, int row_offset, int **out_rp, int **out_ci, int64_t *out_nnz,
+int local_square_pattern_device(int M, const int *d_rp, const int *d_ci, int row_offset, DevBuf<int> &out_rp, DevBuf<int> &out_ci, int64_t *out_nnz,
                                 std::string &err) {
-    *out_rp = *out_ci = nullptr;
+    out_rp.reset(); out_ci.reset();
     *out_nnz = 0;
     if (M <= 0) return 1;
-    Scratch tmp;
-    int *cnt = nullptr, *orp = nullptr, *oci = nullptr;
-    GC_HIP(tmp.alloc(&cnt, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&orp, (size_t)M + 1));
+    DevBuf<int> cnt, orp, oci;
+    GC_HIP(cnt.alloc((size_t)M + 1));
+    GC_HIP(orp.alloc((size_t)M + 1));
     GC_HIP(hipMemsetAsync(cnt + M, 0, sizeof(int), nullptr));
     hipLaunchKernelGGL(slab_count, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, nullptr, M, d_rp, d_ci, row_offset, cnt);
-    void *scan_tmp = nullptr;
+    DevBuf<char> scan_tmp;
     size_t bytes = 0;
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, orp, M + 1, nullptr));
-    GC_HIP(tmp.alloc((char **)&scan_tmp, bytes));
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, cnt, orp, M + 1, nullptr));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt.get(), orp.get(), M + 1, nullptr));
+    GC_HIP(scan_tmp.alloc(bytes));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), bytes, cnt.get(), orp.get(), M + 1, nullptr));
     int total = 0;
     GC_HIP(hipMemcpy(&total, orp + M, sizeof(int), hipMemcpyDeviceToHost));
-    GC_HIP(tmp.alloc(&oci, (size_t)std::max(total, 1)));
+    GC_HIP(oci.alloc((size_t)std::max(total, 1)));
     hipLaunchKernelGGL(slab_fill, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, nullptr, M, d_rp, d_ci, row_offset, orp, oci);
     GC_HIP(hipDeviceSynchronize());
-    tmp.keep(orp); tmp.keep(oci);
-    *out_rp = orp; *out_ci = oci; *out_nnz = total;
+    out_rp = std::move(orp); out_ci = std::move(oci); *out_nnz = total;
     return 0;
 }
 
@@ -966,21 +946,21 @@ __global__ __launch_bounds__(256) void row_similarity(int M, int K, const int *_
 }
 }  // namespace
 
-int row_similarity_graph_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, int **g_rp, int **g_ci, unsigned char **g_w,
+int row_similarity_graph_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, DevBuf<int> &g_rp, DevBuf<int> &g_ci, DevBuf<unsigned char> &g_w,
                                 int64_t *g_nnz, double *shared_fraction, double *near_fraction, std::string &err) {
-    *g_rp = *g_ci = nullptr; *g_w = nullptr; *g_nnz = 0;
+    g_rp.reset(); g_ci.reset(); g_w.reset(); *g_nnz = 0;
     *shared_fraction = *near_fraction = 0.0;
     if (M < 2 || K < 1 || nnz <= 0 || nnz > 0x7fffffffLL || (int64_t)M * kRowSimDeg > 0x7fffffffLL) return 1;
-    Scratch tmp;
-    int *srows = nullptr, *cp = nullptr, *orp = nullptr, *oci = nullptr;
-    unsigned char *ow = nullptr;
-    unsigned long long *d_acc = nullptr, h_acc[4] = {0, 0, 0, 0};
-    GC_HIP(tmp.alloc(&srows, (size_t)nnz));
-    GC_HIP(tmp.alloc(&cp, (size_t)K + 1));
-    GC_HIP(tmp.alloc(&orp, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&oci, (size_t)M * kRowSimDeg));
-    GC_HIP(tmp.alloc(&ow, (size_t)M * kRowSimDeg));
-    GC_HIP(tmp.alloc(&d_acc, 4));
+    DevBuf<int> srows, cp, orp, oci;
+    DevBuf<unsigned char> ow;
+    DevBuf<unsigned long long> d_acc;
+    unsigned long long h_acc[4] = {0, 0, 0, 0};
+    GC_HIP(srows.alloc((size_t)nnz));
+    GC_HIP(cp.alloc((size_t)K + 1));
+    GC_HIP(orp.alloc((size_t)M + 1));
+    GC_HIP(oci.alloc((size_t)M * kRowSimDeg));
+    GC_HIP(ow.alloc((size_t)M * kRowSimDeg));
+    GC_HIP(d_acc.alloc(4));
     GC_HIP(hipMemsetAsync(d_acc, 0, sizeof h_acc, nullptr));
     // the pattern sorted by column: cp = row pointer of A^T, srows = its rows, ascending per column (csr_transpose.hip)
     if (csr_transpose_device(M, K, nnz, d_rp, d_ci, nullptr, cp, srows, nullptr, nullptr, err)) return 2;
@@ -991,8 +971,7 @@ int row_similarity_graph_device(int M, int K, int64_t nnz, const int *d_rp, cons
     GC_HIP(hipGetLastError());
     if (h_acc[1]) *shared_fraction = (double)h_acc[0] / (double)h_acc[1];
     if (h_acc[3]) *near_fraction = (double)h_acc[2] / (double)h_acc[3];
-    tmp.keep(orp); tmp.keep(oci); tmp.keep(ow);
-    *g_rp = orp; *g_ci = oci; *g_w = ow; *g_nnz = (int64_t)M * kRowSimDeg;
+    g_rp = std::move(orp); g_ci = std::move(oci); g_w = std::move(ow); *g_nnz = (int64_t)M * kRowSimDeg;
     return 0;
 }
 
@@ -1069,50 +1048,46 @@ __global__ __launch_bounds__(256) void sym_rows(int M, const int *__restrict__ r
 }
 }  // namespace
 
-int symmetrize_graph_device(int M, int64_t nnz, const int *d_rp, const int *d_ci, const unsigned char *d_w, int **s_rp, int **s_ci,
-                            unsigned char **s_w, int64_t *s_nnz, std::string &err) {
-    *s_rp = *s_ci = nullptr; *s_nnz = 0;
-    if (s_w) *s_w = nullptr;
+int symmetrize_graph_device(int M, int64_t nnz, const int *d_rp, const int *d_ci, const unsigned char *d_w, DevBuf<int> &s_rp, DevBuf<int> &s_ci,
+                            DevBuf<unsigned char> &s_w, int64_t *s_nnz, std::string &err) {
+    s_rp.reset(); s_ci.reset(); s_w.reset(); *s_nnz = 0;
     if (M < 1 || nnz <= 0 || nnz > 0x3fffffffLL) return 1;
-    Scratch tmp;
-    int *key = nullptr, *skey = nullptr, *eid = nullptr, *seid = nullptr, *src = nullptr, *cp = nullptr, *cnt = nullptr, *orp = nullptr, *oci = nullptr;
-    unsigned char *ow = nullptr;
-    GC_HIP(tmp.alloc(&key, (size_t)nnz));
-    GC_HIP(tmp.alloc(&skey, (size_t)nnz));
-    GC_HIP(tmp.alloc(&eid, (size_t)nnz));
-    GC_HIP(tmp.alloc(&seid, (size_t)nnz));
-    GC_HIP(tmp.alloc(&src, (size_t)nnz));
-    GC_HIP(tmp.alloc(&cp, (size_t)M + 2));
-    GC_HIP(tmp.alloc(&cnt, (size_t)M + 1));
-    GC_HIP(tmp.alloc(&orp, (size_t)M + 1));
+    DevBuf<int> key, skey, eid, seid, src, cp, cnt, orp, oci;
+    DevBuf<unsigned char> ow;
+    GC_HIP(key.alloc((size_t)nnz));
+    GC_HIP(skey.alloc((size_t)nnz));
+    GC_HIP(eid.alloc((size_t)nnz));
+    GC_HIP(seid.alloc((size_t)nnz));
+    GC_HIP(src.alloc((size_t)nnz));
+    GC_HIP(cp.alloc((size_t)M + 2));
+    GC_HIP(cnt.alloc((size_t)M + 1));
+    GC_HIP(orp.alloc((size_t)M + 1));
     hipLaunchKernelGGL(sym_keys, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, key, eid, src);
     int bits = 1;
     while (bits < 32 && (1LL << bits) <= (long long)M) ++bits;
-    void *sort_tmp = nullptr;
+    DevBuf<char> sort_tmp;
     size_t bytes = 0;
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, skey, eid, seid, (int)nnz, 0, bits, nullptr));
-    GC_HIP(tmp.alloc((char **)&sort_tmp, bytes));
-    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, key, skey, eid, seid, (int)nnz, 0, bits, nullptr));   // stable: sources ascending per target
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key.get(), skey.get(), eid.get(), seid.get(), (int)nnz, 0, bits, nullptr));
+    GC_HIP(sort_tmp.alloc(bytes));
+    GC_HIP(hipcub::DeviceRadixSort::SortPairs(sort_tmp.get(), bytes, key.get(), skey.get(), eid.get(), seid.get(), (int)nnz, 0, bits, nullptr));   // stable: sources ascending per target
     segment_starts_device(M + 1, nnz, skey, cp, nullptr);
     GC_HIP(hipMemsetAsync(cnt + M, 0, sizeof(int), nullptr));
     hipLaunchKernelGGL(sym_rows<false>, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, d_w, cp, seid, src, cnt, (const int *)nullptr,
                        (int *)nullptr, (unsigned char *)nullptr);
-    void *scan_tmp = nullptr;
+    DevBuf<char> scan_tmp;
     size_t sbytes = 0;
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, cnt, orp, M + 1, nullptr));
-    GC_HIP(tmp.alloc((char **)&scan_tmp, sbytes));
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, sbytes, cnt, orp, M + 1, nullptr));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, sbytes, cnt.get(), orp.get(), M + 1, nullptr));
+    GC_HIP(scan_tmp.alloc(sbytes));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), sbytes, cnt.get(), orp.get(), M + 1, nullptr));
     int total = 0;
     GC_HIP(hipMemcpy(&total, orp + M, sizeof(int), hipMemcpyDeviceToHost));
     if (total <= 0) return 1;
-    GC_HIP(tmp.alloc(&oci, (size_t)total));
-    if (d_w && s_w) GC_HIP(tmp.alloc(&ow, (size_t)total));
+    GC_HIP(oci.alloc((size_t)total));
+    if (d_w) GC_HIP(ow.alloc((size_t)total));
     hipLaunchKernelGGL(sym_rows<true>, dim3(blocks_for(M, 4)), dim3(256), 0, nullptr, M, d_rp, d_ci, d_w, cp, seid, src, (int *)nullptr, orp, oci, ow);
     GC_HIP(hipDeviceSynchronize());
     GC_HIP(hipGetLastError());
-    tmp.keep(orp); tmp.keep(oci);
-    if (ow) { tmp.keep(ow); *s_w = ow; }
-    *s_rp = orp; *s_ci = oci; *s_nnz = total;
+    s_rp = std::move(orp); s_ci = std::move(oci); s_w = std::move(ow); *s_nnz = total;
     return 0;
 }
 
@@ -1191,51 +1166,47 @@ __global__ __launch_bounds__(256) void expand_run_order(int M, int Mr, int run, 
 }
 }  // namespace
 
-int run_graph_device(int M, int run, const int *d_rp, const int *d_ci, int **r_rp, int **r_ci, unsigned char **r_w, int64_t *r_nnz, int *Mr_out,
+int run_graph_device(int M, int run, const int *d_rp, const int *d_ci, DevBuf<int> &r_rp, DevBuf<int> &r_ci, DevBuf<unsigned char> &r_w, int64_t *r_nnz, int *Mr_out,
                      std::string &err) {
-    *r_rp = *r_ci = nullptr; *r_w = nullptr; *r_nnz = 0; *Mr_out = 0;
+    r_rp.reset(); r_ci.reset(); r_w.reset(); *r_nnz = 0; *Mr_out = 0;
     const int Mr = M / run;
     if (Mr < 2 || run < 1) return 1;
-    Scratch tmp;
-    int *cnt = nullptr, *orp = nullptr, *oci = nullptr, *d_over = nullptr;
-    unsigned char *ow = nullptr;
-    GC_HIP(tmp.alloc(&cnt, (size_t)Mr + 1));
-    GC_HIP(tmp.alloc(&orp, (size_t)Mr + 1));
-    GC_HIP(tmp.alloc(&d_over, 1));
+    DevBuf<int> cnt, orp, oci, d_over;
+    DevBuf<unsigned char> ow;
+    GC_HIP(cnt.alloc((size_t)Mr + 1));
+    GC_HIP(orp.alloc((size_t)Mr + 1));
+    GC_HIP(d_over.alloc(1));
     GC_HIP(hipMemsetAsync(d_over, 0, sizeof(int), nullptr));
     GC_HIP(hipMemsetAsync(cnt + Mr, 0, sizeof(int), nullptr));
     hipLaunchKernelGGL(run_graph_rows<false>, dim3(blocks_for(Mr, 4)), dim3(256), 0, nullptr, Mr, run, d_rp, d_ci, cnt, (const int *)nullptr, (int *)nullptr, (unsigned char *)nullptr, d_over);
-    void *scan_tmp = nullptr;
+    DevBuf<char> scan_tmp;
     size_t bytes = 0;
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt, orp, Mr + 1, nullptr));
-    GC_HIP(tmp.alloc((char **)&scan_tmp, bytes));
-    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, cnt, orp, Mr + 1, nullptr));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, cnt.get(), orp.get(), Mr + 1, nullptr));
+    GC_HIP(scan_tmp.alloc(bytes));
+    GC_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), bytes, cnt.get(), orp.get(), Mr + 1, nullptr));
     int total = 0, over = 0;
     GC_HIP(hipMemcpy(&total, orp + Mr, sizeof(int), hipMemcpyDeviceToHost));
     GC_HIP(hipMemcpy(&over, d_over, sizeof(int), hipMemcpyDeviceToHost));
     if (over || total <= 0) return 1;                     // (runs with more than 512 neighbouring runs: not a matrix for this)
-    GC_HIP(tmp.alloc(&oci, (size_t)total));
-    GC_HIP(tmp.alloc(&ow, (size_t)total));
+    GC_HIP(oci.alloc((size_t)total));
+    GC_HIP(ow.alloc((size_t)total));
     hipLaunchKernelGGL(run_graph_rows<true>, dim3(blocks_for(Mr, 4)), dim3(256), 0, nullptr, Mr, run, d_rp, d_ci, (int *)nullptr, orp, oci, ow, (int *)nullptr);
     GC_HIP(hipDeviceSynchronize());
     GC_HIP(hipGetLastError());
-    tmp.keep(orp); tmp.keep(oci); tmp.keep(ow);
-    *r_rp = orp; *r_ci = oci; *r_w = ow; *r_nnz = total; *Mr_out = Mr;
+    r_rp = std::move(orp); r_ci = std::move(oci); r_w = std::move(ow); *r_nnz = total; *Mr_out = Mr;
     return 0;
 }
 
-int expand_run_order_device(int M, int Mr, int run, int runs_per_block, const int *d_order_r, const int *d_group, int **d_order, unsigned char **d_cut,
+int expand_run_order_device(int M, int Mr, int run, int runs_per_block, const int *d_order_r, const int *d_group, DevBuf<int> &d_order, DevBuf<unsigned char> &d_cut,
                             std::string &err) {
-    *d_order = nullptr; *d_cut = nullptr;
-    Scratch tmp;
-    int *o = nullptr;
-    unsigned char *c = nullptr;
-    GC_HIP(tmp.alloc(&o, (size_t)M));
-    GC_HIP(tmp.alloc(&c, (size_t)M));
+    d_order.reset(); d_cut.reset();
+    DevBuf<int> o;
+    DevBuf<unsigned char> c;
+    GC_HIP(o.alloc((size_t)M));
+    GC_HIP(c.alloc((size_t)M));
     hipLaunchKernelGGL(expand_run_order, dim3(blocks_for(M, 256)), dim3(256), 0, nullptr, M, Mr, run, runs_per_block, d_order_r, d_group, o, c);
     GC_HIP(hipDeviceSynchronize());
-    tmp.keep(o); tmp.keep(c);
-    *d_order = o; *d_cut = c;
+    d_order = std::move(o); d_cut = std::move(c);
     return 0;
 }
 

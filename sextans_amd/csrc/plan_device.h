@@ -4,6 +4,8 @@
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
+
 namespace sx {
 
 constexpr int kPlanPartBlocks = 64;   // rows are cut into parts of kPlanPartBlocks * rows_per_block rows; every part starts a
@@ -15,19 +17,19 @@ constexpr int kPlanTailPad = 256;     // zero entries behind the last row (the k
 struct DevicePlan {                   // device arrays in exactly the form the LDS-panel kernels read
     int lpr = 0, rows_per_block = 0, sets = 1;   // rows_per_block = sets * (256 / lpr) row slots
     int nblk = 0;
-    int *d_blk_row = nullptr;         // nblk + 1
-    int *d_dict_cnt = nullptr;        // nblk: dictionary entries (0 = direct block)
-    int *d_dict = nullptr;            // nblk x dict_stride, last column repeated
+    DevBuf<int> d_blk_row;            // nblk + 1
+    DevBuf<int> d_dict_cnt;           // nblk: dictionary entries (0 = direct block)
+    DevBuf<int> d_dict;               // nblk x dict_stride, last column repeated
     int dict_stride = 0;
-    int *d_slot_info = nullptr;       // nblk x rows_per_block x {first packed entry, entries}
-    unsigned short *d_idx16 = nullptr;   // BYTE offset of the entry's B row in the panel (index * 16 * lpr); padding -> pad row
-    int *d_ioff = nullptr;            // nblk x rows_per_block x {start of the slot's index list in d_idx16, shift in bytes to add to every
+    DevBuf<int> d_slot_info;          // nblk x rows_per_block x {first packed entry, entries}
+    DevBuf<unsigned short> d_idx16;      // BYTE offset of the entry's B row in the panel (index * 16 * lpr); padding -> pad row
+    DevBuf<int> d_ioff;               // nblk x rows_per_block x {start of the slot's index list in d_idx16, shift in bytes to add to every
                                       // offset of the list} when lists are SHARED (null: every row has its own list at its first packed entry):
                                       // consecutive rows of a block whose lists are equal up to a constant shift keep one copy (share_index_lists)
     int64_t idx_len = 0;              // entries of d_idx16 (= stream_len without sharing)
     int64_t shared_rows = 0;          // rows whose index list is another row's
-    int *d_col32 = nullptr;           // stream_len when `mixed`, else 1 element
-    float *d_val = nullptr;
+    DevBuf<int> d_col32;              // stream_len when `mixed`, else 1 element
+    DevBuf<float> d_val;
     int64_t stream_len = 0;
     int max_dict = 0;
     int64_t capacity_cuts = 0;        // blocks that ended because the next row's columns no longer fit the dictionary capacity
@@ -43,8 +45,7 @@ int validate_csr_device(int M, int K, int64_t nnz, const int *d_rp, const int *d
 // smallest / largest column index of a device CSR matrix (lo > hi: no entries).  Returns non-zero on a HIP error.
 int column_range_device(int64_t nnz, const int *d_ci, int *lo, int *hi, std::string &err);
 // flag[k / 64] = 1 where the matrix has an entry in that 64-column segment (the only rows of B a call repacks); ceil(K / 64) + 4 bytes
-int column_touch_flags_device(int K, int64_t nnz, const int *d_ci, unsigned char **d_flag, int64_t *touched_segments, std::string &err);
-void free_device_plan(DevicePlan &d);
+int column_touch_flags_device(int K, int64_t nnz, const int *d_ci, DevBuf<unsigned char> &d_flag, int64_t *touched_segments, std::string &err);
 int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, const float *d_v, int lpr, int max_unique,
                             double min_reuse, DevicePlan &out, std::string &err, const unsigned char *d_cut = nullptr,
                             bool share_index_lists = false, int sets = 1);

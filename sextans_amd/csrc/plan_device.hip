@@ -316,16 +316,6 @@ __global__ __launch_bounds__(256) void share_compact(long long nslots, int RB, c
         }                                                                                                      \
     } while (0)
 
-struct Scratch {   // freed on every exit path
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
-    template <class T> hipError_t alloc(T **out, size_t n) {
-        hipError_t e = hipMalloc((void **)out, sizeof(T) * (n ? n : 1));
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-};
-
 }  // namespace
 
 namespace {
@@ -344,12 +334,11 @@ __global__ __launch_bounds__(256) void csr_validate(const int *__restrict__ rp, 
 
 int validate_csr_device(int M, int K, int64_t nnz, const int *d_rp, const int *d_ci, int *bad, std::string &err) {
     *bad = 0;
-    int *d_bad = nullptr;
-    PD_HIP(hipMalloc((void **)&d_bad, sizeof(int)));
+    DevBuf<int> d_bad;
+    PD_HIP(d_bad.alloc(1));
     hipError_t e1 = hipMemset(d_bad, 0, sizeof(int));
     hipLaunchKernelGGL(csr_validate, dim3(2048), dim3(256), 0, nullptr, d_rp, d_ci, M, K, (long long)nnz, d_bad);
     hipError_t e2 = hipMemcpy(bad, d_bad, sizeof(int), hipMemcpyDeviceToHost);
-    (void)hipFree(d_bad);
     PD_HIP(e1);
     PD_HIP(e2);
     return 0;
@@ -369,14 +358,13 @@ __global__ __launch_bounds__(256) void col_minmax(const int *__restrict__ ci, lo
 int column_range_device(int64_t nnz, const int *d_ci, int *lo, int *hi, std::string &err) {
     *lo = 0x7fffffff; *hi = -1;
     if (nnz <= 0) return 0;
-    int *d = nullptr;
-    PD_HIP(hipMalloc((void **)&d, 2 * sizeof(int)));
+    DevBuf<int> d;
+    PD_HIP(d.alloc(2));
     const int init[2] = {0x7fffffff, -1};
     hipError_t e1 = hipMemcpy(d, init, sizeof init, hipMemcpyHostToDevice);
     hipLaunchKernelGGL(col_minmax, dim3(2048), dim3(256), 0, nullptr, d_ci, (long long)nnz, d, d + 1);
     int out[2] = {0x7fffffff, -1};
     hipError_t e2 = hipMemcpy(out, d, sizeof out, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     PD_HIP(e1);
     PD_HIP(e2);
     *lo = out[0]; *hi = out[1];
@@ -391,27 +379,22 @@ __global__ __launch_bounds__(256) void col_touch(const int *__restrict__ ci, lon
 }  // namespace
 
 // flag[k / 64] = 1 where the matrix has an entry in columns [64 (k / 64), 64 (k / 64) + 64): the 64-row segments of B a call has to
-// repack.  ceil(K / 64) + 4 bytes on the device (the tail zero), caller frees.
-int column_touch_flags_device(int K, int64_t nnz, const int *d_ci, unsigned char **d_flag, int64_t *touched_segments, std::string &err) {
-    *d_flag = nullptr;
+// repack.  ceil(K / 64) + 4 bytes on the device (the tail zero).
+int column_touch_flags_device(int K, int64_t nnz, const int *d_ci, DevBuf<unsigned char> &d_flag, int64_t *touched_segments, std::string &err) {
+    d_flag.reset();
     if (touched_segments) *touched_segments = 0;
     const size_t n = (size_t)(K + 63) / 64 + 4;
-    unsigned char *f = nullptr;
-    PD_HIP(hipMalloc((void **)&f, n));
+    DevBuf<unsigned char> f;
+    PD_HIP(f.alloc(n));
     hipError_t e = hipMemsetAsync(f, 0, n, nullptr);
     if (nnz > 0) hipLaunchKernelGGL(col_touch, dim3(2048), dim3(256), 0, nullptr, d_ci, (long long)nnz, f);
     std::vector<unsigned char> host(n);
     hipError_t e2 = hipMemcpy(host.data(), f, n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess || e2 != hipSuccess) { (void)hipFree(f); PD_HIP(e); PD_HIP(e2); }
+    PD_HIP(e);
+    PD_HIP(e2);
     if (touched_segments) for (unsigned char x : host) *touched_segments += x;
-    *d_flag = f;
+    d_flag = std::move(f);
     return 0;
-}
-
-void free_device_plan(DevicePlan &d) {
-    (void)hipFree(d.d_blk_row); (void)hipFree(d.d_dict_cnt); (void)hipFree(d.d_dict); (void)hipFree(d.d_slot_info);
-    (void)hipFree(d.d_idx16); (void)hipFree(d.d_col32); (void)hipFree(d.d_val); (void)hipFree(d.d_ioff);
-    d = DevicePlan();
 }
 
 // 0 = built; 1 = not representable (padded stream exceeds 32-bit entry offsets): caller keeps the row-group kernel;
@@ -419,7 +402,7 @@ void free_device_plan(DevicePlan &d) {
 int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, const float *d_v, int lpr, int max_unique,
                             double min_reuse, DevicePlan &out, std::string &err, const unsigned char *d_cut, bool share_index_lists, int sets) {
     (void)K;
-    free_device_plan(out);
+    out = DevicePlan();
     if (sets < 1 || (sets > 1 && lpr != 4)) { err = "row sets per block: 4 lanes per row only"; return 2; }
     const int RB = 256 / lpr;           // row slots per set (= per workgroup pass)
     const int RBS = RB * sets;          // row slots per block
@@ -431,16 +414,15 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
     const unsigned row_bytes = 16u * (unsigned)lpr;
     const unsigned pad_off = (unsigned)max_unique * row_bytes;   // the +1.0f row sits right behind a full dictionary
     if (pad_off > 0xffffu) { err = "panel capacity does not fit 16-bit byte offsets"; return 2; }
-    Scratch tmp;
     if (M == 0) {
-        PD_HIP(hipMalloc((void **)&out.d_blk_row, sizeof(int)));
+        PD_HIP(out.d_blk_row.alloc(1));
         PD_HIP(hipMemset(out.d_blk_row, 0, sizeof(int)));
-        PD_HIP(hipMalloc((void **)&out.d_dict_cnt, sizeof(int)));
-        PD_HIP(hipMalloc((void **)&out.d_dict, sizeof(int)));
-        PD_HIP(hipMalloc((void **)&out.d_slot_info, sizeof(int)));
-        PD_HIP(hipMalloc((void **)&out.d_idx16, sizeof(unsigned short) * kPlanTailPad));
-        PD_HIP(hipMalloc((void **)&out.d_col32, sizeof(int)));
-        PD_HIP(hipMalloc((void **)&out.d_val, sizeof(float) * kPlanTailPad));
+        PD_HIP(out.d_dict_cnt.alloc(1));
+        PD_HIP(out.d_dict.alloc(1));
+        PD_HIP(out.d_slot_info.alloc(1));
+        PD_HIP(out.d_idx16.alloc(kPlanTailPad));
+        PD_HIP(out.d_col32.alloc(1));
+        PD_HIP(out.d_val.alloc(kPlanTailPad));
         PD_HIP(hipMemset(out.d_idx16, 0, sizeof(unsigned short) * kPlanTailPad));
         PD_HIP(hipMemset(out.d_val, 0, sizeof(float) * kPlanTailPad));
         out.h_blk_row.assign(1, 0);
@@ -449,11 +431,11 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
         return 0;
     }
     // ---- pass A
-    long long *d_part_sum = nullptr;
-    int *d_part_base = nullptr, *d_row_off = nullptr;
-    PD_HIP(tmp.alloc(&d_part_sum, (size_t)nparts));
-    PD_HIP(tmp.alloc(&d_part_base, (size_t)nparts));
-    PD_HIP(tmp.alloc(&d_row_off, (size_t)M + 1));
+    DevBuf<long long> d_part_sum;
+    DevBuf<int> d_part_base, d_row_off;
+    PD_HIP(d_part_sum.alloc((size_t)nparts));
+    PD_HIP(d_part_base.alloc((size_t)nparts));
+    PD_HIP(d_row_off.alloc((size_t)M + 1));
     hipLaunchKernelGGL(plan_part_sums, dim3((unsigned)nparts), dim3(256), 0, nullptr, d_rp, M, PR, d_part_sum);
     std::vector<long long> h_sum((size_t)nparts);
     PD_HIP(hipMemcpy(h_sum.data(), d_part_sum, sizeof(long long) * (size_t)nparts, hipMemcpyDeviceToHost));
@@ -464,13 +446,13 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
     PD_HIP(hipMemcpy(d_part_base, h_base.data(), sizeof(int) * (size_t)nparts, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(plan_row_off, dim3((unsigned)nparts), dim3(256), 0, nullptr, d_rp, M, PR, d_part_base, d_row_off);
     // ---- pass B
-    int *d_pb_row = nullptr, *d_pb_cnt = nullptr, *d_part_nblk = nullptr, *d_part_blk_base = nullptr;
-    PD_HIP(tmp.alloc(&d_pb_row, (size_t)nparts * (size_t)PR));
-    PD_HIP(tmp.alloc(&d_pb_cnt, (size_t)nparts * (size_t)PR));
-    PD_HIP(tmp.alloc(&d_part_nblk, (size_t)nparts));
-    PD_HIP(tmp.alloc(&d_part_blk_base, (size_t)nparts));
-    int *d_part_capcuts = nullptr;
-    PD_HIP(tmp.alloc(&d_part_capcuts, (size_t)nparts));
+    DevBuf<int> d_pb_row, d_pb_cnt, d_part_nblk, d_part_blk_base;
+    PD_HIP(d_pb_row.alloc((size_t)nparts * (size_t)PR));
+    PD_HIP(d_pb_cnt.alloc((size_t)nparts * (size_t)PR));
+    PD_HIP(d_part_nblk.alloc((size_t)nparts));
+    PD_HIP(d_part_blk_base.alloc((size_t)nparts));
+    DevBuf<int> d_part_capcuts;
+    PD_HIP(d_part_capcuts.alloc((size_t)nparts));
     hipLaunchKernelGGL(plan_blocks, dim3((unsigned)nparts), dim3(256), 0, nullptr, d_rp, d_ci, M, PR, RBS, max_unique, min_reuse,
                        d_pb_row, d_pb_cnt, d_part_nblk, d_cut, d_part_capcuts);
     std::vector<int> h_nblk((size_t)nparts), h_bbase((size_t)nparts), h_capcuts((size_t)nparts);
@@ -482,14 +464,14 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
     for (int p = 0; p < nparts; ++p) { h_bbase[(size_t)p] = (int)nblk; nblk += h_nblk[(size_t)p]; }
     PD_HIP(hipMemcpy(d_part_blk_base, h_bbase.data(), sizeof(int) * (size_t)nparts, hipMemcpyHostToDevice));
     out.nblk = (int)nblk;
-    int *d_stats = nullptr;
-    unsigned long long *d_cov = nullptr;
-    PD_HIP(tmp.alloc(&d_stats, 3));
-    PD_HIP(tmp.alloc(&d_cov, 2));
+    DevBuf<int> d_stats;
+    DevBuf<unsigned long long> d_cov;
+    PD_HIP(d_stats.alloc(3));
+    PD_HIP(d_cov.alloc(2));
     PD_HIP(hipMemset(d_stats, 0, 3 * sizeof(int)));
     PD_HIP(hipMemset(d_cov, 0, 2 * sizeof(unsigned long long)));
-    PD_HIP(hipMalloc((void **)&out.d_blk_row, sizeof(int) * ((size_t)nblk + 1)));
-    PD_HIP(hipMalloc((void **)&out.d_dict_cnt, sizeof(int) * (size_t)nblk));
+    PD_HIP(out.d_blk_row.alloc((size_t)nblk + 1));
+    PD_HIP(out.d_dict_cnt.alloc((size_t)nblk));
     hipLaunchKernelGGL(plan_compact, dim3((unsigned)nparts), dim3(256), 0, nullptr, d_rp, M, PR, d_pb_row, d_pb_cnt, d_part_nblk,
                        d_part_blk_base, (int)nblk, out.d_blk_row, out.d_dict_cnt, d_stats, d_cov);
     int h_stats[3] = {0, 0, 0};
@@ -509,11 +491,11 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
     out.dict_stride = dstride;
     const size_t stream = (size_t)total + kPlanTailPad;
     out.stream_len = (int64_t)stream;
-    PD_HIP(hipMalloc((void **)&out.d_dict, sizeof(int) * (size_t)nblk * (size_t)dstride));
-    PD_HIP(hipMalloc((void **)&out.d_slot_info, sizeof(int) * (size_t)nblk * (size_t)RBS * 2));
-    PD_HIP(hipMalloc((void **)&out.d_idx16, sizeof(unsigned short) * stream));
-    PD_HIP(hipMalloc((void **)&out.d_val, sizeof(float) * stream));
-    PD_HIP(hipMalloc((void **)&out.d_col32, sizeof(int) * (out.mixed ? stream : 1)));   // only direct blocks read it
+    PD_HIP(out.d_dict.alloc((size_t)nblk * (size_t)dstride));
+    PD_HIP(out.d_slot_info.alloc((size_t)nblk * (size_t)RBS * 2));
+    PD_HIP(out.d_idx16.alloc(stream));
+    PD_HIP(out.d_val.alloc(stream));
+    PD_HIP(out.d_col32.alloc(out.mixed ? stream : 1));   // only direct blocks read it
     PD_HIP(hipMemsetAsync(out.d_idx16, 0, sizeof(unsigned short) * stream, nullptr));
     PD_HIP(hipMemsetAsync(out.d_val, 0, sizeof(float) * stream, nullptr));
     if (out.mixed) PD_HIP(hipMemsetAsync(out.d_col32, 0, sizeof(int) * stream, nullptr));
@@ -530,37 +512,34 @@ int build_panel_plan_device(int M, int K, const int *d_rp, const int *d_ci, cons
     out.idx_len = out.stream_len;
     if (share_index_lists && !out.mixed && nblk > 0 && lpr == 4) {
         const long long nslots = (long long)nblk * RBS;
-        int *d_cand = nullptr, *d_step = nullptr, *d_root = nullptr, *d_shift = nullptr, *d_len = nullptr, *d_noff = nullptr;
-        PD_HIP(tmp.alloc(&d_cand, (size_t)nslots));
-        PD_HIP(tmp.alloc(&d_step, (size_t)nslots));
-        PD_HIP(tmp.alloc(&d_root, (size_t)nslots));
-        PD_HIP(tmp.alloc(&d_shift, (size_t)nslots));
-        PD_HIP(tmp.alloc(&d_len, (size_t)nslots + 1));
-        PD_HIP(tmp.alloc(&d_noff, (size_t)nslots + 1));
+        DevBuf<int> d_cand, d_step, d_root, d_shift, d_len, d_noff;
+        PD_HIP(d_cand.alloc((size_t)nslots));
+        PD_HIP(d_step.alloc((size_t)nslots));
+        PD_HIP(d_root.alloc((size_t)nslots));
+        PD_HIP(d_shift.alloc((size_t)nslots));
+        PD_HIP(d_len.alloc((size_t)nslots + 1));
+        PD_HIP(d_noff.alloc((size_t)nslots + 1));
         PD_HIP(hipMemsetAsync(d_len + nslots, 0, sizeof(int), nullptr));
         hipLaunchKernelGGL(share_detect, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, nullptr, nslots, RBS, pad_off, row_bytes,
-                           (const int2 *)out.d_slot_info, out.d_idx16, d_cand, d_step);
+                           (const int2 *)out.d_slot_info.get(), out.d_idx16, d_cand, d_step);
         hipLaunchKernelGGL(share_chain, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, nullptr, (int)nblk, RBS,
-                           (int)((kPlanPadRows - 1) * row_bytes), (const int2 *)out.d_slot_info, d_cand, d_step, d_root, d_shift, d_len);
-        void *scan_tmp = nullptr;
+                           (int)((kPlanPadRows - 1) * row_bytes), (const int2 *)out.d_slot_info.get(), d_cand, d_step, d_root, d_shift, d_len);
+        DevBuf<char> scan_tmp;
         size_t bytes = 0;
-        PD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_len, d_noff, (int)(nslots + 1), nullptr));
-        PD_HIP(tmp.alloc((char **)&scan_tmp, bytes));
-        PD_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, bytes, d_len, d_noff, (int)(nslots + 1), nullptr));
+        PD_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, d_len.get(), d_noff.get(), (int)(nslots + 1), nullptr));
+        PD_HIP(scan_tmp.alloc(bytes));
+        PD_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp.get(), bytes, d_len.get(), d_noff.get(), (int)(nslots + 1), nullptr));
         int kept = 0;
         PD_HIP(hipMemcpy(&kept, d_noff + nslots, sizeof(int), hipMemcpyDeviceToHost));
         if ((long long)kept * 10 <= (long long)total * 9) {   // at least a tenth of the index stream goes: worth one more table
-            unsigned short *nidx = nullptr;
-            PD_HIP(hipMalloc((void **)&nidx, sizeof(unsigned short) * ((size_t)kept + kPlanTailPad)));
-            hipError_t e = hipMalloc((void **)&out.d_ioff, sizeof(int2) * (size_t)nslots);
-            if (e != hipSuccess) { (void)hipFree(nidx); PD_HIP(e); }
+            DevBuf<unsigned short> nidx;
+            PD_HIP(nidx.alloc((size_t)kept + kPlanTailPad));
+            PD_HIP(out.d_ioff.alloc(2 * (size_t)nslots));
             PD_HIP(hipMemsetAsync(nidx, 0, sizeof(unsigned short) * ((size_t)kept + kPlanTailPad), nullptr));
-            hipLaunchKernelGGL(share_compact, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, nullptr, nslots, RBS, (const int2 *)out.d_slot_info,
-                               d_root, d_shift, d_noff, out.d_idx16, nidx, (int2 *)out.d_ioff);
-            e = hipDeviceSynchronize();
-            if (e != hipSuccess) { (void)hipFree(nidx); PD_HIP(e); }
-            (void)hipFree(out.d_idx16);
-            out.d_idx16 = nidx;
+            hipLaunchKernelGGL(share_compact, dim3((unsigned)((nslots + 3) / 4)), dim3(256), 0, nullptr, nslots, RBS, (const int2 *)out.d_slot_info.get(),
+                               d_root, d_shift, d_noff, out.d_idx16, nidx, (int2 *)out.d_ioff.get());
+            PD_HIP(hipDeviceSynchronize());
+            out.d_idx16 = std::move(nidx);
             out.idx_len = (int64_t)kept + kPlanTailPad;
         }
     }

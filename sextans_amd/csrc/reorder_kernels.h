@@ -10,7 +10,7 @@
 //     streaming transposes (no permutation; first version: staging in block order, both passes scattering 64-byte rows --
 //     4.2-4.4 TB/s against 6.3 TB/s for the streaming form).
 // The reference lays B and C out for its kernel on the host, outside the timed call (sextans-host.cpp:150-195, 264-270); here the
-// passes are inside the timed step.  Included by engine.hip only.
+// passes are inside the timed step.  Included by engine_launch.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -142,79 +142,75 @@ bool detect_grid_strides(int M, const std::vector<int> &rows, const std::vector<
     return true;
 }
 
-int build_brick_order_device(int M, GridStrides s, int run_rows, int b2, int b3, int super_group, int **d_perm, unsigned char **d_cut,
+int build_brick_order_device(int M, GridStrides s, int run_rows, int b2, int b3, int super_group, DevBuf<int> &d_perm, DevBuf<unsigned char> &d_cut,
                              std::string &err) {
     if (super_group < 1) super_group = 1;
-    *d_perm = nullptr;
-    *d_cut = nullptr;
+    d_perm.reset();
+    d_cut.reset();
     if (M <= 0 || run_rows < 1 || (long long)run_rows * b2 * b3 > 4096) { err = "brick too large"; return 2; }
     const long long nr = (s.s2 + run_rows - 1) / run_rows;                       // runs (bricks) along a grid line
     const long long lines = s.s3 > 0 ? (s.s3 + s.s2 - 1) / s.s2 : ((long long)M + s.s2 - 1) / s.s2;
     const long long n2 = (lines + b2 - 1) / b2;
-    unsigned long long *k_in = nullptr, *k_out = nullptr;
-    int *v_in = nullptr, *v_out = nullptr;
-    unsigned char *cut = nullptr;
-    void *tmp = nullptr;
+    DevBuf<unsigned long long> k_in, k_out;
+    DevBuf<int> v_in, v_out;
+    DevBuf<unsigned char> cut;
+    DevBuf<char> tmp;
     size_t bytes = 0;
-    auto cleanup = [&]() { (void)hipFree(k_in); (void)hipFree(k_out); (void)hipFree(v_in); (void)hipFree(tmp); };
-    hipError_t e = hipMalloc((void **)&k_in, sizeof(unsigned long long) * (size_t)M);
-    if (e == hipSuccess) e = hipMalloc((void **)&k_out, sizeof(unsigned long long) * (size_t)M);
-    if (e == hipSuccess) e = hipMalloc((void **)&v_in, sizeof(int) * (size_t)M);
-    if (e == hipSuccess) e = hipMalloc((void **)&v_out, sizeof(int) * (size_t)M);
-    if (e == hipSuccess) e = hipMalloc((void **)&cut, (size_t)M);
-    if (e != hipSuccess) { cleanup(); (void)hipFree(v_out); (void)hipFree(cut); err = hipGetErrorString(e); return 2; }
+    hipError_t e = k_in.alloc((size_t)M);
+    if (e == hipSuccess) e = k_out.alloc((size_t)M);
+    if (e == hipSuccess) e = v_in.alloc((size_t)M);
+    if (e == hipSuccess) e = v_out.alloc((size_t)M);
+    if (e == hipSuccess) e = cut.alloc((size_t)M);
+    if (e != hipSuccess) { err = hipGetErrorString(e); return 2; }
     hipLaunchKernelGGL(brick_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, nullptr, M, s.s2, s.s3, b2, b3, nr, n2, run_rows, super_group, k_in, v_in);
-    e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k_in, k_out, v_in, v_out, M, 0, 64, nullptr);
-    if (e == hipSuccess) e = hipMalloc(&tmp, bytes);
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp, bytes, k_in, k_out, v_in, v_out, M, 0, 64, nullptr);
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k_in.get(), k_out.get(), v_in.get(), v_out.get(), M, 0, 64, nullptr);
+    if (e == hipSuccess) e = tmp.alloc(bytes);
+    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(tmp.get(), bytes, k_in.get(), k_out.get(), v_in.get(), v_out.get(), M, 0, 64, nullptr);
     if (e == hipSuccess) hipLaunchKernelGGL(brick_cuts, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, nullptr, M, k_out, cut);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    cleanup();
-    if (e != hipSuccess) { (void)hipFree(v_out); (void)hipFree(cut); err = hipGetErrorString(e); return 2; }
-    *d_perm = v_out;
-    *d_cut = cut;
+    if (e != hipSuccess) { err = hipGetErrorString(e); return 2; }
+    d_perm = std::move(v_out);
+    d_cut = std::move(cut);
     return 0;
 }
 
-int permute_csr_rows_device(int M, int64_t nnz, const int *d_rp, const int *d_ci, const float *d_v, const int *d_perm, int **o_rp,
-                            int **o_ci, float **o_v, std::string &err) {
-    *o_rp = nullptr; *o_ci = nullptr; *o_v = nullptr;
-    long long *len = nullptr, *off = nullptr;
-    void *tmp = nullptr;
+int permute_csr_rows_device(int M, int64_t nnz, const int *d_rp, const int *d_ci, const float *d_v, const int *d_perm, DevBuf<int> &o_rp,
+                            DevBuf<int> &o_ci, DevBuf<float> &o_v, std::string &err) {
+    o_rp.reset(); o_ci.reset(); o_v.reset();
+    DevBuf<long long> len, off;
+    DevBuf<char> tmp;
     size_t bytes = 0;
-    int *nrp = nullptr, *nci = nullptr;
-    float *nva = nullptr;
-    auto fail = [&](hipError_t e) { (void)hipFree(len); (void)hipFree(off); (void)hipFree(tmp); (void)hipFree(nrp); (void)hipFree(nci); (void)hipFree(nva);
-                                    err = hipGetErrorString(e); return 2; };
-    hipError_t e = hipMalloc((void **)&len, sizeof(long long) * ((size_t)M + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&off, sizeof(long long) * ((size_t)M + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&nrp, sizeof(int) * ((size_t)M + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&nci, sizeof(int) * (size_t)std::max<int64_t>(nnz, 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&nva, sizeof(float) * (size_t)std::max<int64_t>(nnz, 1));
+    DevBuf<int> nrp, nci;
+    DevBuf<float> nva;
+    auto fail = [&](hipError_t e) { err = hipGetErrorString(e); return 2; };
+    hipError_t e = len.alloc((size_t)M + 1);
+    if (e == hipSuccess) e = off.alloc((size_t)M + 1);
+    if (e == hipSuccess) e = nrp.alloc((size_t)M + 1);
+    if (e == hipSuccess) e = nci.alloc((size_t)std::max<int64_t>(nnz, 1));
+    if (e == hipSuccess) e = nva.alloc((size_t)std::max<int64_t>(nnz, 1));
     if (e != hipSuccess) return fail(e);
     hipLaunchKernelGGL(perm_lengths, dim3((unsigned)((M + 256) / 256)), dim3(256), 0, nullptr, M, d_rp, d_perm, len);
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, len, off, M + 1, nullptr);
-    if (e == hipSuccess) e = hipMalloc(&tmp, bytes);
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, bytes, len, off, M + 1, nullptr);
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, len.get(), off.get(), M + 1, nullptr);
+    if (e == hipSuccess) e = tmp.alloc(bytes);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp.get(), bytes, len.get(), off.get(), M + 1, nullptr);
     if (e != hipSuccess) return fail(e);
     hipLaunchKernelGGL(perm_row_ptr, dim3((unsigned)((M + 256) / 256)), dim3(256), 0, nullptr, M, off, nrp);
     hipLaunchKernelGGL(perm_gather, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, nullptr, M, d_rp, d_ci, d_v, d_perm, nrp, nci, nva);
     e = hipDeviceSynchronize();
     if (e != hipSuccess) return fail(e);
-    (void)hipFree(len); (void)hipFree(off); (void)hipFree(tmp);
-    *o_rp = nrp; *o_ci = nci; *o_v = nva;
+    o_rp = std::move(nrp); o_ci = std::move(nci); o_v = std::move(nva);
     return 0;
 }
 
-int build_slot_rows_device(int nblk, int RB, const int *d_blk_row, const int *d_perm, int **d_slot_row, std::string &err) {
-    *d_slot_row = nullptr;
-    int *out = nullptr;
-    RC_HIP(hipMalloc((void **)&out, sizeof(int) * (size_t)std::max(1, nblk) * (size_t)RB));
+int build_slot_rows_device(int nblk, int RB, const int *d_blk_row, const int *d_perm, DevBuf<int> &d_slot_row, std::string &err) {
+    d_slot_row.reset();
+    DevBuf<int> out;
+    RC_HIP(out.alloc((size_t)std::max(1, nblk) * (size_t)RB));
     if (nblk > 0)
         hipLaunchKernelGGL(slot_rows, dim3((unsigned)(((long long)nblk * RB + 255) / 256)), dim3(256), 0, nullptr, nblk, RB, d_blk_row, d_perm, out);
     hipError_t e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(out); err = hipGetErrorString(e); return 2; }
-    *d_slot_row = out;
+    if (e != hipSuccess) { err = hipGetErrorString(e); return 2; }
+    d_slot_row = std::move(out);
     return 0;
 }
 

@@ -781,10 +781,10 @@ int sextans_csr_permute_symmetric_device(int device, int M, int64_t nnz, const i
     if (hipMalloc((void **)&d_order, sizeof(int) * (size_t)(M ? M : 1)) != hipSuccess || hipMalloc((void **)&d_new, sizeof(int) * (size_t)(M ? M : 1)) != hipSuccess) { drop(); return SEXTANS_ERR_HIP; }
     if (M && (hipMemcpy(d_order, old_of_new.data(), sizeof(int) * (size_t)M, hipMemcpyHostToDevice) != hipSuccess ||
               hipMemcpy(d_new, new_of_old, sizeof(int) * (size_t)M, hipMemcpyHostToDevice) != hipSuccess)) { drop(); return SEXTANS_ERR_HIP; }
-    int *nrp = nullptr, *nci = nullptr;
-    float *nva = nullptr;
-    auto fail = [&](int rc) { drop(); (void)hipFree(nrp); (void)hipFree(nci); (void)hipFree(nva); return rc; };
-    if (sx::permute_csr_rows_device(M, nnz, d_row_ptr, d_col_idx, d_val, d_order, &nrp, &nci, &nva, err)) return fail(SEXTANS_ERR_HIP);
+    sx::DevBuf<int> nrp, nci;   // (the builder's arrays; the caller gets raw copies below, to be released with sextans_device_free)
+    sx::DevBuf<float> nva;
+    auto fail = [&](int rc) { drop(); return rc; };
+    if (sx::permute_csr_rows_device(M, nnz, d_row_ptr, d_col_idx, d_val, d_order, nrp, nci, nva, err)) return fail(SEXTANS_ERR_HIP);
     if (sx::relabel_columns_device(nnz, nci, d_new, err)) return fail(SEXTANS_ERR_HIP);
     if (hipMemcpy(rp.data(), nrp, sizeof(int) * ((size_t)M + 1), hipMemcpyDeviceToHost) != hipSuccess) return fail(SEXTANS_ERR_HIP);
     std::vector<int> long_rows;
@@ -793,15 +793,23 @@ int sextans_csr_permute_symmetric_device(int device, int M, int64_t nnz, const i
         if (n > 4096) return fail(SEXTANS_ERR_INVALID);      // (this tool sorts rows of up to 4096 entries)
         if (n > 256) long_rows.push_back(r);
     }
-    if (M) hipLaunchKernelGGL(k_sort_rows_wave, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, 0, M, nrp, nci, nva);
+    if (M) hipLaunchKernelGGL(k_sort_rows_wave, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, 0, M, nrp.get(), nci.get(), nva.get());
     if (!long_rows.empty()) {
         if (hipMalloc((void **)&d_long, sizeof(int) * long_rows.size()) != hipSuccess ||
             hipMemcpy(d_long, long_rows.data(), sizeof(int) * long_rows.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(SEXTANS_ERR_HIP);
-        hipLaunchKernelGGL(k_sort_rows_wg, dim3((unsigned)long_rows.size()), dim3(256), 0, 0, d_long, nrp, nci, nva);
+        hipLaunchKernelGGL(k_sort_rows_wg, dim3((unsigned)long_rows.size()), dim3(256), 0, 0, d_long, nrp.get(), nci.get(), nva.get());
     }
     if (hipDeviceSynchronize() != hipSuccess) return fail(SEXTANS_ERR_HIP);
+    int *orp = nullptr, *oci = nullptr;
+    float *ova = nullptr;
+    if (hipMalloc((void **)&orp, nrp.bytes()) != hipSuccess || hipMalloc((void **)&oci, nci.bytes()) != hipSuccess || hipMalloc((void **)&ova, nva.bytes()) != hipSuccess ||
+        hipMemcpy(orp, nrp, nrp.bytes(), hipMemcpyDeviceToDevice) != hipSuccess || hipMemcpy(oci, nci, nci.bytes(), hipMemcpyDeviceToDevice) != hipSuccess ||
+        hipMemcpy(ova, nva, nva.bytes(), hipMemcpyDeviceToDevice) != hipSuccess) {
+        (void)hipFree(orp); (void)hipFree(oci); (void)hipFree(ova);
+        return fail(SEXTANS_ERR_HIP);
+    }
     drop();
-    *o_row_ptr = nrp; *o_col_idx = nci; *o_val = nva;
+    *o_row_ptr = orp; *o_col_idx = oci; *o_val = ova;
     return SEXTANS_OK;
 }
 
