@@ -189,23 +189,20 @@ int mark_rowblock_skip(sextans_engine *h) {
     return SEXTANS_OK;
 }
 
-// The routed blocks of [row_begin, row_end) over the B panels the main path has just laid out (`plan` = the segments of d_Bp).
-int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, int N, int row_begin,
-                     int row_end, float alpha, float beta, hipStream_t s) {
+// The routed blocks of [o.row_base, row_end) over the B panels the main path has just laid out (o.B; `plan` = their segments).
+int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const Operands &o, int N, int row_end) {
     for (const Seg &g : plan) {
         const int ncols_panel = g.ntiles * g.width;
-        const int ncols = std::min(N - g.col0, g.last_cols ? (g.ntiles - 1) * g.width + g.last_cols : ncols_panel);
+        const int ncols = std::min(N - g.col0, g.cols());
         const int tiles16 = (ncols + 15) / 16;
         if (tiles16 <= 0) continue;
-        const float *bp = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-        const float *cin = d_C_in + (int64_t)g.col0 * ldc_in;
-        float *cout = d_C_out + (int64_t)g.col0 * ldc;
+        const Operands og = o.at(g.col0);
         auto go = [&](auto T) {
             constexpr int NT = decltype(T)::value;
             const int tgs = (tiles16 + NT - 1) / NT;
-            hipLaunchKernelGGL(sx::spmm_rowblock_mfma_f32<NT>, dim3((unsigned)((h->dense.sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, s, h->dense.d_rb_row0, h->dense.d_rb_gptr, h->dense.d_sb_uptr,
-                               (const int2 *)h->dense.d_sb_ucol.get(), h->dense.d_rb_A, bp, (int64_t)h->K * g.width, g.width, h->K, cin, ldc_in, cout, ldc, h->dense.rb_n, h->dense.sb_n,
-                               tgs, ncols_panel, ncols, row_begin, row_end, alpha, beta);
+            hipLaunchKernelGGL(sx::spmm_rowblock_mfma_f32<NT>, dim3((unsigned)((h->dense.sb_n + 3) / 4) * (unsigned)tgs), dim3(256), 0, o.s, h->dense.d_rb_row0, h->dense.d_rb_gptr, h->dense.d_sb_uptr,
+                               (const int2 *)h->dense.d_sb_ucol.get(), h->dense.d_rb_A, og.B, (int64_t)h->K * g.width, g.width, h->K, og.C_in, o.ldc_in, og.C_out, o.ldc, h->dense.rb_n, h->dense.sb_n,
+                               tgs, ncols_panel, ncols, o.row_base, row_end, o.alpha, o.beta);
         };
         // (a wavefront owns 64 rows x 16 NT columns of C: 16 NT accumulator registers.  NT = 2 = 4 wavefronts per SIMD measured 2 - 4 % ahead of
         // NT = 4 = 2 per SIMD on the dense-block matrix at N = 64 .. 256 -- occupancy over B-fragment reuse; "rowblock_tiles" forces 1 / 4)
@@ -385,11 +382,11 @@ static void launch_bell_mfma(const int *col, const sx::bf16x8 *Af, const sx::bf1
     });
 }
 
-int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
-                       int64_t ldc_in, float *d_C_out, int64_t ldc, hipStream_t s) {
+int launch_dense_tiles(sextans_engine *h, int N, const Operands &o) {
+        hipStream_t s = o.s;
         const int kblocks = (h->K + 31) / 32, ntiles = N / 32;
         const int64_t threads = (int64_t)kblocks * ntiles * 128;
-        hipLaunchKernelGGL(sx::bell_repack_b_f32, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_B, ldb, h->K,
+        hipLaunchKernelGGL(sx::bell_repack_b_f32, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, o.B, o.ldb, h->K,
                            (sx::u32x4 *)h->d_bell_Bf.get(), kblocks, ntiles);
         const auto *Af = (const sx::bf16x8 *)h->dense.d_dense_Af.get();
         const auto *Bf = (const sx::bf16x8 *)h->d_bell_Bf.get();
@@ -400,16 +397,16 @@ int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, 
                                    (size_t)sx::kShMaxRowCols * sizeof(int);
             if (int rc = allow_big_lds(h, reinterpret_cast<const void *>(sx::spmm_bell_mfma_shared), (int)lds)) return rc;
             hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((h->dense.mb + sx::kShRows - 1) / sx::kShRows)),
-                               dim3(sx::kShThreads), lds, s, h->dense.d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense.mb, h->dense.W,
-                               alpha, beta, 0);
+                               dim3(sx::kShThreads), lds, s, h->dense.d_dense_col, Af, Bf, o.C_in, o.ldc_in, o.C_out, o.ldc, h->dense.mb, h->dense.W,
+                               o.alpha, o.beta, 0);
         } else {
-            launch_bell_mfma(h->dense.d_dense_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, h->dense.mb, h->dense.W, ntiles, alpha, beta, s);
+            launch_bell_mfma(h->dense.d_dense_col, Af, Bf, o.C_in, o.ldc_in, o.C_out, o.ldc, h->dense.mb, h->dense.W, ntiles, o.alpha, o.beta, s);
         }
         const int row0 = h->dense.mb * 32;
         if (row0 < h->M) {
             const int64_t tot = (int64_t)(h->M - row0) * N;
-            hipLaunchKernelGGL(sx::scale_tail_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, d_C_in, ldc_in,
-                               d_C_out, ldc, row0, h->M, N, alpha, beta);
+            hipLaunchKernelGGL(sx::scale_tail_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, o.C_in, o.ldc_in,
+                               o.C_out, o.ldc, row0, h->M, N, o.alpha, o.beta);
         }
     return SEXTANS_OK;
 }

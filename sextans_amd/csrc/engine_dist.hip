@@ -56,8 +56,13 @@ static int cc_chunk(sextans_engine *h, int N, float alpha, float beta, int b0, i
     if (p1 <= p0) return SEXTANS_OK;
     Prof p(h, &h->ev_kernel, s);
     launch_slab_rows(false, h->d_Cs, (int64_t)h->M * 16, d_rows + p0, row0, p1 - p0, slab, lmax * 16, N / 16, s);
-    float *base = slab - (int64_t)p0 * 16;     // position p of the clustered order -> slab row p - p0
-    if (int rc = launch_panel_v2(h, 1, h->d_Bp, base, lmax * 16, base, lmax * 16, N / 16, alpha, beta, s, 0, b0, b1, 0, 3)) return rc;
+    Operands o = on_panels(h, Operands{});
+    o.C_in = o.C_out = slab - (int64_t)p0 * 16;     // position p of the clustered order -> slab row p - p0
+    o.ldc_in = o.ldc = lmax * 16;
+    o.alpha = alpha; o.beta = beta; o.s = s;
+    PanelV2 a;
+    a.order = V2Order::kPositions; a.blk_begin = b0; a.blk_end = b1;
+    if (int rc = launch_panel_v2(h, o, N / 16, a)) return rc;
     h->last_kernel = "spmm_csr_panel_v2_reordered";
     return SEXTANS_OK;
 }

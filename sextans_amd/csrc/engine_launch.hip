@@ -94,35 +94,31 @@ void launch_tiles_to_colmajor(const float *tiles, float *C, int64_t ldc, int M, 
     hipLaunchKernelGGL(sx::tiles_to_colmajor, dim3((unsigned)((M + sx::kBlock - 1) / sx::kBlock), (unsigned)ntiles), dim3(sx::kBlock), 0, s, tiles, C, ldc, M, col0, ncols);
 }
 
-void launch_rowgroup(sextans_engine *h, int width, const int *rp, const int *rend, const int *ci, const float *va, bool pieces,
-                     const unsigned char *skip, const float *dBp, const float *dCin, int64_t ldc_in, float *dCout, int64_t ldc, int row_begin,
-                     int row_end, int ntiles, float alpha, float beta, hipStream_t s, int64_t rm_ldb, bool round_robin, const int *groups, int ngroups) {
-    // The LDS-staged A stream walks a block's non-zeros in order, which serialises row groups when rows
-    // are long pieces of one hub row (split mode): there every row group streams its own piece directly.
-    const bool stage = h->opt_stage && !pieces;
-    const int xcd = round_robin ? 0 : (int)h->opt_xcd;
+// What a kernel is told about B: floats between its panels of NT columns (kPanels), or the caller's leading dimension; the layout
+// itself becomes the kernel's RM / BCOL template argument at the launch
+static int64_t b_stride(const sextans_engine *h, const Operands &o, int NT) { return o.layout == BLayout::kPanels ? (int64_t)h->K * NT : o.ldb; }
+
+void launch_rowgroup(sextans_engine *h, int width, const Operands &o, int ntiles, int row_end, const unsigned char *skip, const int *groups, int ngroups) {
     by_width(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR, CH = 2048;
-        const int nrowblk = groups ? ngroups * std::max(1, 128 / RB) : (row_end - row_begin + RB - 1) / RB;
+        const int nrowblk = groups ? ngroups * std::max(1, 128 / RB) : (row_end - o.row_base + RB - 1) / RB;
         if (nrowblk <= 0) return;
         const unsigned nwg = (unsigned)nrowblk * (unsigned)ntiles;
-        const int64_t pstride = rm_ldb > 0 ? rm_ldb : (int64_t)h->K * 4 * LPR;
-        with_bool(h->opt_exact, [&](auto EX) { with_bool(stage, [&](auto ST) { with_bool(rm_ldb > 0, [&](auto RM) {
+        with_bool(h->opt_exact, [&](auto EX) { with_bool(h->opt_stage, [&](auto ST) { with_bool(o.layout == BLayout::kRowMajor, [&](auto RM) {
             hipLaunchKernelGGL((sx::spmm_csr_rowgroup<LPR, CH, decltype(EX)::value, decltype(ST)::value, decltype(RM)::value>), dim3(nwg), dim3(sx::kBlock), 0,
-                               s, rp, rend, ci, va, dBp, pstride, dCin, ldc_in, dCout, ldc, row_begin, row_end, ntiles, nrowblk, alpha, beta, xcd, skip, groups);
+                               o.s, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, o.B, b_stride(h, o, 4 * LPR), o.C_in, o.ldc_in, o.C_out, o.ldc, o.row_base, row_end, ntiles, nrowblk,
+                               o.alpha, o.beta, (int)h->opt_xcd, skip, groups);
         }); }); });
     });
 }
 
-int launch_panel(sextans_engine *h, int width, const float *dBp, const float *dCin, int64_t ldc_in, float *dCout, int64_t ldc, int ntiles,
-                 float alpha, float beta, hipStream_t s, int64_t bcol_ld, int blk_begin, int blk_end, int row_base) {
+int launch_panel(sextans_engine *h, int width, const Operands &o, int ntiles, int blk_begin, int blk_end) {
     const int nblk = blk_end - blk_begin;
     if (nblk <= 0) return SEXTANS_OK;
     if (int rc = restore_plan_streams(h)) return rc;   // (released while a clustered plan served the whole-matrix calls)
     by_width(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR, NT = 4 * LPR;
         const unsigned nwg = (unsigned)nblk * (unsigned)ntiles;
-        const int64_t pstride = bcol_ld > 0 ? bcol_ld : (int64_t)h->K * NT;
         const int xcd = (int)h->opt_xcd;
         // LDS = B panel sized for the largest dictionary of this matrix (rounded to 1 KiB) + C tile.
         const int pad_rows = h->ps.d_ioff ? sx::kWidePadRows : 1;   // (shared index lists may be shifted: their padding entries reach further)
@@ -130,15 +126,15 @@ int launch_panel(sextans_engine *h, int width, const float *dBp, const float *dC
         const int tile_floats = NT * (RB + 1);   // the C tile reuses the panel bytes
         const size_t lds = (size_t)(panel_floats > tile_floats ? panel_floats : tile_floats) * sizeof(int);
         auto go = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(nwg), dim3(sx::kBlock), lds, s, (const int2 *)h->ps.d_row_off.get(), h->ps.d_lidx,
-                               h->ps.d_pcol32, h->ps.d_pval, h->ps.d_blk_row, h->ps.d_dict_ptr, h->ps.d_dict, h->ps.plan_dict_stride, dBp,
-                               pstride, dCin, ldc_in, dCout, ldc, ntiles, nblk, alpha, beta, xcd, panel_floats,
-                               (long long *)h->d_dbg.get(), blk_begin, row_base, (const unsigned char *)h->split.d_skip.get(), (const int2 *)h->ps.d_ioff.get(), pad_rows);
+            hipLaunchKernelGGL(kern, dim3(nwg), dim3(sx::kBlock), lds, o.s, (const int2 *)h->ps.d_row_off.get(), h->ps.d_lidx,
+                               h->ps.d_pcol32, h->ps.d_pval, h->ps.d_blk_row, h->ps.d_dict_ptr, h->ps.d_dict, h->ps.plan_dict_stride, o.B,
+                               b_stride(h, o, NT), o.C_in, o.ldc_in, o.C_out, o.ldc, ntiles, nblk, o.alpha, o.beta, xcd, panel_floats,
+                               (long long *)h->d_dbg.get(), blk_begin, o.row_base, (const unsigned char *)h->split.d_skip.get(), (const int2 *)h->ps.d_ioff.get(), pad_rows);
         };
         with_bool(h->opt_exact, [&](auto EX) {
             constexpr bool E = decltype(EX)::value;
             if (h->ps.plan_mixed) go(sx::spmm_csr_panel<LPR, E, true>);
-            else if (bcol_ld > 0) go(sx::spmm_csr_panel<LPR, E, false, true>);
+            else if (o.layout == BLayout::kColMajor) go(sx::spmm_csr_panel<LPR, E, false, true>);
             else go(sx::spmm_csr_panel<LPR, E, false>);
         });
     });
@@ -166,12 +162,17 @@ struct V2Launch {   // everything decided for one launch
     V2Variant v;
 };
 
-V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_in, int64_t ldc, int64_t bcol_ld, int nblk, int mode, int64_t rm_ldb) {
+// the plan a launch walks
+const sextans_engine::PanelState &v2_plan(const sextans_engine *h, V2Order order) { return order == V2Order::kNatural ? h->ps : h->cluster.psc; }
+
+V2Launch plan_panel_v2(const sextans_engine *h, const Operands &o, int nsuper, int nblk, const PanelV2 &a) {
     V2Launch d{};
-    const sextans_engine::PanelState &P = mode ? h->cluster.psc : h->ps;
-    d.slot_row = (mode == 1 || mode == 2) ? h->cluster.d_slot_row : nullptr;
-    d.skip = mode == 3 ? nullptr : (const unsigned char *)h->split.d_skip.get();   // rows on the piece path: never written by this kernel (mode 2: their staging rows keep C_in)
-    const bool crow = mode == 2 || mode == 3;
+    const int H = a.H;
+    const bool bcol = o.layout == BLayout::kColMajor, rm = o.layout == BLayout::kRowMajor;   // the kernel's BCOL and RM != 0
+    const sextans_engine::PanelState &P = v2_plan(h, a.order);
+    d.slot_row = (a.order == V2Order::kBricks || a.order == V2Order::kReordered) ? h->cluster.d_slot_row : nullptr;
+    d.skip = a.order == V2Order::kPositions ? nullptr : (const unsigned char *)h->split.d_skip.get();   // rows on the piece path: never written by this kernel (kReordered: their staging rows keep C_in)
+    const bool crow = a.order == V2Order::kReordered || a.order == V2Order::kPositions;
     // register-resident batches (16 entries each) per row: from the mean row length of the main matrix, so that matrices
     // with short rows (1-dof stencils: 27 entries) do not fetch six batches per row
     const int64_t mean_len = h->M > 0 ? h->m_nnz / h->M : 0;
@@ -184,11 +185,11 @@ V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_i
         else if (nb == 2 && nb_max == 3) nb = 3;
     }
     d.nb = nb;
-    const bool big = H == 1 && bcol_ld > 0 && nb > 2;   // column-major staging + long rows: the 256-register form (2 workgroups per CU)
+    const bool big = H == 1 && bcol && nb > 2;   // column-major staging + long rows: the 256-register form (2 workgroups per CU)
     int tpw = (int)h->opt_tiles_per_wg;
     if (tpw <= 0 && big) {   // ... in ONE round of workgroups
         tpw = std::min<int>(nsuper, std::max<int>(1, (int)(((int64_t)nblk * nsuper + 2 * h->num_cus - 1) / ((int64_t)2 * h->num_cus))));
-    } else if (tpw <= 0 && rm_ldb > 0 && P.plan_sets == 2 && nsuper >= 4) {
+    } else if (tpw <= 0 && rm && P.plan_sets == 2 && nsuper >= 4) {
         // row-major operands, two row sets per block (short-row 3-D grids), N >= 64: one tile per workgroup.  The workgroups of a block's
         // tiles are neighbours in the launch order, so the 64-byte halves of the B lines their panels are made of are asked for together,
         // and the panel copy is most of what such a block moves (3.4 dictionary rows per matrix row and tile against 26 entries once).
@@ -202,13 +203,12 @@ V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_i
     }
     d.tpw = std::min(tpw, nsuper);
     d.ngrp = (nsuper + d.tpw - 1) / d.tpw;
-    const bool rm = rm_ldb > 0;
-    d.pstride = rm ? rm_ldb : bcol_ld > 0 ? bcol_ld : (int64_t)h->K * 16;
+    d.pstride = b_stride(h, o, 16);
     d.dict = (rm && crow && h->cluster.d_dict_nat) ? h->cluster.d_dict_nat : P.d_dict;
     // LDS = the panel: plan capacity + the +1.0f row.  A clustered plan of a short-row matrix is packed for a 320-row panel
     // (engine_plan.hip: small_panel): 20.5 KB instead of 36.9 KB per workgroup, so the CU holds as many workgroups as the registers
     // allow (5 at <= 96 registers) instead of the 4 the full panel permits -- these launches are latency-bound
-    const bool small_panel = H == 1 && bcol_ld == 0 && P.plan_pad_row == 5 * 64;
+    const bool small_panel = H == 1 && !bcol && P.plan_pad_row == 5 * 64;
     d.lds = small_panel ? (size_t)(5 * 64 + sx::kWidePadRows) * 64 : (size_t)H * sx::kWideHalfBytes;
     // contiguous chunks of row blocks per XCD -- except the reordered form at N <= 32, where handing the blocks of the merge-tree order to
     // the XCDs round-robin measured 1.3 .. 4.5 % faster (renumbered FEM 607 -> 582 us, unstructured mesh 444 -> 424; N = 128: +1.4 % the other way)
@@ -216,25 +216,25 @@ V2Launch plan_panel_v2(const sextans_engine *h, int H, int nsuper, int64_t ldc_i
     d.xcd = crow && h->opt_reordered_xcd >= 0 ? (int)h->opt_reordered_xcd : (crow && nsuper <= 2 && !kReorderedContiguous) ? 0 : (int)h->opt_xcd;
     // ---- the variant ----
     V2Variant &v = d.v;
-    if (H > 1) { v = {H, 6, bcol_ld > 0}; return d; }
-    v = {1, nb, bcol_ld > 0};
+    if (H > 1) { v = {H, 6, bcol}; return d; }
+    v = {1, nb, bcol};
     // small matrices staged from column-major B: dictionary capacity from the plan (5 x 64 covers nasa4704's 300)
-    const bool small_dict = bcol_ld > 0 && P.plan_max_dict <= 5 * 64 && h->opt_small_v2 != 0;
+    const bool small_dict = bcol && P.plan_max_dict <= 5 * 64 && h->opt_small_v2 != 0;
     if (h->opt_phase_timing && h->d_dbg && h->opt_exact && P.plan_sets == 1) {   // diagnostic instantiations: the forms the dispatcher uses most
         v.TIMED = true;
         if (small_dict && nb == 3) { v.DCAP = 5; return d; }
-        if (bcol_ld > 0) { v.NB = 2; return d; }
+        if (bcol) { v.NB = 2; return d; }
         if (nb == 6 && !crow && !small_panel) return d;
         if (nb == 2 && !crow && small_panel) { v.DCAP = 5; return d; }
         v.TIMED = false;
     }
     if (small_dict) { v.NB = nb == 3 ? 3 : 2; v.DCAP = 5; }
     else if (big) { v.NB = nb <= 4 ? 4 : 6; v.BIG = true; }
-    else if (bcol_ld > 0) v.NB = 2;
+    else if (bcol) v.NB = 2;
     else {
         // the caller's row-major operands: the 16-byte C accesses of the staging form on the caller's own rows, B without a repack
         // (C beyond 4 GB -- M * ldc * 4 bytes -- takes the instantiations with 64-bit lane addresses: RM == 2)
-        if (rm) { v.CROW = true; v.RM = (int64_t)h->M * std::max(ldc, ldc_in) * 4 >= ((int64_t)1 << 32) ? 2 : 1; }
+        if (rm) { v.CROW = true; v.RM = (int64_t)h->M * std::max(o.ldc, o.ldc_in) * 4 >= ((int64_t)1 << 32) ? 2 : 1; }
         else v.CROW = crow;   // block-major C staging
         // two row sets per block (short-row clustered plans: every row has <= 32 entries = 2 register-resident batches)
         if (P.plan_sets == 2) { v.NB = 2; v.SETS = 2; }
@@ -281,28 +281,19 @@ using PanelV2Kernels = V2List<
     V2K<1, 2, false>, V2K<1, 3, false>, V2K<1, 4, false>, V2K<1, 6, false>>;
 }  // namespace
 
-int launch_panel_v2(sextans_engine *h, int H, const float *dBp, const float *dCin, int64_t ldc_in, float *dCout, int64_t ldc, int nsuper,
-                    float alpha, float beta, hipStream_t s, int64_t bcol_ld, int blk_begin, int blk_end, int row_base, int mode, int last_cols, int64_t rm_ldb, bool dict_blocks_only) {
-    // dict_blocks_only (mixed plan, split form): the launch walks P.d_dict_blocks instead of [blk_begin, blk_end)
-    // rm_ldb > 0 (sextans_spmm_device_rm): dBp is the caller's ROW-major B with that leading dimension, dCin / dCout its row-major C
-    // (ldc_in / ldc = row strides); mode 2 then reads B through the plan's dictionaries translated back to the caller's column
-    // numbers (h->cluster.d_dict_nat) instead of permuted panels.
-    // mode 1 (grid bricks): the plan over the rows in brick order, whole-matrix calls only; its slot -> row table addresses C.
-    // mode 2 (graph clustering, the reordered form): dBp = permuted panels, dCin == dCout == the row-major staging buffer,
-    // ldc_in == ldc == floats per tile; the same slot -> row table addresses the staging rows.
-    // mode 3 (clustered-order chunks of sextans_dist_spmm): the graph-clustered plan with C addressed BY POSITION in the clustered order
-    // (no slot -> row table): dCin == dCout == a packed slab [tile][position][16] of the chunk, ldc_in == ldc == floats per tile.
-    const sextans_engine::PanelState &P = mode ? h->cluster.psc : h->ps;
-    const int nblk = dict_blocks_only ? P.n_dict_blocks : blk_end - blk_begin;
+int launch_panel_v2(sextans_engine *h, const Operands &o, int nsuper, const PanelV2 &a) {
+    const sextans_engine::PanelState &P = v2_plan(h, a.order);
+    const int blk_end = a.blk_end < 0 ? P.plan_nblk : a.blk_end;
+    const int nblk = a.dict_blocks_only ? P.n_dict_blocks : blk_end - a.blk_begin;
     if (nblk <= 0 || nsuper <= 0) return SEXTANS_OK;
-    if (mode == 0)
+    if (a.order == V2Order::kNatural)
         if (int rc = restore_plan_streams(h)) return rc;   // (released while a clustered plan served the whole-matrix calls)
-    const V2Launch d = plan_panel_v2(h, H, nsuper, ldc_in, ldc, bcol_ld, nblk, mode, rm_ldb);
+    const V2Launch d = plan_panel_v2(h, o, nsuper, nblk, a);
     auto go = [&](auto kern) -> int {
         if (int rc = allow_big_lds(h, reinterpret_cast<const void *>(kern), (int)d.lds)) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk * (unsigned)d.ngrp), dim3(sx::kBlock), d.lds, s, (const int2 *)P.d_row_off.get(),
-                           P.d_lidx, P.d_pval, P.d_blk_row, P.d_dict_ptr, d.dict, P.plan_dict_stride, dBp, d.pstride, dCin, ldc_in, dCout, ldc, nsuper, d.tpw, nblk, alpha, beta, d.xcd,
-                           P.plan_pad_row, blk_begin, row_base, d.skip, (long long *)h->d_dbg.get(), d.slot_row, (const int2 *)P.d_ioff.get(), last_cols, dict_blocks_only ? (const int *)P.d_dict_blocks.get() : (const int *)nullptr);
+        hipLaunchKernelGGL(kern, dim3((unsigned)nblk * (unsigned)d.ngrp), dim3(sx::kBlock), d.lds, o.s, (const int2 *)P.d_row_off.get(),
+                           P.d_lidx, P.d_pval, P.d_blk_row, P.d_dict_ptr, d.dict, P.plan_dict_stride, o.B, d.pstride, o.C_in, o.ldc_in, o.C_out, o.ldc, nsuper, d.tpw, nblk, o.alpha, o.beta, d.xcd,
+                           P.plan_pad_row, a.blk_begin, o.row_base, d.skip, (long long *)h->d_dbg.get(), d.slot_row, (const int2 *)P.d_ioff.get(), a.last_cols, a.dict_blocks_only ? (const int *)P.d_dict_blocks.get() : (const int *)nullptr);
         return SEXTANS_OK;
     };
     return PanelV2Kernels::launch(d.v, h->opt_exact != 0, go);
@@ -326,20 +317,20 @@ void launch_slab_rows(bool scatter, float *tiles, int64_t tile_stride, const int
     });
 }
 
-void launch_window(sextans_engine *h, const float *dBp8, const float *dCin, int64_t ldc_in, float *dCout, int64_t ldc, int ntiles,
-                   int wave_begin, int wave_end, int row_base, float alpha, float beta, hipStream_t s) {
+void launch_window(sextans_engine *h, const Operands &o, int ntiles, int wave_begin, int wave_end) {
     const int nwg = (wave_end - wave_begin + sx::kWinWaves - 1) / sx::kWinWaves;
     if (nwg <= 0) return;
     const size_t lds = (size_t)sx::kWinWaves * (size_t)(h->win.rw + 1) * sx::kWinNT * sizeof(float);
     with_bool(h->opt_exact, [&](auto EX) { with_value<4, 8>((int)h->opt_win_unroll, [&](auto U) {
-        hipLaunchKernelGGL((sx::spmm_csr_window<decltype(EX)::value, decltype(U)::value>), dim3((unsigned)nwg * (unsigned)ntiles), dim3(sx::kWinWaves * 64), lds, s,
-                           (const sx::u32x2 *)h->win.d_wstream.get(), (const int *)h->win.d_wstep0.get(), dBp8, (int64_t)h->K * sx::kWinNT, dCin,
-                           ldc_in, dCout, ldc, h->M, h->win.rw, wave_begin, wave_end, nwg, row_base, alpha, beta, (const unsigned char *)h->split.d_skip.get());
+        hipLaunchKernelGGL((sx::spmm_csr_window<decltype(EX)::value, decltype(U)::value>), dim3((unsigned)nwg * (unsigned)ntiles), dim3(sx::kWinWaves * 64), lds, o.s,
+                           (const sx::u32x2 *)h->win.d_wstream.get(), (const int *)h->win.d_wstep0.get(), o.B, b_stride(h, o, sx::kWinNT), o.C_in,
+                           o.ldc_in, o.C_out, o.ldc, h->M, h->win.rw, wave_begin, wave_end, nwg, o.row_base, o.alpha, o.beta, (const unsigned char *)h->split.d_skip.get());
     }); });
 }
 
-void launch_colwise(sextans_engine *h, bool rm, int N, const float *B, int64_t ldb, const float *dCin, int64_t ldc_in, float *dCout,
-                    int64_t ldc, int row_begin, int row_end, float alpha, float beta, hipStream_t s) {
+void launch_colwise(sextans_engine *h, const Operands &o, int N, int row_end) {
+    const bool rm = o.layout == BLayout::kRowMajor;
+    const int row_begin = o.row_base;
     const int64_t adjacent = h->opt_colwise_tiles_adjacent;
     auto tiles = [&](int width, int col0, int ntiles) {
         int T = 1, nrowblk, adj;
@@ -362,8 +353,8 @@ void launch_colwise(sextans_engine *h, bool rm, int N, const float *B, int64_t l
         }
         const dim3 grid = adj ? dim3((unsigned)nrowblk * (unsigned)ntiles) : dim3((unsigned)nrowblk, (unsigned)(ntiles / T));
         with_bool(h->opt_exact, [&](auto EX) { with_value<16, 8>(width, [&](auto W) { with_bool(rm, [&](auto RM) {
-            hipLaunchKernelGGL((sx::spmm_csr_colwise<decltype(EX)::value, decltype(W)::value, decltype(RM)::value>), grid, dim3(sx::kBlock), 0, s, h->m_rp, h->m_ci,
-                               h->m_v, B, ldb, dCin, ldc_in, dCout, ldc, row_begin, row_end, nrowblk, col0, alpha, beta, (int)h->opt_xcd, (const unsigned char *)h->split.d_skip.get(), adj, T);
+            hipLaunchKernelGGL((sx::spmm_csr_colwise<decltype(EX)::value, decltype(W)::value, decltype(RM)::value>), grid, dim3(sx::kBlock), 0, o.s, h->m_rp, h->m_ci,
+                               h->m_v, o.B, o.ldb, o.C_in, o.ldc_in, o.C_out, o.ldc, row_begin, row_end, nrowblk, col0, o.alpha, o.beta, (int)h->opt_xcd, (const unsigned char *)h->split.d_skip.get(), adj, T);
         }); }); });
     };
     const int n16 = N / 16;
@@ -371,9 +362,9 @@ void launch_colwise(sextans_engine *h, bool rm, int N, const float *B, int64_t l
     if (N % 16) tiles(8, n16 * 16, 1);
 }
 
-void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const float *dCin, int64_t ldc_in, float *dCout, int64_t ldc, int N,
-                   int c0, int c1, int row_base, float alpha, float beta, hipStream_t s, bool permuted_panels, const float *rm_B, int64_t rm_ldb) {
-    // rm_B (sextans_spmm_device_rm): the caller's row-major B and C -- B is one "panel" with rows rm_ldb floats apart
+void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const Operands &o, int c0, int c1, bool permuted_panels) {
+    // row-major operands (sextans_spmm_device_rm): B is one "panel" with rows o.ldb floats apart
+    const bool rm = o.layout == BLayout::kRowMajor;
     // permuted_panels (the reordered form): the 16-column panels hold B row k at row colpos[k]; the chain rows' entries come from
     // their compact relabelled copy (ensure_cluster_plan); 8-column remainder tiles keep the natural panels and the source arrays
     // one workgroup per (chain row, 16- or 8-column tile): chain_fused
@@ -387,7 +378,7 @@ void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const float 
         }
     }
     for (const Seg &g : segs) {
-        const float *bp = rm_B ? rm_B + g.col0 : h->d_Bp + (size_t)h->K * (size_t)g.col0;
+        const float *bp = o.at(g.col0).B;
         const int NT = (g.width >= 16 && g.last_cols != 8) ? 16 : 8;   // (the tail: the first 8-column half of its 16-column panel)
         const int ntiles = g.last_cols == 8 ? 1 : g.ntiles * (g.width / NT);
         const bool perm = permuted_panels && g.width == 16;
@@ -395,34 +386,33 @@ void launch_chains(sextans_engine *h, const std::vector<Seg> &plan, const float 
             constexpr int lds = sx::chain_fused_lds_bytes(decltype(W)::value), threads = sx::chain_fused_threads(decltype(W)::value);
             const auto kern = sx::chain_fused<decltype(W)::value, decltype(EX)::value>;
             (void)allow_big_lds(h, reinterpret_cast<const void *>(kern), lds);
-            hipLaunchKernelGGL(kern, dim3((unsigned)(c1 - c0) * (unsigned)ntiles), dim3((unsigned)threads), (size_t)lds, s, h->split.d_chain_row,
+            hipLaunchKernelGGL(kern, dim3((unsigned)(c1 - c0) * (unsigned)ntiles), dim3((unsigned)threads), (size_t)lds, o.s, h->split.d_chain_row,
                                perm ? h->cluster.d_chain_beg_c : h->split.d_chain_beg, h->split.d_chain_off, (c0 == 0 && c1 == h->split.nchain) ? h->split.d_chain_perm : (const int *)nullptr,
-                               perm ? (const int *)h->cluster.d_chain_ci_perm : h->s_ci, perm ? (const float *)h->cluster.d_chain_v_c : h->s_v, bp, rm_B ? (int64_t)0 : (int64_t)h->K * g.width,
-                               rm_B ? (int)rm_ldb : g.width, dCin, ldc_in, dCout, ldc, g.col0, ntiles, c0, row_base, alpha, beta, rm_B ? 1 : 0);
+                               perm ? (const int *)h->cluster.d_chain_ci_perm : h->s_ci, perm ? (const float *)h->cluster.d_chain_v_c : h->s_v, bp, rm ? (int64_t)0 : (int64_t)h->K * g.width,
+                               rm ? (int)o.ldb : g.width, o.C_in, o.ldc_in, o.C_out, o.ldc, g.col0, ntiles, c0, o.row_base, o.alpha, o.beta, rm ? 1 : 0);
         }); });
     }
 }
 
-void launch_hub_pieces(sextans_engine *h, int width, const sextans_engine::PieceTable &t, const float *dBp, int ntiles, int col0, int v0,
-                       int v1, hipStream_t s, const int *colpos, int64_t rm_ldb) {
+void launch_hub_pieces(sextans_engine *h, int width, const sextans_engine::PieceTable &t, const Operands &o, int ntiles, int col0, int v0,
+                       int v1, const int *colpos) {
     float *P = h->d_P + (int64_t)col0 * h->split.nv;
     by_width(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR;
         const int nblk = (v1 - v0 + RB - 1) / RB;
         if (nblk <= 0) return;
-        with_bool(h->opt_exact, [&](auto EX) { with_bool(rm_ldb > 0, [&](auto RM) {
-            hipLaunchKernelGGL((sx::spmm_csr_pieces<LPR, decltype(EX)::value, decltype(RM)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, s, t.d_vrp,
-                               t.d_vend, h->s_ci, h->s_v, dBp, rm_ldb > 0 ? rm_ldb : (int64_t)h->K * 4 * LPR, P, (int64_t)h->split.nv, v0, v1, ntiles, colpos);
+        with_bool(h->opt_exact, [&](auto EX) { with_bool(o.layout == BLayout::kRowMajor, [&](auto RM) {
+            hipLaunchKernelGGL((sx::spmm_csr_pieces<LPR, decltype(EX)::value, decltype(RM)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, o.s, t.d_vrp,
+                               t.d_vend, h->s_ci, h->s_v, o.B, b_stride(h, o, 4 * LPR), P, (int64_t)h->split.nv, v0, v1, ntiles, colpos);
         }); });
     });
 }
 
-void launch_fold(sextans_engine *h, const sextans_engine::PieceTable &t, int hub0, int hub1, int N, const float *dCin, int64_t ldc_in,
-                 float *dCout, int64_t ldc, int row_base, float alpha, float beta, bool rm, hipStream_t s) {
+void launch_fold(sextans_engine *h, const sextans_engine::PieceTable &t, int hub0, int hub1, int N, const Operands &o) {
     const int64_t tot = (int64_t)(hub1 - hub0) * N;
     with_bool(h->opt_exact, [&](auto EX) {
-        hipLaunchKernelGGL(sx::fold_hub_pieces<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t.d_vfirst, t.d_row, h->d_P,
-                           (int64_t)h->split.nv, dCin, ldc_in, dCout, ldc, hub0, hub1 - hub0, N, row_base, alpha, beta, rm ? 1 : 0);
+        hipLaunchKernelGGL(sx::fold_hub_pieces<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, o.s, t.d_vfirst, t.d_row, h->d_P,
+                           (int64_t)h->split.nv, o.C_in, o.ldc_in, o.C_out, o.ldc, hub0, hub1 - hub0, N, o.row_base, o.alpha, o.beta, o.c_rm ? 1 : 0);
     });
 }
 
@@ -441,37 +431,35 @@ void launch_transpose(bool aligned, bool to_cm, const float *src, float *dst, in
 }
 
 // ---- bf16 dense operands (spmm_bf16_kernels.h) -----------------------------------------------------------------------------------
-void launch_rowgroup_bf16(sextans_engine *h, int width, const uint16_t *B, int64_t ldb, const void *dCin, int64_t ldc_in, void *dCout,
-                          int64_t ldc, int ntiles, float alpha, float beta, bool cbf16, hipStream_t s) {
+void launch_rowgroup_bf16(sextans_engine *h, int width, const OperandsBf16 &o, int ntiles) {
     by_width_bf16(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR, CH = 2048;
         const int nrowblk = (h->M + RB - 1) / RB;
-        with_bool(h->opt_exact, [&](auto EX) { with_bool(h->opt_stage, [&](auto ST) { with_bool(cbf16, [&](auto CB) {
+        with_bool(h->opt_exact, [&](auto EX) { with_bool(h->opt_stage, [&](auto ST) { with_bool(o.c_elem == 2, [&](auto CB) {
             hipLaunchKernelGGL((sx::spmm_csr_rowgroup_bf16<LPR, CH, decltype(EX)::value, decltype(ST)::value, decltype(CB)::value>), dim3((unsigned)nrowblk * (unsigned)ntiles),
-                               dim3(sx::kBlock), 0, s, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, B, ldb, dCin, ldc_in, dCout, ldc, h->M, ntiles, nrowblk, alpha, beta,
+                               dim3(sx::kBlock), 0, o.s, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, o.B, o.ldb, (const void *)o.C_in, o.ldc_in, (void *)o.C_out, o.ldc, h->M, ntiles, nrowblk, o.alpha, o.beta,
                                (int)h->opt_xcd, (const unsigned char *)h->split.d_skip.get());
         }); }); });
     });
 }
 
-void launch_hub_pieces_bf16(sextans_engine *h, int width, const sextans_engine::PieceTable &t, const uint16_t *B, int64_t ldb, int ntiles, int col0, int v0, int v1, hipStream_t s) {
+void launch_hub_pieces_bf16(sextans_engine *h, int width, const sextans_engine::PieceTable &t, const OperandsBf16 &o, int ntiles, int col0, int v0, int v1) {
     by_width_bf16(width, [&](auto L) {
         constexpr int LPR = decltype(L)::value, RB = sx::kBlock / LPR;
         const int nblk = (v1 - v0 + RB - 1) / RB;
         if (nblk <= 0) return;
         with_bool(h->opt_exact, [&](auto EX) {
-            hipLaunchKernelGGL((sx::spmm_csr_pieces_bf16<LPR, decltype(EX)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, s, t.d_vrp, t.d_vend,
-                               h->s_ci, h->s_v, B, ldb, h->d_P + (int64_t)col0 * h->split.nv, (int64_t)h->split.nv, v0, v1, ntiles);
+            hipLaunchKernelGGL((sx::spmm_csr_pieces_bf16<LPR, decltype(EX)::value>), dim3((unsigned)nblk * (unsigned)ntiles), dim3(sx::kBlock), 0, o.s, t.d_vrp, t.d_vend,
+                               h->s_ci, h->s_v, o.B, o.ldb, h->d_P + (int64_t)col0 * h->split.nv, (int64_t)h->split.nv, v0, v1, ntiles);
         });
     });
 }
 
-void launch_fold_bf16(sextans_engine *h, const sextans_engine::PieceTable &t, int N, const uint16_t *dCin, int64_t ldc_in, uint16_t *dCout,
-                      int64_t ldc, float alpha, float beta, hipStream_t s) {
+void launch_fold_bf16(sextans_engine *h, const sextans_engine::PieceTable &t, int N, const OperandsBf16 &o) {
     const int64_t tot = (int64_t)h->split.nhub * N;
     with_bool(h->opt_exact, [&](auto EX) {
-        hipLaunchKernelGGL(sx::fold_hub_pieces_bf16<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, t.d_vfirst, t.d_row, h->d_P,
-                           (int64_t)h->split.nv, dCin, ldc_in, dCout, ldc, h->split.nhub, N, alpha, beta);
+        hipLaunchKernelGGL(sx::fold_hub_pieces_bf16<decltype(EX)::value>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, o.s, t.d_vfirst, t.d_row, h->d_P,
+                           (int64_t)h->split.nv, (const uint16_t *)o.C_in, o.ldc_in, (uint16_t *)o.C_out, o.ldc, h->split.nhub, N, o.alpha, o.beta);
     });
 }
 
@@ -515,7 +503,7 @@ const char *with_rowblocks(sextans_engine *h, const char *name) {
     h->last_kernel_buf = std::string(name) + "+rowblock_mfma_f32";
     return h->last_kernel_buf.c_str();
 }
-const char *kernel_name(int main, bool hubs, bool dense) {
+const char *kernel_name(MainKernel main, bool hubs, bool dense) {
     static const char *names[4][2][2] = {
         {{"spmm_csr_rowgroup", "spmm_csr_rowgroup+dense_tiles_mfma"},
          {"spmm_csr_rowgroup+hub_pieces", "spmm_csr_rowgroup+hub_pieces+dense_tiles_mfma"}},
@@ -525,7 +513,7 @@ const char *kernel_name(int main, bool hubs, bool dense) {
          {"spmm_csr_window+hub_pieces", "spmm_csr_window+hub_pieces+dense_tiles_mfma"}},
         {{"spmm_csr_panel_v2", "spmm_csr_panel_v2+dense_tiles_mfma"},
          {"spmm_csr_panel_v2+hub_pieces", "spmm_csr_panel_v2+hub_pieces+dense_tiles_mfma"}}};
-    return names[main][hubs ? 1 : 0][dense ? 1 : 0];
+    return names[(int)main][hubs ? 1 : 0][dense ? 1 : 0];
 }
 
 }  // namespace sxe

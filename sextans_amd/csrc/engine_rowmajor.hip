@@ -69,39 +69,44 @@ namespace {
 // Everything sextans_spmm_device_rm decides for one call (route_rm), before anything is launched
 struct RouteRM {
     enum Path { kColwise, kPanelV2, kRowgroup, kTranspose } path = kTranspose;
-    bool aligned = false;        // 16-byte aligned operands with leading dimensions that are multiples of 4
-    int mode = -1;               // kPanelV2: launch_panel_v2's mode -- 0 natural order, 1 grid bricks, 2 graph clustering
+    bool aligned = false;        // 16-byte accesses on the caller's operands (rm_aligned, bf16_aligned)
+    V2Order order = V2Order::kNatural;   // kPanelV2: the plan launch_panel_v2 walks
     bool split = false;          // kPanelV2 on a mixed plan: dictionary blocks there, the other blocks' rows on the gather kernel
     std::vector<Seg> segs;       // kRowgroup: the tiling of N
 };
 
-RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
+// fp32 operands: 16-byte aligned with leading dimensions that are multiples of 4
+bool rm_aligned(const Operands &o) {
+    return ((reinterpret_cast<uintptr_t>(o.B) | reinterpret_cast<uintptr_t>(o.C_in) | reinterpret_cast<uintptr_t>(o.C_out)) & 15) == 0 && o.ldb % 4 == 0 &&
+           o.ldc_in % 4 == 0 && o.ldc % 4 == 0;
+}
+
+// Asked with what it reads of the operands: the alignment verdict, B's leading dimension (in floats) and N
+RouteRM route_rm(const sextans_engine *h, const Tiling &t, bool aligned, int64_t ldb, int N) {
     RouteRM r;
     const bool colwise = colwise_wanted(h);
-    r.aligned = ((reinterpret_cast<uintptr_t>(c.B) | reinterpret_cast<uintptr_t>(c.C_in) | reinterpret_cast<uintptr_t>(c.C_out)) & 15) == 0 &&
-                c.ldb % 4 == 0 && c.ldc_in % 4 == 0 && c.ldc % 4 == 0;
+    r.aligned = aligned;
     // 32-bit offsets inside the kernel: floats into B (C beyond 4 GB: the kernel's 64-bit form, launch_panel_v2)
-    const bool fits = (int64_t)h->K * c.ldb < ((int64_t)1 << 32);
+    const bool fits = (int64_t)h->K * ldb < ((int64_t)1 << 32);
     // Rows on the long-row paths (pieces, exact chains): from the caller's row-major B into its row-major C as well -- the piece kernel's
     // 16-byte gathers and the chain producers' LDS-DMA read B rows ldb floats apart instead of panel rows, the fold and the chain
     // consumer write C[r * ldc + n].  The main kernels skip those rows (d_skip), so the order between the launches does not matter;
     // the chains run beside the main kernel on the engine's side stream, as in the column-major form.
     const bool hubs = h->split.nhub > 0, chains = h->split.nchain > 0;
-    const bool long_ok = (!hubs && !chains) || (r.aligned && (!chains || (h->aux_stream && h->ev_fork && h->ev_join && c.ldb < ((int64_t)1 << 31))));
+    const bool long_ok = (!hubs && !chains) || (r.aligned && (!chains || (h->aux_stream && h->ev_fork && h->ev_join && ldb < ((int64_t)1 << 31))));
     if (colwise && r.aligned && !hubs && !chains && csr_only(h) && h->m_nnz > 0) {   // short rows in a local numbering: lane per row, 16-byte accesses
         r.path = RouteRM::kColwise;
         return r;
     }
     if (t.W == 16 && (h->opt_kernel == 0 || h->opt_kernel == 2) && h->opt_panel_v2 != 0 && h->opt_cols_per_lane != 8 && csr_only(h) &&
         !(colwise && !hubs && !chains) && r.aligned && fits && long_ok && h->m_nnz > 0) {
-        if (h->cluster.state == 2) r.mode = 2;
-        else if (h->cluster.state == 1) r.mode = 1;
-        else if (t.panel && (!h->ps.plan_mixed || (h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_kernel == 0)) && h->ps.plan_max_dict <= kWideMaxDict) r.mode = 0;
+        if (h->cluster.state == 2) { r.order = V2Order::kReordered; r.path = RouteRM::kPanelV2; }
+        else if (h->cluster.state == 1) { r.order = V2Order::kBricks; r.path = RouteRM::kPanelV2; }
+        else if (t.panel && (!h->ps.plan_mixed || (h->ps.d_rg_skip && h->opt_split_mixed != 0 && h->opt_kernel == 0)) && h->ps.plan_max_dict <= kWideMaxDict) r.path = RouteRM::kPanelV2;
     }
-    if (r.mode == 2 && h->cluster.d_colpos && !h->cluster.d_dict_nat) r.mode = -1;   // (cannot happen after rm_plan; kept as a guard)
-    if (r.mode >= 0) {
-        r.path = RouteRM::kPanelV2;
-        r.split = r.mode == 0 && h->ps.plan_mixed;
+    if (r.order == V2Order::kReordered && h->cluster.d_colpos && !h->cluster.d_dict_nat) r.path = RouteRM::kTranspose;   // (cannot happen after rm_plan; kept as a guard)
+    if (r.path == RouteRM::kPanelV2) {
+        r.split = r.order == V2Order::kNatural && h->ps.plan_mixed;
         return r;
     }
     // The gather kernel on a matrix without rows on the piece / chain / dense-tile paths: a row of row-major B IS what its lanes fetch
@@ -109,7 +114,7 @@ RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
     if (!t.panel && !t.window && !(colwise && !hubs && !chains) && r.aligned && long_ok && (h->opt_kernel == 0 || h->opt_kernel == 1) && csr_only(h) && h->m_nnz > 0) {
         r.path = RouteRM::kRowgroup;
         r.segs = t.segs;
-        if (c.N == 8) r.segs.assign(1, Seg{8, 0, 1});   // (the plan above was made for 16 columns)
+        if (N == 8) r.segs.assign(1, Seg{8, 0, 1});   // (the plan above was made for 16 columns)
         return r;
     }
     // Everything else (lane-per-row / window kernels, mixed plans, rows on the piece and chain paths, dense tiles, unaligned operands):
@@ -118,8 +123,8 @@ RouteRM route_rm(const sextans_engine *h, const Call &c, const Tiling &t) {
 }
 
 int run_rm_colwise(sextans_engine *h, const Call &c) {
-    Prof p(h, &h->ev_kernel, c.s);
-    launch_colwise(h, true, c.N, c.B, c.ldb, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, h->M, c.alpha, c.beta, c.s);
+    Prof p(h, &h->ev_kernel, c.o.s);
+    launch_colwise(h, c.o, c.N, h->M);
     h->last_kernel = "spmm_csr_colwise_rowmajor";
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
@@ -127,25 +132,24 @@ int run_rm_colwise(sextans_engine *h, const Call &c) {
 
 // The paths on the caller's row-major operands (kPanelV2, kRowgroup), rows on the long-row paths included
 int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
-    Prof p(h, &h->ev_kernel, c.s);
+    Prof p(h, &h->ev_kernel, c.o.s);
     const bool long_rows = h->split.nhub > 0 || h->split.nchain > 0;
     if (h->split.nchain > 0) {
         std::vector<Seg> segs;   // tiles of the chain kernel: 16-column tiles and an 8-column tail (never past column N of a B row)
         if (c.N / 16) segs.push_back(Seg{16, 0, c.N / 16});
         if (c.N % 16) segs.push_back(Seg{8, c.N / 16 * 16, 1});
-        if (int rc = fork_chains(h, c, segs, 0, h->split.nchain, true)) return rc;
+        if (int rc = fork_chains(h, c.o, segs, 0, h->split.nchain)) return rc;
     }
     // the gather kernel: over the rows of the blocks without a dictionary (split form of a mixed plan), or over all rows
     auto rowgroups = [&](const std::vector<Seg> &segs, const unsigned char *skip, const int *groups, int ngroups) {
-        for (const Seg &g : segs)
-            launch_rowgroup(h, g.width, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, skip, c.B + g.col0, c.C_in + g.col0, c.ldc_in, c.C_out + g.col0, c.ldc,
-                            0, h->M, g.ntiles, c.alpha, c.beta, c.s, c.ldb, false, groups, ngroups);
+        for (const Seg &g : segs) launch_rowgroup(h, g.width, c.o.at(g.col0), g.ntiles, h->M, skip, groups, ngroups);
     };
     if (r.path == RouteRM::kPanelV2) {
-        const int ntiles = (c.N + 15) / 16, last_cols = c.N % 16 ? 8 : 16;
-        const sextans_engine::PanelState &P = r.mode ? h->cluster.psc : h->ps;
-        if (int rc = launch_panel_v2(h, 1, c.B, c.C_in, c.ldc_in, c.C_out, c.ldc, ntiles, c.alpha, c.beta, c.s, 0, 0, P.plan_nblk, 0, r.mode, last_cols, c.ldb, r.split))
-            return rc;
+        PanelV2 a;
+        a.order = r.order;
+        a.last_cols = c.N % 16 ? 8 : 16;
+        a.dict_blocks_only = r.split;
+        if (int rc = launch_panel_v2(h, c.o, (c.N + 15) / 16, a)) return rc;
         if (r.split) rowgroups(wide_first(c.N), h->ps.d_rg_skip, h->ps.d_rg_groups, h->ps.rg_ngroups);
     } else {
         rowgroups(r.segs, h->split.d_skip, nullptr, 0);
@@ -153,13 +157,13 @@ int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
     if (h->split.nhub > 0) {   // the long rows' pieces and their fold
         const sextans_engine::PieceTable &pt = h->split.by_len;
         const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->split.nhub];
-        for (const Seg &g : wide_first(c.N)) launch_hub_pieces(h, g.width, pt, c.B + g.col0, g.ntiles, g.col0, v0, v1, c.s, nullptr, c.ldb);
-        launch_fold(h, pt, 0, h->split.nhub, c.N, c.C_in, c.ldc_in, c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+        for (const Seg &g : wide_first(c.N)) launch_hub_pieces(h, g.width, pt, c.o.at(g.col0), g.ntiles, g.col0, v0, v1);
+        launch_fold(h, pt, 0, h->split.nhub, c.N, c.o);
     }
-    if (h->split.nchain > 0) SX_HIP(hipStreamWaitEvent(c.s, h->ev_join, 0));
+    if (h->split.nchain > 0) SX_HIP(hipStreamWaitEvent(c.o.s, h->ev_join, 0));
     h->last_kernel = r.path == RouteRM::kRowgroup ? (long_rows ? "spmm_csr_rowgroup_rowmajor+long_rows" : "spmm_csr_rowgroup_rowmajor")
-                     : r.mode == 2 ? (long_rows ? "spmm_csr_panel_v2_rowmajor_clustered+long_rows" : "spmm_csr_panel_v2_rowmajor_clustered")
-                                   : (long_rows ? "spmm_csr_panel_v2_rowmajor+long_rows" : "spmm_csr_panel_v2_rowmajor");
+                     : r.order == V2Order::kReordered ? (long_rows ? "spmm_csr_panel_v2_rowmajor_clustered+long_rows" : "spmm_csr_panel_v2_rowmajor_clustered")
+                                                      : (long_rows ? "spmm_csr_panel_v2_rowmajor+long_rows" : "spmm_csr_panel_v2_rowmajor");
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
@@ -169,43 +173,49 @@ int run_rm_direct(sextans_engine *h, const Call &c, const RouteRM &r) {
 // C_out may alias, so one C buffer)
 int run_rm_transpose(sextans_engine *h, const Call &c, bool aligned) {
     const int N = c.N;
+    const Operands &o = c.o;
     h->lean_prepare = false;
     const size_t nB = (size_t)h->K * (size_t)N, nC = (size_t)h->M * (size_t)N;
     if (int rc = reserve(h->d_rmB, nB)) return rc;
     if (int rc = reserve(h->d_rmC, nC)) return rc;
     {
-        Prof p(h, &h->ev_repack, c.s);
-        launch_transpose(aligned, true, c.B, h->d_rmB, c.ldb, h->K, h->K, N, c.s);
-        launch_transpose(aligned, true, c.C_in, h->d_rmC, c.ldc_in, h->M, h->M, N, c.s);
+        Prof p(h, &h->ev_repack, o.s);
+        launch_transpose(aligned, true, o.B, h->d_rmB, o.ldb, h->K, h->K, N, o.s);
+        launch_transpose(aligned, true, o.C_in, h->d_rmC, o.ldc_in, h->M, h->M, N, o.s);
     }
-    if (int rc = sextans_spmm_device_rows(h, N, c.alpha, h->d_rmB, h->K, c.beta, h->d_rmC, h->M, h->d_rmC, h->M, 0, h->M, 0, (void *)c.s)) return rc;
+    if (int rc = sextans_spmm_device_rows(h, N, o.alpha, h->d_rmB, h->K, o.beta, h->d_rmC, h->M, h->d_rmC, h->M, 0, h->M, 0, (void *)o.s)) return rc;
     {
-        Prof p(h, &h->ev_post, c.s);
-        launch_transpose(aligned, false, h->d_rmC, c.C_out, c.ldc, h->M, h->M, N, c.s);
+        Prof p(h, &h->ev_post, o.s);
+        launch_transpose(aligned, false, h->d_rmC, o.C_out, o.ldc, h->M, h->M, N, o.s);
     }
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
 
 // ---- bf16 dense operands on the row-major entry (spmm_bf16_kernels.h) --------------------------------------------------------------
-struct CallBf16 {
-    int N; float alpha; const uint16_t *B; int64_t ldb; float beta; const void *C_in; int64_t ldc_in; void *C_out; int64_t ldc; bool cbf16; hipStream_t s;
+struct CallBf16 {   // o.C_in / o.C_out in bytes, o.c_elem bytes per element
+    OperandsBf16 o; int N = 0;
+    bool cbf16() const { return o.c_elem == 2; }
 };
 
 // The native route: the gather kernel (and the piece path of long rows) on the caller's bf16 buffers.  The very arrays run_rm_direct
 // passes (m_rp / m_ci / m_v, the piece table by_len) -- what a value refresh rewrites.
 int run_rm_bf16_native(sextans_engine *h, const CallBf16 &c) {
-    Prof p(h, &h->ev_kernel, c.s);
-    const size_t esz = c.cbf16 ? 2 : 4;
-    for (const Seg &g : bf16_tiles(c.N))
-        launch_rowgroup_bf16(h, g.width, c.B + g.col0, c.ldb, (const char *)c.C_in + esz * (size_t)g.col0, c.ldc_in, (char *)c.C_out + esz * (size_t)g.col0, c.ldc,
-                             g.ntiles, c.alpha, c.beta, c.cbf16, c.s);
+    const OperandsBf16 &o = c.o;
+    Prof p(h, &h->ev_kernel, o.s);
+    for (const Seg &g : bf16_tiles(c.N)) launch_rowgroup_bf16(h, g.width, o.at(g.col0), g.ntiles);
     if (h->split.nhub > 0) {   // the long rows' pieces (raw fp32 sums into P) and their fold
         const sextans_engine::PieceTable &pt = h->split.by_len;
         const int v0 = pt.h_vfirst[0], v1 = pt.h_vfirst[(size_t)h->split.nhub];
-        for (const Seg &g : bf16_tiles(c.N)) launch_hub_pieces_bf16(h, g.width, pt, c.B + g.col0, c.ldb, g.ntiles, g.col0, v0, v1, c.s);
-        if (c.cbf16) launch_fold_bf16(h, pt, c.N, (const uint16_t *)c.C_in, c.ldc_in, (uint16_t *)c.C_out, c.ldc, c.alpha, c.beta, c.s);
-        else launch_fold(h, pt, 0, h->split.nhub, c.N, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, c.alpha, c.beta, true, c.s);
+        for (const Seg &g : bf16_tiles(c.N)) launch_hub_pieces_bf16(h, g.width, pt, o.at(g.col0), g.ntiles, g.col0, v0, v1);
+        if (c.cbf16()) {
+            launch_fold_bf16(h, pt, c.N, o);
+        } else {   // fp32 C: the fold of the fp32 route
+            Operands f;
+            f.C_in = (const float *)o.C_in; f.ldc_in = o.ldc_in; f.C_out = (float *)o.C_out; f.ldc = o.ldc; f.c_rm = true;
+            f.alpha = o.alpha; f.beta = o.beta; f.s = o.s;
+            launch_fold(h, pt, 0, h->split.nhub, c.N, f);
+        }
     }
     h->last_kernel = h->split.nhub > 0 ? "spmm_csr_rowgroup_rowmajor_bf16+long_rows" : "spmm_csr_rowgroup_rowmajor_bf16";
     SX_HIP(hipGetLastError());
@@ -223,19 +233,21 @@ int ensure_bf16_workspaces(sextans_engine *h, int N, bool cbf16) {
 
 // Every other route: fp32 copies of B (and of a bf16 C) in the engine's workspaces around the fp32 row-major entry point
 int run_rm_bf16_converted(sextans_engine *h, const CallBf16 &c) {
-    if (int rc = ensure_bf16_workspaces(h, c.N, c.cbf16)) return rc;
+    const OperandsBf16 &o = c.o;
+    const int N = c.N;
+    if (int rc = ensure_bf16_workspaces(h, N, c.cbf16())) return rc;
     {
-        Prof p(h, &h->ev_repack, c.s);
-        launch_widen(c.B, c.ldb, h->mat.d_bfB, c.N, h->K, c.N, c.s);
-        if (c.cbf16) launch_widen((const uint16_t *)c.C_in, c.ldc_in, h->mat.d_bfC, c.N, h->M, c.N, c.s);
+        Prof p(h, &h->ev_repack, o.s);
+        launch_widen(o.B, o.ldb, h->mat.d_bfB, N, h->K, N, o.s);
+        if (c.cbf16()) launch_widen((const uint16_t *)o.C_in, o.ldc_in, h->mat.d_bfC, N, h->M, N, o.s);
     }
     SX_HIP(hipGetLastError());
-    if (!c.cbf16) {
-        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->mat.d_bfB, c.N, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, (void *)c.s)) return rc;
+    if (!c.cbf16()) {
+        if (int rc = sextans_spmm_device_rm(h, N, o.alpha, h->mat.d_bfB, N, o.beta, (const float *)o.C_in, o.ldc_in, (float *)o.C_out, o.ldc, (void *)o.s)) return rc;
     } else {
-        if (int rc = sextans_spmm_device_rm(h, c.N, c.alpha, h->mat.d_bfB, c.N, c.beta, h->mat.d_bfC, c.N, h->mat.d_bfC, c.N, (void *)c.s)) return rc;
-        Prof p(h, &h->ev_post, c.s);
-        launch_round(h->mat.d_bfC, c.N, (uint16_t *)c.C_out, c.ldc, h->M, c.N, c.s);
+        if (int rc = sextans_spmm_device_rm(h, N, o.alpha, h->mat.d_bfB, N, o.beta, h->mat.d_bfC, N, h->mat.d_bfC, N, (void *)o.s)) return rc;
+        Prof p(h, &h->ev_post, o.s);
+        launch_round(h->mat.d_bfC, N, (uint16_t *)o.C_out, o.ldc, h->M, N, o.s);
     }
     SX_HIP(hipGetLastError());
     ++h->mat.bf16_converted_calls;
@@ -243,18 +255,27 @@ int run_rm_bf16_converted(sextans_engine *h, const CallBf16 &c) {
 }
 
 // 16-byte accesses on the caller's buffers: aligned bases, whole 16-byte groups per row; 32-bit byte offsets into B
-bool bf16_aligned(const sextans_engine *h, const CallBf16 &c) {
-    const int64_t cm = c.cbf16 ? 8 : 4;
-    return (int64_t)h->K * c.ldb * 2 < ((int64_t)1 << 32) && ((reinterpret_cast<uintptr_t>(c.B) | reinterpret_cast<uintptr_t>(c.C_in) | reinterpret_cast<uintptr_t>(c.C_out)) & 15) == 0 &&
-           c.ldb % 8 == 0 && c.ldc_in % cm == 0 && c.ldc % cm == 0;
+bool bf16_aligned(const sextans_engine *h, const OperandsBf16 &o) {
+    const int64_t cm = 16 / o.c_elem;
+    return (int64_t)h->K * o.ldb * 2 < ((int64_t)1 << 32) && ((reinterpret_cast<uintptr_t>(o.B) | reinterpret_cast<uintptr_t>(o.C_in) | reinterpret_cast<uintptr_t>(o.C_out)) & 15) == 0 &&
+           o.ldb % 8 == 0 && o.ldc_in % cm == 0 && o.ldc % cm == 0;
 }
 // route_rm's decision for the call, unchanged: native where it is the gather kernel and no row is an exact chain
-// (asked with the caller's leading dimensions; a call that converts asks again inside sextans_spmm_device_rm with ldb = N of the
-// workspace -- route_rm looks at ldb only for alignment and the 32-bit limit of the panel paths, so the two cannot disagree on the gather route)
+// (asked with the caller's leading dimension; a call that converts asks again inside sextans_spmm_device_rm with ldb = N of the
+// workspace -- route_rm looks at ldb only for the 32-bit limit of the panel paths, so the two cannot disagree on the gather route;
+// operands that pass bf16_aligned are aligned in route_rm's sense too)
 bool bf16_native(const sextans_engine *h, const CallBf16 &c, const Tiling &t) {
-    if (!bf16_aligned(h, c) || h->split.nchain > 0) return false;
-    const Call f{c.N, c.alpha, (const float *)c.B, c.ldb, c.beta, (const float *)c.C_in, c.ldc_in, (float *)c.C_out, c.ldc, 0, h->M, 0, c.s, true};
-    return route_rm(h, f, t).path == RouteRM::kRowgroup;
+    if (!bf16_aligned(h, c.o) || h->split.nchain > 0) return false;
+    return route_rm(h, t, true, c.o.ldb, c.N).path == RouteRM::kRowgroup;
+}
+// the bf16 entry points' operands (C addressed in bytes)
+CallBf16 bf16_call(int N, float alpha, const uint16_t *d_B, int64_t ldb, float beta, const void *d_C_in, int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, hipStream_t s) {
+    CallBf16 c;
+    c.N = N;
+    c.o.B = d_B; c.o.ldb = ldb; c.o.layout = BLayout::kRowMajor;
+    c.o.C_in = (const char *)d_C_in; c.o.ldc_in = ldc_in; c.o.C_out = (char *)d_C_out; c.o.ldc = ldc; c.o.c_rm = true;
+    c.o.c_elem = c_dtype == SEXTANS_DTYPE_BF16 ? 2 : 4; c.o.alpha = alpha; c.o.beta = beta; c.o.s = s;
+    return c;
 }
 }  // namespace
 extern "C" {
@@ -279,8 +300,12 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
     if (h->M == 0) return SEXTANS_OK;
     Tiling t;
     if (int rc = rm_plan(h, N, s, &t)) return rc;
-    const Call c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, 0, h->M, 0, s, true};
-    const RouteRM r = route_rm(h, c, t);
+    Call c;
+    c.N = N; c.row_end = h->M;
+    c.o.B = d_B; c.o.ldb = ldb; c.o.layout = BLayout::kRowMajor;
+    c.o.C_in = d_C_in; c.o.ldc_in = ldc_in; c.o.C_out = d_C_out; c.o.ldc = ldc; c.o.c_rm = true;
+    c.o.alpha = alpha; c.o.beta = beta; c.o.s = s;
+    const RouteRM r = route_rm(h, t, rm_aligned(c.o), ldb, N);
     switch (r.path) {
         case RouteRM::kColwise: return run_rm_colwise(h, c);
         case RouteRM::kTranspose: return run_rm_transpose(h, c, r.aligned);
@@ -297,7 +322,7 @@ int sextans_spmm_device_rm_bf16(sextans_handle_t h, int N, float alpha, const ui
     if (h->M == 0) return SEXTANS_OK;
     Tiling t;
     if (int rc = rm_plan(h, N, s, &t)) return rc;
-    const CallBf16 c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, c_dtype == SEXTANS_DTYPE_BF16, s};
+    const CallBf16 c = bf16_call(N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, c_dtype, s);
     return bf16_native(h, c, t) ? run_rm_bf16_native(h, c) : run_rm_bf16_converted(h, c);
 }
 
@@ -316,9 +341,9 @@ int sextans_prepare_rm_bf16(sextans_handle_t h, int N, int c_dtype, int transpos
     if (int rc = rm_plan(h, N, s, &t)) return rc;
     // the route of a call with aligned operands; where that is native nothing more is needed (a call with unaligned operands on such a
     // matrix converts and sizes the copies itself)
-    const CallBf16 c{N, 1.f, nullptr, N, 0.f, nullptr, N, nullptr, N, c_dtype == SEXTANS_DTYPE_BF16, s};
+    const CallBf16 c = bf16_call(N, 1.f, nullptr, N, 0.f, nullptr, N, nullptr, N, c_dtype, s);
     if (bf16_native(h, c, t)) return SEXTANS_OK;
-    return ensure_bf16_workspaces(h, N, c.cbf16);
+    return ensure_bf16_workspaces(h, N, c.cbf16());
 }
 
 }  // extern "C"

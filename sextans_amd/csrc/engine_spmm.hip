@@ -8,11 +8,13 @@ using namespace sxe;
 
 namespace sxe {
 // The chains need one or two wavefronts for about a millisecond: on their own stream, beside the main kernel (fork after the B
-// panels are in place, join before the call's work on `s` is considered complete).  rm: from the caller's row-major B.
-int fork_chains(sextans_engine *h, const Call &c, const std::vector<Seg> &segs, int ch0, int ch1, bool rm) {
-    SX_HIP(hipEventRecord(h->ev_fork, c.s));
+// panels are in place, join before the call's work on o.s is considered complete).
+int fork_chains(sextans_engine *h, const Operands &o, const std::vector<Seg> &segs, int ch0, int ch1) {
+    SX_HIP(hipEventRecord(h->ev_fork, o.s));
     SX_HIP(hipStreamWaitEvent(h->aux_stream, h->ev_fork, 0));
-    launch_chains(h, segs, c.C_in, c.ldc_in, c.C_out, c.ldc, c.N, ch0, ch1, c.row_begin, c.alpha, c.beta, h->aux_stream, false, rm ? c.B : nullptr, rm ? c.ldb : 0);
+    Operands aux = o;
+    aux.s = h->aux_stream;
+    launch_chains(h, segs, aux, ch0, ch1);
     SX_HIP(hipEventRecord(h->ev_join, h->aux_stream));
     return SEXTANS_OK;
 }
@@ -143,8 +145,8 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
     // 32-bit byte offsets inside the wide kernels: panels and C columns (wide_fits), and the caller's B when the kernel stages
     // from it (wide_fits_b)
     const bool wide_fits = h->ps.plan_max_dict <= kWideMaxDict && (int64_t)h->K * 64 < ((int64_t)1 << 32) &&
-                           std::max(c.ldc, c.ldc_in) * 64 < ((int64_t)1 << 32);
-    const bool wide_fits_b = wide_fits && (!r.fuse_b || c.ldb * 64 < ((int64_t)1 << 32));
+                           std::max(c.o.ldc, c.o.ldc_in) * 64 < ((int64_t)1 << 32);
+    const bool wide_fits_b = wide_fits && (!r.fuse_b || c.o.ldb * 64 < ((int64_t)1 << 32));
     // N = 16 t + 8 on the register-resident panel kernel: the 8-column tail used to go to the gather kernel (the plan is built for
     // 16-column tiles) -- 4M-row FEM matrix: N = 24 2 152 us per step against 1 099 at N = 32.  It now runs as one more 16-column tile:
     // its B panel is zero in the 8 columns that do not exist, the kernel neither loads nor stores C there (`last_cols`), the passes of
@@ -177,26 +179,31 @@ RouteCM route_cm(const sextans_engine *h, const Call &c, Tiling t) {
 
 int run_window(sextans_engine *h, const Call &c, const RouteCM &r) {
     const int N = c.N;
-    hipStream_t s = c.s;
+    hipStream_t s = c.o.s;
     // B in 8-column panels (the reference's N tile), then one tile-major launch
     if (!r.skip_repack) {
         Prof p(h, &h->ev_repack, s);
-        launch_repack(8, c.B, c.ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->mat.d_touched);
+        launch_repack(8, c.o.B, c.o.ldb, h->d_Bp, h->K, 0, N / 8, s, h->col_lo, h->col_hi, -1, h->mat.d_touched);
         h->bp_layout = r.layout;
     }
     {
         Prof p(h, &h->ev_kernel, s);
+        const Operands o = on_panels(h, c.o);
         const int w0 = c.row_begin / h->win.rw, w1 = (c.row_end + h->win.rw - 1) / h->win.rw;
-        launch_window(h, h->d_Bp, c.C_in, c.ldc_in, c.C_out, c.ldc, N / 8, w0, w1, c.row_begin, c.alpha, c.beta, s);
+        launch_window(h, o, N / 8, w0, w1);
         const std::vector<Seg> p8{{8, 0, N / 8}};
         if (r.hubs) {
-            launch_hub_pieces(h, 8, *r.pt, h->d_Bp, N / 8, 0, r.v0, r.v1, s);
-            launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+            launch_hub_pieces(h, 8, *r.pt, o, N / 8, 0, r.v0, r.v1);
+            launch_fold(h, *r.pt, r.hub0, r.hub1, N, o);
         }
-        if (r.chains) launch_chains(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, r.ch0, r.ch1, c.row_begin, c.alpha, c.beta, s);
-        h->last_kernel = kernel_name(2, r.hubs || r.chains, h->dense.W > 0);
+        if (r.chains) launch_chains(h, p8, o, r.ch0, r.ch1);
+        h->last_kernel = kernel_name(MainKernel::kWindow, r.hubs || r.chains, h->dense.W > 0);
         if (h->dense.rb_n > 0) {
-            if (int rc = launch_rowblocks(h, p8, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
+            // (the row-block kernel takes a 16-column tile from ONE panel: 8-column panels go to it one at a time.  As one segment, the way
+            // this call was written before, columns 8 .. 15 of every tile were summed from column 0's B and stored)
+            std::vector<Seg> each;
+            for (int t = 0; t < N / 8; ++t) each.push_back(Seg{8, 8 * t, 1});
+            if (int rc = launch_rowblocks(h, each, o, N, c.row_end)) return rc;
             h->last_kernel = with_rowblocks(h, h->last_kernel);
         }
     }
@@ -205,8 +212,8 @@ int run_window(sextans_engine *h, const Call &c, const RouteCM &r) {
 }
 
 int run_colwise(sextans_engine *h, const Call &c) {
-    Prof p(h, &h->ev_kernel, c.s);
-    launch_colwise(h, false, c.N, c.B, c.ldb, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.row_end, c.alpha, c.beta, c.s);
+    Prof p(h, &h->ev_kernel, c.o.s);
+    launch_colwise(h, c.o, c.N, c.row_end);
     h->last_kernel = "spmm_csr_colwise";
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
@@ -214,87 +221,84 @@ int run_colwise(sextans_engine *h, const Call &c) {
 
 // One segment's main launch(es) and, for rows on the piece path, its piece launch
 int launch_segment(sextans_engine *h, const Call &c, const RouteCM &r, const Seg &g, RouteCM::Launch l) {
-    hipStream_t s = c.s;
-    const float *bp = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-    const float *cin = c.C_in + (int64_t)g.col0 * c.ldc_in;
-    float *cout = c.C_out + (int64_t)g.col0 * c.ldc;
-    const float *bsrc = r.fuse_b ? c.B + (int64_t)g.col0 * c.ldb : bp;
-    const int64_t bld = r.fuse_b ? c.ldb : 0;
+    const Operands panels = on_panels(h, c.o).at(g.col0);       // the segment on the repacked panels
+    const Operands src = r.fuse_b ? c.o.at(g.col0) : panels;    // ... or staged from the caller's column-major B
     const int *colpos = nullptr;   // of the piece launch at the end
+    PanelV2 a;
+    a.blk_begin = r.blk0; a.blk_end = r.blk1;
     switch (l) {
-        case RouteCM::kReorderedV2:
-            if (int rc = launch_panel_v2(h, 1, bp, h->d_Cs, r.cs_tile, h->d_Cs, r.cs_tile, g.ntiles, c.alpha, c.beta, s, 0, 0, h->cluster.psc.plan_nblk, 0, 2))
+        case RouteCM::kReorderedV2: {
+            Operands staged = panels;   // C: the row-major staging buffer, every block of the clustered plan
+            staged.C_in = staged.C_out = h->d_Cs; staged.ldc_in = staged.ldc = r.cs_tile; staged.row_base = 0;
+            a = PanelV2{};
+            a.order = V2Order::kReordered;
+            if (int rc = launch_panel_v2(h, staged, g.ntiles, a))
                 return rc;   // (a merged tail tile needs no mask here: its staging columns exist, the pass below writes back the valid ones)
             // rows on the piece path: their partial sums from the PERMUTED panels (column c sits at row colpos[c]); folded into C
             // behind the staging -> C pass below, which leaves C_in in their rows
             colpos = h->cluster.d_colpos;
             break;
+        }
         case RouteCM::kV2Wide: {
             const int nsuper = g.ntiles / 2;
-            if (int rc = launch_panel_v2(h, 2, bsrc, cin, c.ldc_in, cout, c.ldc, nsuper, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin))
-                return rc;
-            if (g.ntiles & 1) {
-                const int64_t c0 = (int64_t)nsuper * 32;
-                if (int rc = launch_panel(h, 16, r.fuse_b ? bsrc + c0 * c.ldb : bsrc + c0 * (int64_t)h->K, cin + c0 * c.ldc_in, c.ldc_in,
-                                          cout + c0 * c.ldc, c.ldc, 1, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin))
-                    return rc;
-            }
+            a.H = 2;
+            if (int rc = launch_panel_v2(h, src, nsuper, a)) return rc;
+            if (g.ntiles & 1)   // the odd 16-column tile behind the super tiles
+                if (int rc = launch_panel(h, 16, src.at(nsuper * 32), 1, r.blk0, r.blk1)) return rc;
             break;
         }
         case RouteCM::kSplitMixed:
-            if (int rc = launch_panel_v2(h, 1, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, 0, r.blk0, r.blk1, c.row_begin, 0, 16, 0, true))
-                return rc;
-            launch_rowgroup(h, 16, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->ps.d_rg_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end, g.ntiles,
-                            c.alpha, c.beta, s, 0, false, h->ps.d_rg_groups, h->ps.rg_ngroups);
+            a.dict_blocks_only = true;
+            if (int rc = launch_panel_v2(h, src, g.ntiles, a)) return rc;
+            launch_rowgroup(h, 16, panels, g.ntiles, c.row_end, h->ps.d_rg_skip, h->ps.d_rg_groups, h->ps.rg_ngroups);
             break;
         case RouteCM::kV2:
-            if (int rc = launch_panel_v2(h, 1, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.clustered ? 0 : r.blk0,
-                                         r.clustered ? h->cluster.psc.plan_nblk : r.blk1, c.row_begin, r.clustered ? 1 : 0, g.last_cols ? g.last_cols : 16))
-                return rc;
+            if (r.clustered) { a = PanelV2{}; a.order = V2Order::kBricks; }
+            if (g.last_cols) a.last_cols = g.last_cols;
+            if (int rc = launch_panel_v2(h, src, g.ntiles, a)) return rc;
             break;
-        default:   // the panel or the gather kernel, at the segment's width
-            if (l == RouteCM::kPanel) {
-                if (int rc = launch_panel(h, g.width, bsrc, cin, c.ldc_in, cout, c.ldc, g.ntiles, c.alpha, c.beta, s, bld, r.blk0, r.blk1, c.row_begin)) return rc;
-            } else {
-                launch_rowgroup(h, g.width, h->m_rp, h->m_rp + 1, h->m_ci, h->m_v, false, h->split.d_skip, bp, cin, c.ldc_in, cout, c.ldc, c.row_begin, c.row_end,
-                                g.ntiles, c.alpha, c.beta, s);
-            }
+        case RouteCM::kPanel:
+            if (int rc = launch_panel(h, g.width, src, g.ntiles, r.blk0, r.blk1)) return rc;
+            break;
+        case RouteCM::kRowgroup:
+            launch_rowgroup(h, g.width, panels, g.ntiles, c.row_end, h->split.d_skip);
     }
-    if (r.hubs) launch_hub_pieces(h, g.width, *r.pt, bp, g.ntiles, g.col0, r.v0, r.v1, s, colpos);   // (every spmm_csr_panel_v2 segment is 16 columns wide)
+    if (r.hubs) launch_hub_pieces(h, g.width, *r.pt, panels, g.ntiles, g.col0, r.v0, r.v1, colpos);   // (every spmm_csr_panel_v2 segment is 16 columns wide)
     return SEXTANS_OK;
 }
 
 int run_segments(sextans_engine *h, const Call &c, const RouteCM &r) {
     const int N = c.N;
-    hipStream_t s = c.s;
-    auto seg_cols = [](const Seg &g) { return g.last_cols ? (g.ntiles - 1) * g.width + g.last_cols : g.ntiles * g.width; };
+    hipStream_t s = c.o.s;
+    const Operands panels = on_panels(h, c.o);
     if (!r.skip_repack || r.reordered) {
         Prof p(h, &h->ev_repack, s);
         if (!r.skip_repack) {
             h->bp_layout = r.layout;
             for (const Seg &g : r.segs) {
                 float *dst = h->d_Bp + (size_t)h->K * (size_t)g.col0;
-                if (r.reordered && g.width == 16 && h->cluster.d_colpos) launch_repack_perm(h, c.B, c.ldb, dst, g.col0, g.ntiles, seg_cols(g), s);
-                else launch_repack(g.width, c.B, c.ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, seg_cols(g), h->mat.d_touched);
+                if (r.reordered && g.width == 16 && h->cluster.d_colpos) launch_repack_perm(h, c.o.B, c.o.ldb, dst, g.col0, g.ntiles, g.cols(), s);
+                else launch_repack(g.width, c.o.B, c.o.ldb, dst, h->K, g.col0, g.ntiles, s, h->col_lo, h->col_hi, g.cols(), h->mat.d_touched);
             }
         }
         if (r.reordered)
             for (const Seg &g : r.segs)
                 if (g.width == 16)
-                    launch_repack(16, c.C_in, c.ldc_in, h->d_Cs, h->M, g.col0, g.ntiles, s, 0, -1, seg_cols(g));   // C_in -> row-major tiles
+                    launch_repack(16, c.o.C_in, c.o.ldc_in, h->d_Cs, h->M, g.col0, g.ntiles, s, 0, -1, g.cols());   // C_in -> row-major tiles
     }
     {
         Prof p(h, &h->ev_kernel, s);
         if (r.chains && !r.reordered)
-            if (int rc = fork_chains(h, c, r.segs, r.ch0, r.ch1, false)) return rc;
+            if (int rc = fork_chains(h, panels, r.segs, r.ch0, r.ch1)) return rc;
         for (size_t i = 0; i < r.segs.size(); ++i)
             if (int rc = launch_segment(h, c, r, r.segs[i], r.launch[i])) return rc;
-        if (r.hubs && !r.reordered) launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+        if (r.hubs && !r.reordered) launch_fold(h, *r.pt, r.hub0, r.hub1, N, panels);
         if (r.chains && !r.reordered) SX_HIP(hipStreamWaitEvent(s, h->ev_join, 0));
         const bool v2_used = std::any_of(r.launch, r.launch + r.segs.size(), [](RouteCM::Launch l) { return l < RouteCM::kPanel; });
-        h->last_kernel = r.reordered ? "spmm_csr_panel_v2_reordered" : kernel_name(v2_used ? 3 : r.panel ? 1 : 0, r.hubs || r.chains, h->dense.W > 0);
+        h->last_kernel = r.reordered ? "spmm_csr_panel_v2_reordered"
+                                     : kernel_name(v2_used ? MainKernel::kPanelV2 : r.panel ? MainKernel::kPanel : MainKernel::kRowgroup, r.hubs || r.chains, h->dense.W > 0);
         if (h->dense.rb_n > 0) {   // dense blocks of 16 rows on the fp32 matrix cores, from the same panels (the kernels above skipped their rows)
-            if (int rc = launch_rowblocks(h, r.segs, c.C_in, c.ldc_in, c.C_out, c.ldc, N, c.row_begin, c.row_end, c.alpha, c.beta, s)) return rc;
+            if (int rc = launch_rowblocks(h, r.segs, panels, N, c.row_end)) return rc;
             h->last_kernel = with_rowblocks(h, h->last_kernel);
         }
     }
@@ -302,10 +306,10 @@ int run_segments(sextans_engine *h, const Call &c, const RouteCM &r) {
         Prof p(h, &h->ev_post, s);
         for (const Seg &g : r.segs)
             if (g.width == 16)
-                launch_tiles_to_colmajor(h->d_Cs, c.C_out, c.ldc, h->M, g.col0, g.ntiles, seg_cols(g), s);
-        if (r.hubs) launch_fold(h, *r.pt, r.hub0, r.hub1, N, c.C_in, c.ldc_in, c.C_out, c.ldc, c.row_begin, c.alpha, c.beta, false, s);
+                launch_tiles_to_colmajor(h->d_Cs, c.o.C_out, c.o.ldc, h->M, g.col0, g.ntiles, g.cols(), s);
+        if (r.hubs) launch_fold(h, *r.pt, r.hub0, r.hub1, N, panels);
         // chain rows write C themselves: behind the staging -> C pass (which left C_in in their rows), from the permuted panels
-        if (r.chains) launch_chains(h, r.segs, c.C_in, c.ldc_in, c.C_out, c.ldc, N, r.ch0, r.ch1, c.row_begin, c.alpha, c.beta, s, true);
+        if (r.chains) launch_chains(h, r.segs, panels, r.ch0, r.ch1, true);
     }
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
@@ -356,6 +360,11 @@ int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float
     if (nrows == 0) return SEXTANS_OK;
     Tiling t;
     if (int rc = prepare(h, N, whole, &t)) return rc;
+    Call c;
+    c.N = N; c.row_begin = row_begin; c.row_end = row_end; c.flags = flags; c.whole = whole;
+    c.o.B = d_B; c.o.ldb = ldb;   // (column-major: OperandsT's defaults)
+    c.o.C_in = d_C_in; c.o.ldc_in = ldc_in; c.o.C_out = d_C_out; c.o.ldc = ldc;
+    c.o.alpha = alpha; c.o.beta = beta; c.o.s = s; c.o.row_base = row_begin;
     if (h->dense.W > 0) {
         // Dense tiles first, on the matrix cores: C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block
         // rows (and alpha * 0 + beta * C_in below them); the CSR kernels then add alpha * (A_rest * B) on top
@@ -364,10 +373,9 @@ int sextans_spmm_device_rows(sextans_handle_t h, int N, float alpha, const float
             g_last_error = "mfma_dense_tiles = 1 needs whole-matrix calls and N % 32 == 0";
             return SEXTANS_ERR_INVALID;
         }
-        if (int rc = launch_dense_tiles(h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, s)) return rc;
-        beta = 1.0f; d_C_in = d_C_out; ldc_in = ldc;
+        if (int rc = launch_dense_tiles(h, N, c.o)) return rc;
+        c.o.beta = 1.0f; c.o.C_in = d_C_out; c.o.ldc_in = ldc;
     }
-    const Call c{N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, row_begin, row_end, flags, s, whole};
     const RouteCM r = route_cm(h, c, std::move(t));
     switch (r.path) {
         case RouteCM::kWindow: return run_window(h, c, r);

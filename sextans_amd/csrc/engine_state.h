@@ -3,7 +3,8 @@
 //   engine_spmm.hip     the column-major SpMM entry (sextans_spmm_device_rows): route_cm decides, run_* launch
 //   engine_rowmajor.hip the row-major entries (sextans_spmm_device_rm, its bf16 form), sextans_prepare and rm_plan
 //   engine_host.hip     host-buffer and reference-shaped entry points (sextans_spmm_host, sextans_invoke, sextans_spmm_csr)
-//   engine_launch.hip   every launch of an SpMM kernel (engine_launch.h): the only unit that instantiates them (dispatch.h)
+//   engine_launch.hip   every launch of an SpMM kernel (engine_launch.h): the only unit that instantiates them (dispatch.h); it is
+//                       handed the dense operands as one Operands (below), the layout of B named by BLayout
 //   engine_plan.hip     everything prepared once per matrix, outside every timed region: long-row split, packed panel plans
 //                       (natural / clustered / reordered), window stream -- the analogue of the reference's host-side scheduling
 //                       and packing (sextans-host.cpp:114-148)
@@ -50,19 +51,45 @@ using sx::DevBuf;
 struct EventPair { hipEvent_t a, b; };
 constexpr int kRowsNoFuseB = 0x100;   // internal flag of sextans_spmm_device_rows: always stage from the repacked panel
 constexpr int kPanelFloats = 9216;    // at most 36 KiB of LDS for the B panel (576 rows at N-tile 16)
-struct Seg { int width, col0, ntiles; int last_cols = 0; };   // N is covered by segments of equally wide tiles; last_cols != 0: valid columns of the
-                                                               // segment's LAST tile (8: the tail of N = 16 t + 8 merged into the 16-column segment)
+struct Seg {   // N is covered by segments of equally wide tiles; last_cols != 0: valid columns of the segment's LAST tile (8: the tail of
+    int width, col0, ntiles, last_cols = 0;   // N = 16 t + 8 merged into the 16-column segment)
+    int cols() const { return last_cols ? (ntiles - 1) * width + last_cols : ntiles * width; }   // the segment's valid columns
+};
 struct Tiling {                  // what prepare() decided for an N-column call
     std::vector<Seg> segs;       // N in segments of equally wide tiles
     int W = 0;                   // main tile width: the packed plan is built for it
     bool panel = false;          // the LDS-panel plan serves the main rows
     bool window = false;         // ... or the K-window kernel
 };
-// One SpMM as the caller asked for it: operands, row range [row_begin, row_end) (whole: all of the matrix), flags, stream
-struct Call {
-    int N; float alpha; const float *B; int64_t ldb; float beta; const float *C_in; int64_t ldc_in; float *C_out; int64_t ldc;
-    int row_begin, row_end, flags; hipStream_t s; bool whole;
+// Where B lies: repacked panels in the engine's d_Bp, or the caller's own matrix in either layout
+enum class BLayout { kPanels, kColMajor, kRowMajor };
+// The dense operands of a call or of one launch: what the routes hand the launch layer (engine_launch.h).  TB / TC: element types of B
+// and C -- float, or (the bf16 entry) uint16_t and bytes.
+template <class TB, class TC>
+struct OperandsT {
+    const TB *B = nullptr;
+    int64_t ldb = 0;             // elements between B's columns (kColMajor; kPanels: K, a column's share of every panel) or rows (kRowMajor)
+    BLayout layout = BLayout::kColMajor;
+    const TC *C_in = nullptr;
+    TC *C_out = nullptr;
+    int64_t ldc_in = 0, ldc = 0; // ... between C's columns, or its rows (c_rm); the staging forms of spmm_csr_panel_v2: floats per tile
+    bool c_rm = false;           // C is row-major
+    int c_elem = 1;              // TCs per element of C (the bf16 entry addresses C in bytes: 4 = fp32, 2 = bf16)
+    float alpha = 1.f, beta = 0.f;
+    hipStream_t s = nullptr;
+    int row_base = 0;            // the C pointers address this row as their row 0 (row-range calls)
+    OperandsT at(int64_t col) const {   // advanced to column `col` (a segment's first): the one place that knows how each layout steps over columns
+        OperandsT o = *this;
+        o.B += layout == BLayout::kRowMajor ? col : col * ldb;
+        o.C_in += c_rm ? col * c_elem : col * ldc_in;
+        o.C_out += c_rm ? col * c_elem : col * ldc;
+        return o;
+    }
 };
+using Operands = OperandsT<float, float>;
+using OperandsBf16 = OperandsT<uint16_t, char>;
+// One SpMM as the caller asked for it: operands (o.B: the caller's B), row range [row_begin, row_end) (whole: all of the matrix), flags
+struct Call { Operands o; int N = 0, row_begin = 0, row_end = 0, flags = 0; bool whole = true; };
 }  // namespace sxe
 
 struct sextans_engine {
@@ -421,18 +448,17 @@ inline bool colwise_wanted(const sextans_engine *h) { return h->opt_kernel == 4 
 // every row of the main matrix is on the CSR kernels: no dense tiles on the matrix cores, no routed row blocks
 inline bool csr_only(const sextans_engine *h) { return h->dense.W == 0 && h->dense.rb_n == 0; }
 // dense 32x32 tiles on the matrix cores (engine_bell.hip): C_out = alpha * (A_dense * bf16(B)) + beta * C_in for the full block rows
-int launch_dense_tiles(sextans_engine *h, int N, float alpha, const float *d_B, int64_t ldb, float beta, const float *d_C_in,
-                       int64_t ldc_in, float *d_C_out, int64_t ldc, hipStream_t s);
-// dense row blocks on the fp32 matrix cores (engine_bell.hip): the routed blocks of [row_begin, row_end) from the B panels in d_Bp
-int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, int N, int row_begin,
-                     int row_end, float alpha, float beta, hipStream_t s);
+int launch_dense_tiles(sextans_engine *h, int N, const Operands &o);
+// dense row blocks on the fp32 matrix cores (engine_bell.hip): the routed blocks of [o.row_base, row_end) from the B panels o.B
+int launch_rowblocks(sextans_engine *h, const std::vector<Seg> &plan, const Operands &o, int N, int row_end);
 int mark_rowblock_skip(sextans_engine *h);   // after ensure_split: the routed rows join the rows the CSR kernels never write
 
 int rm_plan(sextans_engine *h, int N, hipStream_t s, Tiling *out = nullptr);   // engine_rowmajor.hip: planning half of sextans_spmm_device_rm
 // argument checks of the bf16 row-major entry points (engine_rowmajor.hip): SEXTANS_ERR_INVALID or SEXTANS_OK, nothing touched
 int check_rm_bf16_args(sextans_handle_t h, int N, const uint16_t *d_B, int64_t ldb, const void *d_C_in, int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype);
-// engine_spmm.hip: the exact chains [ch0, ch1) of a call on the engine's side stream, beside its main kernel (rm: from the caller's row-major B)
-int fork_chains(sextans_engine *h, const Call &c, const std::vector<Seg> &segs, int ch0, int ch1, bool rm);
+// engine_spmm.hip: the exact chains [ch0, ch1) of a call on the engine's side stream, beside its main kernel on o.s (o.B: the repacked
+// panels, or the caller's row-major B)
+int fork_chains(sextans_engine *h, const Operands &o, const std::vector<Seg> &segs, int ch0, int ch1);
 // engine_dist.hip: position -> row table of the clustered plan (+ row0), also what sextans_export_row_order reads
 void cc_table(sextans_engine *h, int row0, int *d_out, hipStream_t s);
 

@@ -331,6 +331,33 @@ def test_a_few_long_rows_do_not_take_the_clustered_plans_away(engine, oracle, N)
         _set(engine)
 
 
+def test_reordered_form_with_a_bucketed_row_and_an_exact_chain(engine, oracle):
+    """The reordered form at N = 24 (16 columns reordered + an 8-column tail, merged into the 16-column segment or not: route_cm decides
+    from the workspaces) with one row on the piece path and one exact chain: pieces and chain read the PERMUTED panels, fold and chain
+    write the caller's C behind the staging -> C pass."""
+    from sextans_amd import meshgen
+    rp, ci, v, M = _fem(18, 17, 16, 3)
+    rp, ci, v = _with_long_rows(rp, ci, v, M, [9], 700)                 # > 512 entries: piece path, one piece
+    rp, ci, v = _with_long_rows(rp, ci, v, M, [M // 2], 3000, seed=2)   # > 1024: exact chain
+    rp, ci, v = meshgen.permute_symmetric(rp, ci, v, M, meshgen.node_permutation(M // 3, 3, 4))
+    N = 24
+    B, C0 = _operands(np.random.RandomState(N), M, M, N)
+    want = C0.copy()
+    oracle.spmm(M, N, M, ALPHA, rp, ci, v, B, BETA, want)
+    try:
+        _set(engine, row_cluster=2, fuse_b=0)
+        engine.set_matrix_csr(M, M, rp, ci, v)
+        for rp_time in (1, 3):
+            out = C0.copy()
+            engine.spmm(N, ALPHA, B, BETA, out, rp_time=rp_time)
+            assert engine.last_kernel() == "spmm_csr_panel_v2_reordered", engine.last_kernel()
+            assert np.array_equal(out.view(np.uint32), want.view(np.uint32)), rp_time
+        assert int(engine.get_stat("row_cluster")) == 2 and int(engine.get_stat("piece_path_rows")) == 2
+        assert int(engine.get_stat("exact_chain_rows")) == 1 and int(engine.get_stat("reassociated_rows")) == 0
+    finally:
+        _set(engine)
+
+
 def test_dof_major_numbering_gets_the_graph_plan(engine, oracle):
     """All x unknowns, then all y, then all z (what block-field FEM codes write): a row's 81 columns sit in three far-apart ranges, the
     grid detector still finds the strides, but a brick holds ONE unknown per node and its dictionary is three times the node-major one

@@ -75,6 +75,46 @@ def test_dense_blocks_bitwise_equal_to_the_fma_chain(sx, oracle, N):
         assert "rowblock" not in e.last_kernel()
 
 
+def test_dense_blocks_beside_the_window_kernel(sx, oracle):
+    """"kernel" = 3: the routed blocks are summed from the 8-column panels the window kernel's repack laid out.  Routed rows: the bits of the
+    fma chain, (a); the rows left to the window kernel, whose "exact" = 0 form states a tolerance only: the bits of the same call without
+    routing, (b)."""
+    rs = np.random.RandomState(3)
+    N = 16
+    rp, ci, v, M, K = _dense_blocks(rs, 20, 30, 4)
+    M_full = M
+    extra_rp, extra_ci, extra_v = random_csr(rs, 9, K, 20)   # rows that stay on the window kernel
+    rp = np.concatenate([rp, rp[-1] + extra_rp[1:]]).astype(np.int32)
+    ci = np.concatenate([ci, extra_ci]).astype(np.int32); v = np.concatenate([v, extra_v]).astype(np.float32)
+    M += 9
+    B = rs.uniform(-1, 1, K * N).astype(np.float32); C0 = rs.uniform(-1, 1, M * N).astype(np.float32)
+    want = C0.copy()
+    oracle.spmm_fma(M, N, K, ALPHA, rp, ci, v, B, BETA, want)
+    with sx.Engine(0) as e:
+        e.set_option("exact", 0)
+        e.set_option("kernel", 3)
+        e.set_option("window_rows", 320)
+        e.set_matrix_csr(M, K, rp, ci, v)
+        plain = _run(e, M, N, K, B, C0).reshape(N, M)
+        assert e.last_kernel() == "spmm_csr_window", e.last_kernel()
+        e.set_option("mfma_dense_tiles", 2)
+        got = _run(e, M, N, K, B, C0).reshape(N, M)
+        assert e.last_kernel() == "spmm_csr_window+rowblock_mfma_f32", e.last_kernel()
+        assert int(e.get_stat("dense_tiles")) == M_full // 16
+        assert np.array_equal(got[:, :M_full].view(np.uint32), want.reshape(N, M)[:, :M_full].view(np.uint32))
+        assert np.array_equal(got[:, M_full:].view(np.uint32), plain[:, M_full:].view(np.uint32))
+        # two wavefront-aligned row ranges, the second on the panels the first one repacked: the bits of the whole-matrix call
+        import torch
+        st = torch.cuda.current_stream().cuda_stream
+        dB = torch.from_numpy(B).cuda(); dC = torch.from_numpy(C0).cuda(); out = torch.full((M * N,), float("nan"), device="cuda")
+        for i, (c0, c1) in enumerate(((0, 320), (320, M))):
+            e.spmm_device_rows(N, ALPHA, dB.data_ptr(), K, BETA, dC.data_ptr() + 4 * c0, M, out.data_ptr() + 4 * c0, M, c0, c1,
+                               reuse_b_panels=i > 0, stream=st)
+            assert e.last_kernel() == "spmm_csr_window+rowblock_mfma_f32", (i, e.last_kernel())
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy().reshape(N, M).view(np.uint32), got.view(np.uint32))
+
+
 @pytest.mark.parametrize("dof,thr", [(6, 50), (3, 30), (3, 50)])
 def test_fem_row_blocks_partial_routing(sx, oracle, dof, thr):
     """A 3-D FEM matrix: 6-dof node blocks fill their 16 x 4 fragments to ~0.6 (routed at the default threshold), 3-dof ones to ~0.35

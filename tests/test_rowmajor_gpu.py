@@ -283,6 +283,7 @@ def test_rowmajor_long_rows_pieces_and_exact_chains(engine, oracle, N):
             assert engine.last_kernel() == kernel or engine.last_kernel() in kernel, (name, N, engine.last_kernel())
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (name, N, kw)
         assert engine.get_stat("piece_path_rows") > 0 and len(engine.reassociated_rows()) == 0
+        assert engine.get_stat("exact_chain_rows") > 0     # (every case has rows beyond the chain threshold: the chain kernel ran beside the main one)
         # the column-major entry point on the same engine afterwards
         cm = np.ascontiguousarray(C0.T).reshape(-1).copy()
         engine.spmm(N, ALPHA, np.ascontiguousarray(B.T).reshape(-1), BETA, cm)

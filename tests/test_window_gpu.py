@@ -133,6 +133,40 @@ def test_row_ranges_and_strides_device_resident(engine, oracle):
     assert np.array_equal(out.cpu().numpy().view(np.uint32), want.view(np.uint32))
 
 
+def test_long_rows_beside_the_window_kernel(engine, oracle):
+    """Strict order with one bucketed long row (piece path, one piece) and one exact-chain row beside the window kernel: the whole
+    matrix, then two wavefront-aligned row ranges, the second one on the 8-column panels the first one repacked.  Every launch of a
+    call reads those panels and addresses C from the range's first row: bit-identical."""
+    import torch
+    rs = np.random.RandomState(77)
+    M, K, N, RW = 640, 2000, 16, 320
+    lens = rs.poisson(9, M)
+    lens[5], lens[400] = 300, 1500                          # bucketed (> max(32, 2 x mean)) / exact chain (> 1024)
+    rp = np.zeros(M + 1, np.int32); rp[1:] = np.cumsum(lens)
+    ci = np.concatenate([np.sort(rs.choice(K, l, replace=False)) for l in lens]).astype(np.int32)
+    v = rs.uniform(-1, 1, rp[-1]).astype(np.float32)
+    B = rs.uniform(-1, 1, K * N).astype(np.float32)
+    C0 = rs.uniform(-1, 1, M * N).astype(np.float32)
+    want = C0.copy()
+    oracle.spmm(M, N, K, ALPHA, rp, ci, v, B, BETA, want)
+    engine.set_option("exact_chain", 1)
+    out = run(engine, M, K, rp, ci, v, N, ALPHA, B, BETA, C0, bucket_rows=-1, window_rows=RW, window_cols=512)
+    assert engine.get_stat("piece_path_rows") == 2 and engine.get_stat("exact_chain_rows") == 1 and len(engine.reassociated_rows()) == 0
+    assert engine.last_kernel() == "spmm_csr_window+hub_pieces"
+    assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    dB = torch.from_numpy(B).cuda(); dCin = torch.from_numpy(C0).cuda()
+    st = torch.cuda.current_stream().cuda_stream
+    got = torch.full((M * N,), float("nan"), device="cuda")
+    for i, (c0, c1) in enumerate(((0, RW), (RW, M))):       # row 5 lies in the first range, row 400 in the second
+        slab = torch.full(((c1 - c0) * N,), float("nan"), device="cuda")
+        engine.spmm_device_rows(N, ALPHA, dB.data_ptr(), K, BETA, dCin.data_ptr() + 4 * c0, M, slab.data_ptr(), c1 - c0,
+                                c0, c1, reuse_b_panels=i > 0, stream=st)
+        assert engine.last_kernel() == "spmm_csr_window+hub_pieces", (i, engine.last_kernel())
+        got.view(N, M)[:, c0:c1] = slab.view(N, c1 - c0)
+    torch.cuda.synchronize()
+    assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32))
+
+
 def test_auto_dispatch_rules(engine, sx):
     """kernel=0: small B (fits the L2s) and matrices with B-row reuse never take the window kernel; a skewed
     matrix is rejected even when forced candidates exist."""
