@@ -437,7 +437,8 @@ int sextans_spmm_device_rm(sextans_handle_t h, int N, float alpha, const float *
 #define SEXTANS_LAYOUT_COLMAJOR 0
 #define SEXTANS_LAYOUT_ROWMAJOR 1
 /* SEXTANS_LAYOUT_ROWMAJOR_T: the backward-pass forms -- A^T (sextans_csr_transpose_device) and everything the row-major calls of
- * sextans_spmm_t_device_rm build (plans, workspaces) on the companion engine, the row table of sextans_sddmm_device_rm and the tables of sextans_row_softmax_device.  After it, a transposed call for N, an SDDMM call and a row-softmax call allocate nothing
+ * sextans_spmm_t_device_rm build (plans, workspaces) on the companion engine, the row table of sextans_sddmm_device_rm and the tables of sextans_row_softmax_device -- those of A and, for the column pass of
+ * sextans_attention_backward_device, those of A^T.  After it, a transposed call for N, an SDDMM call, a row-softmax call and the fused attention calls allocate nothing
  * and do not synchronise with the host: they may be captured into a hipGraph.  (Layout 2 is unused.) */
 #define SEXTANS_LAYOUT_ROWMAJOR_T 3
 int sextans_prepare(sextans_handle_t h, int N, int layout, void *stream);
@@ -535,6 +536,53 @@ int sextans_sddmm_device_rm(sextans_handle_t h, int N, float alpha, const float 
  * blocked-ELL bf16 matrix is not covered); nnz == 0 or M == 0: OK, nothing to do. */
 int sextans_row_softmax_device(sextans_handle_t h, float scale, const float *d_x, float *d_p, void *stream);
 int sextans_row_softmax_backward_device(sextans_handle_t h, float scale, const float *d_p, const float *d_g, float *d_dx, void *stream);
+
+/* ---- Fused multi-head attention on A's pattern: what sddmm -> row_softmax -> value refresh -> spmm computes per head, in one kernel
+ * pass per direction for all heads, with nothing of size nnz written and no value refresh.  Closest thing in the reference: none.
+ *
+ * Operands are ROW-major fp32 with the heads side by side in a row: Q is M x (heads * d), head h in columns [h * d, (h + 1) * d) -- a
+ * contiguous (M, heads, d) array --, K is K x (heads * d), V is K x (heads * dv), O and G are M x (heads * dv); lse and delta are
+ * M x heads, dense.  Every operand has its own leading dimension (floats between rows).  d_bias: NULL, or nnz floats in the CSR entry
+ * order the matrix was set with, shared by all heads -- an explicit pointer: A's own VALUES ARE NEITHER READ NOR WRITTEN.
+ * For every row r, head h and stored entry e = (r, c):
+ *     forward    s_e = scale * (<Q[r,h,:], K[c,h,:]> + bias_e);   m = max_e s_e;   Z = sum_e exp(s_e - m)
+ *                O[r,h,:] = (sum_e exp(s_e - m) * V[c,h,:]) / Z;   lse[r,h] = m + log Z
+ *     backward   delta[r,h] = <O[r,h,:], G[r,h,:]>;   p_e = exp(s_e - lse[r,h]);   ds_e = p_e * (<G[r,h,:], V[c,h,:]> - delta[r,h])
+ *                dQ[r,h,:] = sum_e scale ds_e K[c,h,:];   dK[c,h,:] = sum_e scale ds_e Q[r,h,:];   dV[c,h,:] = sum_e p_e G[r,h,:]
+ *                dbias_e = sum_h scale ds_e   (d_dbias != NULL; heads added in ascending order)
+ * The forward is an online softmax (a running m, Z and accumulator, rescaled when m grows); the backward recomputes p from lse in two
+ * passes, rows of A for delta, dQ and dbias, rows of A^T (sextans_csr_transpose_device's arrays and entry permutation) for dK and dV.
+ * fp32 throughout, FMA in the dot products and accumulations, exp as in the row softmax; every sum runs in an order fixed by the
+ * pattern and the launch shape and there are no float atomics: the same call gives the same bits on every run and every stream.  The
+ * same arithmetic in SEXTANS_MODE_STRICT and SEXTANS_MODE_FAST.  NOT BIT-EQUAL to the composition of sextans_sddmm_device_rm,
+ * sextans_row_softmax_device and sextans_spmm_device_rm (which rounds every product and associates its sums differently): equal within
+ * the tolerance of a chain of fp32 operations.
+ * Special values as sextans_row_softmax_device: a -inf score beside finite ones contributes exactly 0; a row of only -inf scores, or
+ * with a +inf or NaN score, gives NaN in that (row, head); an empty row writes O = +0 and lse = -inf.  Empty rows and columns get zero
+ * gradients; every element of O, lse, delta, dQ, dK, dV (and dbias) is written.
+ * d and dv: multiples of 8 in [8, 128]; both are served by one register width, the smallest of 8 / 16 / 32 / 64 / 128 floats that
+ * holds the larger, with predicated loads.  Leading dimensions: >= heads * d (heads * dv), multiples of 4; every pointer 16-byte
+ * aligned.  The outputs must not overlap the inputs or each other.
+ * Work is dealt by non-zero count with the row softmax's tables (a group of lanes sized to the row takes a (row, head); K and V rows
+ * come in as 16-byte gathers; the Q row and the accumulator stay in registers); rows -- in the column pass: columns -- of more than
+ * 2048 entries get one workgroup per head whose four wavefronts are merged through LDS in a fixed order (one row is not split over
+ * workgroups).  The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call also
+ * builds A^T (the arrays and the companion engine's tables only, none of its SpMM plans); both synchronise then.
+ * sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) builds all of it ahead.  After that a call allocates nothing, reads nothing
+ * back and does not synchronise: it can be captured into a hipGraph.  Nothing is allocated beyond those tables (stat "device_bytes":
+ * the terms of the row softmax and of A^T).
+ * sextans_last_kernel: "attention_fused" / "attention_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, heads < 1, d or dv not a multiple of 8 in [8, 128], a leading dimension too small or not a multiple
+ * of 4, a misaligned pointer, a NULL pointer other than d_bias / d_dbias with nnz > 0; SEXTANS_ERR_STATE: no CSR matrix set.  M == 0
+ * or nnz == 0: OK -- O and the gradients are zeroed, lse = -inf. */
+int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream);
+int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv,
+    float *d_dbias, void *stream);
 
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *

@@ -71,7 +71,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_csr_transpose_device", "sextans_spmm_t_device_rm", "sextans_sddmm_device_rm",
     "sextans_update_values", "sextans_update_values_device",
     "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16",
-    "sextans_row_softmax_device", "sextans_row_softmax_backward_device"))
+    "sextans_row_softmax_device", "sextans_row_softmax_backward_device",
+    "sextans_attention_device", "sextans_attention_backward_device"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 
@@ -266,6 +267,12 @@ def lib():
     L.sextans_prepare_rm_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.sextans_row_softmax_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_row_softmax_backward_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.sextans_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                    C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -770,6 +777,22 @@ class Engine:
     def row_softmax_backward_device(self, scale, d_p, d_g, d_dx, stream=None):
         """dx = scale * p * (g - sum_row p g) (sextans_row_softmax_backward_device); d_dx may be d_g or d_p."""
         _check(lib().sextans_row_softmax_backward_device(self._h, scale, d_p, d_g, d_dx, stream), "row_softmax_backward_device")
+
+    def attention_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, stream=None):
+        """Fused multi-head attention on A's pattern (sextans_attention_device): O[r, h, :] = softmax_e(scale * (<Q[r, h, :], K[c, h, :]> +
+        bias_e)) V[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads floats).  Heads lie side
+        by side in a row (a contiguous (rows, heads, d) tensor); d_bias: None, or nnz floats in CSR entry order shared by all heads.  A's
+        own values are not read."""
+        _check(lib().sextans_attention_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, stream),
+               "attention_device")
+
+    def attention_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta,
+                                  d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, stream=None):
+        """dQ, dK, dV (and, d_dbias not None, the bias gradient: nnz floats) of attention_device from its O and lse and the upstream
+        gradient G (sextans_attention_backward_device); d_delta: M * heads floats of workspace the call writes."""
+        _check(lib().sextans_attention_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
+                                                       d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, stream),
+               "attention_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

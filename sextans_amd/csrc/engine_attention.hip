@@ -1,0 +1,122 @@
+// engine_attention.hip -- fused multi-head attention over the pattern of the CSR matrix on an engine handle (include/sextans_amd.h):
+//   sextans_attention_device            O = softmax(scale * (Q K^T + bias) on A's pattern) V per head, and the rows' log-sum-exp
+//   sextans_attention_backward_device   dQ, dK, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
+// Kernels and the lane mapping: attention_kernels.h.  The row pass uses the row softmax's tables of this engine, the column pass those
+// of the companion engine that holds A^T (engine_transpose.hip) -- no table of its own, and A's values are never read.
+#include "attention_kernels.h"
+#include "engine_state.h"
+
+namespace sxe {
+namespace {
+
+bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
+bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
+uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
+int check_dims(sextans_handle_t h, int heads, int d, int dv) {
+    if (!h || heads < 1 || bad_dim(d) || bad_dim(dv)) return SEXTANS_ERR_INVALID;
+    return SEXTANS_OK;
+}
+
+template <int PASS, int T, int P, int U>
+void launch_width(const sextans_engine *e, const sx::AttnArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
+    hipLaunchKernelGGL((sx::attn_rows<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow, nw,
+                       heads_inside ? 1 : 0);
+    if (e->softmax.nchunks > 0)
+        hipLaunchKernelGGL((sx::attn_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
+                           e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
+}
+
+// e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  One register width serves both
+// head dimensions: the smallest of 8 / 16 / 32 / 64 / 128 floats that holds the larger one.
+template <int PASS>
+void launch_pass(const sextans_engine *e, const sx::AttnArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const int w = a.d > a.dv ? a.d : a.dv;
+    constexpr bool F = PASS == sx::kAttnForward;
+    if (w <= 8) launch_width<PASS, 2, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
+    else if (w <= 16) launch_width<PASS, 4, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
+    else if (w <= 32) launch_width<PASS, 8, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
+    else if (w <= 64) launch_width<PASS, 8, 2, F ? 4 : 2>(e, a, perm, heads_inside, s);
+    else launch_width<PASS, 8, 4, F ? 2 : 1>(e, a, perm, heads_inside, s);
+}
+
+void fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s) {
+    if (!out || rows <= 0 || cols <= 0) return;
+    hipLaunchKernelGGL(sx::attn_fill, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
+}
+
+}  // namespace
+}  // namespace sxe
+
+using namespace sxe;
+
+extern "C" {
+
+int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                             const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+    if (int rc = check_dims(h, heads, d, dv)) return rc;   // nothing here needs a device
+    if (bad_ld(ldq, (int64_t)heads * d) || bad_ld(ldk, (int64_t)heads * d) || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv))
+        return SEXTANS_ERR_INVALID;
+    if (((bits(d_Q) | bits(d_K) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->M == 0 || h->nnz == 0) {   // every row is empty
+        fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
+        fill(d_lse, h->M, heads, heads, -INFINITY, s);
+        SX_HIP(hipGetLastError());
+        return SEXTANS_OK;
+    }
+    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    sx::AttnArgs a{};
+    a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
+    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+    SX_HIP(hipGetLastError());
+    h->last_kernel = h->softmax.nchunks > 0 ? "attention_fused+long_rows" : "attention_fused";
+    return SEXTANS_OK;
+}
+
+int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
+                                      int64_t ldk, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse,
+                                      const float *d_G, int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV,
+                                      int64_t lddv, float *d_dbias, void *stream) {
+    if (int rc = check_dims(h, heads, d, dv)) return rc;
+    const int64_t hd = (int64_t)heads * d, hdv = (int64_t)heads * dv;
+    if (bad_ld(ldq, hd) || bad_ld(ldk, hd) || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) || bad_ld(lddq, hd) || bad_ld(lddk, hd) ||
+        bad_ld(lddv, hdv))
+        return SEXTANS_ERR_INVALID;
+    if (((bits(d_Q) | bits(d_K) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dQ) | bits(d_dK) | bits(d_dV) |
+          bits(d_dbias)) & 15) != 0)
+        return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV)) return SEXTANS_ERR_INVALID;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->M == 0 || h->nnz == 0) {
+        fill(d_delta, h->M, heads, heads, 0.0f, s);
+        fill(d_dQ, h->M, (int)hd, lddq, 0.0f, s);
+        fill(d_dK, h->K, (int)hd, lddk, 0.0f, s);
+        fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
+        SX_HIP(hipGetLastError());
+        return SEXTANS_OK;
+    }
+    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = ensure_transpose(h, s)) return rc;
+    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
+    sx::AttnArgs a{};
+    a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
+    a.out_delta = d_delta; a.dQ = d_dQ; a.dK = d_dK; a.dV = d_dV; a.dbias = d_dbias;
+    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+    a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
+    launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
+    launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+    SX_HIP(hipGetLastError());
+    h->last_kernel = (h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0) ? "attention_fused_backward+long_rows" : "attention_fused_backward";
+    return SEXTANS_OK;
+}
+
+}  // extern "C"

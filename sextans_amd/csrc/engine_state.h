@@ -9,6 +9,7 @@
 //                       (natural / clustered / reordered), window stream -- the analogue of the reference's host-side scheduling
 //                       and packing (sextans-host.cpp:114-148)
 //   engine_softmax.hip  row softmax on A's pattern, forward and backward (sextans_row_softmax_device, ..._backward_device)
+//   engine_attention.hip  fused multi-head attention on A's pattern, forward and backward (sextans_attention_device, ..._backward_device)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
 //   engine_transpose.hip  the backward pass: A^T behind a companion engine (sextans_spmm_t_device_rm) and the SDDMM
@@ -426,6 +427,7 @@ void free_dense(sextans_engine *h);
 void free_matrix(sextans_engine *h);
 void free_backward(sextans_engine *h);                     // engine_transpose.hip: A^T, its companion and the SDDMM row table
 int validate_matrix(sextans_engine *h);                    // engine_transpose.hip: row_ptr / columns of a caller-provided device matrix, once
+int ensure_transpose(sextans_engine *h, hipStream_t s);    // engine_transpose.hip: A^T's arrays (h->at) and the companion engine h->tr, once per matrix
 void free_softmax(sextans_engine *h);                      // engine_softmax.hip: the row-softmax tables and workspace
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)

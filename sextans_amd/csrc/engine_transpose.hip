@@ -34,8 +34,6 @@ int validate_matrix(sextans_engine *h) {   // a device matrix nobody has looked 
     return SEXTANS_OK;
 }
 
-namespace {
-
 // A^T and its companion engine, once per matrix (the values are those of this moment; sextans_update_values* brings newer ones through d_tperm)
 int ensure_transpose(sextans_engine *h, hipStream_t s) {
     if (h->tr) return SEXTANS_OK;
@@ -66,6 +64,8 @@ int ensure_transpose(sextans_engine *h, hipStream_t s) {
     return SEXTANS_OK;
 }
 
+namespace {
+
 // The row of the first entry of every wavefront range of the SDDMM kernel, once per matrix: the kernel reads two ints per wavefront
 // instead of searching row_ptr (a 64-ary search per wavefront made 2 scattered row_ptr requests per entry: 4x the L2 requests of the
 // row-group gather kernel on the FEM, profiles/train_step_pmc_fem_N16.txt)
@@ -92,6 +92,7 @@ int prepare_transposed(sextans_engine *h, int N, hipStream_t s) {
     SX_HIP(hipStreamSynchronize(s));
     if (h->K == 0) return SEXTANS_OK;
     if (int rc = ensure_transpose(h, s)) return rc;
+    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // the column pass of sextans_attention_backward_device walks A^T's rows
     return sextans_prepare(h->tr, N, SEXTANS_LAYOUT_ROWMAJOR, s);
 }
 

@@ -24,11 +24,9 @@
 
 #include <cmath>
 
-namespace sx {
+#include "row_softmax_common.h"
 
-constexpr int kSoftmaxWaveEntries = 256;   // entries a wavefront's rows start in
-constexpr int kSoftmaxPieces = 8;          // 16-byte pieces per lane
-constexpr int kSoftmaxChunk = 64 * 4 * kSoftmaxPieces;   // 2048: what one wavefront holds; longer rows (counted from their aligned start) take the long-row path
+namespace sx {
 
 // wrow[w] = first row r with rp[r] >= 256 w (w < nw), wrow[nw] = M: wavefront w owns rows [wrow[w], wrow[w + 1]).  Once per matrix.
 __global__ __launch_bounds__(256) void softmax_wave_rows(int M, const int *__restrict__ rp, long long nw, int *__restrict__ wrow) {
@@ -43,8 +41,6 @@ __global__ __launch_bounds__(256) void softmax_wave_rows(int M, const int *__res
     }
     wrow[w] = lo;
 }
-
-__device__ __forceinline__ int softmax_row_span(int b, int e) { return e - (b & ~3); }   // entries from the row's aligned start to its end
 
 // long rows: cnt[0] += 1, cnt[1] += chunks, per row longer than one wavefront's registers.  Once per matrix (integer atomics: a count)
 __global__ __launch_bounds__(256) void softmax_count_long(int M, const int *__restrict__ rp, int *__restrict__ cnt) {
@@ -70,21 +66,6 @@ __global__ __launch_bounds__(256) void softmax_fill_long(int M, const int *__res
         for (int i = 0; i < n && base + i < nchunks; ++i) tab[base + i] = make_int2((int)r, i);
     }
 }
-
-template <int G>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, G));
-    return v;
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {   // butterfly: a + b on both sides of every exchange, so every lane ends with the same bits
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, G));
-    return v;
-}
-
-__device__ __forceinline__ float softmax_exp(float d) { return __builtin_amdgcn_exp2f(__fmul_rn(d, 1.4426950408889634f)); }
 
 // The lanes' pieces of one span [a0, a0 + span) of an array (a0 a multiple of 4; entries below `lo` belong to the previous row): piece
 // k < NP of lane `sub` of a group of G lanes is entries 4 (sub + G k) .. + 3.  NP is a template parameter chosen per wavefront (group

@@ -17,6 +17,7 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
     S = sddmm(A, X, Y, alpha=1.0, beta=0.0)        S_e = alpha * <X[r, :], Y[c, :]> + beta * A_e on A's pattern
     P = row_softmax(S, scale=1.0)                  softmax over every row's stored entries
     O = sparse_attention(A, Q, K, V, scale=None, bias=False)  = spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V)
+    O = sparse_attention(A, Q, K, V, ..., fused=True)         the same in one kernel pass per direction, all heads of (rows, H, d) at once
 
 S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
 other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
@@ -469,17 +470,112 @@ def row_softmax(S, scale=1.0, fast=False):
     return _carry(_RowSoftmaxFunction.apply(S, float(scale), bool(fast)), crow, col)
 
 
-def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False):
-    """softmax(scale * (Q K^T [+ A]) restricted to A's pattern) V:  spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V).
-    A (M x Kk) gives the pattern -- and, with bias=True, an additive bias / mask through its values; Q is (M, d), K (Kk, d), V (Kk, dv);
-    scale=None means 1 / sqrt(d).  Differentiable in Q, K, V and (bias=True) A.  A composition of the three ops on one cached engine,
-    not a fused kernel: S and P are materialised (the backward needs P)."""
+def _heads_operand(t, dp):
+    """A (rows, H, d) tensor as the fused kernels read it: t itself where it lies that way (fp32, heads side by side in a row, d % 8 == 0,
+    16-byte aligned base and row stride), else a zero-padded contiguous fp32 copy (rows, H, dp)."""
+    rows, H, d = t.shape
+    if (t.dtype == torch.float32 and d == dp and t.stride(2) == 1 and (H == 1 or t.stride(1) == d) and t.stride(0) >= H * d and
+            t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0):
+        return t, t.stride(0)
+    out = torch.zeros((rows, H, dp), dtype=torch.float32, device=t.device)
+    out[:, :, :d] = t
+    return out, H * dp
+
+
+class _FusedAttentionFunction(torch.autograd.Function):
+    """sparse_attention(fused=True): one kernel pass forward (sextans_attention_device), a row pass and a column pass backward
+    (sextans_attention_backward_device), all heads at once.  Nothing of size nnz is kept: the backward recomputes the probabilities from
+    the rows' log-sum-exp.  A's values enter as an explicit bias pointer, never through the engine: no value refresh anywhere."""
+
+    @staticmethod
+    def forward(ctx, A, Q, K, V, scale, bias, fast):
+        M, Kk = A.shape
+        H, d, dv = Q.shape[1], Q.shape[2], V.shape[2]
+        dp, dvp = -(-d // 8) * 8, -(-dv // 8) * 8
+        dev = A.device.index or 0
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, Kk), dev, fast, values_needed=False)
+        Qr, ldq = _heads_operand(Q.detach(), dp)
+        Kr, ldk = _heads_operand(K.detach(), dp)
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        b = _vals32(val) if bias else None
+        O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
+        lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
+        ent.eng.attention_device(H, dp, dvp, scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv,
+                                 b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(),
+                                 torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, val, Q, K, V, O, lse)
+        ctx.shape, ctx.scale, ctx.bias, ctx.fast, ctx.dev = (M, Kk), scale, bias, fast, dev
+        return O if dvp == dv else O[:, :, :dv]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, val, Q, K, V, O, lse = ctx.saved_tensors
+        M, Kk = ctx.shape
+        H, d, dv = Q.shape[1], Q.shape[2], V.shape[2]
+        dp, dvp = -(-d // 8) * 8, O.shape[2]
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        Qr, ldq = _heads_operand(Q.detach(), dp)
+        Kr, ldk = _heads_operand(K.detach(), dp)
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        Gr, ldg = _heads_operand(G, dvp)           # (a copy when G has zero strides, e.g. after .sum(), or dv % 8 != 0)
+        want_bias = ctx.bias and ctx.needs_input_grad[0]
+        b = _vals32(val) if ctx.bias else None
+        delta = torch.empty((M, H), dtype=torch.float32, device=G.device)
+        dQ = torch.empty((M, H, dp), dtype=torch.float32, device=G.device)
+        dK = torch.empty((Kk, H, dp), dtype=torch.float32, device=G.device)
+        dV = torch.empty((Kk, H, dvp), dtype=torch.float32, device=G.device)
+        db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
+        ent.eng.attention_backward_device(H, dp, dvp, ctx.scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv,
+                                          b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg,
+                                          delta.data_ptr(), dQ.data_ptr(), H * dp, dK.data_ptr(), H * dp, dV.data_ptr(), H * dvp,
+                                          db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
+        gQ = (dQ if dp == d else dQ[:, :, :d]).to(Q.dtype) if ctx.needs_input_grad[1] else None
+        gK = (dK if dp == d else dK[:, :, :d]).to(K.dtype) if ctx.needs_input_grad[2] else None
+        gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if ctx.needs_input_grad[3] else None
+        return gA, gQ, gK, gV, None, None, None
+
+
+def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False):
+    """softmax(scale * (Q K^T [+ A]) restricted to A's pattern) V, per head.
+    A (M x Kk) gives the pattern -- and, with bias=True, an additive bias / mask through its values, shared by all heads; Q is (M, d),
+    K (Kk, d), V (Kk, dv), or with heads (M, H, d), (Kk, H, d), (Kk, H, dv); the result has V's rank.  scale=None means 1 / sqrt(d).
+    Differentiable in Q, K, V and (bias=True) A.
+    fused=False (default): spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V), a composition of the three ops on one cached engine
+    with S and P materialised (the backward needs P) and handed to the engine as value refreshes; with heads, once per head, the
+    results stacked.
+    fused=True: one kernel pass per direction for all heads (sextans_attention_device / sextans_attention_backward_device): online
+    softmax, nothing of size nnz written, no value refresh; the backward keeps O and M * H floats instead of S and P.  Within the
+    tolerance of a chain of fp32 operations of the composition, not bit-equal to it.  Head dimensions up to 128; those that are not
+    multiples of 8, and operands that do not lie as the kernels read them, are copied with zero padding."""
     _check_sparse(A, "sparse_attention")
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (Q, K, V)):
         raise TypeError("sparse_attention expects CUDA/HIP dense Q, K and V")
-    if Q.dim() != 2 or K.dim() != 2 or V.dim() != 2 or V.shape[0] != A.shape[1]:
+    if not fused and Q.dim() == 2 and K.dim() == 2 and V.dim() == 2:
+        if V.shape[0] != A.shape[1]:
+            raise ValueError("shape mismatch")
+        if scale is None:
+            scale = 1.0 / math.sqrt(Q.shape[1])
+        S = sddmm(A, Q, K, 1.0, 1.0 if bias else 0.0, fast)
+        return spmm(row_softmax(S, scale, fast), V, fast=fast)
+    if any(t.dim() not in (2, 3) for t in (Q, K, V)):
+        raise ValueError("Q, K and V are (rows, d) or (rows, heads, d)")
+    Q3, K3, V3 = (t if t.dim() == 3 else t.unsqueeze(1) for t in (Q, K, V))
+    M, Kk = A.shape
+    H, d = Q3.shape[1], Q3.shape[2]
+    if K3.shape[1] != H or V3.shape[1] != H:
+        raise ValueError("Q, K and V differ in their number of heads")
+    if Q3.shape[0] != M or K3.shape[0] != Kk or V3.shape[0] != Kk or K3.shape[2] != d or H == 0 or d == 0 or V3.shape[2] == 0:
         raise ValueError("shape mismatch")
     if scale is None:
-        scale = 1.0 / math.sqrt(Q.shape[1])
-    S = sddmm(A, Q, K, 1.0, 1.0 if bias else 0.0, fast)
-    return spmm(row_softmax(S, scale, fast), V, fast=fast)
+        scale = 1.0 / math.sqrt(d)
+    if not fused:
+        out = torch.stack([sparse_attention(A, Q3[:, h], K3[:, h], V3[:, h], scale, bias, fast) for h in range(H)], dim=1)
+    else:
+        if d > 128 or V3.shape[2] > 128:
+            raise ValueError("fused sparse_attention: head dimensions up to 128")
+        out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast))
+    return out if V.dim() == 3 else out[:, 0]
