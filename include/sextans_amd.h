@@ -584,6 +584,57 @@ int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int 
     float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv,
     float *d_dbias, void *stream);
 
+/* ---- Fused graph attention (GAT, as GATConv in PyG / DGL) on A's pattern: the fused attention above with an ADDITIVE score and a
+ * LeakyReLU in front of the softmax, in one kernel pass per direction for all heads.  Closest thing in the reference: none.
+ *
+ * An edge e = (r, c) -- source c, destination r -- is scored from two scalars per node and head instead of a dot product.  Operands are
+ * ROW-major fp32: adst and dadst are M x heads, asrc and dasrc K x heads (entry [i * ld + h]; ld >= heads is the only condition on
+ * these four leading dimensions: they are read and written one float at a time); V and dV are K x (heads * dv) with head h in columns
+ * [h * dv, (h + 1) * dv), O and G are M x (heads * dv); lse and delta are M x heads, dense.  d_bias: NULL (bias_e = 0), or nnz floats
+ * in the CSR entry order the matrix was set with, shared by all heads -- an explicit pointer: A's own VALUES ARE NEITHER READ NOR
+ * WRITTEN.  For every row r, head h and stored entry e = (r, c), in entry order:
+ *     forward    z_e = (adst[r,h] + asrc[c,h]) + bias_e          (this order of the two adds)
+ *                s_e = z_e > 0 ? z_e : negative_slope * z_e       (a -inf z stays -inf for every slope, 0 included; NaN stays NaN)
+ *                m = max_e s_e;   Z = sum_e exp(s_e - m);   O[r,h,:] = (sum_e exp(s_e - m) * V[c,h,:]) / Z;   lse[r,h] = m + log Z
+ *     backward   delta[r,h] = <O[r,h,:], G[r,h,:]>;   p_e = exp(s_e - lse[r,h]);   ds_e = p_e * (<G[r,h,:], V[c,h,:]> - delta[r,h])
+ *                dz_e = z_e > 0 ? ds_e : negative_slope * ds_e    (z == 0 takes the slope, as torch's leaky_relu backward)
+ *                dadst[r,h] = sum_e dz_e;   dasrc[c,h] = sum_e dz_e;   dV[c,h,:] = sum_e p_e G[r,h,:]
+ *                dbias_e = sum_h dz_e   (d_dbias != NULL; heads added in ascending order)
+ * The forward is an online softmax (a running m, Z and accumulator, rescaled when m grows); the backward recomputes z and p from lse
+ * in two passes, rows of A for delta, dadst and dbias, rows of A^T (sextans_csr_transpose_device's arrays and entry permutation) for
+ * dasrc and dV.  Nothing of size nnz is read or written besides bias and dbias.
+ * Arithmetic and determinism: fp32 throughout, FMA in the dot products <O, G>, <G, V> and in the V / G accumulations, exp as in the row
+ * softmax (exp2 of a rounded product); every sum runs in an order fixed by the pattern and the launch shape and there are no float
+ * atomics: the same call gives the same bits on every run and every stream.  The same arithmetic in SEXTANS_MODE_STRICT and
+ * SEXTANS_MODE_FAST.
+ * Special values: a -inf score (a -inf bias: a mask) beside finite ones contributes exactly 0, to O and to every gradient; a row of only
+ * -inf scores, or with a +inf or NaN score, gives NaN in that (row, head); an empty row writes O = +0 and lse = -inf.  Empty rows and
+ * columns get zero gradients; every element of O, lse, delta, dadst, dasrc, dV (and dbias) is written.
+ * dv: a multiple of 8 in [8, 128]; it alone sets the register width, the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.
+ * negative_slope: finite and >= 0 (1 makes the activation the identity).  Leading dimensions of V, O, G, dV: >= heads * dv, multiples of
+ * 4; every pointer 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * Work is dealt by non-zero count with the row softmax's tables exactly as in sextans_attention_device (a group of lanes sized to the
+ * row takes a (row, head); per entry one 4-byte load and one gathered V -- column pass: G -- row; rows or columns of more than 2048
+ * entries get one workgroup per head, merged through LDS in a fixed order).  The first forward call on a matrix validates it and
+ * builds the row softmax's tables; the first backward call also builds A^T (its arrays and the companion engine's tables only); both
+ * synchronise then.  sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) builds all of it ahead.  After either, a call allocates
+ * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.  Nothing is allocated beyond those tables
+ * (stat "device_bytes": the terms of the row softmax and of A^T).
+ * sextans_last_kernel: "gat_fused" / "gat_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, heads < 1, dv not a multiple of 8 in [8, 128], negative_slope negative, NaN or infinite, ldadst /
+ * ldasrc / lddadst / lddasrc < heads, another leading dimension too small or not a multiple of 4, a misaligned pointer -- checked in
+ * this order, then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for a NULL pointer other than
+ * d_bias / d_dbias with nnz > 0: the order of sextans_attention_device, all before any device is touched.  M == 0 or nnz == 0: OK -- O
+ * and the gradients are zeroed, lse = -inf. */
+int sextans_gat_attention_device(sextans_handle_t h, int heads, int dv, float negative_slope,
+    const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream);
+int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope,
+    const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv,
+    float *d_dbias, void *stream);
+
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *
  * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or

@@ -72,7 +72,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_update_values", "sextans_update_values_device",
     "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16",
     "sextans_row_softmax_device", "sextans_row_softmax_backward_device",
-    "sextans_attention_device", "sextans_attention_backward_device"))
+    "sextans_attention_device", "sextans_attention_backward_device",
+    "sextans_gat_attention_device", "sextans_gat_attention_backward_device"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 
@@ -273,6 +274,12 @@ def lib():
                                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                     C.c_void_p]
+    L.sextans_gat_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_gat_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                        C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -793,6 +800,22 @@ class Engine:
         _check(lib().sextans_attention_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
                                                        d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, stream),
                "attention_backward_device")
+
+    def gat_attention_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, stream=None):
+        """Fused graph attention on A's pattern (sextans_gat_attention_device): O[r, h, :] = softmax_e(LeakyReLU((adst[r, h] + asrc[c, h]) +
+        bias_e)) V[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads floats).  adst is
+        M x heads, asrc K x heads (ld >= heads), V K x (heads * dv) with the heads side by side; d_bias: None, or nnz floats in CSR entry
+        order shared by all heads.  A's own values are not read."""
+        _check(lib().sextans_gat_attention_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo,
+                                                  d_lse, stream), "gat_attention_device")
+
+    def gat_attention_backward_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg,
+                                      d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, stream=None):
+        """dadst, dasrc, dV (and, d_dbias not None, the bias gradient: nnz floats) of gat_attention_device from its O and lse and the
+        upstream gradient G (sextans_gat_attention_backward_device); d_delta: M * heads floats of workspace the call writes."""
+        _check(lib().sextans_gat_attention_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias,
+                                                           d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv,
+                                                           d_dbias, stream), "gat_attention_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -75,6 +75,7 @@ __device__ __forceinline__ float attn_dot(const float *x, const float *y) {   //
 // "other" the index stored with an entry.
 template <int PASS, int T_, int P_, int U_>
 struct AttnPass {
+    using Args = AttnArgs;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? W : 2 * W;   // forward: m, Z, acc; rows: dQ; cols: dK, dV
     const AttnArgs &a;
@@ -235,16 +236,18 @@ struct AttnPass {
 
 // The rows [wrow[w], wrow[w + 1]) of wavefront w.  heads_inside: a slot group takes all heads of its row one after the other (the
 // row pass with dbias: one lane then owns an entry for every head); otherwise (row, head) pairs are dealt to the groups.
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void attn_rows(AttnArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                 const int *__restrict__ wrow, long long nw, int heads_inside) {
+// (Pass: AttnPass, or the additive-score GatPass of gat_kernels.h -- the row walking does not know how an entry is scored)
+template <class Pass>
+__device__ __forceinline__ void attn_rows_body(const typename Pass::Args a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                               const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
+    constexpr int T = Pass::T;
     constexpr int S = 64 / T;   // slots per wavefront
     const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (w >= nw) return;   // (no barrier in this kernel)
     const int ra = wrow[w], rb = wrow[w + 1];
     if (ra >= rb) return;
-    AttnPass<PASS, T, P, U> ps(a, ci, perm, lane % T);
+    Pass ps(a, ci, perm, lane % T);
     const int slot = lane / T;
     const int HS = heads_inside ? 1 : a.H, nh = heads_inside ? a.H : 1;
     // a long row (it leaves the kernel) can only be the last row that starts in the range: it does not count
@@ -305,12 +308,18 @@ __global__ __launch_bounds__(256) void attn_rows(AttnArgs a, const int *__restri
     }
 }
 
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void attn_rows(AttnArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
+                                                 const int *__restrict__ wrow, long long nw, int heads_inside) {
+    attn_rows_body<AttnPass<PASS, T, P, U>>(a, rp, ci, perm, wrow, nw, heads_inside);
+}
+
 // One workgroup per long row (the workgroup of its chunk 0 in the softmax's chunk table) and head -- heads_inside: per long row, the
 // heads one after the other.  The four wavefronts' states meet in LDS and are merged by the first slot in wavefront order.
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void attn_long(AttnArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                 const int2 *__restrict__ tab, int heads_inside) {
-    using Pass = AttnPass<PASS, T, P, U>;
+template <class Pass>
+__device__ __forceinline__ void attn_long_body(const typename Pass::Args a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                               const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
+    constexpr int T = Pass::T;
     __shared__ float s_f[4][Pass::NF][T];
     const int2 rc = tab[blockIdx.x];
     if (rc.y != 0) return;   // (uniform: before every barrier)
@@ -344,11 +353,10 @@ __global__ __launch_bounds__(256) void attn_long(AttnArgs a, const int *__restri
     }
 }
 
-// rows x cols floats at leading dimension ld <- value (the degenerate calls: no entries, no rows)
-__global__ __launch_bounds__(256) void attn_fill(long long rows, int cols, long long ld, float value, float *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * cols) return;
-    out[(i / cols) * ld + i % cols] = value;
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void attn_long(AttnArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
+                                                 const int2 *__restrict__ tab, int heads_inside) {
+    attn_long_body<AttnPass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
 }
 
 }  // namespace sx

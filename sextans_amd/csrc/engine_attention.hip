@@ -6,7 +6,25 @@
 #include "attention_kernels.h"
 #include "engine_state.h"
 
+namespace sx {
+
+// rows x cols floats at leading dimension ld <- value (the degenerate calls: no entries, no rows)
+__global__ __launch_bounds__(256) void attn_fill(long long rows, int cols, long long ld, float value, float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * cols) return;
+    out[(i / cols) * ld + i % cols] = value;
+}
+
+}  // namespace sx
+
 namespace sxe {
+
+// (declared in engine_state.h: engine_gat.hip fills its degenerate calls' outputs with it too)
+void attention_fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s) {
+    if (!out || rows <= 0 || cols <= 0) return;
+    hipLaunchKernelGGL(sx::attn_fill, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
+}
+
 namespace {
 
 bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
@@ -41,11 +59,6 @@ void launch_pass(const sextans_engine *e, const sx::AttnArgs &a, const int *perm
     else launch_width<PASS, 8, 4, F ? 2 : 1>(e, a, perm, heads_inside, s);
 }
 
-void fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s) {
-    if (!out || rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(sx::attn_fill, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
-}
-
 }  // namespace
 }  // namespace sxe
 
@@ -64,8 +77,8 @@ int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
-        fill(d_lse, h->M, heads, heads, -INFINITY, s);
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
@@ -97,10 +110,10 @@ int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int 
     SX_HIP(hipSetDevice(h->device));
     hipStream_t s = (hipStream_t)stream;
     if (h->M == 0 || h->nnz == 0) {
-        fill(d_delta, h->M, heads, heads, 0.0f, s);
-        fill(d_dQ, h->M, (int)hd, lddq, 0.0f, s);
-        fill(d_dK, h->K, (int)hd, lddk, 0.0f, s);
-        fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
+        attention_fill(d_dQ, h->M, (int)hd, lddq, 0.0f, s);
+        attention_fill(d_dK, h->K, (int)hd, lddk, 0.0f, s);
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }

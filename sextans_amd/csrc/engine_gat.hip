@@ -1,0 +1,116 @@
+// engine_gat.hip -- fused graph attention (GAT) over the pattern of the CSR matrix on an engine handle (include/sextans_amd.h):
+//   sextans_gat_attention_device            O = softmax(LeakyReLU(adst[r] + asrc[c] + bias) on A's pattern) V per head, and the rows' log-sum-exp
+//   sextans_gat_attention_backward_device   dadst, dasrc, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
+// Kernels: gat_kernels.h (the additive score) on the row walking of attention_kernels.h.  Tables as in engine_attention.hip: the row
+// softmax's of this engine for the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
+#include "engine_state.h"
+#include "gat_kernels.h"
+
+namespace sxe {
+namespace {
+
+bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
+bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
+bool bad_slope(float s) { return !(s >= 0.0f) || std::isinf(s); }
+uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
+
+template <int PASS, int T, int P, int U>
+void launch_width(const sextans_engine *e, const sx::GatArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
+    hipLaunchKernelGGL((sx::gat_rows<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow, nw,
+                       heads_inside ? 1 : 0);
+    if (e->softmax.nchunks > 0)
+        hipLaunchKernelGGL((sx::gat_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
+                           e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
+}
+
+// e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  The slot width follows dv alone:
+// the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.  Entries in flight per slot (U), as measured: the forward
+// keeps the dot-product kernels' 4 (2 at width 128) -- 8 was slower on config 4 -- and so forms the same batches, the same (m, Z, acc)
+// bits; the backward passes hold one gathered row per entry instead of two and run twice as many, 4 (2 at width 128).
+// COUPLING with AttnPass (tests/test_gat_attention_gpu.py, identity activation): at slope 1, d a_dst is rounding residue and is compared
+// with the dot-product kernel's dQ[..., 0], which holds only while both make the same roundings -- the forward's U and batches as in
+// engine_attention.hip, and in the row pass a slot adding its entries j, j + E, j + 2 E, .. one after the other (an order U does not
+// change).  Retune either kernel's forward U or the walk's order and that comparison has to be looked at again.
+template <int PASS>
+void launch_pass(const sextans_engine *e, const sx::GatArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    if (a.dv <= 8) launch_width<PASS, 2, 1, 4>(e, a, perm, heads_inside, s);
+    else if (a.dv <= 16) launch_width<PASS, 4, 1, 4>(e, a, perm, heads_inside, s);
+    else if (a.dv <= 32) launch_width<PASS, 8, 1, 4>(e, a, perm, heads_inside, s);
+    else if (a.dv <= 64) launch_width<PASS, 8, 2, 4>(e, a, perm, heads_inside, s);
+    else launch_width<PASS, 8, 4, 2>(e, a, perm, heads_inside, s);
+}
+
+}  // namespace
+}  // namespace sxe
+
+using namespace sxe;
+
+extern "C" {
+
+int sextans_gat_attention_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc,
+                                 int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+    if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (ldadst < heads || ldasrc < heads || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv)) return SEXTANS_ERR_INVALID;
+    if (((bits(d_adst) | bits(d_asrc) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->M == 0 || h->nnz == 0) {   // every row is empty
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
+        SX_HIP(hipGetLastError());
+        return SEXTANS_OK;
+    }
+    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    sx::GatArgs a{};
+    a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
+    a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo;
+    a.H = heads; a.dv = dv; a.slope = negative_slope;
+    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+    SX_HIP(hipGetLastError());
+    h->last_kernel = h->softmax.nchunks > 0 ? "gat_fused+long_rows" : "gat_fused";
+    return SEXTANS_OK;
+}
+
+int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst,
+                                          const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O,
+                                          int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dadst, int64_t lddadst,
+                                          float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv, float *d_dbias, void *stream) {
+    if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;
+    const int64_t hdv = (int64_t)heads * dv;
+    if (ldadst < heads || ldasrc < heads || lddadst < heads || lddasrc < heads || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) ||
+        bad_ld(lddv, hdv))
+        return SEXTANS_ERR_INVALID;
+    if (((bits(d_adst) | bits(d_asrc) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dadst) | bits(d_dasrc) |
+          bits(d_dV) | bits(d_dbias)) & 15) != 0)
+        return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dadst || !d_dasrc || !d_dV)) return SEXTANS_ERR_INVALID;
+    SX_HIP(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (h->M == 0 || h->nnz == 0) {
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
+        attention_fill(d_dadst, h->M, heads, lddadst, 0.0f, s);
+        attention_fill(d_dasrc, h->K, heads, lddasrc, 0.0f, s);
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
+        SX_HIP(hipGetLastError());
+        return SEXTANS_OK;
+    }
+    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = ensure_transpose(h, s)) return rc;
+    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
+    sx::GatArgs a{};
+    a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
+    a.out_delta = d_delta; a.dadst = d_dadst; a.dasrc = d_dasrc; a.dV = d_dV; a.dbias = d_dbias;
+    a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddadst = lddadst; a.lddasrc = lddasrc; a.lddv = lddv;
+    a.H = heads; a.dv = dv; a.slope = negative_slope;
+    launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
+    launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+    SX_HIP(hipGetLastError());
+    h->last_kernel = (h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0) ? "gat_fused_backward+long_rows" : "gat_fused_backward";
+    return SEXTANS_OK;
+}
+
+}  // extern "C"

@@ -430,6 +430,7 @@ int validate_matrix(sextans_engine *h);                    // engine_transpose.h
 int ensure_transpose(sextans_engine *h, hipStream_t s);    // engine_transpose.hip: A^T's arrays (h->at) and the companion engine h->tr, once per matrix
 void free_softmax(sextans_engine *h);                      // engine_softmax.hip: the row-softmax tables and workspace
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
+void attention_fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s);   // engine_attention.hip: rows x cols floats <- value (degenerate calls)
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)
 int transposed_options(sextans_engine *h, const char *key, int64_t value);   // engine.hip: one option (nullptr: all) onto the companion
 int allow_big_lds(sextans_engine *h, const void *kern, int bytes);

@@ -18,6 +18,8 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
     P = row_softmax(S, scale=1.0)                  softmax over every row's stored entries
     O = sparse_attention(A, Q, K, V, scale=None, bias=False)  = spmm(row_softmax(sddmm(A, Q, K, beta=bias), scale), V)
     O = sparse_attention(A, Q, K, V, ..., fused=True)         the same in one kernel pass per direction, all heads of (rows, H, d) at once
+    O = gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False)   graph attention (GATConv): the additive score
+                                                   softmax(leaky_relu(a_dst[r] + a_src[c] [+ A_e])) V per head, fused the same way
 
 S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
 other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
@@ -578,4 +580,106 @@ def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False
         if d > 128 or V3.shape[2] > 128:
             raise ValueError("fused sparse_attention: head dimensions up to 128")
         out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast))
+    return out if V.dim() == 3 else out[:, 0]
+
+
+def _scalars_operand(t):
+    """A (rows, H) tensor of per-node, per-head scalars as the GAT kernels read it: t itself where it lies that way (fp32, the heads of a
+    row next to each other, rows at least H apart, 16-byte aligned base), else a contiguous fp32 copy."""
+    rows, H = t.shape
+    if t.dtype == torch.float32 and (H == 1 or t.stride(1) == 1) and t.stride(0) >= H and t.data_ptr() % 16 == 0:
+        return t, t.stride(0)
+    out = torch.empty((rows, H), dtype=torch.float32, device=t.device)
+    out.copy_(t)
+    return out, H
+
+
+class _GatAttentionFunction(torch.autograd.Function):
+    """gat_attention(): one kernel pass forward (sextans_gat_attention_device), a row pass and a column pass backward
+    (sextans_gat_attention_backward_device), all heads at once.  Nothing of size nnz is kept: the backward recomputes the scores and the
+    probabilities from the rows' log-sum-exp.  A's values enter as an explicit bias pointer, never through the engine: no value refresh
+    anywhere."""
+
+    @staticmethod
+    def forward(ctx, A, adst, asrc, V, slope, bias, fast):
+        M, Kk = A.shape
+        H, dv = V.shape[1], V.shape[2]
+        dvp = -(-dv // 8) * 8
+        dev = A.device.index or 0
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, Kk), dev, fast, values_needed=False)
+        ad, ldad = _scalars_operand(adst.detach())
+        as_, ldas = _scalars_operand(asrc.detach())
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        b = _vals32(val) if bias else None
+        O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
+        lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
+        ent.eng.gat_attention_device(H, dvp, slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv,
+                                     b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(),
+                                     torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, val, adst, asrc, V, O, lse)
+        ctx.shape, ctx.slope, ctx.bias, ctx.fast, ctx.dev = (M, Kk), slope, bias, fast, dev
+        return O if dvp == dv else O[:, :, :dv]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, val, adst, asrc, V, O, lse = ctx.saved_tensors
+        M, Kk = ctx.shape
+        H, dv = V.shape[1], V.shape[2]
+        dvp = O.shape[2]
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        ad, ldad = _scalars_operand(adst.detach())
+        as_, ldas = _scalars_operand(asrc.detach())
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        Gr, ldg = _heads_operand(G, dvp)           # (a copy when G has zero strides, e.g. after .sum(), or dv % 8 != 0)
+        want_bias = ctx.bias and ctx.needs_input_grad[0]
+        b = _vals32(val) if ctx.bias else None
+        delta = torch.empty((M, H), dtype=torch.float32, device=G.device)
+        dad = torch.empty((M, H), dtype=torch.float32, device=G.device)
+        das = torch.empty((Kk, H), dtype=torch.float32, device=G.device)
+        dV = torch.empty((Kk, H, dvp), dtype=torch.float32, device=G.device)
+        db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
+        ent.eng.gat_attention_backward_device(H, dvp, ctx.slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv,
+                                              b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg,
+                                              delta.data_ptr(), dad.data_ptr(), H, das.data_ptr(), H, dV.data_ptr(), H * dvp,
+                                              db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
+        gad = dad.to(adst.dtype) if ctx.needs_input_grad[1] else None
+        gas = das.to(asrc.dtype) if ctx.needs_input_grad[2] else None
+        gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if ctx.needs_input_grad[3] else None
+        return gA, gad, gas, gV, None, None, None
+
+
+def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False):
+    """Graph attention (GAT, as GATConv in PyG / DGL) on A's pattern, per head:
+        softmax over row r's stored entries (r, c) of leaky_relu(a_dst[r] + a_src[c] [+ A_e], negative_slope), times V.
+    A (M x Kk) gives the edges -- entry (r, c): source c, destination r -- and, with bias=True, an additive edge term / mask through its
+    values, shared by all heads (-inf masks an edge for every slope).  a_dst is (M,) or (M, H), a_src (Kk,) or (Kk, H): the two halves
+    of GAT's attention vector applied to the transformed node features; V is (Kk, dv) or (Kk, H, dv), the result has V's rank.
+    One kernel pass per direction for all heads (sextans_gat_attention_device / sextans_gat_attention_backward_device): online softmax,
+    nothing of size nnz written, no value refresh; the backward keeps O and M * H floats.  Differentiable in a_dst, a_src, V and
+    (bias=True) A; gradients come in the operands' dtypes.  dv up to 128; a dv that is not a multiple of 8, and operands that do not lie
+    as the kernels read them, are copied (V with zero padding).  negative_slope: finite, >= 0."""
+    _check_sparse(A, "gat_attention")
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (a_dst, a_src, V)):
+        raise TypeError("gat_attention expects CUDA/HIP dense a_dst, a_src and V")
+    if V.dim() not in (2, 3) or a_dst.dim() not in (1, 2) or a_src.dim() not in (1, 2):
+        raise ValueError("a_dst and a_src are (rows,) or (rows, heads), V is (rows, dv) or (rows, heads, dv)")
+    V3 = V if V.dim() == 3 else V.unsqueeze(1)
+    ad2 = a_dst if a_dst.dim() == 2 else a_dst.unsqueeze(1)
+    as2 = a_src if a_src.dim() == 2 else a_src.unsqueeze(1)
+    M, Kk = A.shape
+    H, dv = V3.shape[1], V3.shape[2]
+    if ad2.shape[1] != H or as2.shape[1] != H:
+        raise ValueError("a_dst, a_src and V differ in their number of heads")
+    if ad2.shape[0] != M or as2.shape[0] != Kk or V3.shape[0] != Kk or H == 0 or dv == 0:
+        raise ValueError("shape mismatch")
+    if dv > 128:
+        raise ValueError("gat_attention: dv up to 128")
+    slope = float(negative_slope)
+    if not (slope >= 0.0) or math.isinf(slope):
+        raise ValueError("negative_slope must be finite and >= 0")
+    out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast))
     return out if V.dim() == 3 else out[:, 0]
