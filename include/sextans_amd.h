@@ -635,6 +635,52 @@ int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv,
     float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv,
     float *d_dbias, void *stream);
 
+/* ---- Max / min aggregation SpMM: C = A (x) B with the row's SUM replaced by its maximum or minimum, and the entries that won (what
+ * torch.sparse.mm(A, B, "amax" / "amin") computes on the CPU, reduce="max" in PyG, copy_u_max in DGL).  Closest thing in the reference:
+ * none.
+ *
+ * A is the engine's M x K CSR pattern, B row-major K x N fp32 (B[k * ldb + n]), C row-major M x N fp32, arg row-major M x N int32.
+ * d_val: nnz floats in the CSR entry order the matrix was set with -- an explicit pointer like the attention entries' bias; NULL = the
+ * engine's current values (as set, or as of the last sextans_update_values*).  No value refresh happens and none of the engine's packed
+ * forms is read or written.  For every row r and column n, over the stored entries e = (r, c) of the row:
+ *     forward    p_e = val[e] * B[c, n]                           (one fp32 product rounded to nearest, never fused)
+ *                C[r, n] = max_e p_e (SEXTANS_REDUCE_MAX) / min_e p_e (SEXTANS_REDUCE_MIN);   arg[r, n] = the winning e, its position in
+ *                the CSR arrays.  Among equal products the SMALLEST e wins (+0 and -0 compare equal: the first one wins); if any p_e is
+ *                NaN, C[r, n] is that NaN and arg the smallest e with a NaN product.  A row without stored entries: C = +0, arg = -1.
+ *                Stored explicit zeros take part like any entry.  (np.argmax / np.argmin over the row's (entries x N) product block.)
+ *     backward   dB[c, n]  = sum over the entries e of column c whose row r has arg[r, n] == e of val[e] * G[r, n]
+ *                dval[e]   = sum over the n with arg[r, n] == e of G[r, n] * B[c, n]
+ *                (a tied or NaN position sends its gradient to the one winner, as torch's CPU kernel does)
+ * C and arg are BIT-DETERMINED by these rules: every product is rounded on its own and the comparison (is NaN, product, entry) is a
+ * total order, so they do not depend on how a row is split over lanes, wavefronts or the long-row workgroup, nor on the mode.  The
+ * backward sums use FMA and run in an order fixed by the pattern and the launch shape; there are no atomics anywhere: dB is a GATHER
+ * over the rows of A^T (sextans_csr_transpose_device's arrays and entry permutation), dval a row pass in which one lane owns an entry.
+ * The same call gives the same bits on every run and every stream.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 tiles: the columns are cut into tiles of the smallest of 8 / 16 / 32 / 64 /
+ * 128 floats that holds min(N, 128), which play the part the heads play in sextans_attention_device (a group of lanes sized to the row
+ * takes a (row, tile); per entry one 4-byte column load, one 4-byte value load and the 16-byte pieces of one gathered B row; rows --
+ * column pass: columns -- of more than 2048 entries get one workgroup per tile, merged through LDS).  The last tile may be partial.
+ * Leading dimensions: >= N, multiples of 4 (all of them, whether or not their pointer is NULL); every pointer 16-byte aligned.  The
+ * outputs must not overlap the inputs or each other.
+ * d_arg may be NULL in the forward (inference).  In the backward d_dB or d_dval may be NULL, not both; d_B may be NULL when d_dval is.
+ * The backward writes every element of dB (K x N) and of dval (nnz) it is given: columns without entries get zeros.
+ * The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call with d_dB also builds
+ * A^T (its arrays and the companion engine's tables only); both synchronise then.  After that a call allocates nothing, reads nothing
+ * back and does not synchronise: it can be captured into a hipGraph.  Nothing is allocated beyond those tables (stat "device_bytes":
+ * the terms of the row softmax and of A^T).
+ * sextans_last_kernel: "spmm_reduce" / "spmm_reduce_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, op not SEXTANS_REDUCE_MAX / _MIN, N < 8 or not a multiple of 8, a leading dimension below N or not a
+ * multiple of 4, a misaligned pointer, (backward) d_dB and d_dval both NULL -- checked in this order, then the handle's state
+ * (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a required pointer that is NULL with
+ * nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- C and dB are zeroed, arg = -1. */
+#define SEXTANS_REDUCE_MAX 1
+#define SEXTANS_REDUCE_MIN 2
+int sextans_spmm_reduce_device_rm(sextans_handle_t h, int op, int N, const float *d_val, const float *d_B, int64_t ldb,
+                                  float *d_C, int64_t ldc, int32_t *d_arg, int64_t ldarg, void *stream);
+int sextans_spmm_reduce_backward_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb,
+                                           const int32_t *d_arg, int64_t ldarg, const float *d_G, int64_t ldg,
+                                           float *d_dB, int64_t lddb, float *d_dval, void *stream);
+
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *
  * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or

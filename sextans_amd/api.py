@@ -73,9 +73,11 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16",
     "sextans_row_softmax_device", "sextans_row_softmax_backward_device",
     "sextans_attention_device", "sextans_attention_backward_device",
-    "sextans_gat_attention_device", "sextans_gat_attention_backward_device"))
+    "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
+    "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
+REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
 
 
 class _Optional:
@@ -280,6 +282,10 @@ def lib():
                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p]
+    L.sextans_spmm_reduce_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int64, C.c_void_p]
+    L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -816,6 +822,20 @@ class Engine:
         _check(lib().sextans_gat_attention_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias,
                                                            d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv,
                                                            d_dbias, stream), "gat_attention_backward_device")
+
+    def spmm_reduce_device_rm(self, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream=None):
+        """Max / min aggregation (sextans_spmm_reduce_device_rm): C[r, n] = max (REDUCE_MAX) or min (REDUCE_MIN) over row r's stored
+        entries e = (r, c) of d_val[e] * B[c, n], arg[r, n] (int32; d_arg None: not written) the winning entry's position in the CSR
+        arrays -- first of equal products, first NaN; an empty row gives +0 and -1.  d_val: nnz floats in entry order, None = the
+        engine's current values.  B, C and arg row-major, N % 8 == 0."""
+        _check(lib().sextans_spmm_reduce_device_rm(self._h, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream), "spmm_reduce_device_rm")
+
+    def spmm_reduce_backward_device_rm(self, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream=None):
+        """dB (K x N) and dval (nnz floats) of spmm_reduce_device_rm from its arg and the upstream gradient G
+        (sextans_spmm_reduce_backward_device_rm): every position's gradient goes to the entry that won it.  d_dB or d_dval may be
+        None (not both); d_B may be None when d_dval is."""
+        _check(lib().sextans_spmm_reduce_backward_device_rm(self._h, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream),
+               "spmm_reduce_backward_device_rm")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -10,6 +10,8 @@
 //                       and packing (sextans-host.cpp:114-148)
 //   engine_softmax.hip  row softmax on A's pattern, forward and backward (sextans_row_softmax_device, ..._backward_device)
 //   engine_attention.hip  fused multi-head attention on A's pattern, forward and backward (sextans_attention_device, ..._backward_device)
+//   engine_gat.hip      fused graph attention (GAT) on A's pattern (sextans_gat_attention_device, ..._backward_device)
+//   engine_reduce.hip   max / min aggregation SpMM, forward and backward (sextans_spmm_reduce_device_rm, ..._backward_device_rm)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
 //   engine_transpose.hip  the backward pass: A^T behind a companion engine (sextans_spmm_t_device_rm) and the SDDMM

@@ -21,6 +21,13 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
     O = gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False)   graph attention (GATConv): the additive score
                                                    softmax(leaky_relu(a_dst[r] + a_src[c] [+ A_e])) V per head, fused the same way
 
+Max / min / mean aggregation over a node's neighbours (GraphSAGE-pool, PNA, EdgeConv; torch.sparse.mm(A, B, reduce) on the CPU, reduce="max"
+in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
+
+    C = spmm_reduce(A, B, reduce="amax")           C[r, n] = max ("amin": min) over row r's stored entries (r, c) of A_e * B[c, n]; an empty
+                                                   row gives 0.  One kernel pass, nothing of size nnz x N materialised; return_arg=True
+                                                   also returns the winning entries.  "mean" / "sum": spmm() (divided by the row lengths)
+
 S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
 other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
 """
@@ -683,3 +690,105 @@ def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False
         raise ValueError("negative_slope must be finite and >= 0")
     out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast))
     return out if V.dim() == 3 else out[:, 0]
+
+
+_REDUCE_OPS = {"amax": api.REDUCE_MAX, "amin": api.REDUCE_MIN}
+
+
+def _reduce_forward(A, B, op, fast, want_arg):
+    """(C, arg) of the engine's max / min aggregation, both (M, Np) with N padded up to a multiple of 8 (zero columns of B); arg is None
+    unless asked for."""
+    M, K = A.shape
+    N = B.shape[1]
+    Np = api.round_up_n(N)
+    crow, col = _index_tensors(A)
+    val = A.values()
+    ent = _entry_for_parts(crow, col, val, (M, K), A.device.index or 0, fast, values_needed=False)
+    Brm = _rowmajor(B.detach(), K, N, Np)
+    v = _vals32(val)
+    C = torch.empty((M, Np), dtype=torch.float32, device=A.device)
+    arg = torch.empty((M, Np), dtype=torch.int32, device=A.device) if want_arg else None
+    ent.eng.spmm_reduce_device_rm(op, Np, v.data_ptr() if v.numel() else None, Brm.data_ptr() if Brm.numel() else None, Brm.stride(0),
+                                  C.data_ptr() if C.numel() else None, Np, arg.data_ptr() if arg is not None and arg.numel() else None, Np,
+                                  torch.cuda.current_stream(A.device).cuda_stream)
+    return C, arg
+
+
+class _SpmmReduceFunction(torch.autograd.Function):
+    """spmm_reduce(): one kernel pass forward (sextans_spmm_reduce_device_rm) that also records the winning entry of every (row, column),
+    a column pass over A^T and a row pass backward (sextans_spmm_reduce_backward_device_rm): every position's gradient goes to the
+    entry that won it -- val_e * G to dB, G * B to dA.  A's values enter as an explicit pointer, never through the engine: no value
+    refresh anywhere.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, B, op, fast):
+        N = B.shape[1]
+        C, arg = _reduce_forward(A, B, op, fast, True)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B, arg)
+        ctx.shape, ctx.fast, ctx.dev = tuple(A.shape), fast, A.device.index or 0
+        out_arg = arg if arg.shape[1] == N else arg[:, :N]
+        ctx.mark_non_differentiable(out_arg)
+        return (C if C.shape[1] == N else C[:, :N]), out_arg
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _):
+        crow, col, val, B, arg = ctx.saved_tensors
+        M, K = ctx.shape
+        N = B.shape[1]
+        Np = arg.shape[1]
+        want_a, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_a or want_b):
+            return None, None, None, None
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        Grm = _rowmajor(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
+        Brm = _rowmajor(B.detach(), K, N, Np) if want_a else None
+        v = _vals32(val)
+        dB = torch.empty((K, Np), dtype=torch.float32, device=G.device) if want_b else None
+        dv = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_a else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        if ptr(dB) is not None or ptr(dv) is not None:   # (else: no element to write)
+            ent.eng.spmm_reduce_backward_device_rm(Np, ptr(v), ptr(Brm), Brm.stride(0) if Brm is not None else Np, ptr(arg), Np, ptr(Grm),
+                                                   Grm.stride(0), ptr(dB), Np, ptr(dv), torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, dv.to(val.dtype), size=(M, K)) if want_a else None
+        gB = (dB if Np == N else dB[:, :N]).to(B.dtype) if want_b else None
+        return gA, gB, None, None
+
+
+def spmm_reduce(A, B, reduce="amax", return_arg=False, fast=False):
+    """The product A B with the sum over a row's entries replaced by another reduction (torch.sparse.mm(A, B, reduce) on the CPU):
+    A is an (M, K) sparse_csr matrix, B a dense (K, N) tensor, the result a dense fp32 (M, N) tensor.
+    reduce="amax" / "amin": C[r, n] = max / min over row r's stored entries e = (r, c) of A_e * B[c, n] (one rounded fp32 product); a row
+    without entries gives 0; stored zeros take part; a NaN product wins.  One kernel pass (sextans_spmm_reduce_device_rm) -- nothing of
+    size nnz x N is materialised -- with bits that do not depend on the launch shape or on `fast`, which only selects the cached engine.
+    Differentiable in B and in A (dA: a sparse_csr tensor on A's index tensors, in A's value dtype): each position's gradient goes to
+    the one entry that won it, the first of equal products, as torch's CPU kernel does.  return_arg=True: also the int32 (M, N) tensor of
+    the winning entries' positions in A's CSR arrays (-1 in an empty row; not differentiable).  A's values are handed to the kernel as a
+    pointer: no value refresh of the cached engine.  An N that is not a multiple of 8, and a B the kernel cannot read where it lies, are
+    copied with zero padding, as spmm() does.
+    reduce="mean": spmm(A, B) divided by the rows' entry counts (an empty row: 0); reduce="sum": spmm(A, B).  Both are compositions of
+    differentiable ops; return_arg is refused for them."""
+    if reduce not in ("amax", "amin", "mean", "sum"):
+        raise ValueError("reduce must be 'amax', 'amin', 'mean' or 'sum'")
+    if return_arg and reduce in ("mean", "sum"):
+        raise ValueError("return_arg needs reduce='amax' or 'amin'")
+    if reduce == "sum":
+        return spmm(A, B, fast=fast)
+    if reduce == "mean":
+        crow = _index_tensors(A)[0]
+        out = spmm(A, B, fast=fast)
+        return out / (crow[1:] - crow[:-1]).clamp(min=1).to(out.dtype)[:, None]
+    _check_sparse(A, "spmm_reduce")
+    if not (isinstance(B, torch.Tensor) and B.is_cuda):
+        raise TypeError("spmm_reduce expects a CUDA/HIP dense B")
+    if B.dim() != 2 or B.shape[0] != A.shape[1] or B.shape[1] == 0:
+        raise ValueError("shape mismatch")
+    op = _REDUCE_OPS[reduce]
+    if torch.is_grad_enabled() and (A.requires_grad or B.requires_grad):
+        C, arg = _SpmmReduceFunction.apply(A, B, op, bool(fast))
+    else:
+        C, arg = _reduce_forward(A, B, op, bool(fast), bool(return_arg))
+        N = B.shape[1]
+        if C.shape[1] != N:
+            C, arg = C[:, :N], (arg[:, :N] if arg is not None else None)
+    return (C, arg) if return_arg else C
