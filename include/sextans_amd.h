@@ -635,6 +635,55 @@ int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv,
     float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv,
     float *d_dbias, void *stream);
 
+/* ---- Fused GATv2 graph attention (as GATv2Conv in PyG / DGL) on A's pattern: the score's activation sits INSIDE the projection, so no
+ * pair of per-node scalars expresses it; the message is the gathered source row itself.  One kernel pass per direction for all heads.
+ * Closest thing in the reference: none.
+ *
+ * Operands are ROW-major fp32 with the heads side by side in a row: x_dst, dx_dst, O and G are M x (heads * d), x_src and dx_src are
+ * K x (heads * d), head h in columns [h * d, (h + 1) * d); att and datt are heads * d floats, contiguous; lse and delta are M x heads,
+ * dense.  d_bias: NULL (bias_e = 0), or nnz floats in the CSR entry order the matrix was set with, shared by all heads -- an explicit
+ * pointer: A's own VALUES ARE NEITHER READ NOR WRITTEN.  For every row r, head h and stored entry e = (r, c):
+ *     forward    z_e[k] = x_dst[r,h,k] + x_src[c,h,k]                      (one rounded add, the same bits in every pass)
+ *                l_e[k] = z_e[k] > 0 ? z_e[k] : negative_slope * z_e[k]     (plain LeakyReLU: the mask is the bias, not z)
+ *                s_e = <att[h,:], l_e> + bias_e                             (the bias is added after the dot product)
+ *                m = max_e s_e;   Z = sum_e exp(s_e - m);   O[r,h,:] = (sum_e exp(s_e - m) * x_src[c,h,:]) / Z;   lse[r,h] = m + log Z
+ *     backward   delta[r,h] = <O[r,h,:], G[r,h,:]>;   p_e = exp(s_e - lse[r,h]);   ds_e = p_e * (<G[r,h,:], x_src[c,h,:]> - delta[r,h])
+ *                g_e[k] = ds_e * att[h,k] * (z_e[k] > 0 ? 1 : negative_slope)   (z == 0 takes the slope, as torch's leaky_relu backward)
+ *                dx_dst[r,h,:] = sum_e g_e;   dx_src[c,h,:] = sum_e (p_e G[r,h,:] + g_e);   dbias_e = sum_h ds_e   (d_dbias != NULL)
+ *                datt_rows[r,h,:] = sum_e ds_e l_e;   datt[h,k] = sum_r datt_rows[r,h,k]
+ * There is no separate V operand: the message is x_src, as in GATv2Conv.  x_dst and x_src may be the same array (a square pattern with
+ * shared weights); the two gradients are still written separately and the caller adds them.
+ * The sum over r in datt runs in a FIXED two-level order that defines its bits: part[c, j] adds the rows 256 c, 256 c + 1, .. of chunk c
+ * in ascending order starting from +0, datt[j] adds part[0, j], part[1, j], .. in ascending order starting from +0, every add rounded to
+ * nearest.  d_work: sextans_gatv2_workspace_floats(h, heads, d) = M * heads * d + ceil(M / 256) * heads * d floats handed in by the
+ * caller; after the call it holds datt_rows (M x (heads * d), dense) followed by part (ceil(M / 256) x (heads * d)).  d_delta: M * heads
+ * floats, written.
+ * Arithmetic and determinism as sextans_gat_attention_device: fp32 throughout, FMA in the dot products and accumulations, exp as in the
+ * row softmax, no float atomics, the same bits on every run and every stream, the same arithmetic in both modes.  Special values: a
+ * -inf bias beside finite ones contributes exactly 0 to O and to every gradient; a row of only -inf scores, or with a +inf or NaN
+ * score, gives NaN in that (row, head); an empty row writes O = +0, lse = -inf and zero gradient and datt_rows rows; columns without
+ * entries get zero dx_src rows.
+ * d: a multiple of 8 in [8, 128]; it alone sets the register width (8 / 16 / 32 / 64 / 128 floats).  negative_slope: finite and >= 0.
+ * Leading dimensions: >= heads * d, multiples of 4; every pointer 16-byte aligned.  The outputs must not overlap the inputs or each
+ * other.  Work is dealt exactly as in sextans_attention_device; per entry the forward and the row pass gather ONE row (x_src[c]: score
+ * operand and message at once), the column pass two (x_dst[r], G[r]).  Tables, the first calls' synchronisation, sextans_prepare and
+ * hipGraph capture as for sextans_gat_attention_device: after the first backward call nothing is allocated, read back or synchronised.
+ * sextans_last_kernel: "gatv2_fused" / "gatv2_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, heads < 1, d not a multiple of 8 in [8, 128], negative_slope negative, NaN or infinite, a leading
+ * dimension too small or not a multiple of 4, a misaligned pointer -- checked in this order, then the handle's state (SEXTANS_ERR_STATE:
+ * no CSR matrix set), then SEXTANS_ERR_INVALID for a NULL pointer other than d_bias / d_dbias with nnz > 0; all before any device is
+ * touched.  sextans_gatv2_workspace_floats returns the error code negated.  M == 0 or nnz == 0: OK -- O, the gradients, datt and the
+ * workspace are zeroed, lse = -inf. */
+int64_t sextans_gatv2_workspace_floats(sextans_handle_t h, int heads, int d);
+int sextans_gatv2_attention_device(sextans_handle_t h, int heads, int d, float negative_slope,
+    const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs, const float *d_att,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream);
+int sextans_gatv2_attention_backward_device(sextans_handle_t h, int heads, int d, float negative_slope,
+    const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs, const float *d_att,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dxdst, int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work,
+    float *d_dbias, void *stream);
+
 /* ---- Max / min aggregation SpMM: C = A (x) B with the row's SUM replaced by its maximum or minimum, and the entries that won (what
  * torch.sparse.mm(A, B, "amax" / "amin") computes on the CPU, reduce="max" in PyG, copy_u_max in DGL).  Closest thing in the reference:
  * none.

@@ -74,6 +74,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_row_softmax_device", "sextans_row_softmax_backward_device",
     "sextans_attention_device", "sextans_attention_backward_device",
     "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
+    "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
     "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
@@ -282,6 +283,14 @@ def lib():
                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p]
+    L.sextans_gatv2_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.sextans_gatv2_workspace_floats.restype = C.c_int64
+    L.sextans_gatv2_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_gatv2_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]
     L.sextans_spmm_reduce_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                 C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -822,6 +831,31 @@ class Engine:
         _check(lib().sextans_gat_attention_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias,
                                                            d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv,
                                                            d_dbias, stream), "gat_attention_backward_device")
+
+    def gatv2_workspace_floats(self, heads, d):
+        """Floats of workspace gatv2_attention_backward_device needs on this matrix (sextans_gatv2_workspace_floats):
+        M * heads * d for datt_rows plus ceil(M / 256) * heads * d for the chunk sums."""
+        n = lib().sextans_gatv2_workspace_floats(self._h, heads, d)
+        if n < 0:
+            _check(int(-n), "gatv2_workspace_floats")
+        return int(n)
+
+    def gatv2_attention_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, stream=None):
+        """Fused GATv2 attention on A's pattern (sextans_gatv2_attention_device): O[r, h, :] = softmax_e(<att[h, :], LeakyReLU(x_dst[r, h, :] +
+        x_src[c, h, :])> + bias_e) x_src[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads
+        floats).  x_dst is M x (heads * d), x_src K x (heads * d) with the heads side by side, att heads * d floats; d_bias: None, or nnz
+        floats in CSR entry order shared by all heads.  A's own values are not read."""
+        _check(lib().sextans_gatv2_attention_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse,
+                                                    stream), "gatv2_attention_device")
+
+    def gatv2_attention_backward_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G, ldg,
+                                        d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias, stream=None):
+        """dx_dst, dx_src, datt (heads * d floats, summed over the rows in a fixed two-level order) and, d_dbias not None, the bias gradient
+        of gatv2_attention_device from its O and lse and the upstream gradient G (sextans_gatv2_attention_backward_device); d_delta:
+        M * heads floats, d_work: gatv2_workspace_floats(heads, d) floats of workspace the call writes (datt_rows, then the chunk sums)."""
+        _check(lib().sextans_gatv2_attention_backward_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo,
+                                                             d_lse, d_G, ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias,
+                                                             stream), "gatv2_attention_backward_device")
 
     def spmm_reduce_device_rm(self, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream=None):
         """Max / min aggregation (sextans_spmm_reduce_device_rm): C[r, n] = max (REDUCE_MAX) or min (REDUCE_MIN) over row r's stored

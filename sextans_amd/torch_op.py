@@ -20,6 +20,8 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
     O = sparse_attention(A, Q, K, V, ..., fused=True)         the same in one kernel pass per direction, all heads of (rows, H, d) at once
     O = gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False)   graph attention (GATConv): the additive score
                                                    softmax(leaky_relu(a_dst[r] + a_src[c] [+ A_e])) V per head, fused the same way
+    O = gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False)   GATv2 (GATv2Conv): the activation inside the projection
+                                                   softmax(<att, leaky_relu(x_dst[r] + x_src[c])> [+ A_e]) x_src per head, fused the same way
 
 Max / min / mean aggregation over a node's neighbours (GraphSAGE-pool, PNA, EdgeConv; torch.sparse.mm(A, B, reduce) on the CPU, reduce="max"
 in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
@@ -690,6 +692,98 @@ def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False
         raise ValueError("negative_slope must be finite and >= 0")
     out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast))
     return out if V.dim() == 3 else out[:, 0]
+
+
+class _Gatv2AttentionFunction(torch.autograd.Function):
+    """gatv2_attention(): one kernel pass forward (sextans_gatv2_attention_device), a row pass, a column pass and the two-level datt sum
+    backward (sextans_gatv2_attention_backward_device), all heads at once.  Nothing of size nnz is kept: the backward recomputes the
+    scores and the probabilities from the rows' log-sum-exp.  A's values enter as an explicit bias pointer: no value refresh anywhere.
+    x_dst and x_src may be the same tensor: autograd adds the two gradients."""
+
+    @staticmethod
+    def forward(ctx, A, xdst, xsrc, att, slope, bias, fast):
+        M, Kk = A.shape
+        H, d = xdst.shape[1], xdst.shape[2]
+        dp = -(-d // 8) * 8
+        dev = A.device.index or 0
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, Kk), dev, fast, values_needed=False)
+        xd, ldxd = _heads_operand(xdst.detach(), dp)
+        xs, ldxs = _heads_operand(xsrc.detach(), dp)
+        at, _ = _heads_operand(att.detach().unsqueeze(0), dp)      # (1, H, dp): heads * dp floats, contiguous
+        b = _vals32(val) if bias else None
+        O = torch.empty((M, H, dp), dtype=torch.float32, device=A.device)
+        lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
+        ent.eng.gatv2_attention_device(H, dp, slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(),
+                                       b.data_ptr() if b is not None else None, O.data_ptr(), H * dp, lse.data_ptr(),
+                                       torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, val, xdst, xsrc, att, O, lse)
+        ctx.shape, ctx.slope, ctx.bias, ctx.fast, ctx.dev = (M, Kk), slope, bias, fast, dev
+        return O if dp == d else O[:, :, :d]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, val, xdst, xsrc, att, O, lse = ctx.saved_tensors
+        M, Kk = ctx.shape
+        H, d = xdst.shape[1], xdst.shape[2]
+        dp = O.shape[2]
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        xd, ldxd = _heads_operand(xdst.detach(), dp)
+        xs, ldxs = _heads_operand(xsrc.detach(), dp)
+        at, _ = _heads_operand(att.detach().unsqueeze(0), dp)
+        Gr, ldg = _heads_operand(G, dp)           # (a copy when G has zero strides, e.g. after .sum(), or d % 8 != 0)
+        want_bias = ctx.bias and ctx.needs_input_grad[0]
+        b = _vals32(val) if ctx.bias else None
+        delta = torch.empty((M, H), dtype=torch.float32, device=G.device)
+        dxd = torch.empty((M, H, dp), dtype=torch.float32, device=G.device)
+        dxs = torch.empty((Kk, H, dp), dtype=torch.float32, device=G.device)
+        dat = torch.empty((H, dp), dtype=torch.float32, device=G.device)
+        work = torch.empty((max(ent.eng.gatv2_workspace_floats(H, dp), 1),), dtype=torch.float32, device=G.device)
+        db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
+        ent.eng.gatv2_attention_backward_device(H, dp, ctx.slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(),
+                                                b.data_ptr() if b is not None else None, O.data_ptr(), H * dp, lse.data_ptr(), Gr.data_ptr(), ldg,
+                                                delta.data_ptr(), dxd.data_ptr(), H * dp, dxs.data_ptr(), H * dp, dat.data_ptr(), work.data_ptr(),
+                                                db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
+        gxd = (dxd if dp == d else dxd[:, :, :d]).to(xdst.dtype) if ctx.needs_input_grad[1] else None
+        gxs = (dxs if dp == d else dxs[:, :, :d]).to(xsrc.dtype) if ctx.needs_input_grad[2] else None
+        gat = (dat if dp == d else dat[:, :d]).to(att.dtype) if ctx.needs_input_grad[3] else None
+        return gA, gxd, gxs, gat, None, None, None
+
+
+def gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False, fast=False):
+    """GATv2 graph attention (as GATv2Conv in PyG / DGL) on A's pattern, per head:
+        softmax over row r's stored entries (r, c) of <att, leaky_relu(x_dst[r] + x_src[c], negative_slope)> [+ A_e], times x_src.
+    A (M x Kk) gives the edges -- entry (r, c): source c, destination r -- and, with bias=True, an additive edge term / mask through its
+    values, shared by all heads and added after the dot product (-inf masks an edge).  x_dst is (M, H, d), x_src (Kk, H, d), att (H, d);
+    or, for one head, (M, d), (Kk, d) and (d,).  The result has x_dst's rank.  The message is x_src itself, as in GATv2Conv; on a square
+    pattern x_dst and x_src may be the same tensor (share_weights=True), whose gradient is then the sum of both.
+    One kernel pass per direction for all heads (sextans_gatv2_attention_device / sextans_gatv2_attention_backward_device): online
+    softmax, nothing of size nnz written -- no (nnz, H, d) tensor of summed rows --, no value refresh; the backward keeps O and M * H
+    floats and takes M * H * d floats of workspace for att's gradient, which is summed in a fixed order: the same bits on every run.
+    Differentiable in x_dst, x_src, att and (bias=True) A; gradients come in the operands' dtypes.  d up to 128; a d that is not a
+    multiple of 8, and operands that do not lie as the kernels read them, are copied with zero padding.  negative_slope: finite, >= 0."""
+    _check_sparse(A, "gatv2_attention")
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (x_dst, x_src, att)):
+        raise TypeError("gatv2_attention expects CUDA/HIP dense x_dst, x_src and att")
+    if x_dst.dim() not in (2, 3) or x_src.dim() != x_dst.dim() or att.dim() != x_dst.dim() - 1:
+        raise ValueError("x_dst, x_src and att are (rows, heads, d), (rows, heads, d) and (heads, d), or (rows, d), (rows, d) and (d,)")
+    xd3, xs3, at2 = (x_dst, x_src, att) if x_dst.dim() == 3 else (x_dst.unsqueeze(1), x_src.unsqueeze(1), att.unsqueeze(0))
+    M, Kk = A.shape
+    H, d = xd3.shape[1], xd3.shape[2]
+    if xs3.shape[1] != H or at2.shape[0] != H:
+        raise ValueError("x_dst, x_src and att differ in their number of heads")
+    if xd3.shape[0] != M or xs3.shape[0] != Kk or xs3.shape[2] != d or at2.shape[1] != d or H == 0 or d == 0:
+        raise ValueError("shape mismatch")
+    if d > 128:
+        raise ValueError("gatv2_attention: d up to 128")
+    slope = float(negative_slope)
+    if not (slope >= 0.0) or math.isinf(slope):
+        raise ValueError("negative_slope must be finite and >= 0")
+    out = _Gatv2AttentionFunction.apply(A, xd3, xs3, at2, slope, bool(bias), bool(fast))
+    return out if x_dst.dim() == 3 else out[:, 0]
 
 
 _REDUCE_OPS = {"amax": api.REDUCE_MAX, "amin": api.REDUCE_MIN}
