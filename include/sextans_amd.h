@@ -572,6 +572,7 @@ int sextans_row_softmax_backward_device(sextans_handle_t h, float scale, const f
  * back and does not synchronise: it can be captured into a hipGraph.  Nothing is allocated beyond those tables (stat "device_bytes":
  * the terms of the row softmax and of A^T).
  * sextans_last_kernel: "attention_fused" / "attention_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * ("+dropout" comes before it from the dropout entries below.)
  * SEXTANS_ERR_INVALID: h == NULL, heads < 1, d or dv not a multiple of 8 in [8, 128], a leading dimension too small or not a multiple
  * of 4, a misaligned pointer, a NULL pointer other than d_bias / d_dbias with nnz > 0; SEXTANS_ERR_STATE: no CSR matrix set.  M == 0
  * or nnz == 0: OK -- O and the gradients are zeroed, lse = -inf. */
@@ -621,6 +622,7 @@ int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int 
  * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.  Nothing is allocated beyond those tables
  * (stat "device_bytes": the terms of the row softmax and of A^T).
  * sextans_last_kernel: "gat_fused" / "gat_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * ("+dropout" comes before it from the dropout entries below.)
  * SEXTANS_ERR_INVALID: h == NULL, heads < 1, dv not a multiple of 8 in [8, 128], negative_slope negative, NaN or infinite, ldadst /
  * ldasrc / lddadst / lddasrc < heads, another leading dimension too small or not a multiple of 4, a misaligned pointer -- checked in
  * this order, then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for a NULL pointer other than
@@ -669,6 +671,7 @@ int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv,
  * operand and message at once), the column pass two (x_dst[r], G[r]).  Tables, the first calls' synchronisation, sextans_prepare and
  * hipGraph capture as for sextans_gat_attention_device: after the first backward call nothing is allocated, read back or synchronised.
  * sextans_last_kernel: "gatv2_fused" / "gatv2_fused_backward", "+long_rows" appended when the workgroup path ran.
+ * ("+dropout" comes before it from the dropout entries below.)
  * SEXTANS_ERR_INVALID: h == NULL, heads < 1, d not a multiple of 8 in [8, 128], negative_slope negative, NaN or infinite, a leading
  * dimension too small or not a multiple of 4, a misaligned pointer -- checked in this order, then the handle's state (SEXTANS_ERR_STATE:
  * no CSR matrix set), then SEXTANS_ERR_INVALID for a NULL pointer other than d_bias / d_dbias with nnz > 0; all before any device is
@@ -683,6 +686,64 @@ int sextans_gatv2_attention_backward_device(sextans_handle_t h, int heads, int d
     const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
     float *d_delta, float *d_dxdst, int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work,
     float *d_dbias, void *stream);
+
+/* ---- Attention dropout inside the three fused attentions above: dropout on the NORMALISED attention coefficients (GATConv / GATv2Conv's
+ * dropout in PyG and DGL, attn_drop of graph transformers), which the fused kernels never materialise.  The mask is made inside the
+ * kernels by a counter-based generator and recomputed by all three passes: no state of size nnz, no atomics, the same bits on every
+ * run, capturable.  Closest thing in the reference: none.
+ *
+ * With m_e,h = 1 / (1 - p) where (entry e, head h) is kept and 0 where it is dropped -- scores, m, Z, lse and p_e = exp(s_e - lse) stay
+ * exactly as in the entries without dropout (dropped entries still count in Z, so the special-value rules are unchanged):
+ *     forward    O[r,h,:] = sum_e (m_e p_e) V[c,h,:]                         (GATv2: x_src[c,h,:])
+ *     backward   delta[r,h] = <O[r,h,:], G[r,h,:]>   (the dropped O: sum_e p_e m_e <G, V_e> = <O, G>)
+ *                ds_e = p_e * (m_e * <G[r,h,:], V[c,h,:]> - delta[r,h])
+ *                dV[c,h,:] = sum_e (m_e p_e) G[r,h,:]                        (GATv2: the p_e G term of dx_src)
+ * and everything downstream of ds_e as before (dQ, dK, dz, dadst, dasrc, g_e, dx_dst, datt_rows, datt, dbias).  m_e p_e and
+ * m_e <G, V> are one rounded multiply each.  A row whose entries are all dropped gives O = +0, lse as without dropout, and zero ds_e.
+ * The mask (csrc/dropout_hash.h; uint64 arithmetic wraps):
+ *     mix(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  x ^ (x >> 31)
+ *     key  = mix(seed + step)                        step = *d_step, or 0 when d_step == NULL
+ *     u    = (uint32)(mix(key + e * heads + h) >> 32)   e: the entry's position in the CSR arrays as set (also in the column pass), h: head
+ *     keep = u >= thresh,  thresh = (uint32)((double)p * 4294967296.0);   m = keep ? 1.0f / (1.0f - p) : 0.0f   (two rounded fp32 operations)
+ * d_step: NULL, or ONE 8-byte aligned uint64 in device memory that every thread reads once.  It exists so that a captured hipGraph
+ * draws a new mask on each replay: the caller bumps the word between replays (on the stream); nothing is read back or synchronised.
+ * The backward call must get the p, seed and step of its forward.
+ * drop == NULL or p == 0: exactly the entry without "_dropout" -- the same kernels, the same bits.  p > 0 launches a compile-time
+ * variant of the same kernels (the same row walking, lane groups, long-row workgroups, merges and order of every sum) that costs two
+ * 64-bit multiplies per (entry, head) and slot lane; sextans_last_kernel then carries "+dropout" (before "+long_rows").
+ * SEXTANS_ERR_INVALID additionally for p negative, NaN or >= 1 and a misaligned d_step, checked right after heads, the head
+ * dimensions and negative_slope (scale has no check) and before the leading dimensions; everything else as the entries without dropout.
+ * sextans_dropout_mask_device writes the nnz * heads multipliers m, [e * heads + h], of the handle's matrix (what the fused kernels
+ * recompute; for compositions that materialise the coefficients, and for tests); drop must not be NULL, d_mult 16-byte aligned.
+ * sextans_dropout_keep_host needs no device and no handle: keep[i * heads + h] = 1 where (entry first + i, head h) is kept, for
+ * i in [0, count); SEXTANS_ERR_INVALID for first or count negative, heads < 1, a bad p, keep == NULL with count > 0. */
+typedef struct { float p; uint64_t seed; const uint64_t *d_step; } sextans_dropout;
+int sextans_attention_dropout_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream);
+int sextans_attention_dropout_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv,
+    float *d_dbias, const sextans_dropout *drop, void *stream);
+int sextans_gat_attention_dropout_device(sextans_handle_t h, int heads, int dv, float negative_slope,
+    const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream);
+int sextans_gat_attention_dropout_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope,
+    const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv,
+    float *d_dbias, const sextans_dropout *drop, void *stream);
+int sextans_gatv2_attention_dropout_device(sextans_handle_t h, int heads, int d, float negative_slope,
+    const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs, const float *d_att,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream);
+int sextans_gatv2_attention_dropout_backward_device(sextans_handle_t h, int heads, int d, float negative_slope,
+    const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs, const float *d_att,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dxdst, int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work,
+    float *d_dbias, const sextans_dropout *drop, void *stream);
+int sextans_dropout_mask_device(sextans_handle_t h, int heads, const sextans_dropout *drop, float *d_mult, void *stream);
+int sextans_dropout_keep_host(int64_t first, int64_t count, int heads, float p, uint64_t seed, uint64_t step, uint8_t *keep);
 
 /* ---- Max / min aggregation SpMM: C = A (x) B with the row's SUM replaced by its maximum or minimum, and the entries that won (what
  * torch.sparse.mm(A, B, "amax" / "amin") computes on the CPU, reduce="max" in PyG, copy_u_max in DGL).  Closest thing in the reference:

@@ -53,6 +53,19 @@ class Edges(C.Structure):
                 ("edge_list_ptr", C.POINTER(C.c_int32)), ("channel", C.POINTER(C.c_uint64) * 8)]
 
 
+class Dropout(C.Structure):
+    """sextans_dropout: attention dropout of the fused attention entries.  p in [0, 1), a 64-bit seed and d_step: None, or the address of
+    ONE uint64 in device memory that is added to the seed (a captured graph's caller bumps it between replays)."""
+    _fields_ = [("p", C.c_float), ("seed", C.c_uint64), ("d_step", C.c_void_p)]
+
+    def __init__(self, p=0.0, seed=0, d_step=None):
+        super().__init__(p, int(seed) & 0xFFFFFFFFFFFFFFFF, d_step)
+
+
+def _drop_ref(drop):
+    return C.byref(drop) if drop is not None else None
+
+
 class SextansError(RuntimeError):
     def __init__(self, code, where=""):
         self.code = code
@@ -75,7 +88,11 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_attention_device", "sextans_attention_backward_device",
     "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
     "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
-    "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm"))
+    "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm",
+    "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
+    "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
+    "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
+    "sextans_dropout_mask_device", "sextans_dropout_keep_host"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
@@ -291,6 +308,13 @@ def lib():
                                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                           C.c_void_p, C.c_void_p]
+    dp = C.POINTER(Dropout)
+    for name in ("attention", "gat_attention", "gatv2_attention"):   # the plain entry's arguments with the dropout pointer before the stream
+        for suffix in ("device", "backward_device"):
+            plain = getattr(L, "sextans_%s_%s" % (name, suffix)).argtypes
+            getattr(L, "sextans_%s_dropout_%s" % (name, suffix)).argtypes = plain[:-1] + [dp, C.c_void_p]
+    L.sextans_dropout_mask_device.argtypes = [C.c_void_p, C.c_int, dp, C.c_void_p, C.c_void_p]
+    L.sextans_dropout_keep_host.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]
     L.sextans_spmm_reduce_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                 C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -857,6 +881,47 @@ class Engine:
                                                              d_lse, d_G, ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias,
                                                              stream), "gatv2_attention_backward_device")
 
+    # Attention dropout (sextans_*_dropout_device): the entries above with `drop`, a Dropout or None, before the stream.  drop None or
+    # drop.p == 0: exactly the entry above.  The backward call takes the Dropout of its forward.
+    def attention_dropout_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, drop, stream=None):
+        _check(lib().sextans_attention_dropout_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
+                                                      _drop_ref(drop), stream), "attention_dropout_device")
+
+    def attention_dropout_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta,
+                                          d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, drop, stream=None):
+        _check(lib().sextans_attention_dropout_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
+                                                               d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, _drop_ref(drop),
+                                                               stream), "attention_dropout_backward_device")
+
+    def gat_attention_dropout_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, drop,
+                                     stream=None):
+        _check(lib().sextans_gat_attention_dropout_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O,
+                                                          ldo, d_lse, _drop_ref(drop), stream), "gat_attention_dropout_device")
+
+    def gat_attention_dropout_backward_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse,
+                                              d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, drop, stream=None):
+        _check(lib().sextans_gat_attention_dropout_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv,
+                                                                   d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc,
+                                                                   d_dV, lddv, d_dbias, _drop_ref(drop), stream),
+               "gat_attention_dropout_backward_device")
+
+    def gatv2_attention_dropout_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, drop,
+                                       stream=None):
+        _check(lib().sextans_gatv2_attention_dropout_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo,
+                                                            d_lse, _drop_ref(drop), stream), "gatv2_attention_dropout_device")
+
+    def gatv2_attention_dropout_backward_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G,
+                                                ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias, drop, stream=None):
+        _check(lib().sextans_gatv2_attention_dropout_backward_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias,
+                                                                     d_O, ldo, d_lse, d_G, ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt,
+                                                                     d_work, d_dbias, _drop_ref(drop), stream),
+               "gatv2_attention_dropout_backward_device")
+
+    def dropout_mask_device(self, heads, drop, d_mult, stream=None):
+        """The nnz * heads dropout multipliers of this matrix, [e * heads + h]: 1 / (1 - p) where (entry, head) is kept, 0 where it is
+        dropped (sextans_dropout_mask_device) -- what the fused dropout kernels recompute."""
+        _check(lib().sextans_dropout_mask_device(self._h, heads, _drop_ref(drop), d_mult, stream), "dropout_mask_device")
+
     def spmm_reduce_device_rm(self, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream=None):
         """Max / min aggregation (sextans_spmm_reduce_device_rm): C[r, n] = max (REDUCE_MAX) or min (REDUCE_MIN) over row r's stored
         entries e = (r, c) of d_val[e] * B[c, n], arg[r, n] (int32; d_arg None: not written) the winning entry's position in the CSR
@@ -899,6 +964,16 @@ class Engine:
 
     def last_kernel(self):
         return lib().sextans_last_kernel(self._h).decode()
+
+
+def dropout_keep_host(first, count, heads, p, seed, step=0):
+    """The attention-dropout mask on the host, no device needed (sextans_dropout_keep_host): a (count, heads) uint8 array, 1 where
+    (entry first + i, head h) is kept."""
+    keep = np.zeros((max(count, 0), max(heads, 0)), np.uint8)
+    m64 = 0xFFFFFFFFFFFFFFFF
+    _check(lib().sextans_dropout_keep_host(first, count, heads, p, int(seed) & m64, int(step) & m64, keep.ctypes.data if keep.size else None),
+           "dropout_keep_host")
+    return keep
 
 
 def spmm_csr(M, N, K, NNZ, ALPHA, CSRRowPtr, CSRColIndex, CSRVal, mat_B, BETA, mat_C):

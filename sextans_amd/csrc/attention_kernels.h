@@ -29,7 +29,9 @@
 
 #include <climits>
 #include <cmath>
+#include <type_traits>
 
+#include "dropout_hash.h"
 #include "row_softmax_common.h"
 
 namespace sx {
@@ -43,6 +45,22 @@ struct AttnArgs {
     int H, d, dv;
     float scale;
 };
+
+// Attention dropout (the *_dropout_device entries; dropout_hash.h): the multiplier m_e,h = 1 / (1 - p) or 0 of (entry, head) is
+// recomputed from a hash wherever it is needed.  Scores, m, Z and lse do not see it; the forward's accumulator takes m p, the backward
+// applies it to <G, V> and to the p G accumulation.  A COMPILE-TIME variant of the passes (DROP): the kernels without it are the code
+// they were before it existed.
+struct AttnDropArgs : AttnArgs { DropArgs drop; };
+
+__device__ __forceinline__ uint64_t drop_key(const DropArgs &d) {
+    // (volatile: a vector load of the word a captured graph's caller bumps between replays)
+    const uint64_t step = d.step ? *reinterpret_cast<const volatile uint64_t *>(d.step) : 0;
+    return dropout_key(d.seed, step);
+}
+// e: the entry's position in the CSR arrays as set (the column pass: perm of the walked position)
+__device__ __forceinline__ float drop_mult(const DropArgs &d, uint64_t key, int e, int H, int h) {
+    return dropout_u32(key, (uint64_t)e, (uint32_t)H, (uint32_t)h) >= d.thresh ? d.inv_keep : 0.0f;
+}
 
 // pieces t, t + T, .. of a row of n floats: x[4 k ..] = row[4 (t + T k) ..], zero beyond n (or when the lane has no row)
 template <int T, int P>
@@ -73,20 +91,23 @@ __device__ __forceinline__ float attn_dot(const float *x, const float *y) {   //
 
 // One slot's view of a pass.  "own" is the row of the pattern walked (a row of A; the column pass: a row of A^T = a column of A),
 // "other" the index stored with an entry.
-template <int PASS, int T_, int P_, int U_>
+template <int PASS, int T_, int P_, int U_, bool DROP = false>
 struct AttnPass {
-    using Args = AttnArgs;
+    using Args = std::conditional_t<DROP, AttnDropArgs, AttnArgs>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? W : 2 * W;   // forward: m, Z, acc; rows: dQ; cols: dK, dV
-    const AttnArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0;
     float x[W], y[W];   // the own row's vectors: Q (forward), Q and G (rows), K and V (cols)
     float f[NF];
     float lse = 0.f, delta = 0.f;
+    uint64_t key = 0;   // DROP: the mask's key
 
-    __device__ __forceinline__ AttnPass(const AttnArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ AttnPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {
+        if constexpr (DROP) key = drop_key(a.drop);
+    }
 
     // the slot takes (own, head): `writer` = it is the one slot of its group that stores per-(row, head) results
     __device__ __forceinline__ void begin(bool act, int own, int head, bool writer) {
@@ -136,9 +157,13 @@ struct AttnPass {
                 bs[u] = (a.bias && valid[u]) ? a.bias[e[u]] : 0.0f;
             }
         }
-        float s[U];
+        float s[U], mk[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) s[u] = __fmul_rn(a.scale, __fadd_rn(attn_dot<T, W>(x, p1[u]), bs[u]));
+        if constexpr (DROP) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, valid[u] ? (PASS == kAttnBackwardCols ? perm[e[u]] : e[u]) : 0, a.H, h);
+        }
         if (PASS == kAttnForward) {
             float mn = f[0];
 #pragma unroll
@@ -154,21 +179,24 @@ struct AttnPass {
             for (int u = 0; u < U; ++u) {
                 const float p = softmax_exp(__fsub_rn(s[u], mref));
                 f[1] = __fadd_rn(f[1], p);
+                float pm = p;
+                if constexpr (DROP) pm = __fmul_rn(mk[u], p);
 #pragma unroll
-                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(p, p2[u][i], f[2 + i]);
+                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(pm, p2[u][i], f[2 + i]);
             }
             f[0] = mn;
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const float p = valid[u] ? softmax_exp(__fsub_rn(s[u], ls[u])) : 0.0f;
-                const float dp = attn_dot<T, W>(y, p2[u]);
+                float dp = attn_dot<T, W>(y, p2[u]), pm = p;
+                if constexpr (DROP) { dp = __fmul_rn(mk[u], dp); pm = __fmul_rn(mk[u], p); }
                 const float ds = valid[u] ? __fmul_rn(a.scale, __fmul_rn(p, __fsub_rn(dp, dl[u]))) : 0.0f;
 #pragma unroll
                 for (int i = 0; i < W; ++i) f[i] = __fmaf_rn(ds, p1[u][i], f[i]);
                 if (PASS == kAttnBackwardCols) {
 #pragma unroll
-                    for (int i = 0; i < W; ++i) f[W + i] = __fmaf_rn(p, p2[u][i], f[W + i]);
+                    for (int i = 0; i < W; ++i) f[W + i] = __fmaf_rn(pm, p2[u][i], f[W + i]);
                 } else if (a.dbias && valid[u] && t == 0) {
                     // the heads of an entry are taken by this lane one after the other, in ascending order: a plain read-modify-write
                     a.dbias[e[u]] = h == 0 ? ds : __fadd_rn(a.dbias[e[u]], ds);
@@ -357,6 +385,18 @@ template <int PASS, int T, int P, int U>
 __global__ __launch_bounds__(256) void attn_long(AttnArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
                                                  const int2 *__restrict__ tab, int heads_inside) {
     attn_long_body<AttnPass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
+}
+
+// the same two kernels with the dropout mask (launched only when p > 0)
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void attn_rows_drop(AttnDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                      const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
+    attn_rows_body<AttnPass<PASS, T, P, U, true>>(a, rp, ci, perm, wrow, nw, heads_inside);
+}
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void attn_long_drop(AttnDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                      const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
+    attn_long_body<AttnPass<PASS, T, P, U, true>>(a, rp, ci, perm, tab, heads_inside);
 }
 
 }  // namespace sx

@@ -1,6 +1,8 @@
 // engine_attention.hip -- fused multi-head attention over the pattern of the CSR matrix on an engine handle (include/sextans_amd.h):
 //   sextans_attention_device            O = softmax(scale * (Q K^T + bias) on A's pattern) V per head, and the rows' log-sum-exp
 //   sextans_attention_backward_device   dQ, dK, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
+//   sextans_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
+//   sextans_dropout_mask_device, sextans_dropout_keep_host        the mask itself: nnz * heads multipliers on the device, keep flags on the host
 // Kernels and the lane mapping: attention_kernels.h.  The row pass uses the row softmax's tables of this engine, the column pass those
 // of the companion engine that holds A^T (engine_transpose.hip) -- no table of its own, and A's values are never read.
 #include "attention_kernels.h"
@@ -9,6 +11,13 @@
 namespace sx {
 
 // rows x cols floats at leading dimension ld <- value (the degenerate calls: no entries, no rows)
+// out[i] = the dropout multiplier of (entry i / heads, head i % heads): the hash's counter is i itself
+__global__ __launch_bounds__(256) void dropout_mask(DropArgs d, long long n, float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = dropout_u32(drop_key(d), (uint64_t)i, 1u, 0u) >= d.thresh ? d.inv_keep : 0.0f;
+}
+
 __global__ __launch_bounds__(256) void attn_fill(long long rows, int cols, long long ld, float value, float *__restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= rows * cols) return;
@@ -45,11 +54,21 @@ void launch_width(const sextans_engine *e, const sx::AttnArgs &a, const int *per
         hipLaunchKernelGGL((sx::attn_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
                            e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
 }
+// the dropout variant of the same two kernels (p > 0 only)
+template <int PASS, int T, int P, int U>
+void launch_width(const sextans_engine *e, const sx::AttnDropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
+    hipLaunchKernelGGL((sx::attn_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
+                       nw, heads_inside ? 1 : 0);
+    if (e->softmax.nchunks > 0)
+        hipLaunchKernelGGL((sx::attn_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
+                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
+}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  One register width serves both
 // head dimensions: the smallest of 8 / 16 / 32 / 64 / 128 floats that holds the larger one.
-template <int PASS>
-void launch_pass(const sextans_engine *e, const sx::AttnArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+template <int PASS, class Args>
+void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
     const int w = a.d > a.dv ? a.d : a.dv;
     constexpr bool F = PASS == sx::kAttnForward;
     if (w <= 8) launch_width<PASS, 2, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
@@ -64,11 +83,15 @@ void launch_pass(const sextans_engine *e, const sx::AttnArgs &a, const int *perm
 
 using namespace sxe;
 
-extern "C" {
+namespace {
 
-int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
-                             const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+int attention_forward(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                      const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop,
+                      void *stream) {
     if (int rc = check_dims(h, heads, d, dv)) return rc;   // nothing here needs a device
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     if (bad_ld(ldq, (int64_t)heads * d) || bad_ld(ldk, (int64_t)heads * d) || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv))
         return SEXTANS_ERR_INVALID;
     if (((bits(d_Q) | bits(d_K) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
@@ -87,17 +110,28 @@ int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
-    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+    const bool lr = h->softmax.nchunks > 0;
+    if (drop) {
+        sx::AttnDropArgs ad{};
+        static_cast<sx::AttnArgs &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
+        h->last_kernel = lr ? "attention_fused+dropout+long_rows" : "attention_fused+dropout";
+    } else {
+        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+        h->last_kernel = lr ? "attention_fused+long_rows" : "attention_fused";
+    }
     SX_HIP(hipGetLastError());
-    h->last_kernel = h->softmax.nchunks > 0 ? "attention_fused+long_rows" : "attention_fused";
     return SEXTANS_OK;
 }
 
-int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
-                                      int64_t ldk, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse,
-                                      const float *d_G, int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV,
-                                      int64_t lddv, float *d_dbias, void *stream) {
+int attention_backward(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                       const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G,
+                       int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, float *d_dbias,
+                       const sextans_dropout *drop, void *stream) {
     if (int rc = check_dims(h, heads, d, dv)) return rc;
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     const int64_t hd = (int64_t)heads * d, hdv = (int64_t)heads * dv;
     if (bad_ld(ldq, hd) || bad_ld(ldk, hd) || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) || bad_ld(lddq, hd) || bad_ld(lddk, hd) ||
         bad_ld(lddv, hdv))
@@ -125,10 +159,77 @@ int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int 
     a.out_delta = d_delta; a.dQ = d_dQ; a.dK = d_dK; a.dV = d_dV; a.dbias = d_dbias;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
-    launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-    launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
+    if (drop) {
+        sx::AttnDropArgs ad{};
+        static_cast<sx::AttnArgs &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "attention_fused_backward+dropout+long_rows" : "attention_fused_backward+dropout";
+    } else {
+        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "attention_fused_backward+long_rows" : "attention_fused_backward";
+    }
     SX_HIP(hipGetLastError());
-    h->last_kernel = (h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0) ? "attention_fused_backward+long_rows" : "attention_fused_backward";
+    return SEXTANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sextans_attention_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
+                             const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+    return attention_forward(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, nullptr, stream);
+}
+
+int sextans_attention_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
+                                      int64_t ldk, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse,
+                                      const float *d_G, int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV,
+                                      int64_t lddv, float *d_dbias, void *stream) {
+    return attention_backward(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk,
+                              d_dV, lddv, d_dbias, nullptr, stream);
+}
+
+int sextans_attention_dropout_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
+                                     int64_t ldk, const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse,
+                                     const sextans_dropout *drop, void *stream) {
+    return attention_forward(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, drop, stream);
+}
+
+int sextans_attention_dropout_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
+                                              int64_t ldk, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo,
+                                              const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK,
+                                              int64_t lddk, float *d_dV, int64_t lddv, float *d_dbias, const sextans_dropout *drop, void *stream) {
+    return attention_backward(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk,
+                              d_dV, lddv, d_dbias, drop, stream);
+}
+
+/* nnz * heads multipliers, [e * heads + h]: what the fused dropout kernels recompute, written out (the composition path, tests) */
+int sextans_dropout_mask_device(sextans_handle_t h, int heads, const sextans_dropout *drop, float *d_mult, void *stream) {
+    if (!h || heads < 1 || !drop || sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if ((bits(d_mult) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    const long long n = (long long)h->nnz * heads;
+    if (n == 0) return SEXTANS_OK;
+    if (!d_mult) return SEXTANS_ERR_INVALID;
+    SX_HIP(hipSetDevice(h->device));
+    hipLaunchKernelGGL(sx::dropout_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       sx::dropout_args(drop->p, drop->seed, drop->d_step), n, d_mult);
+    SX_HIP(hipGetLastError());
+    h->last_kernel = "dropout_mask";
+    return SEXTANS_OK;
+}
+
+int sextans_dropout_keep_host(int64_t first, int64_t count, int heads, float p, uint64_t seed, uint64_t step, uint8_t *keep) {
+    if (first < 0 || count < 0 || heads < 1 || sx::dropout_bad(p, nullptr) || (count > 0 && !keep)) return SEXTANS_ERR_INVALID;
+    const uint64_t key = sx::dropout_key(seed, step);
+    const uint32_t thresh = sx::dropout_thresh(p);
+    for (int64_t i = 0; i < count; ++i)
+        for (int hh = 0; hh < heads; ++hh)
+            keep[i * heads + hh] = sx::dropout_u32(key, (uint64_t)(first + i), (uint32_t)heads, (uint32_t)hh) >= thresh ? 1 : 0;
     return SEXTANS_OK;
 }
 

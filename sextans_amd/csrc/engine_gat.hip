@@ -1,6 +1,7 @@
 // engine_gat.hip -- fused graph attention (GAT) over the pattern of the CSR matrix on an engine handle (include/sextans_amd.h):
 //   sextans_gat_attention_device            O = softmax(LeakyReLU(adst[r] + asrc[c] + bias) on A's pattern) V per head, and the rows' log-sum-exp
 //   sextans_gat_attention_backward_device   dadst, dasrc, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
+//   sextans_gat_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
 // Kernels: gat_kernels.h (the additive score) on the row walking of attention_kernels.h.  Tables as in engine_attention.hip: the row
 // softmax's of this engine for the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
 #include "engine_state.h"
@@ -23,6 +24,16 @@ void launch_width(const sextans_engine *e, const sx::GatArgs &a, const int *perm
         hipLaunchKernelGGL((sx::gat_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
                            e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
 }
+// the dropout variant of the same two kernels (p > 0 only)
+template <int PASS, int T, int P, int U>
+void launch_width(const sextans_engine *e, const sx::GatDropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
+    hipLaunchKernelGGL((sx::gat_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
+                       nw, heads_inside ? 1 : 0);
+    if (e->softmax.nchunks > 0)
+        hipLaunchKernelGGL((sx::gat_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
+                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
+}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  The slot width follows dv alone:
 // the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.  Entries in flight per slot (U), as measured: the forward
@@ -32,8 +43,8 @@ void launch_width(const sextans_engine *e, const sx::GatArgs &a, const int *perm
 // with the dot-product kernel's dQ[..., 0], which holds only while both make the same roundings -- the forward's U and batches as in
 // engine_attention.hip, and in the row pass a slot adding its entries j, j + E, j + 2 E, .. one after the other (an order U does not
 // change).  Retune either kernel's forward U or the walk's order and that comparison has to be looked at again.
-template <int PASS>
-void launch_pass(const sextans_engine *e, const sx::GatArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+template <int PASS, class Args>
+void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
     if (a.dv <= 8) launch_width<PASS, 2, 1, 4>(e, a, perm, heads_inside, s);
     else if (a.dv <= 16) launch_width<PASS, 4, 1, 4>(e, a, perm, heads_inside, s);
     else if (a.dv <= 32) launch_width<PASS, 8, 1, 4>(e, a, perm, heads_inside, s);
@@ -46,11 +57,14 @@ void launch_pass(const sextans_engine *e, const sx::GatArgs &a, const int *perm,
 
 using namespace sxe;
 
-extern "C" {
+namespace {
 
-int sextans_gat_attention_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc,
-                                 int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+int gat_forward(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc,
+                const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     if (ldadst < heads || ldasrc < heads || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv)) return SEXTANS_ERR_INVALID;
     if (((bits(d_adst) | bits(d_asrc) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
@@ -68,17 +82,28 @@ int sextans_gat_attention_device(sextans_handle_t h, int heads, int dv, float ne
     a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
-    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+    const bool lr = h->softmax.nchunks > 0;
+    if (drop) {
+        sx::GatDropArgs ad{};
+        static_cast<sx::GatArgs &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
+        h->last_kernel = lr ? "gat_fused+dropout+long_rows" : "gat_fused+dropout";
+    } else {
+        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+        h->last_kernel = lr ? "gat_fused+long_rows" : "gat_fused";
+    }
     SX_HIP(hipGetLastError());
-    h->last_kernel = h->softmax.nchunks > 0 ? "gat_fused+long_rows" : "gat_fused";
     return SEXTANS_OK;
 }
 
-int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst,
-                                          const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O,
-                                          int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dadst, int64_t lddadst,
-                                          float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv, float *d_dbias, void *stream) {
+int gat_backward(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc,
+                 const float *d_V, int64_t ldv, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+                 float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv, float *d_dbias,
+                 const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     const int64_t hdv = (int64_t)heads * dv;
     if (ldadst < heads || ldasrc < heads || lddadst < heads || lddasrc < heads || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) ||
         bad_ld(lddv, hdv))
@@ -106,11 +131,53 @@ int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv,
     a.out_delta = d_delta; a.dadst = d_dadst; a.dasrc = d_dasrc; a.dV = d_dV; a.dbias = d_dbias;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddadst = lddadst; a.lddasrc = lddasrc; a.lddv = lddv;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
-    launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-    launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
+    if (drop) {
+        sx::GatDropArgs ad{};
+        static_cast<sx::GatArgs &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "gat_fused_backward+dropout+long_rows" : "gat_fused_backward+dropout";
+    } else {
+        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "gat_fused_backward+long_rows" : "gat_fused_backward";
+    }
     SX_HIP(hipGetLastError());
-    h->last_kernel = (h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0) ? "gat_fused_backward+long_rows" : "gat_fused_backward";
     return SEXTANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sextans_gat_attention_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc,
+                                 int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+    return gat_forward(h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, nullptr, stream);
+}
+
+int sextans_gat_attention_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst,
+                                          const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, const float *d_O,
+                                          int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dadst, int64_t lddadst,
+                                          float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv, float *d_dbias, void *stream) {
+    return gat_backward(h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst,
+                        lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, nullptr, stream);
+}
+
+int sextans_gat_attention_dropout_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst,
+                                         const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo,
+                                         float *d_lse, const sextans_dropout *drop, void *stream) {
+    return gat_forward(h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, drop, stream);
+}
+
+int sextans_gat_attention_dropout_backward_device(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst,
+                                                  const float *d_asrc, int64_t ldasrc, const float *d_V, int64_t ldv, const float *d_bias,
+                                                  const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg, float *d_delta,
+                                                  float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv,
+                                                  float *d_dbias, const sextans_dropout *drop, void *stream) {
+    return gat_backward(h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst,
+                        lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, drop, stream);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 //   sextans_gatv2_workspace_floats            the floats of workspace the backward needs (datt_rows, then the chunk sums)
 //   sextans_gatv2_attention_device            O = softmax(att . LeakyReLU(x_dst[r] + x_src[c]) + bias on A's pattern) x_src per head, and lse
 //   sextans_gatv2_attention_backward_device   dx_dst, dx_src, datt (and dbias): a row pass over A, a column pass over A^T, the two-level datt sum
+//   sextans_gatv2_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
 // Kernels: gatv2_kernels.h on the row walking of attention_kernels.h.  Tables as in engine_gat.hip: the row softmax's of this engine for
 // the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
 #include "engine_state.h"
@@ -24,6 +25,16 @@ void launch_width(const sextans_engine *e, const sx::Gatv2Args &a, const int *pe
         hipLaunchKernelGGL((sx::gatv2_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
                            e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
 }
+// the dropout variant of the same two kernels (p > 0 only)
+template <int PASS, int T, int P, int U>
+void launch_width(const sextans_engine *e, const sx::Gatv2DropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
+    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
+    hipLaunchKernelGGL((sx::gatv2_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
+                       nw, heads_inside ? 1 : 0);
+    if (e->softmax.nchunks > 0)
+        hipLaunchKernelGGL((sx::gatv2_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
+                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
+}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  The slot width follows d alone:
 // the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.  Entries in flight per slot (U): the forward takes the GAT forward's 4
@@ -34,8 +45,8 @@ void launch_width(const sextans_engine *e, const sx::Gatv2Args &a, const int *pe
 // LeakyReLU(x_dst[r,h,0] + x_src[c,h,0]), and O and lse are compared BIT FOR BIT with gat_attention on those scalars and V = x_src.  That
 // holds only while both forwards form the same batches -- the same T, P and U per width as engine_gat.hip's forward -- and make the
 // same roundings after the score.  Retune either forward's U or the walk's order and that comparison has to be looked at again.
-template <int PASS>
-void launch_pass(const sextans_engine *e, const sx::Gatv2Args &a, const int *perm, bool heads_inside, hipStream_t s) {
+template <int PASS, class Args>
+void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
     constexpr bool F = PASS == sx::kAttnForward;
     if (a.d <= 8) launch_width<PASS, 2, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
     else if (a.d <= 16) launch_width<PASS, 4, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
@@ -60,9 +71,16 @@ int64_t sextans_gatv2_workspace_floats(sextans_handle_t h, int heads, int d) {
     return (int64_t)h->M * hd + chunks_of(h->M) * hd;
 }
 
-int sextans_gatv2_attention_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc,
-                                   int64_t ldxs, const float *d_att, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+int gatv2_forward(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs,
+                  const float *d_att, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(d) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd)) return SEXTANS_ERR_INVALID;
     if (((bits(d_xdst) | bits(d_xsrc) | bits(d_att) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
@@ -81,17 +99,28 @@ int sextans_gatv2_attention_device(sextans_handle_t h, int heads, int d, float n
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.att = d_att; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo;
     a.H = heads; a.d = d; a.slope = negative_slope;
-    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+    const bool lr = h->softmax.nchunks > 0;
+    if (drop) {
+        sx::Gatv2DropArgs ad{};
+        static_cast<sx::Gatv2Args &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
+        h->last_kernel = lr ? "gatv2_fused+dropout+long_rows" : "gatv2_fused+dropout";
+    } else {
+        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
+        h->last_kernel = lr ? "gatv2_fused+long_rows" : "gatv2_fused";
+    }
     SX_HIP(hipGetLastError());
-    h->last_kernel = h->softmax.nchunks > 0 ? "gatv2_fused+long_rows" : "gatv2_fused";
     return SEXTANS_OK;
 }
 
-int sextans_gatv2_attention_backward_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd,
-                                            const float *d_xsrc, int64_t ldxs, const float *d_att, const float *d_bias, const float *d_O, int64_t ldo,
-                                            const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dxdst, int64_t lddxd,
-                                            float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work, float *d_dbias, void *stream) {
+int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs,
+                   const float *d_att, const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+                   float *d_delta, float *d_dxdst, int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work, float *d_dbias,
+                   const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(d) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;
+    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
+    if (drop && drop->p == 0.0f) drop = nullptr;
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd) || bad_ld(ldg, hd) || bad_ld(lddxd, hd) || bad_ld(lddxs, hd)) return SEXTANS_ERR_INVALID;
     if (((bits(d_xdst) | bits(d_xsrc) | bits(d_att) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dxdst) | bits(d_dxsrc) |
@@ -122,13 +151,55 @@ int sextans_gatv2_attention_backward_device(sextans_handle_t h, int heads, int d
     a.out_delta = d_delta; a.dxdst = d_dxdst; a.dxsrc = d_dxsrc; a.datt_rows = d_work; a.dbias = d_dbias;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo; a.ldg = ldg; a.lddxd = lddxd; a.lddxs = lddxs;
     a.H = heads; a.d = d; a.slope = negative_slope;
-    launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-    launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
+    if (drop) {
+        sx::Gatv2DropArgs ad{};
+        static_cast<sx::Gatv2Args &>(ad) = a;
+        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
+        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "gatv2_fused_backward+dropout+long_rows" : "gatv2_fused_backward+dropout";
+    } else {
+        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
+        h->last_kernel = lr ? "gatv2_fused_backward+long_rows" : "gatv2_fused_backward";
+    }
     hipLaunchKernelGGL(sx::gatv2_datt_chunks, dim3((unsigned)nchunks), dim3(256), 0, s, d_work, (long long)h->M, (int)hd, d_part);
     hipLaunchKernelGGL(sx::gatv2_datt_total, dim3((unsigned)((hd + 255) / 256)), dim3(256), 0, s, d_part, (long long)nchunks, (int)hd, d_datt);
     SX_HIP(hipGetLastError());
-    h->last_kernel = (h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0) ? "gatv2_fused_backward+long_rows" : "gatv2_fused_backward";
     return SEXTANS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sextans_gatv2_attention_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc,
+                                   int64_t ldxs, const float *d_att, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, void *stream) {
+    return gatv2_forward(h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, nullptr, stream);
+}
+
+int sextans_gatv2_attention_backward_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd,
+                                            const float *d_xsrc, int64_t ldxs, const float *d_att, const float *d_bias, const float *d_O, int64_t ldo,
+                                            const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dxdst, int64_t lddxd,
+                                            float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work, float *d_dbias, void *stream) {
+    return gatv2_backward(h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dxdst, lddxd,
+                          d_dxsrc, lddxs, d_datt, d_work, d_dbias, nullptr, stream);
+}
+
+int sextans_gatv2_attention_dropout_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd,
+                                           const float *d_xsrc, int64_t ldxs, const float *d_att, const float *d_bias, float *d_O, int64_t ldo,
+                                           float *d_lse, const sextans_dropout *drop, void *stream) {
+    return gatv2_forward(h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, drop, stream);
+}
+
+int sextans_gatv2_attention_dropout_backward_device(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd,
+                                                    const float *d_xsrc, int64_t ldxs, const float *d_att, const float *d_bias, const float *d_O,
+                                                    int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg, float *d_delta, float *d_dxdst,
+                                                    int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work, float *d_dbias,
+                                                    const sextans_dropout *drop, void *stream) {
+    return gatv2_backward(h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dxdst, lddxd,
+                          d_dxsrc, lddxs, d_datt, d_work, d_dbias, drop, stream);
 }
 
 }  // extern "C"

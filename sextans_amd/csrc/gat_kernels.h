@@ -28,25 +28,29 @@ struct GatArgs {
     int H, dv;
     float slope;
 };
+struct GatDropArgs : GatArgs { DropArgs drop; };   // attention dropout: the DROP variant of the pass (attention_kernels.h)
 
 // LeakyReLU that keeps a -inf mask for every slope (0 * -inf would be NaN); NaN stays NaN
 __device__ __forceinline__ float gat_act(float z, float slope) { return (z > 0.0f || z == -INFINITY) ? z : __fmul_rn(slope, z); }
 
 // One slot's view of a pass: the interface of AttnPass.
-template <int PASS, int T_, int P_, int U_>
+template <int PASS, int T_, int P_, int U_, bool DROP = false>
 struct GatPass {
-    using Args = GatArgs;
+    using Args = std::conditional_t<DROP, GatDropArgs, GatArgs>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? 1 : 1 + W;   // forward: m, Z, acc; rows: dadst; cols: dasrc, dV
-    const GatArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0;
     float y[W];   // the own row's vector: G (rows), V (cols)
     float f[NF];
     float own = 0.f, lse = 0.f, delta = 0.f;   // own: adst[r,h] (forward, rows), asrc[c,h] (cols)
+    uint64_t key = 0;   // DROP: the mask's key
 
-    __device__ __forceinline__ GatPass(const GatArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ GatPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {
+        if constexpr (DROP) key = drop_key(a.drop);
+    }
 
     __device__ __forceinline__ void begin(bool act, int own_row, int head, bool writer) {
         h = head;
@@ -93,11 +97,15 @@ struct GatPass {
                 bs[u] = (a.bias && valid[u]) ? a.bias[e[u]] : 0.0f;
             }
         }
-        float z[U], s[U];
+        float z[U], s[U], mk[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             z[u] = __fadd_rn(__fadd_rn(own, sc[u]), bs[u]);   // (adst + asrc) + bias in every pass: the first add commutes
             s[u] = gat_act(z[u], a.slope);
+        }
+        if constexpr (DROP) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, valid[u] ? (PASS == kAttnBackwardCols ? perm[e[u]] : e[u]) : 0, a.H, h);
         }
         if (PASS == kAttnForward) {
             float mn = f[0];
@@ -114,21 +122,24 @@ struct GatPass {
             for (int u = 0; u < U; ++u) {
                 const float p = softmax_exp(__fsub_rn(s[u], mref));
                 f[1] = __fadd_rn(f[1], p);
+                float pm = p;
+                if constexpr (DROP) pm = __fmul_rn(mk[u], p);
 #pragma unroll
-                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(p, p2[u][i], f[2 + i]);
+                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(pm, p2[u][i], f[2 + i]);
             }
             f[0] = mn;
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const float p = valid[u] ? softmax_exp(__fsub_rn(s[u], ls[u])) : 0.0f;
-                const float dp = attn_dot<T, W>(y, p2[u]);
+                float dp = attn_dot<T, W>(y, p2[u]), pm = p;
+                if constexpr (DROP) { dp = __fmul_rn(mk[u], dp); pm = __fmul_rn(mk[u], p); }
                 const float ds = valid[u] ? __fmul_rn(p, __fsub_rn(dp, dl[u])) : 0.0f;
                 const float dz = z[u] > 0.0f ? ds : __fmul_rn(a.slope, ds);   // (z == 0 takes the slope)
                 f[0] = __fadd_rn(f[0], dz);
                 if (PASS == kAttnBackwardCols) {
 #pragma unroll
-                    for (int i = 0; i < W; ++i) f[1 + i] = __fmaf_rn(p, p2[u][i], f[1 + i]);
+                    for (int i = 0; i < W; ++i) f[1 + i] = __fmaf_rn(pm, p2[u][i], f[1 + i]);
                 } else if (a.dbias && valid[u] && t == 0) {
                     // the heads of an entry are taken by this lane one after the other, in ascending order: a plain read-modify-write
                     a.dbias[e[u]] = h == 0 ? dz : __fadd_rn(a.dbias[e[u]], dz);
@@ -204,6 +215,18 @@ template <int PASS, int T, int P, int U>
 __global__ __launch_bounds__(256) void gat_long(GatArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
                                                 const int2 *__restrict__ tab, int heads_inside) {
     attn_long_body<GatPass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
+}
+
+// the same two kernels with the dropout mask (launched only when p > 0)
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void gat_rows_drop(GatDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                     const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
+    attn_rows_body<GatPass<PASS, T, P, U, true>>(a, rp, ci, perm, wrow, nw, heads_inside);
+}
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void gat_long_drop(GatDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                     const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
+    attn_long_body<GatPass<PASS, T, P, U, true>>(a, rp, ci, perm, tab, heads_inside);
 }
 
 }  // namespace sx

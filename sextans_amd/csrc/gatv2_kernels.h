@@ -30,22 +30,26 @@ struct Gatv2Args {
     int H, d;
     float slope;
 };
+struct Gatv2DropArgs : Gatv2Args { DropArgs drop; };   // attention dropout: the DROP variant of the pass (attention_kernels.h)
 
 // One slot's view of a pass: the interface of AttnPass / GatPass.
-template <int PASS, int T_, int P_, int U_>
+template <int PASS, int T_, int P_, int U_, bool DROP = false>
 struct Gatv2Pass {
-    using Args = Gatv2Args;
+    using Args = std::conditional_t<DROP, Gatv2DropArgs, Gatv2Args>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? 2 * W : W;   // forward: m, Z, acc; rows: dx_dst, datt_rows; cols: dx_src
-    const Gatv2Args &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0;
     float x[W], w[W], y[W];   // the own row (x_dst; cols: x_src), the head's att, G of the own row (rows pass only)
     float f[NF];
     float lse = 0.f, delta = 0.f;
+    uint64_t key = 0;   // DROP: the mask's key
 
-    __device__ __forceinline__ Gatv2Pass(const Gatv2Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ Gatv2Pass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {
+        if constexpr (DROP) key = drop_key(a.drop);
+    }
 
     __device__ __forceinline__ void begin(bool act, int own_row, int head, bool writer) {
         h = head;
@@ -93,6 +97,11 @@ struct Gatv2Pass {
                 bs[u] = (a.bias && valid[u]) ? a.bias[e[u]] : 0.0f;
             }
         }
+        float mk[U];
+        if constexpr (DROP) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, valid[u] ? (PASS == kAttnBackwardCols ? perm[e[u]] : e[u]) : 0, a.H, h);
+        }
         if (PASS == kAttnForward) {
             float s[U];
 #pragma unroll
@@ -119,8 +128,10 @@ struct Gatv2Pass {
             for (int u = 0; u < U; ++u) {
                 const float p = softmax_exp(__fsub_rn(s[u], mref));
                 f[1] = __fadd_rn(f[1], p);
+                float pm = p;
+                if constexpr (DROP) pm = __fmul_rn(mk[u], p);
 #pragma unroll
-                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(p, p1[u][i], f[2 + i]);
+                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(pm, p1[u][i], f[2 + i]);
             }
             f[0] = mn;
         } else {
@@ -137,11 +148,12 @@ struct Gatv2Pass {
                 const float s = __fadd_rn(attn_dot<T, W>(w, l), bs[u]);
                 const float p = valid[u] ? softmax_exp(__fsub_rn(s, ls[u])) : 0.0f;
                 // <G[r], x_src[c]>: rows: G is the own row's, x_src gathered; cols: the other way round
-                const float dp = PASS == kAttnBackwardCols ? attn_dot<T, W>(p2[u % NG], x) : attn_dot<T, W>(y, p1[u]);
+                float dp = PASS == kAttnBackwardCols ? attn_dot<T, W>(p2[u % NG], x) : attn_dot<T, W>(y, p1[u]), pm = p;
+                if constexpr (DROP) { dp = __fmul_rn(mk[u], dp); pm = __fmul_rn(mk[u], p); }
                 const float ds = valid[u] ? __fmul_rn(p, __fsub_rn(dp, dl[u])) : 0.0f;
                 if (PASS == kAttnBackwardCols) {
 #pragma unroll
-                    for (int i = 0; i < W; ++i) f[i] = __fmaf_rn(ds, c[i], __fmaf_rn(p, p2[u % NG][i], f[i]));
+                    for (int i = 0; i < W; ++i) f[i] = __fmaf_rn(ds, c[i], __fmaf_rn(pm, p2[u % NG][i], f[i]));
                 } else {
 #pragma unroll
                     for (int i = 0; i < W; ++i) {
@@ -224,6 +236,18 @@ template <int PASS, int T, int P, int U>
 __global__ __launch_bounds__(256) void gatv2_long(Gatv2Args a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
                                                   const int2 *__restrict__ tab, int heads_inside) {
     attn_long_body<Gatv2Pass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
+}
+
+// the same two kernels with the dropout mask (launched only when p > 0)
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void gatv2_rows_drop(Gatv2DropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                       const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
+    attn_rows_body<Gatv2Pass<PASS, T, P, U, true>>(a, rp, ci, perm, wrow, nw, heads_inside);
+}
+template <int PASS, int T, int P, int U>
+__global__ __launch_bounds__(256) void gatv2_long_drop(Gatv2DropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
+                                                       const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
+    attn_long_body<Gatv2Pass<PASS, T, P, U, true>>(a, rp, ci, perm, tab, heads_inside);
 }
 
 // datt = the sum of datt_rows over ALL rows, in two levels whose order is the definition of datt's bits (no atomics):

@@ -23,6 +23,14 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
     O = gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False)   GATv2 (GATv2Conv): the activation inside the projection
                                                    softmax(<att, leaky_relu(x_dst[r] + x_src[c])> [+ A_e]) x_src per head, fused the same way
 
+Dropout on the normalised attention coefficients (GATConv / GATv2Conv's dropout, attn_drop), made INSIDE the fused kernels from a hash
+of (seed, step, entry, head) -- the coefficients are never materialised, so it cannot be applied from outside:
+
+    O = sparse_attention_dropout(A, Q, K, V, dropout, seed=None, step=None, scale=None, bias=False, fast=False, fused=False)
+    O = gat_attention_dropout(A, a_dst, a_src, V, dropout, seed=None, step=None, negative_slope=0.2, bias=False, fast=False)
+    O = gatv2_attention_dropout(A, x_dst, x_src, att, dropout, seed=None, step=None, negative_slope=0.2, bias=False, fast=False)
+    m = dropout_mask(A, heads, p, seed, step=None)   the (nnz, heads) multipliers themselves: 1 / (1 - p) or 0
+
 Max / min / mean aggregation over a node's neighbours (GraphSAGE-pool, PNA, EdgeConv; torch.sparse.mm(A, B, reduce) on the CPU, reduce="max"
 in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
 
@@ -493,13 +501,78 @@ def _heads_operand(t, dp):
     return out, H * dp
 
 
+def _check_dropout(p):
+    p = float(p)
+    if not (0.0 <= p < 1.0):
+        raise ValueError("dropout must be in [0, 1)")
+    return p
+
+
+def _draw_seed(seed):
+    """seed=None: one int64 from torch's default CPU generator, so torch.manual_seed reproduces a run"""
+    return int(torch.empty((), dtype=torch.int64).random_()) if seed is None else int(seed)
+
+
+def _check_step(step, device):
+    if step is None:
+        return None
+    if not (isinstance(step, torch.Tensor) and step.is_cuda and step.numel() == 1 and step.dtype in (torch.int64, torch.uint64) and
+            step.device == device):
+        raise TypeError("step must be None or a one-element int64 / uint64 tensor on A's device")
+    return step
+
+
+def _drop_struct(p, seed, step):
+    """The engine's view of (dropout, seed, step): None when nothing is dropped (the entries without dropout are then called)"""
+    return api.Dropout(p, seed, step.data_ptr() if step is not None else None) if p > 0.0 else None
+
+
+def dropout_mask(A, heads, p, seed, step=None):
+    """The attention-dropout multipliers the fused kernels apply (sextans_dropout_mask_device): an (nnz, heads) fp32 tensor on A's
+    device, 1 / (1 - p) where (entry, head) is kept, 0 where it is dropped; entries in A's CSR order.  step: None (0), or a one-element
+    int64 / uint64 tensor on the device whose value is added to the seed when the kernel runs."""
+    _check_sparse(A, "dropout_mask")
+    p = _check_dropout(p)
+    heads = int(heads)
+    if heads < 1:
+        raise ValueError("heads must be >= 1")
+    step = _check_step(step, A.device)
+    crow, col = _index_tensors(A)
+    val = A.values()
+    ent = _entry_for_parts(crow, col, val, tuple(A.shape), A.device.index or 0, False, values_needed=False)
+    out = torch.empty((val.numel(), heads), dtype=torch.float32, device=A.device)
+    if out.numel():
+        ent.eng.dropout_mask_device(heads, api.Dropout(p, int(seed), step.data_ptr() if step is not None else None), out.data_ptr(),
+                                    torch.cuda.current_stream(A.device).cuda_stream)
+    return out
+
+
+class _ScaleValuesFunction(torch.autograd.Function):
+    """P with its values multiplied by a constant vector (one head's column of dropout_mask): the composition's dropout.  The gradient
+    is the upstream gradient's values times the same vector."""
+
+    @staticmethod
+    def forward(ctx, P, mult):
+        crow, col = _index_tensors(P)
+        ctx.save_for_backward(crow, col, mult)
+        ctx.shape, ctx.vdtype = tuple(P.shape), P.values().dtype
+        return torch.sparse_csr_tensor(crow, col, (P.values().detach().to(torch.float32) * mult).to(ctx.vdtype), size=ctx.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, mult = ctx.saved_tensors
+        g = _grad_values(G, crow, col, int(mult.numel()))
+        return torch.sparse_csr_tensor(crow, col, (g * mult).to(ctx.vdtype), size=ctx.shape), None
+
+
 class _FusedAttentionFunction(torch.autograd.Function):
     """sparse_attention(fused=True): one kernel pass forward (sextans_attention_device), a row pass and a column pass backward
     (sextans_attention_backward_device), all heads at once.  Nothing of size nnz is kept: the backward recomputes the probabilities from
     the rows' log-sum-exp.  A's values enter as an explicit bias pointer, never through the engine: no value refresh anywhere."""
 
     @staticmethod
-    def forward(ctx, A, Q, K, V, scale, bias, fast):
+    def forward(ctx, A, Q, K, V, scale, bias, fast, p=0.0, seed=0, step=None):
         M, Kk = A.shape
         H, d, dv = Q.shape[1], Q.shape[2], V.shape[2]
         dp, dvp = -(-d // 8) * 8, -(-dv // 8) * 8
@@ -513,11 +586,17 @@ class _FusedAttentionFunction(torch.autograd.Function):
         b = _vals32(val) if bias else None
         O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
         lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
-        ent.eng.attention_device(H, dp, dvp, scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv,
-                                 b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(),
-                                 torch.cuda.current_stream(A.device).cuda_stream)
+        args = (H, dp, dvp, scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv, b.data_ptr() if b is not None else None,
+                O.data_ptr(), H * dvp, lse.data_ptr())
+        drop = _drop_struct(p, seed, step)
+        stream = torch.cuda.current_stream(A.device).cuda_stream
+        if drop is None:
+            ent.eng.attention_device(*args, stream)
+        else:
+            ent.eng.attention_dropout_device(*args, drop, stream)
         ctx.save_for_backward(crow, col, val, Q, K, V, O, lse)
         ctx.shape, ctx.scale, ctx.bias, ctx.fast, ctx.dev = (M, Kk), scale, bias, fast, dev
+        ctx.drop = (p, seed, step)   # the backward recomputes the forward's mask
         return O if dvp == dv else O[:, :, :dv]
 
     @staticmethod
@@ -539,15 +618,20 @@ class _FusedAttentionFunction(torch.autograd.Function):
         dK = torch.empty((Kk, H, dp), dtype=torch.float32, device=G.device)
         dV = torch.empty((Kk, H, dvp), dtype=torch.float32, device=G.device)
         db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
-        ent.eng.attention_backward_device(H, dp, dvp, ctx.scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv,
-                                          b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg,
-                                          delta.data_ptr(), dQ.data_ptr(), H * dp, dK.data_ptr(), H * dp, dV.data_ptr(), H * dvp,
-                                          db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        args = (H, dp, dvp, ctx.scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv, b.data_ptr() if b is not None else None,
+                O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg, delta.data_ptr(), dQ.data_ptr(), H * dp, dK.data_ptr(), H * dp,
+                dV.data_ptr(), H * dvp, db.data_ptr() if db is not None else None)
+        drop = _drop_struct(*ctx.drop)
+        stream = torch.cuda.current_stream(G.device).cuda_stream
+        if drop is None:
+            ent.eng.attention_backward_device(*args, stream)
+        else:
+            ent.eng.attention_dropout_backward_device(*args, drop, stream)
         gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
         gQ = (dQ if dp == d else dQ[:, :, :d]).to(Q.dtype) if ctx.needs_input_grad[1] else None
         gK = (dK if dp == d else dK[:, :, :d]).to(K.dtype) if ctx.needs_input_grad[2] else None
         gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if ctx.needs_input_grad[3] else None
-        return gA, gQ, gK, gV, None, None, None
+        return gA, gQ, gK, gV, None, None, None, None, None, None
 
 
 def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False):
@@ -562,6 +646,34 @@ def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False
     softmax, nothing of size nnz written, no value refresh; the backward keeps O and M * H floats instead of S and P.  Within the
     tolerance of a chain of fp32 operations of the composition, not bit-equal to it.  Head dimensions up to 128; those that are not
     multiples of 8, and operands that do not lie as the kernels read them, are copied with zero padding."""
+    return _sparse_attention(A, Q, K, V, scale, bias, fast, fused, 0.0, 0, None)
+
+
+def sparse_attention_dropout(A, Q, K, V, dropout, seed=None, step=None, scale=None, bias=False, fast=False, fused=False):
+    """sparse_attention() with dropout on the normalised attention coefficients (attn_drop): every (entry, head) coefficient is zeroed
+    with probability `dropout` and the others are multiplied by 1 / (1 - dropout), after the softmax (dropped entries still count in the
+    row's sum).  dropout in [0, 1), else ValueError; 0 is sparse_attention() itself, bit for bit.
+    The mask is a hash of (seed + step, entry, head), bit-reproducible.  seed=None draws one int64 from torch's default CPU generator, so
+    torch.manual_seed reproduces a run; step: None, or a one-element int64 / uint64 tensor on the device that the kernels read when
+    they run -- a captured graph draws a new mask on every replay when the caller bumps it in between.  The backward uses the forward's
+    seed and step.
+    fused=True: the mask is recomputed inside the kernels of all three passes (sextans_attention_dropout_device /
+    sextans_attention_dropout_backward_device); nothing of size nnz exists.  fused=False: the composition with P multiplied by
+    dropout_mask()'s column of the head before the SpMM -- the same mask, so both agree within the tolerance of sparse_attention()."""
+    return _sparse_attention(A, Q, K, V, scale, bias, fast, fused, _check_dropout(dropout), seed, step)
+
+
+def _composed_attention(A, Q, K, V, scale, bias, fast, mult):
+    """one head of the composition; mult: None, or the head's column of dropout_mask()"""
+    S = sddmm(A, Q, K, 1.0, 1.0 if bias else 0.0, fast)
+    P = row_softmax(S, scale, fast)
+    if mult is not None:
+        crow, col = _index_tensors(P)
+        P = _carry(_ScaleValuesFunction.apply(P, mult), crow, col)
+    return spmm(P, V, fast=fast)
+
+
+def _sparse_attention(A, Q, K, V, scale, bias, fast, fused, p, seed, step):
     _check_sparse(A, "sparse_attention")
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (Q, K, V)):
         raise TypeError("sparse_attention expects CUDA/HIP dense Q, K and V")
@@ -570,8 +682,8 @@ def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False
             raise ValueError("shape mismatch")
         if scale is None:
             scale = 1.0 / math.sqrt(Q.shape[1])
-        S = sddmm(A, Q, K, 1.0, 1.0 if bias else 0.0, fast)
-        return spmm(row_softmax(S, scale, fast), V, fast=fast)
+        mult = dropout_mask(A, 1, p, _draw_seed(seed), step)[:, 0] if p > 0.0 else None
+        return _composed_attention(A, Q, K, V, scale, bias, fast, mult)
     if any(t.dim() not in (2, 3) for t in (Q, K, V)):
         raise ValueError("Q, K and V are (rows, d) or (rows, heads, d)")
     Q3, K3, V3 = (t if t.dim() == 3 else t.unsqueeze(1) for t in (Q, K, V))
@@ -583,12 +695,19 @@ def sparse_attention(A, Q, K, V, scale=None, bias=False, fast=False, fused=False
         raise ValueError("shape mismatch")
     if scale is None:
         scale = 1.0 / math.sqrt(d)
+    if p > 0.0:
+        seed, step = _draw_seed(seed), _check_step(step, A.device)
     if not fused:
-        out = torch.stack([sparse_attention(A, Q3[:, h], K3[:, h], V3[:, h], scale, bias, fast) for h in range(H)], dim=1)
+        mult = dropout_mask(A, H, p, seed, step) if p > 0.0 else None
+        out = torch.stack([_composed_attention(A, Q3[:, h], K3[:, h], V3[:, h], scale, bias, fast,
+                                               mult[:, h].contiguous() if mult is not None else None) for h in range(H)], dim=1)
     else:
         if d > 128 or V3.shape[2] > 128:
             raise ValueError("fused sparse_attention: head dimensions up to 128")
-        out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast))
+        if p > 0.0:
+            out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast), p, seed, step)
+        else:
+            out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast), 0.0, 0, None)
     return out if V.dim() == 3 else out[:, 0]
 
 
@@ -610,7 +729,7 @@ class _GatAttentionFunction(torch.autograd.Function):
     anywhere."""
 
     @staticmethod
-    def forward(ctx, A, adst, asrc, V, slope, bias, fast):
+    def forward(ctx, A, adst, asrc, V, slope, bias, fast, p=0.0, seed=0, step=None):
         M, Kk = A.shape
         H, dv = V.shape[1], V.shape[2]
         dvp = -(-dv // 8) * 8
@@ -624,11 +743,17 @@ class _GatAttentionFunction(torch.autograd.Function):
         b = _vals32(val) if bias else None
         O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
         lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
-        ent.eng.gat_attention_device(H, dvp, slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv,
-                                     b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(),
-                                     torch.cuda.current_stream(A.device).cuda_stream)
+        args = (H, dvp, slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv, b.data_ptr() if b is not None else None,
+                O.data_ptr(), H * dvp, lse.data_ptr())
+        drop = _drop_struct(p, seed, step)
+        stream = torch.cuda.current_stream(A.device).cuda_stream
+        if drop is None:
+            ent.eng.gat_attention_device(*args, stream)
+        else:
+            ent.eng.gat_attention_dropout_device(*args, drop, stream)
         ctx.save_for_backward(crow, col, val, adst, asrc, V, O, lse)
         ctx.shape, ctx.slope, ctx.bias, ctx.fast, ctx.dev = (M, Kk), slope, bias, fast, dev
+        ctx.drop = (p, seed, step)   # the backward recomputes the forward's mask
         return O if dvp == dv else O[:, :, :dv]
 
     @staticmethod
@@ -650,15 +775,20 @@ class _GatAttentionFunction(torch.autograd.Function):
         das = torch.empty((Kk, H), dtype=torch.float32, device=G.device)
         dV = torch.empty((Kk, H, dvp), dtype=torch.float32, device=G.device)
         db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
-        ent.eng.gat_attention_backward_device(H, dvp, ctx.slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv,
-                                              b.data_ptr() if b is not None else None, O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg,
-                                              delta.data_ptr(), dad.data_ptr(), H, das.data_ptr(), H, dV.data_ptr(), H * dvp,
-                                              db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        args = (H, dvp, ctx.slope, ad.data_ptr(), ldad, as_.data_ptr(), ldas, Vr.data_ptr(), ldv, b.data_ptr() if b is not None else None,
+                O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg, delta.data_ptr(), dad.data_ptr(), H, das.data_ptr(), H,
+                dV.data_ptr(), H * dvp, db.data_ptr() if db is not None else None)
+        drop = _drop_struct(*ctx.drop)
+        stream = torch.cuda.current_stream(G.device).cuda_stream
+        if drop is None:
+            ent.eng.gat_attention_backward_device(*args, stream)
+        else:
+            ent.eng.gat_attention_dropout_backward_device(*args, drop, stream)
         gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
         gad = dad.to(adst.dtype) if ctx.needs_input_grad[1] else None
         gas = das.to(asrc.dtype) if ctx.needs_input_grad[2] else None
         gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if ctx.needs_input_grad[3] else None
-        return gA, gad, gas, gV, None, None, None
+        return gA, gad, gas, gV, None, None, None, None, None, None
 
 
 def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False):
@@ -671,6 +801,18 @@ def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False
     nothing of size nnz written, no value refresh; the backward keeps O and M * H floats.  Differentiable in a_dst, a_src, V and
     (bias=True) A; gradients come in the operands' dtypes.  dv up to 128; a dv that is not a multiple of 8, and operands that do not lie
     as the kernels read them, are copied (V with zero padding).  negative_slope: finite, >= 0."""
+    return _gat_attention(A, a_dst, a_src, V, negative_slope, bias, fast, 0.0, 0, None)
+
+
+def gat_attention_dropout(A, a_dst, a_src, V, dropout, seed=None, step=None, negative_slope=0.2, bias=False, fast=False):
+    """gat_attention() with dropout on the normalised attention coefficients, as GATConv(dropout=...) in PyG and attn_drop in DGL (the
+    GAT paper trains with 0.6): made inside the fused kernels of all three passes (sextans_gat_attention_dropout_device /
+    sextans_gat_attention_dropout_backward_device), nothing of size nnz exists.  dropout, seed and step as in
+    sparse_attention_dropout(); dropout=0 is gat_attention() itself, bit for bit."""
+    return _gat_attention(A, a_dst, a_src, V, negative_slope, bias, fast, _check_dropout(dropout), seed, step)
+
+
+def _gat_attention(A, a_dst, a_src, V, negative_slope, bias, fast, p, seed, step):
     _check_sparse(A, "gat_attention")
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (a_dst, a_src, V)):
         raise TypeError("gat_attention expects CUDA/HIP dense a_dst, a_src and V")
@@ -690,7 +832,10 @@ def gat_attention(A, a_dst, a_src, V, negative_slope=0.2, bias=False, fast=False
     slope = float(negative_slope)
     if not (slope >= 0.0) or math.isinf(slope):
         raise ValueError("negative_slope must be finite and >= 0")
-    out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast))
+    if p > 0.0:
+        out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast), p, _draw_seed(seed), _check_step(step, A.device))
+    else:
+        out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast), 0.0, 0, None)
     return out if V.dim() == 3 else out[:, 0]
 
 
@@ -701,7 +846,7 @@ class _Gatv2AttentionFunction(torch.autograd.Function):
     x_dst and x_src may be the same tensor: autograd adds the two gradients."""
 
     @staticmethod
-    def forward(ctx, A, xdst, xsrc, att, slope, bias, fast):
+    def forward(ctx, A, xdst, xsrc, att, slope, bias, fast, p=0.0, seed=0, step=None):
         M, Kk = A.shape
         H, d = xdst.shape[1], xdst.shape[2]
         dp = -(-d // 8) * 8
@@ -715,11 +860,17 @@ class _Gatv2AttentionFunction(torch.autograd.Function):
         b = _vals32(val) if bias else None
         O = torch.empty((M, H, dp), dtype=torch.float32, device=A.device)
         lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
-        ent.eng.gatv2_attention_device(H, dp, slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(),
-                                       b.data_ptr() if b is not None else None, O.data_ptr(), H * dp, lse.data_ptr(),
-                                       torch.cuda.current_stream(A.device).cuda_stream)
+        args = (H, dp, slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(), b.data_ptr() if b is not None else None, O.data_ptr(),
+                H * dp, lse.data_ptr())
+        drop = _drop_struct(p, seed, step)
+        stream = torch.cuda.current_stream(A.device).cuda_stream
+        if drop is None:
+            ent.eng.gatv2_attention_device(*args, stream)
+        else:
+            ent.eng.gatv2_attention_dropout_device(*args, drop, stream)
         ctx.save_for_backward(crow, col, val, xdst, xsrc, att, O, lse)
         ctx.shape, ctx.slope, ctx.bias, ctx.fast, ctx.dev = (M, Kk), slope, bias, fast, dev
+        ctx.drop = (p, seed, step)   # the backward recomputes the forward's mask
         return O if dp == d else O[:, :, :d]
 
     @staticmethod
@@ -742,15 +893,20 @@ class _Gatv2AttentionFunction(torch.autograd.Function):
         dat = torch.empty((H, dp), dtype=torch.float32, device=G.device)
         work = torch.empty((max(ent.eng.gatv2_workspace_floats(H, dp), 1),), dtype=torch.float32, device=G.device)
         db = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_bias else None
-        ent.eng.gatv2_attention_backward_device(H, dp, ctx.slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(),
-                                                b.data_ptr() if b is not None else None, O.data_ptr(), H * dp, lse.data_ptr(), Gr.data_ptr(), ldg,
-                                                delta.data_ptr(), dxd.data_ptr(), H * dp, dxs.data_ptr(), H * dp, dat.data_ptr(), work.data_ptr(),
-                                                db.data_ptr() if db is not None else None, torch.cuda.current_stream(G.device).cuda_stream)
+        args = (H, dp, ctx.slope, xd.data_ptr(), ldxd, xs.data_ptr(), ldxs, at.data_ptr(), b.data_ptr() if b is not None else None,
+                O.data_ptr(), H * dp, lse.data_ptr(), Gr.data_ptr(), ldg, delta.data_ptr(), dxd.data_ptr(), H * dp, dxs.data_ptr(), H * dp,
+                dat.data_ptr(), work.data_ptr(), db.data_ptr() if db is not None else None)
+        drop = _drop_struct(*ctx.drop)
+        stream = torch.cuda.current_stream(G.device).cuda_stream
+        if drop is None:
+            ent.eng.gatv2_attention_backward_device(*args, stream)
+        else:
+            ent.eng.gatv2_attention_dropout_backward_device(*args, drop, stream)
         gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
         gxd = (dxd if dp == d else dxd[:, :, :d]).to(xdst.dtype) if ctx.needs_input_grad[1] else None
         gxs = (dxs if dp == d else dxs[:, :, :d]).to(xsrc.dtype) if ctx.needs_input_grad[2] else None
         gat = (dat if dp == d else dat[:, :d]).to(att.dtype) if ctx.needs_input_grad[3] else None
-        return gA, gxd, gxs, gat, None, None, None
+        return gA, gxd, gxs, gat, None, None, None, None, None, None
 
 
 def gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False, fast=False):
@@ -765,6 +921,17 @@ def gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False, fast=F
     floats and takes M * H * d floats of workspace for att's gradient, which is summed in a fixed order: the same bits on every run.
     Differentiable in x_dst, x_src, att and (bias=True) A; gradients come in the operands' dtypes.  d up to 128; a d that is not a
     multiple of 8, and operands that do not lie as the kernels read them, are copied with zero padding.  negative_slope: finite, >= 0."""
+    return _gatv2_attention(A, x_dst, x_src, att, negative_slope, bias, fast, 0.0, 0, None)
+
+
+def gatv2_attention_dropout(A, x_dst, x_src, att, dropout, seed=None, step=None, negative_slope=0.2, bias=False, fast=False):
+    """gatv2_attention() with dropout on the normalised attention coefficients, as GATv2Conv(dropout=...) in PyG: made inside the fused
+    kernels of all three passes (sextans_gatv2_attention_dropout_device / sextans_gatv2_attention_dropout_backward_device).  dropout,
+    seed and step as in sparse_attention_dropout(); dropout=0 is gatv2_attention() itself, bit for bit."""
+    return _gatv2_attention(A, x_dst, x_src, att, negative_slope, bias, fast, _check_dropout(dropout), seed, step)
+
+
+def _gatv2_attention(A, x_dst, x_src, att, negative_slope, bias, fast, p, seed, step):
     _check_sparse(A, "gatv2_attention")
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (x_dst, x_src, att)):
         raise TypeError("gatv2_attention expects CUDA/HIP dense x_dst, x_src and att")
@@ -782,7 +949,10 @@ def gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False, fast=F
     slope = float(negative_slope)
     if not (slope >= 0.0) or math.isinf(slope):
         raise ValueError("negative_slope must be finite and >= 0")
-    out = _Gatv2AttentionFunction.apply(A, xd3, xs3, at2, slope, bool(bias), bool(fast))
+    if p > 0.0:
+        out = _Gatv2AttentionFunction.apply(A, xd3, xs3, at2, slope, bool(bias), bool(fast), p, _draw_seed(seed), _check_step(step, A.device))
+    else:
+        out = _Gatv2AttentionFunction.apply(A, xd3, xs3, at2, slope, bool(bias), bool(fast), 0.0, 0, None)
     return out if x_dst.dim() == 3 else out[:, 0]
 
 
