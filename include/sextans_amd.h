@@ -791,6 +791,52 @@ int sextans_spmm_reduce_backward_device_rm(sextans_handle_t h, int N, const floa
                                            const int32_t *d_arg, int64_t ldarg, const float *d_G, int64_t ldg,
                                            float *d_dB, int64_t lddb, float *d_dval, void *stream);
 
+/* ---- SpMM with a feature VECTOR per stored entry (edge-feature message passing: continuous-filter convolution / u_mul_e_sum, GINE /
+ * relu(u_add_e) summed, edge -> node reduction / copy_e_sum).  Closest thing in the reference: none -- its PEs weight an entry with a
+ * scalar.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * B row-major K x N fp32 (B[k * ldb + n]), C and G row-major M x N, E and dE row-major nnz x N IN THE CSR ENTRY ORDER the matrix was set
+ * with: E[e * lde + n] belongs to the entry at position e of the CSR arrays (offsets are 64-bit: nnz * N may exceed 2^31).
+ * For the stored entry e = (r, c) and column n the message is ONE rounded fp32 operation, never fused with the sum:
+ *     SEXTANS_EDGE_MUL       m = B[c, n] * E[e, n]
+ *     SEXTANS_EDGE_ADD       m = B[c, n] + E[e, n]
+ *     SEXTANS_EDGE_ADD_RELU  s = B[c, n] + E[e, n];  m = s > 0 ? s : (s != s ? s : +0)
+ *     SEXTANS_EDGE_COPY      m = E[e, n]                    (d_B is not read and may be NULL)
+ *     forward    C[r, n]  = sum over row r's entries of m   (fp32 adds rounded to nearest, in an order fixed by the pattern and the
+ *                launch shape; a row without entries gives +0; NaN and +-inf reach the rows and columns whose entries hold them only)
+ *     backward   dE[e, n] = G[r, n] * B[c, n] (MUL) | G[r, n] (ADD, COPY) | (B[c, n] + E[e, n] > 0 ? G[r, n] : +0) (ADD_RELU)
+ *                -- one rounded operation per element: BIT-DETERMINED
+ *                dB[c, n] = sum over the entries of column c of G[r, n] * E[e, n] (MUL, fused multiply-add) | G[r, n] (ADD) | the masked
+ *                G[r, n] (ADD_RELU); a column without entries gives 0.  COPY has no dB.
+ * There are no atomics anywhere: dB is a GATHER over the rows of A^T (sextans_csr_transpose_device's arrays and entry permutation), dE
+ * a row pass in which one group of lanes owns an (entry, tile) and stores it.  The same call gives the same bits on every run and stream.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 tiles: the columns are cut into tiles of the smallest of 8 / 16 / 32 / 64 /
+ * 128 floats that holds min(N, 128), which play the part the heads play in sextans_attention_device (per entry one 4-byte column load,
+ * the 16-byte pieces of one gathered B row and of the entry's own E row; rows -- column pass: columns -- of more than 2048 entries get
+ * one workgroup per tile, merged through LDS).  The last tile may be partial.  E is read once per pass, dE written once.
+ * Leading dimensions: >= N, multiples of 4 (all of them, whether or not their pointer is NULL); every pointer 16-byte aligned.  The
+ * outputs must not overlap the inputs or each other.
+ * Backward: d_dB or d_dE may be NULL, not both; d_dB must be NULL with SEXTANS_EDGE_COPY.  Needed with nnz > 0: d_G always; MUL: d_E for
+ * dB, d_B for dE; ADD_RELU: d_B and d_E; ADD and COPY: neither (NULL is accepted).  The backward writes every element of dB (K x N) and
+ * of dE (nnz x N) it is given.
+ * The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call with d_dB also builds
+ * A^T (its arrays and the companion engine's tables only); both synchronise then.  After that a call allocates nothing, reads nothing
+ * back and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_edge" / "spmm_edge_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, op not one of the four, N < 8 or not a multiple of 8 or more than 65535 tiles, a leading dimension
+ * below N or not a multiple of 4, a misaligned pointer, (backward) d_dB and d_dE both NULL, d_dB with COPY -- then the handle's state
+ * (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a required pointer that is NULL with
+ * nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- C and dB are zeroed, dE has no element. */
+#define SEXTANS_EDGE_MUL 1
+#define SEXTANS_EDGE_ADD 2
+#define SEXTANS_EDGE_ADD_RELU 3
+#define SEXTANS_EDGE_COPY 4
+int sextans_spmm_edge_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
+                                float *d_C, int64_t ldc, void *stream);
+int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
+                                         const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
+
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *
  * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or

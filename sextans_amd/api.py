@@ -89,6 +89,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
     "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
     "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm",
+    "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -96,6 +97,7 @@ _OPTIONAL_SYMBOLS = frozenset((
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
+EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
 
 
 class _Optional:
@@ -319,6 +321,10 @@ def lib():
                                                 C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_spmm_edge_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_int64, C.c_void_p]
+    L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -935,6 +941,19 @@ class Engine:
         None (not both); d_B may be None when d_dval is."""
         _check(lib().sextans_spmm_reduce_backward_device_rm(self._h, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream),
                "spmm_reduce_backward_device_rm")
+
+    def spmm_edge_device_rm(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
+        """SpMM with a feature vector per stored entry (sextans_spmm_edge_device_rm): C[r, n] = sum over row r's entries e = (r, c) of
+        B[c, n] * E[e, n] (EDGE_MUL), B + E (EDGE_ADD), relu(B + E) (EDGE_ADD_RELU) or E[e, n] (EDGE_COPY: d_B may be None).  Only the
+        pattern is used; E is (nnz, N) row-major in the CSR entry order.  B, E and C row-major, N % 8 == 0; an empty row gives +0."""
+        _check(lib().sextans_spmm_edge_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream), "spmm_edge_device_rm")
+
+    def spmm_edge_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream=None):
+        """dB (K x N) and dE (nnz x N) of spmm_edge_device_rm from the upstream gradient G (sextans_spmm_edge_backward_device_rm): a
+        column pass over A^T and a row pass over A, no atomics.  d_dB or d_dE may be None (not both; d_dB must be None with EDGE_COPY);
+        d_B / d_E may be None where the op's gradient does not read them."""
+        _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
+               "spmm_edge_backward_device_rm")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -38,6 +38,14 @@ in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
                                                    row gives 0.  One kernel pass, nothing of size nnz x N materialised; return_arg=True
                                                    also returns the winning entries.  "mean" / "sum": spmm() (divided by the row lengths)
 
+Edge-feature message passing -- a feature VECTOR per stored entry instead of a scalar weight (SchNet's CFConv / diagonal NNConv, GINEConv,
+the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_sum in DGL), on the cached engine of the pattern:
+
+    C = spmm_edge(A, B, E, op="mul", reduce="sum") C[r, n] = sum over row r's stored entries e = (r, c) of B[c, n] * E[e, n] ("add": B + E,
+                                                   "add_relu": relu(B + E), "copy": E[e, n], B=None); E is (nnz, N) in A's entry order.  One
+                                                   kernel pass per direction, E the only nnz x N tensor, no atomics; "mean": / row length
+    A, perm = from_edge_index(edge_index, num_dst, num_src)   the sparse_csr A of a PyG edge list, and perm with E = edge_attr[perm]
+
 S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
 other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
 """
@@ -1056,3 +1064,135 @@ def spmm_reduce(A, B, reduce="amax", return_arg=False, fast=False):
         if C.shape[1] != N:
             C, arg = C[:, :N], (arg[:, :N] if arg is not None else None)
     return (C, arg) if return_arg else C
+
+
+_EDGE_OPS = {"mul": api.EDGE_MUL, "add": api.EDGE_ADD, "add_relu": api.EDGE_ADD_RELU, "copy": api.EDGE_COPY}
+
+
+def _edge_forward(A, B, E, op, fast):
+    """C (M, Np) of the engine's edge-feature SpMM, N padded up to a multiple of 8 (zero columns of B and E); B is None for EDGE_COPY."""
+    M, K = A.shape
+    nnz, N = E.shape
+    Np = api.round_up_n(N)
+    crow, col = _index_tensors(A)
+    ent = _entry_for_parts(crow, col, A.values(), (M, K), A.device.index or 0, fast, values_needed=False)
+    Brm = _rowmajor(B.detach(), K, N, Np) if B is not None else None
+    Erm = _rowmajor(E.detach(), nnz, N, Np)
+    C = torch.empty((M, Np), dtype=torch.float32, device=A.device)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    if C.numel():
+        ent.eng.spmm_edge_device_rm(op, Np, ptr(Brm), Brm.stride(0) if Brm is not None else Np, ptr(Erm), Erm.stride(0), ptr(C), Np,
+                                    torch.cuda.current_stream(A.device).cuda_stream)
+    return C
+
+
+class _SpmmEdgeFunction(torch.autograd.Function):
+    """spmm_edge(): one kernel pass forward (sextans_spmm_edge_device_rm); backward a column pass over A^T for dB and a row pass over A
+    that stores dE (sextans_spmm_edge_backward_device_rm).  Only the gradients autograd asks for are computed, and only the operands
+    their formulas read are handed over.  A's values never enter: no gradient for A, no value refresh.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, B, E, op, fast):
+        N = E.shape[1]
+        C = _edge_forward(A, B, E, op, fast)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B, E)
+        ctx.shape, ctx.op, ctx.fast, ctx.dev = tuple(A.shape), op, fast, A.device.index or 0
+        return C if C.shape[1] == N else C[:, :N]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, val, B, E = ctx.saved_tensors
+        M, K = ctx.shape
+        op = ctx.op
+        nnz, N = E.shape
+        Np = api.round_up_n(N)
+        want_b, want_e = B is not None and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (want_b or want_e):
+            return None, None, None, None, None
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        need_b = op == api.EDGE_ADD_RELU or (op == api.EDGE_MUL and want_e)
+        need_e = op == api.EDGE_ADD_RELU or (op == api.EDGE_MUL and want_b)
+        Grm = _rowmajor(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
+        Brm = _rowmajor(B.detach(), K, N, Np) if need_b else None
+        Erm = _rowmajor(E.detach(), nnz, N, Np) if need_e else None
+        dB = torch.empty((K, Np), dtype=torch.float32, device=G.device) if want_b else None
+        dE = torch.empty((nnz, Np), dtype=torch.float32, device=G.device) if want_e else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        if ptr(dB) is not None or ptr(dE) is not None:   # (else: no element to write)
+            ent.eng.spmm_edge_backward_device_rm(op, Np, ptr(Brm), Brm.stride(0) if Brm is not None else Np, ptr(Erm),
+                                                 Erm.stride(0) if Erm is not None else Np, ptr(Grm), Grm.stride(0), ptr(dB), Np, ptr(dE), Np,
+                                                 torch.cuda.current_stream(G.device).cuda_stream)
+        gB = (dB if Np == N else dB[:, :N]).to(B.dtype) if want_b else None
+        gE = (dE if Np == N else dE[:, :N]).to(E.dtype) if want_e else None
+        return None, gB, gE, None, None
+
+
+def spmm_edge(A, B, E, op="mul", reduce="sum", fast=False):
+    """Message passing with a feature vector per stored entry: C[r, :] = sum over row r's stored entries e = (r, c) of m_e, where
+      op="mul"       m_e = B[c, :] * E[e, :]        (continuous-filter convolution: CFConv, diagonal NNConv; u_mul_e_sum)
+      op="add"       m_e = B[c, :] + E[e, :]        (u_add_e_sum)
+      op="add_relu"  m_e = relu(B[c, :] + E[e, :])  (GINEConv's aggregation)
+      op="copy"      m_e = E[e, :], B=None          (scatter of edge features onto their destination nodes; copy_e_sum)
+    A is an (M, K) sparse_csr matrix of which only the PATTERN is used (its values are not read, the cached engine is not refreshed and
+    A gets no gradient); B is (K, N) or (K, H, d), E is (nnz, N) or (nnz, H, d) IN A'S CSR ENTRY ORDER (from_edge_index() gives the
+    permutation for an edge list); the result has B's trailing shape (E's for "copy"), fp32.  One kernel pass
+    (sextans_spmm_edge_device_rm): E is the only tensor of size nnz x N, every message is one rounded fp32 operation, the sums have an
+    order fixed by the pattern -- no atomics, the same bits on every run; an empty row gives 0.  reduce="mean": the sum divided by the
+    row's entry count clamped to >= 1, a composition.  Differentiable in B and E; only the gradients asked for are computed (a column
+    pass over A^T for dB, a row pass that writes dE once).  `fast` only selects the cached engine.  An N that is not a multiple of 8, and
+    operands the kernel cannot read where they lie, are copied with zero padding, as spmm() does."""
+    if op not in _EDGE_OPS:
+        raise ValueError("op must be 'mul', 'add', 'add_relu' or 'copy'")
+    if reduce not in ("sum", "mean"):
+        raise ValueError("reduce must be 'sum' or 'mean'")
+    _check_sparse(A, "spmm_edge")
+    if (B is None) != (op == "copy"):
+        raise ValueError("spmm_edge: B=None goes with op='copy', and only with it")
+    if not (isinstance(E, torch.Tensor) and E.is_cuda and (B is None or (isinstance(B, torch.Tensor) and B.is_cuda))):
+        raise TypeError("spmm_edge expects CUDA/HIP dense B and E")
+    if E.dim() not in (2, 3) or (B is not None and (B.dim() != E.dim() or B.shape[1:] != E.shape[1:])):
+        raise ValueError("spmm_edge: B is (K, N) or (K, H, d), E (nnz, N) or (nnz, H, d) with the same trailing shape")
+    M, K = A.shape
+    if E.shape[0] != A.values().numel() or (B is not None and B.shape[0] != K) or 0 in E.shape[1:]:
+        raise ValueError("shape mismatch")
+    tail = tuple(E.shape[1:])
+    B2 = B.reshape(K, math.prod(tail)) if B is not None else None
+    E2 = E.reshape(E.shape[0], math.prod(tail))
+    code = _EDGE_OPS[op]
+    if torch.is_grad_enabled() and ((B2 is not None and B2.requires_grad) or E2.requires_grad):
+        out = _SpmmEdgeFunction.apply(A, B2, E2, code, bool(fast))
+    else:
+        out = _edge_forward(A, B2, E2, code, bool(fast))
+        if out.shape[1] != E2.shape[1]:
+            out = out[:, :E2.shape[1]]
+    if reduce == "mean":
+        crow = _index_tensors(A)[0]
+        out = out / (crow[1:] - crow[:-1]).clamp(min=1).to(out.dtype)[:, None]
+    return out.reshape((M,) + tail)
+
+
+def from_edge_index(edge_index, num_dst, num_src, values=None):
+    """The sparse_csr matrix of an edge list, and the permutation that brings per-edge data into its entry order.
+    edge_index: (2, nnz) integers, row 0 the SOURCE and row 1 the DESTINATION of every edge (PyG's convention): edge i is the entry
+    A[dst_i, src_i] of the (num_dst, num_src) matrix.  The edges are sorted stably by (dst, src).  Returns (A, perm): A's values are
+    values[perm] (ones when values is None), and edge_attr[perm] is the E of spmm_edge() in A's entry order.  A duplicate edge raises
+    ValueError (multigraphs: not supported).  Plain torch; run it once per graph."""
+    if not isinstance(edge_index, torch.Tensor) or edge_index.dim() != 2 or edge_index.shape[0] != 2 or edge_index.is_floating_point():
+        raise ValueError("edge_index must be a (2, nnz) integer tensor")
+    num_dst, num_src = int(num_dst), int(num_src)
+    nnz = edge_index.shape[1]
+    src, dst = edge_index[0].long(), edge_index[1].long()
+    if nnz and (int(src.min()) < 0 or int(src.max()) >= num_src or int(dst.min()) < 0 or int(dst.max()) >= num_dst):
+        raise ValueError("edge_index out of range")
+    if values is not None and values.shape[0] != nnz:
+        raise ValueError("values must have one element per edge")
+    key, perm = torch.sort(dst * num_src + src, stable=True)
+    if nnz > 1 and bool((key[1:] == key[:-1]).any()):
+        raise ValueError("from_edge_index: duplicate edge (multigraphs are not supported)")
+    itype = torch.int32 if max(num_dst, num_src, nnz) < 2 ** 31 else torch.int64
+    crow = torch.zeros(num_dst + 1, dtype=torch.int64, device=edge_index.device)
+    crow[1:] = torch.cumsum(torch.bincount(dst, minlength=num_dst), 0)
+    vals = values[perm] if values is not None else torch.ones(nnz, dtype=torch.float32, device=edge_index.device)
+    A = torch.sparse_csr_tensor(crow.to(itype), src[perm].to(itype), vals, size=(num_dst, num_src))
+    return A, perm
