@@ -3,14 +3,14 @@
 //   sextans_attention_backward_device   dQ, dK, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
 //   sextans_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
 //   sextans_dropout_mask_device, sextans_dropout_keep_host        the mask itself: nnz * heads multipliers on the device, keep flags on the host
-// Kernels and the lane mapping: attention_kernels.h.  The row pass uses the row softmax's tables of this engine, the column pass those
-// of the companion engine that holds A^T (engine_transpose.hip) -- no table of its own, and A's values are never read.
+// Passes: attention_kernels.h on the row walking of pattern_pass.h, launched through pattern_launch.h.  The row pass uses the row
+// softmax's tables of this engine, the column pass those of the companion engine that holds A^T (engine_transpose.hip) -- no table of
+// its own, and A's values are never read.
 #include "attention_kernels.h"
-#include "engine_state.h"
+#include "pattern_launch.h"
 
 namespace sx {
 
-// rows x cols floats at leading dimension ld <- value (the degenerate calls: no entries, no rows)
 // out[i] = the dropout multiplier of (entry i / heads, head i % heads): the hash's counter is i itself
 __global__ __launch_bounds__(256) void dropout_mask(DropArgs d, long long n, float *__restrict__ out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -18,64 +18,32 @@ __global__ __launch_bounds__(256) void dropout_mask(DropArgs d, long long n, flo
     out[i] = dropout_u32(drop_key(d), (uint64_t)i, 1u, 0u) >= d.thresh ? d.inv_keep : 0.0f;
 }
 
-__global__ __launch_bounds__(256) void attn_fill(long long rows, int cols, long long ld, float value, float *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * cols) return;
-    out[(i / cols) * ld + i % cols] = value;
-}
-
 }  // namespace sx
 
 namespace sxe {
 
-// (declared in engine_state.h: engine_gat.hip fills its degenerate calls' outputs with it too)
+// (declared in engine_state.h: the other four families fill their degenerate calls' outputs with it too)
 void attention_fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s) {
-    if (!out || rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(sx::attn_fill, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
+    fill<float>(out, rows, cols, ld, value, s);
 }
 
 namespace {
-
-bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
-bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
-uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
 
 int check_dims(sextans_handle_t h, int heads, int d, int dv) {
     if (!h || heads < 1 || bad_dim(d) || bad_dim(dv)) return SEXTANS_ERR_INVALID;
     return SEXTANS_OK;
 }
 
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::AttnArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::attn_rows<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow, nw,
-                       heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::attn_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
-                           e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
-// the dropout variant of the same two kernels (p > 0 only)
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::AttnDropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::attn_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
-                       nw, heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::attn_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
-                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
-
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  One register width serves both
 // head dimensions: the smallest of 8 / 16 / 32 / 64 / 128 floats that holds the larger one.
+// Entries in flight per slot (U): the forward 4, the backward passes 2; half of that at width 128.
 template <int PASS, class Args>
 void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const int w = a.d > a.dv ? a.d : a.dv;
-    constexpr bool F = PASS == sx::kAttnForward;
-    if (w <= 8) launch_width<PASS, 2, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (w <= 16) launch_width<PASS, 4, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (w <= 32) launch_width<PASS, 8, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (w <= 64) launch_width<PASS, 8, 2, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else launch_width<PASS, 8, 4, F ? 2 : 1>(e, a, perm, heads_inside, s);
+    constexpr bool F = PASS == sx::kAttnForward, DROP = std::is_same_v<Args, sx::AttnDropArgs>;
+    for_width(a.d > a.dv ? a.d : a.dv, [&](auto w) {
+        using W = decltype(w);
+        launch_pattern<sx::AttnPass<PASS, W::T, W::P, W::k128 ? (F ? 2 : 1) : (F ? 4 : 2), DROP>>(e, a, perm, heads_inside, s);
+    });
 }
 
 }  // namespace
@@ -85,16 +53,17 @@ using namespace sxe;
 
 namespace {
 
-// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+// both entry points of a pass end here (drop == NULL: the plain one)
 int attention_forward(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
                       const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop,
                       void *stream) {
     if (int rc = check_dims(h, heads, d, dv)) return rc;   // nothing here needs a device
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     if (bad_ld(ldq, (int64_t)heads * d) || bad_ld(ldk, (int64_t)heads * d) || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv))
         return SEXTANS_ERR_INVALID;
-    if (((bits(d_Q) | bits(d_K) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_Q, d_K, d_V, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
@@ -110,17 +79,8 @@ int attention_forward(sextans_handle_t h, int heads, int d, int dv, float scale,
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
-    const bool lr = h->softmax.nchunks > 0;
-    if (drop) {
-        sx::AttnDropArgs ad{};
-        static_cast<sx::AttnArgs &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
-        h->last_kernel = lr ? "attention_fused+dropout+long_rows" : "attention_fused+dropout";
-    } else {
-        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
-        h->last_kernel = lr ? "attention_fused+long_rows" : "attention_fused";
-    }
+    with_dropout<sx::AttnDropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
+    name_pass(h, "attention_fused", drop != nullptr, h->softmax.nchunks > 0);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
@@ -130,15 +90,14 @@ int attention_backward(sextans_handle_t h, int heads, int d, int dv, float scale
                        int64_t ldg, float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv, float *d_dbias,
                        const sextans_dropout *drop, void *stream) {
     if (int rc = check_dims(h, heads, d, dv)) return rc;
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     const int64_t hd = (int64_t)heads * d, hdv = (int64_t)heads * dv;
     if (bad_ld(ldq, hd) || bad_ld(ldk, hd) || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) || bad_ld(lddq, hd) || bad_ld(lddk, hd) ||
         bad_ld(lddv, hdv))
         return SEXTANS_ERR_INVALID;
-    if (((bits(d_Q) | bits(d_K) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dQ) | bits(d_dK) | bits(d_dV) |
-          bits(d_dbias)) & 15) != 0)
-        return SEXTANS_ERR_INVALID;
+    if (misaligned(d_Q, d_K, d_V, d_bias, d_O, d_lse, d_G, d_delta, d_dQ, d_dK, d_dV, d_dbias)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV)) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
@@ -151,27 +110,17 @@ int attention_backward(sextans_handle_t h, int heads, int d, int dv, float scale
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (int rc = ensure_transpose(h, s)) return rc;
-    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
+    if (int rc = ensure_backward_tables(h, s)) return rc;
     sx::AttnArgs a{};
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dQ = d_dQ; a.dK = d_dK; a.dV = d_dV; a.dbias = d_dbias;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
-    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
-    if (drop) {
-        sx::AttnDropArgs ad{};
-        static_cast<sx::AttnArgs &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "attention_fused_backward+dropout+long_rows" : "attention_fused_backward+dropout";
-    } else {
-        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "attention_fused_backward+long_rows" : "attention_fused_backward";
-    }
+    with_dropout<sx::AttnDropArgs>(a, drop, [&](const auto &args) {
+        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+    });
+    name_pass(h, "attention_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
@@ -210,7 +159,7 @@ int sextans_attention_dropout_backward_device(sextans_handle_t h, int heads, int
 /* nnz * heads multipliers, [e * heads + h]: what the fused dropout kernels recompute, written out (the composition path, tests) */
 int sextans_dropout_mask_device(sextans_handle_t h, int heads, const sextans_dropout *drop, float *d_mult, void *stream) {
     if (!h || heads < 1 || !drop || sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
-    if ((bits(d_mult) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_mult)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     const long long n = (long long)h->nnz * heads;
     if (n == 0) return SEXTANS_OK;

@@ -1,30 +1,14 @@
 // engine_edge.hip -- SpMM with a feature vector per stored entry over the CSR pattern on an engine handle (include/sextans_amd.h):
 //   sextans_spmm_edge_device_rm            C[r, :] = sum over row r's entries of B[c, :] (op) E[e, :]   (mul / add / relu(add) / copy)
 //   sextans_spmm_edge_backward_device_rm   dB and dE from the upstream gradient: a column pass over A^T, a row pass over A
-// Kernels: spmm_edge_kernels.h on the row walking of attention_kernels.h.  Tables as in engine_reduce.hip: the row softmax's of this
+// Kernels: spmm_edge_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_reduce.hip: the row softmax's of this
 // engine for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  Only the pattern is read:
 // neither the engine's values nor any of its packed forms is read or touched.
-#include "engine_state.h"
+#include "pattern_launch.h"
 #include "spmm_edge_kernels.h"
 
 namespace sxe {
 namespace {
-
-bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
-uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
-constexpr int kMaxTiles = 65535;   // the long-row kernel's grid has one y per column tile
-
-template <int PASS, int OP, int T, int P, int U>
-void launch_width(const sextans_engine *e, sx::EdgeArgs a, const int *perm, hipStream_t s) {
-    a.tile = 4 * T * P;
-    a.H = (a.N + a.tile - 1) / a.tile;
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::edge_rows<PASS, OP, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm,
-                       e->softmax.d_sm_wrow, nw, 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::edge_long<PASS, OP, T, P, U>), dim3((unsigned)e->softmax.nchunks, (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
-                           e->d_ci, perm, e->softmax.d_sm_tab, 0);
-}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  N is cut into tiles of the smallest
 // of 8 / 16 / 32 / 64 / 128 floats that holds min(N, 128); the last tile may be partial; the tiles sit in the grid in every pass (the row
@@ -32,11 +16,10 @@ void launch_width(const sextans_engine *e, sx::EdgeArgs a, const int *perm, hipS
 // costs up to two loads of a tile's pieces; untuned.
 template <int PASS, int OP>
 void launch_pass(const sextans_engine *e, const sx::EdgeArgs &a, const int *perm, hipStream_t s) {
-    if (a.N <= 8) launch_width<PASS, OP, 2, 1, 4>(e, a, perm, s);
-    else if (a.N <= 16) launch_width<PASS, OP, 4, 1, 4>(e, a, perm, s);
-    else if (a.N <= 32) launch_width<PASS, OP, 8, 1, 4>(e, a, perm, s);
-    else if (a.N <= 64) launch_width<PASS, OP, 8, 2, 4>(e, a, perm, s);
-    else launch_width<PASS, OP, 8, 4, 2>(e, a, perm, s);
+    for_width(a.N, [&](auto w) {
+        using W = decltype(w);
+        launch_pattern<sx::EdgePass<PASS, OP, W::T, W::P, W::k128 ? 2 : 4>>(e, tiled<W>(a), perm, false, s);
+    });
 }
 
 template <int PASS>
@@ -48,7 +31,6 @@ void launch_op(int op, const sextans_engine *e, const sx::EdgeArgs &a, const int
 }
 
 bool bad_op(int op) { return op < SEXTANS_EDGE_MUL || op > SEXTANS_EDGE_COPY; }
-bool bad_n(int N) { return N < 8 || (N % 8) != 0 || (N + 127) / 128 > kMaxTiles; }
 
 }  // namespace
 }  // namespace sxe
@@ -61,7 +43,7 @@ int sextans_spmm_edge_device_rm(sextans_handle_t h, int op, int N, const float *
                                 float *d_C, int64_t ldc, void *stream) {
     if (!h || bad_op(op) || bad_n(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_ld(ldb, N) || bad_ld(lde, N) || bad_ld(ldc, N)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_B) | bits(d_E) | bits(d_C)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_B, d_E, d_C)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
     if (h->nnz > 0 && ((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C)) return SEXTANS_ERR_INVALID;
@@ -86,7 +68,7 @@ int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, cons
                                          const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream) {
     if (!h || bad_op(op) || bad_n(N)) return SEXTANS_ERR_INVALID;
     if (bad_ld(ldb, N) || bad_ld(lde, N) || bad_ld(ldg, N) || bad_ld(lddb, N) || bad_ld(ldde, N)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_B) | bits(d_E) | bits(d_G) | bits(d_dB) | bits(d_dE)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_B, d_E, d_G, d_dB, d_dE)) return SEXTANS_ERR_INVALID;
     if (!d_dB && !d_dE) return SEXTANS_ERR_INVALID;
     if (d_dB && op == SEXTANS_EDGE_COPY) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
@@ -104,11 +86,7 @@ int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, cons
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (d_dB) {
-        if (int rc = ensure_transpose(h, s)) return rc;
-        if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
-    }
+    if (int rc = d_dB ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
     sx::EdgeArgs a{};
     a.B = d_B; a.E = d_E; a.G = d_G; a.dB = d_dB; a.dE = d_dE;
     a.ldb = ldb; a.lde = lde; a.ldg = ldg; a.lddb = lddb; a.ldde = ldde; a.N = N;

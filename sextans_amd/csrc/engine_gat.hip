@@ -2,38 +2,13 @@
 //   sextans_gat_attention_device            O = softmax(LeakyReLU(adst[r] + asrc[c] + bias) on A's pattern) V per head, and the rows' log-sum-exp
 //   sextans_gat_attention_backward_device   dadst, dasrc, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
 //   sextans_gat_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
-// Kernels: gat_kernels.h (the additive score) on the row walking of attention_kernels.h.  Tables as in engine_attention.hip: the row
+// Kernels: gat_kernels.h (the additive score) on the row walking of pattern_pass.h.  Tables as in engine_attention.hip: the row
 // softmax's of this engine for the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
-#include "engine_state.h"
 #include "gat_kernels.h"
+#include "pattern_launch.h"
 
 namespace sxe {
 namespace {
-
-bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
-bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
-bool bad_slope(float s) { return !(s >= 0.0f) || std::isinf(s); }
-uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
-
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::GatArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::gat_rows<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow, nw,
-                       heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::gat_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
-                           e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
-// the dropout variant of the same two kernels (p > 0 only)
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::GatDropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::gat_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
-                       nw, heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::gat_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
-                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  The slot width follows dv alone:
 // the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.  Entries in flight per slot (U), as measured: the forward
@@ -45,11 +20,11 @@ void launch_width(const sextans_engine *e, const sx::GatDropArgs &a, const int *
 // change).  Retune either kernel's forward U or the walk's order and that comparison has to be looked at again.
 template <int PASS, class Args>
 void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
-    if (a.dv <= 8) launch_width<PASS, 2, 1, 4>(e, a, perm, heads_inside, s);
-    else if (a.dv <= 16) launch_width<PASS, 4, 1, 4>(e, a, perm, heads_inside, s);
-    else if (a.dv <= 32) launch_width<PASS, 8, 1, 4>(e, a, perm, heads_inside, s);
-    else if (a.dv <= 64) launch_width<PASS, 8, 2, 4>(e, a, perm, heads_inside, s);
-    else launch_width<PASS, 8, 4, 2>(e, a, perm, heads_inside, s);
+    constexpr bool DROP = std::is_same_v<Args, sx::GatDropArgs>;
+    for_width(a.dv, [&](auto w) {
+        using W = decltype(w);
+        launch_pattern<sx::GatPass<PASS, W::T, W::P, W::k128 ? 2 : 4, DROP>>(e, a, perm, heads_inside, s);
+    });
 }
 
 }  // namespace
@@ -59,14 +34,15 @@ using namespace sxe;
 
 namespace {
 
-// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+// both entry points of a pass end here (drop == NULL: the plain one)
 int gat_forward(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc,
                 const float *d_V, int64_t ldv, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     if (ldadst < heads || ldasrc < heads || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_adst) | bits(d_asrc) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_adst, d_asrc, d_V, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
@@ -82,17 +58,8 @@ int gat_forward(sextans_handle_t h, int heads, int dv, float negative_slope, con
     a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
-    const bool lr = h->softmax.nchunks > 0;
-    if (drop) {
-        sx::GatDropArgs ad{};
-        static_cast<sx::GatArgs &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
-        h->last_kernel = lr ? "gat_fused+dropout+long_rows" : "gat_fused+dropout";
-    } else {
-        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
-        h->last_kernel = lr ? "gat_fused+long_rows" : "gat_fused";
-    }
+    with_dropout<sx::GatDropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
+    name_pass(h, "gat_fused", drop != nullptr, h->softmax.nchunks > 0);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
@@ -102,15 +69,14 @@ int gat_backward(sextans_handle_t h, int heads, int dv, float negative_slope, co
                  float *d_delta, float *d_dadst, int64_t lddadst, float *d_dasrc, int64_t lddasrc, float *d_dV, int64_t lddv, float *d_dbias,
                  const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(dv) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     const int64_t hdv = (int64_t)heads * dv;
     if (ldadst < heads || ldasrc < heads || lddadst < heads || lddasrc < heads || bad_ld(ldv, hdv) || bad_ld(ldo, hdv) || bad_ld(ldg, hdv) ||
         bad_ld(lddv, hdv))
         return SEXTANS_ERR_INVALID;
-    if (((bits(d_adst) | bits(d_asrc) | bits(d_V) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dadst) | bits(d_dasrc) |
-          bits(d_dV) | bits(d_dbias)) & 15) != 0)
-        return SEXTANS_ERR_INVALID;
+    if (misaligned(d_adst, d_asrc, d_V, d_bias, d_O, d_lse, d_G, d_delta, d_dadst, d_dasrc, d_dV, d_dbias)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dadst || !d_dasrc || !d_dV)) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
@@ -123,27 +89,17 @@ int gat_backward(sextans_handle_t h, int heads, int dv, float negative_slope, co
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (int rc = ensure_transpose(h, s)) return rc;
-    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
+    if (int rc = ensure_backward_tables(h, s)) return rc;
     sx::GatArgs a{};
     a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dadst = d_dadst; a.dasrc = d_dasrc; a.dV = d_dV; a.dbias = d_dbias;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddadst = lddadst; a.lddasrc = lddasrc; a.lddv = lddv;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
-    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
-    if (drop) {
-        sx::GatDropArgs ad{};
-        static_cast<sx::GatArgs &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "gat_fused_backward+dropout+long_rows" : "gat_fused_backward+dropout";
-    } else {
-        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "gat_fused_backward+long_rows" : "gat_fused_backward";
-    }
+    with_dropout<sx::GatDropArgs>(a, drop, [&](const auto &args) {
+        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+    });
+    name_pass(h, "gat_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }

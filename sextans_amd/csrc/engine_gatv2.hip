@@ -3,38 +3,13 @@
 //   sextans_gatv2_attention_device            O = softmax(att . LeakyReLU(x_dst[r] + x_src[c]) + bias on A's pattern) x_src per head, and lse
 //   sextans_gatv2_attention_backward_device   dx_dst, dx_src, datt (and dbias): a row pass over A, a column pass over A^T, the two-level datt sum
 //   sextans_gatv2_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
-// Kernels: gatv2_kernels.h on the row walking of attention_kernels.h.  Tables as in engine_gat.hip: the row softmax's of this engine for
+// Kernels: gatv2_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_gat.hip: the row softmax's of this engine for
 // the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
-#include "engine_state.h"
 #include "gatv2_kernels.h"
+#include "pattern_launch.h"
 
 namespace sxe {
 namespace {
-
-bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }
-bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
-bool bad_slope(float s) { return !(s >= 0.0f) || std::isinf(s); }
-uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
-
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::Gatv2Args &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::gatv2_rows<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow, nw,
-                       heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::gatv2_long<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a, e->d_rp,
-                           e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
-// the dropout variant of the same two kernels (p > 0 only)
-template <int PASS, int T, int P, int U>
-void launch_width(const sextans_engine *e, const sx::Gatv2DropArgs &a, const int *perm, bool heads_inside, hipStream_t s) {
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::gatv2_rows_drop<PASS, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm, e->softmax.d_sm_wrow,
-                       nw, heads_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::gatv2_long_drop<PASS, T, P, U>), dim3((unsigned)e->softmax.nchunks, heads_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
-                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, heads_inside ? 1 : 0);
-}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  The slot width follows d alone:
 // the smallest of 8 / 16 / 32 / 64 / 128 floats that holds it.  Entries in flight per slot (U): the forward takes the GAT forward's 4
@@ -47,12 +22,11 @@ void launch_width(const sextans_engine *e, const sx::Gatv2DropArgs &a, const int
 // same roundings after the score.  Retune either forward's U or the walk's order and that comparison has to be looked at again.
 template <int PASS, class Args>
 void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool heads_inside, hipStream_t s) {
-    constexpr bool F = PASS == sx::kAttnForward;
-    if (a.d <= 8) launch_width<PASS, 2, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (a.d <= 16) launch_width<PASS, 4, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (a.d <= 32) launch_width<PASS, 8, 1, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else if (a.d <= 64) launch_width<PASS, 8, 2, F ? 4 : 2>(e, a, perm, heads_inside, s);
-    else launch_width<PASS, 8, 4, F ? 2 : 1>(e, a, perm, heads_inside, s);
+    constexpr bool F = PASS == sx::kAttnForward, DROP = std::is_same_v<Args, sx::Gatv2DropArgs>;
+    for_width(a.d, [&](auto w) {
+        using W = decltype(w);
+        launch_pattern<sx::Gatv2Pass<PASS, W::T, W::P, W::k128 ? (F ? 2 : 1) : (F ? 4 : 2), DROP>>(e, a, perm, heads_inside, s);
+    });
 }
 
 int64_t chunks_of(int64_t M) { return (M + sx::kGatv2Chunk - 1) / sx::kGatv2Chunk; }
@@ -75,15 +49,16 @@ int64_t sextans_gatv2_workspace_floats(sextans_handle_t h, int heads, int d) {
 
 namespace {
 
-// drop == NULL or p == 0: the plain kernels, the plain bits (both entry points of a pass end here)
+// both entry points of a pass end here (drop == NULL: the plain one)
 int gatv2_forward(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs,
                   const float *d_att, const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(d) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_xdst) | bits(d_xsrc) | bits(d_att) | bits(d_bias) | bits(d_O) | bits(d_lse)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_xdst, d_xsrc, d_att, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
     SX_HIP(hipSetDevice(h->device));
@@ -99,17 +74,8 @@ int gatv2_forward(sextans_handle_t h, int heads, int d, float negative_slope, co
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.att = d_att; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo;
     a.H = heads; a.d = d; a.slope = negative_slope;
-    const bool lr = h->softmax.nchunks > 0;
-    if (drop) {
-        sx::Gatv2DropArgs ad{};
-        static_cast<sx::Gatv2Args &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnForward>(h, ad, nullptr, false, s);
-        h->last_kernel = lr ? "gatv2_fused+dropout+long_rows" : "gatv2_fused+dropout";
-    } else {
-        launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
-        h->last_kernel = lr ? "gatv2_fused+long_rows" : "gatv2_fused";
-    }
+    with_dropout<sx::Gatv2DropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
+    name_pass(h, "gatv2_fused", drop != nullptr, h->softmax.nchunks > 0);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
@@ -119,13 +85,12 @@ int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, c
                    float *d_delta, float *d_dxdst, int64_t lddxd, float *d_dxsrc, int64_t lddxs, float *d_datt, float *d_work, float *d_dbias,
                    const sextans_dropout *drop, void *stream) {
     if (!h || heads < 1 || bad_dim(d) || bad_slope(negative_slope)) return SEXTANS_ERR_INVALID;
-    if (drop && sx::dropout_bad(drop->p, drop->d_step)) return SEXTANS_ERR_INVALID;
-    if (drop && drop->p == 0.0f) drop = nullptr;
+    const Dropout mode = dropout_mode(drop);
+    if (mode == Dropout::kInvalid) return SEXTANS_ERR_INVALID;
+    if (mode == Dropout::kPlain) drop = nullptr;
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd) || bad_ld(ldg, hd) || bad_ld(lddxd, hd) || bad_ld(lddxs, hd)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_xdst) | bits(d_xsrc) | bits(d_att) | bits(d_bias) | bits(d_O) | bits(d_lse) | bits(d_G) | bits(d_delta) | bits(d_dxdst) | bits(d_dxsrc) |
-          bits(d_datt) | bits(d_work) | bits(d_dbias)) & 15) != 0)
-        return SEXTANS_ERR_INVALID;
+    if (misaligned(d_xdst, d_xsrc, d_att, d_bias, d_O, d_lse, d_G, d_delta, d_dxdst, d_dxsrc, d_datt, d_work, d_dbias)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > 0 && (!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse || !d_G || !d_delta || !d_dxdst || !d_dxsrc || !d_datt || !d_work))
         return SEXTANS_ERR_INVALID;
@@ -143,27 +108,17 @@ int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, c
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (int rc = ensure_transpose(h, s)) return rc;
-    if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
+    if (int rc = ensure_backward_tables(h, s)) return rc;
     sx::Gatv2Args a{};
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.att = d_att; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dxdst = d_dxdst; a.dxsrc = d_dxsrc; a.datt_rows = d_work; a.dbias = d_dbias;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo; a.ldg = ldg; a.lddxd = lddxd; a.lddxs = lddxs;
     a.H = heads; a.d = d; a.slope = negative_slope;
-    const bool lr = h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0;
-    if (drop) {
-        sx::Gatv2DropArgs ad{};
-        static_cast<sx::Gatv2Args &>(ad) = a;
-        ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
-        launch_pass<sx::kAttnBackwardRows>(h, ad, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, ad, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "gatv2_fused_backward+dropout+long_rows" : "gatv2_fused_backward+dropout";
-    } else {
-        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
-        h->last_kernel = lr ? "gatv2_fused_backward+long_rows" : "gatv2_fused_backward";
-    }
+    with_dropout<sx::Gatv2DropArgs>(a, drop, [&](const auto &args) {
+        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
+        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+    });
+    name_pass(h, "gatv2_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
     hipLaunchKernelGGL(sx::gatv2_datt_chunks, dim3((unsigned)nchunks), dim3(256), 0, s, d_work, (long long)h->M, (int)hd, d_part);
     hipLaunchKernelGGL(sx::gatv2_datt_total, dim3((unsigned)((hd + 255) / 256)), dim3(256), 0, s, d_part, (long long)nchunks, (int)hd, d_datt);
     SX_HIP(hipGetLastError());

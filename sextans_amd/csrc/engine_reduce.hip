@@ -1,60 +1,25 @@
 // engine_reduce.hip -- max / min aggregation SpMM over the CSR matrix on an engine handle (include/sextans_amd.h):
 //   sextans_spmm_reduce_device_rm            C[r, :] = max / min over row r's entries of val[e] * B[c, :], and the winning entries (arg)
 //   sextans_spmm_reduce_backward_device_rm   dB and dval from arg and the upstream gradient: a column pass over A^T, a row pass over A
-// Kernels: spmm_reduce_kernels.h on the row walking of attention_kernels.h.  Tables as in engine_attention.hip: the row softmax's of this
+// Kernels: spmm_reduce_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_attention.hip: the row softmax's of this
 // engine for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  The values come through
 // an explicit pointer (NULL: the engine's current ones); none of the engine's packed forms is read or touched.
-#include "engine_state.h"
+#include "pattern_launch.h"
 #include "spmm_reduce_kernels.h"
-
-namespace sx {
-
-// rows x cols ints at leading dimension ld <- value (the degenerate forward: arg = -1)
-__global__ __launch_bounds__(256) void reduce_fill_int(long long rows, int cols, long long ld, int value, int *__restrict__ out) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * cols) return;
-    out[(i / cols) * ld + i % cols] = value;
-}
-
-}  // namespace sx
 
 namespace sxe {
 namespace {
-
-bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
-uintptr_t bits(const void *p) { return reinterpret_cast<uintptr_t>(p); }
-constexpr int kMaxTiles = 65535;   // the long-row kernel's grid has one y per column tile
-
-template <int PASS, int OP, int T, int P, int U>
-void launch_width(const sextans_engine *e, sx::ReduceArgs a, const int *perm, bool tiles_inside, hipStream_t s) {
-    a.tile = 4 * T * P;
-    a.H = (a.N + a.tile - 1) / a.tile;
-    const long long nw = (long long)e->softmax.d_sm_wrow.size() - 1;
-    hipLaunchKernelGGL((sx::reduce_rows<PASS, OP, T, P, U>), dim3((unsigned)((nw + 3) / 4)), dim3(256), 0, s, a, e->d_rp, e->d_ci, perm,
-                       e->softmax.d_sm_wrow, nw, tiles_inside ? 1 : 0);
-    if (e->softmax.nchunks > 0)
-        hipLaunchKernelGGL((sx::reduce_long<PASS, OP, T, P, U>), dim3((unsigned)e->softmax.nchunks, tiles_inside ? 1u : (unsigned)a.H), dim3(256), 0, s, a,
-                           e->d_rp, e->d_ci, perm, e->softmax.d_sm_tab, tiles_inside ? 1 : 0);
-}
 
 // e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  N is cut into tiles of the smallest
 // of 8 / 16 / 32 / 64 / 128 floats that holds min(N, 128); the last tile may be partial.  Entries in flight per slot (U): the attention
 // forward's 4 (2 at width 128) in every pass -- an entry costs one gathered row (the column pass: an arg and a G row).
 template <int PASS, int OP>
 void launch_pass(const sextans_engine *e, const sx::ReduceArgs &a, const int *perm, bool tiles_inside, hipStream_t s) {
-    if (a.N <= 8) launch_width<PASS, OP, 2, 1, 4>(e, a, perm, tiles_inside, s);
-    else if (a.N <= 16) launch_width<PASS, OP, 4, 1, 4>(e, a, perm, tiles_inside, s);
-    else if (a.N <= 32) launch_width<PASS, OP, 8, 1, 4>(e, a, perm, tiles_inside, s);
-    else if (a.N <= 64) launch_width<PASS, OP, 8, 2, 4>(e, a, perm, tiles_inside, s);
-    else launch_width<PASS, OP, 8, 4, 2>(e, a, perm, tiles_inside, s);
+    for_width(a.N, [&](auto w) {
+        using W = decltype(w);
+        launch_pattern<sx::ReducePass<PASS, OP, W::T, W::P, W::k128 ? 2 : 4>>(e, tiled<W>(a), perm, tiles_inside, s);
+    });
 }
-
-void fill_int(int *out, int64_t rows, int cols, int64_t ld, int value, hipStream_t s) {
-    if (!out || rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(sx::reduce_fill_int, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
-}
-
-bool bad_n(int N) { return N < 8 || (N % 8) != 0 || (N + 127) / 128 > kMaxTiles; }
 
 }  // namespace
 }  // namespace sxe
@@ -67,7 +32,7 @@ int sextans_spmm_reduce_device_rm(sextans_handle_t h, int op, int N, const float
                                   int32_t *d_arg, int64_t ldarg, void *stream) {
     if (!h || (op != SEXTANS_REDUCE_MAX && op != SEXTANS_REDUCE_MIN) || bad_n(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_ld(ldb, N) || bad_ld(ldc, N) || bad_ld(ldarg, N)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_val) | bits(d_B) | bits(d_C) | bits(d_arg)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_val, d_B, d_C, d_arg)) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
     if (h->nnz > 0 && (!d_B || !d_C)) return SEXTANS_ERR_INVALID;
@@ -75,7 +40,7 @@ int sextans_spmm_reduce_device_rm(sextans_handle_t h, int op, int N, const float
     hipStream_t s = (hipStream_t)stream;
     if (h->M == 0 || h->nnz == 0) {   // every row is empty
         attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        fill_int(d_arg, h->M, N, ldarg, -1, s);
+        fill<int>(d_arg, h->M, N, ldarg, -1, s);
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
@@ -94,7 +59,7 @@ int sextans_spmm_reduce_backward_device_rm(sextans_handle_t h, int N, const floa
                                            int64_t ldarg, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dval, void *stream) {
     if (!h || bad_n(N)) return SEXTANS_ERR_INVALID;
     if (bad_ld(ldb, N) || bad_ld(ldarg, N) || bad_ld(ldg, N) || bad_ld(lddb, N)) return SEXTANS_ERR_INVALID;
-    if (((bits(d_val) | bits(d_B) | bits(d_arg) | bits(d_G) | bits(d_dB) | bits(d_dval)) & 15) != 0) return SEXTANS_ERR_INVALID;
+    if (misaligned(d_val, d_B, d_arg, d_G, d_dB, d_dval)) return SEXTANS_ERR_INVALID;
     if (!d_dB && !d_dval) return SEXTANS_ERR_INVALID;
     if (!h->d_rp) return SEXTANS_ERR_STATE;
     if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
@@ -106,11 +71,7 @@ int sextans_spmm_reduce_backward_device_rm(sextans_handle_t h, int N, const floa
         SX_HIP(hipGetLastError());
         return SEXTANS_OK;
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (d_dB) {
-        if (int rc = ensure_transpose(h, s)) return rc;
-        if (int rc = ensure_softmax_tables(h->tr, s)) return rc;   // A^T's rows: the tables of the column pass
-    }
+    if (int rc = d_dB ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
     sx::ReduceArgs a{};
     a.val = d_val ? d_val : h->d_v; a.B = d_B; a.arg = d_arg; a.G = d_G; a.dB = d_dB; a.dval = d_dval;
     a.ldb = ldb; a.ldarg = ldarg; a.ldg = ldg; a.lddb = lddb; a.N = N;

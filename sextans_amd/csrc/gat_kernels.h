@@ -10,7 +10,7 @@
 // fp32 throughout, FMA in the dot products and the V / G accumulations, exp as in the softmax kernels.  Nothing of size nnz is written or
 // read besides the bias.
 //
-// The pass below plugs into the row walking of attention_kernels.h (attn_rows_body, attn_long_body): the same slots of T lanes per
+// The pass below plugs into the row walking of pattern_pass.h (attn_rows_body, attn_long_body): the same slots of T lanes per
 // (row, head), the same groups of E slots per row, the same second walk, long-row workgroups and merges -- so the same fixed order of
 // every sum.  What differs is the entry: it costs ONE 4-byte load (asrc[c,h]; in the column pass adst, lse and delta of the other row,
 // the same address in all T lanes of the slot) and one gathered row (V; in the column pass G) -- no K row, no dot product for the score.
@@ -39,6 +39,7 @@ struct GatPass {
     using Args = std::conditional_t<DROP, GatDropArgs, GatArgs>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? 1 : 1 + W;   // forward: m, Z, acc; rows: dadst; cols: dasrc, dV
+    static constexpr bool kMerge = true;
     const Args &a;
     const int *ci, *perm;
     const int t;
@@ -148,22 +149,6 @@ struct GatPass {
         }
     }
 
-    // entries j, j + E, .. of the n entries that start at b, U at a time (the loop is uniform over the wavefront)
-    __device__ __forceinline__ void walk(bool act, int b, int n, int j, int E) {
-        if (!act) n = 0;
-#pragma unroll 1
-        for (int k0 = j; __any(k0 < n); k0 += E * U) {
-            int e[U];
-            bool valid[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                valid[u] = k0 + u * E < n;
-                e[u] = b + k0 + u * E;
-            }
-            batch(e, valid);
-        }
-    }
-
     // g <- g (+) o: commutative operations only, so both sides of a butterfly exchange compute the same bits
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnForward) {
@@ -177,12 +162,6 @@ struct GatPass {
 #pragma unroll
             for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
         }
-    }
-    __device__ __forceinline__ void merge(int off) {   // with the slot `off` lanes away
-        float o[NF];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) o[i] = __shfl_xor(f[i], off);
-        combine(f, o);
     }
 
     // n: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
@@ -204,29 +183,5 @@ struct GatPass {
         }
     }
 };
-
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gat_rows(GatArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<GatPass<PASS, T, P, U>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gat_long(GatArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<GatPass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
-}
-
-// the same two kernels with the dropout mask (launched only when p > 0)
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gat_rows_drop(GatDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                     const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<GatPass<PASS, T, P, U, true>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gat_long_drop(GatDropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                     const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<GatPass<PASS, T, P, U, true>>(a, rp, ci, perm, tab, heads_inside);
-}
 
 }  // namespace sx

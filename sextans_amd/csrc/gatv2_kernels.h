@@ -14,7 +14,7 @@
 // the add commutes, so the row pass and the column pass see the bits of z the forward saw.  The LeakyReLU is the plain one (a -inf z is
 // not special: the mask is the bias, which is added after the dot product).  Nothing of size nnz is written or read besides the bias.
 //
-// The pass below plugs into the row walking of attention_kernels.h (attn_rows_body, attn_long_body) like GatPass: the same slots of T
+// The pass below plugs into the row walking of pattern_pass.h (attn_rows_body, attn_long_body) like GatPass: the same slots of T
 // lanes per (row, head), the same groups of E slots per row, the same second walk, long-row workgroups and merges -- so the same fixed
 // order of every sum.  An entry costs ONE gathered row in the forward and the row pass (x_src[c]: it is both the score's operand and the
 // message) and two in the column pass (x_dst[r], G[r]) plus lse and delta of the other row.  The slot width follows d alone.
@@ -38,6 +38,7 @@ struct Gatv2Pass {
     using Args = std::conditional_t<DROP, Gatv2DropArgs, Gatv2Args>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? 2 * W : W;   // forward: m, Z, acc; rows: dx_dst, datt_rows; cols: dx_src
+    static constexpr bool kMerge = true;
     const Args &a;
     const int *ci, *perm;
     const int t;
@@ -169,22 +170,6 @@ struct Gatv2Pass {
         }
     }
 
-    // entries j, j + E, .. of the n entries that start at b, U at a time (the loop is uniform over the wavefront)
-    __device__ __forceinline__ void walk(bool act, int b, int n, int j, int E) {
-        if (!act) n = 0;
-#pragma unroll 1
-        for (int k0 = j; __any(k0 < n); k0 += E * U) {
-            int e[U];
-            bool valid[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                valid[u] = k0 + u * E < n;
-                e[u] = b + k0 + u * E;
-            }
-            batch(e, valid);
-        }
-    }
-
     // g <- g (+) o: commutative operations only, so both sides of a butterfly exchange compute the same bits
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnForward) {
@@ -198,12 +183,6 @@ struct Gatv2Pass {
 #pragma unroll
             for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
         }
-    }
-    __device__ __forceinline__ void merge(int off) {   // with the slot `off` lanes away
-        float o[NF];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) o[i] = __shfl_xor(f[i], off);
-        combine(f, o);
     }
 
     // n: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
@@ -225,30 +204,6 @@ struct Gatv2Pass {
         }
     }
 };
-
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gatv2_rows(Gatv2Args a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                  const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<Gatv2Pass<PASS, T, P, U>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gatv2_long(Gatv2Args a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                  const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<Gatv2Pass<PASS, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
-}
-
-// the same two kernels with the dropout mask (launched only when p > 0)
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gatv2_rows_drop(Gatv2DropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                       const int *__restrict__ perm, const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<Gatv2Pass<PASS, T, P, U, true>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-template <int PASS, int T, int P, int U>
-__global__ __launch_bounds__(256) void gatv2_long_drop(Gatv2DropArgs a, const int *__restrict__ rp, const int *__restrict__ ci,
-                                                       const int *__restrict__ perm, const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<Gatv2Pass<PASS, T, P, U, true>>(a, rp, ci, perm, tab, heads_inside);
-}
 
 // datt = the sum of datt_rows over ALL rows, in two levels whose order is the definition of datt's bits (no atomics):
 //   level 1  part[c, j] = ((+0 + datt_rows[256 c, j]) + datt_rows[256 c + 1, j]) + ..   over the rows of chunk c, ascending

@@ -8,13 +8,13 @@
 //   backward rows  dE[e, n] = G[r, n] * B[c, n] | G[r, n] | (B + E > 0 ? G[r, n] : +0) | G[r, n]   (one rounded operation, stored directly)
 //
 // Only A's PATTERN is read; E and dE are (nnz, N) row-major in A's entry order, addressed as (long long)e * ld.  The passes plug into the
-// row walking of attention_kernels.h (attn_rows_body, attn_long_body) as ReducePass does; COLUMN TILES of at most 128 floats play the
+// row walking of pattern_pass.h (attn_rows_body, attn_long_body) as ReducePass does; COLUMN TILES of at most 128 floats play the
 // heads' part: a slot of T lanes owns one (row, tile), lane t holds the 16-byte pieces t, t + T, .. of the tile, the last tile of a row
 // may be partial (pieces beyond N predicated off).  The forward's and the column pass's state is the tile's partial sums, merged by
 // __fadd_rn; the row pass has no state: each (entry, tile) belongs to one slot, which stores its dE piece.  No atomics; sums in an order
 // fixed by the pattern and the launch shape.
 #pragma once
-#include "attention_kernels.h"
+#include "pattern_pass.h"
 
 namespace sx {
 
@@ -37,6 +37,7 @@ struct EdgePass {
     using Args = EdgeArgs;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnBackwardRows ? 1 : W;   // forward: C's sums; cols: dB's; rows: nothing to merge
+    static constexpr bool kMerge = PASS != kAttnBackwardRows;
     // what an entry reads besides the own row's vector
     static constexpr bool kGather = PASS == kAttnForward ? OP != kEdgeCopy                               // B[c]
                                   : PASS == kAttnBackwardCols ? true                                       // G[r]
@@ -105,33 +106,10 @@ struct EdgePass {
         }
     }
 
-    // entries j, j + E, .. of the n entries that start at b, U at a time (the loop is uniform over the wavefront)
-    __device__ __forceinline__ void walk(bool act, int b, int cnt, int j, int E) {
-        if (!act) cnt = 0;
-#pragma unroll 1
-        for (int k0 = j; __any(k0 < cnt); k0 += E * U) {
-            int e[U];
-            bool valid[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                valid[u] = k0 + u * E < cnt;
-                e[u] = b + k0 + u * E;
-            }
-            batch(e, valid);
-        }
-    }
-
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnBackwardRows) return;
 #pragma unroll
         for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
-    }
-    __device__ __forceinline__ void merge(int off) {   // with the slot `off` lanes away
-        if (PASS == kAttnBackwardRows) return;
-        float o[NF];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) o[i] = __shfl_xor(f[i], off);
-        combine(f, o);
     }
 
     __device__ __forceinline__ void finish(bool writer, int own, int) {
@@ -141,17 +119,5 @@ struct EdgePass {
         else attn_store<T, P>(f, a.dB + r * a.lddb + (long long)h * a.tile, n, t);
     }
 };
-
-template <int PASS, int OP, int T, int P, int U>
-__global__ __launch_bounds__(256) void edge_rows(EdgeArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                 const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<EdgePass<PASS, OP, T, P, U>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-
-template <int PASS, int OP, int T, int P, int U>
-__global__ __launch_bounds__(256) void edge_long(EdgeArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                 const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<EdgePass<PASS, OP, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
-}
 
 }  // namespace sx

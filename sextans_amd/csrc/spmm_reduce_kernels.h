@@ -8,7 +8,7 @@
 //   backward cols  (over A^T)  dB[c, n] = sum over the entries e of column c with arg[r, n] == e of val[e] * G[r, n]
 //   backward rows  dval[e] = sum over the n with arg[r, n] == e of G[r, n] * B[c, n]
 //
-// The passes below plug into the row walking of attention_kernels.h (attn_rows_body, attn_long_body) exactly as GatPass does; COLUMN
+// The passes below plug into the row walking of pattern_pass.h (attn_rows_body, attn_long_body) exactly as GatPass does; COLUMN
 // TILES of at most 128 floats play the heads' part: a slot of T lanes owns one (row, tile), lane t holds the 16-byte pieces t, t + T, ..
 // of the tile, the last tile of a row may be partial (pieces beyond N predicated off).  The forward's partial state per float is
 // (best product, best position), the position kept in f[] as its bit pattern so that the bodies' shuffles and LDS merge move it like
@@ -18,7 +18,7 @@
 // the slot, "heads_inside") sums the selected G * B over its pieces and a butterfly; one lane owns dval[e] for every tile and adds the
 // tiles in ascending order.  No atomics; sums in an order fixed by the pattern and the launch shape.
 #pragma once
-#include "attention_kernels.h"
+#include "pattern_pass.h"
 
 namespace sx {
 
@@ -60,6 +60,7 @@ struct ReducePass {
     using Args = ReduceArgs;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 * W : PASS == kAttnBackwardRows ? 1 : W;   // forward: best, position; rows: nothing to merge; cols: dB
+    static constexpr bool kMerge = PASS != kAttnBackwardRows;
     const ReduceArgs &a;
     const int *ci, *perm;
     const int t;
@@ -144,22 +145,6 @@ struct ReducePass {
         }
     }
 
-    // entries j, j + E, .. of the n entries that start at b, U at a time (the loop is uniform over the wavefront)
-    __device__ __forceinline__ void walk(bool act, int b, int cnt, int j, int E) {
-        if (!act) cnt = 0;
-#pragma unroll 1
-        for (int k0 = j; __any(k0 < cnt); k0 += E * U) {
-            int e[U];
-            bool valid[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                valid[u] = k0 + u * E < cnt;
-                e[u] = b + k0 + u * E;
-            }
-            batch(e, valid);
-        }
-    }
-
     // g <- g (+) o: both sides of a butterfly exchange end with the same bits (the comparison is a total order on distinct positions)
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnForward) {
@@ -174,13 +159,6 @@ struct ReducePass {
 #pragma unroll
             for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
         }
-    }
-    __device__ __forceinline__ void merge(int off) {   // with the slot `off` lanes away
-        if (PASS == kAttnBackwardRows) return;
-        float o[NF];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) o[i] = __shfl_xor(f[i], off);
-        combine(f, o);
     }
 
     // a position still at INT_MAX: the row has no entry -- (+0, -1)
@@ -210,17 +188,5 @@ struct ReducePass {
         }
     }
 };
-
-template <int PASS, int OP, int T, int P, int U>
-__global__ __launch_bounds__(256) void reduce_rows(ReduceArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                   const int *__restrict__ wrow, long long nw, int heads_inside) {
-    attn_rows_body<ReducePass<PASS, OP, T, P, U>>(a, rp, ci, perm, wrow, nw, heads_inside);
-}
-
-template <int PASS, int OP, int T, int P, int U>
-__global__ __launch_bounds__(256) void reduce_long(ReduceArgs a, const int *__restrict__ rp, const int *__restrict__ ci, const int *__restrict__ perm,
-                                                   const int2 *__restrict__ tab, int heads_inside) {
-    attn_long_body<ReducePass<PASS, OP, T, P, U>>(a, rp, ci, perm, tab, heads_inside);
-}
 
 }  // namespace sx

@@ -1,12 +1,16 @@
 """The device code of a built library, in a form two builds can be compared by (`diff -r` of two output directories):
 
-    python tools/kernel_set.py sextans_amd/lib/libsextans_amd.so OUTDIR
+    python tools/kernel_set.py sextans_amd/lib/libsextans_amd.so OUTDIR [NAMELESS_REGEX]
 
 Unbundles the gfx950 code objects of the library (llvm-objdump --offloading) and writes, one line per distinct kernel name (the .kd symbols):
   names.txt   the sorted names                     counts.txt  in how many code objects the kernel appears
   res.txt     VGPR / AGPR / SGPR / LDS / scratch / spill figures from the code-object notes
-  dis.txt     SHA-256 of the kernel's disassembly, instruction text only (no addresses, no encodings)
-Used for profiles/engine_split_kernels.txt: a host-only change leaves all four files as they were."""
+  dis.txt     SHA-256 of the kernel's disassembly, instruction text only (no addresses, no encodings, no padding behind the last s_endpgm)
+Used for profiles/engine_split_kernels.txt: a host-only change leaves all four files as they were.
+With NAMELESS_REGEX (searched in the mangled names) two more files, for a change that RENAMES kernels without touching their code:
+  multiset.txt  the matching kernels as sorted "dis-hash | res row | copies" lines, no names: equal before and after such a change
+  rest.txt      every other kernel as "name copies | res row | dis-hash": a diff of two builds' files is empty
+Used for profiles/pattern_pass_kernels.txt."""
 import collections
 import hashlib
 import os
@@ -44,6 +48,8 @@ for co in cos:
     cur = None
     buf = []
     def flush():
+        while buf and buf[-1] in ("", "s_nop 0", "..."):   # the padding behind a kernel depends on what follows it in .text, not on the kernel
+            buf.pop()
         if cur is not None and cur in names:
             dis.setdefault(cur, set()).add(hashlib.sha256("\n".join(buf).encode()).hexdigest())
     for l in d.splitlines():
@@ -62,5 +68,13 @@ with open(os.path.join(out, "res.txt"), "w") as f:
     f.write("".join("%s %s\n" % (n, " | ".join(sorted(res.get(n, ["?"])))) for n in sorted(count)))
 with open(os.path.join(out, "dis.txt"), "w") as f:
     f.write("".join("%s %s\n" % (n, " ".join(sorted(dis.get(n, ["?"])))) for n in sorted(count)))
+if len(sys.argv) > 3:
+    row = lambda n: (" ".join(sorted(dis.get(n, ["?"]))), " | ".join(sorted(res.get(n, ["?"]))), count[n])
+    match = [n for n in sorted(count) if re.search(sys.argv[3], n)]
+    with open(os.path.join(out, "multiset.txt"), "w") as f:
+        f.write("".join(sorted("%s | %s | %d\n" % row(n) for n in match)))
+    with open(os.path.join(out, "rest.txt"), "w") as f:
+        f.write("".join("%s %d | %s | %s\n" % (n, row(n)[2], row(n)[1], row(n)[0]) for n in sorted(count) if n not in match))
+    print(len(match), "kernels match", sys.argv[3])
 print(len(cos), "gfx950 code objects,", len(count), "distinct kernels,", sum(count.values()), "kernel copies,",
       sum(1 for n in count if n not in res), "without notes,", sum(1 for n in count if n not in dis), "without disassembly")
