@@ -837,6 +837,46 @@ int sextans_spmm_edge_device_rm(sextans_handle_t h, int op, int N, const float *
 int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
                                          const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
 
+/* ---- Edge features inside the fused attention: a key row and a value row per stored entry (PyG's TransformerConv(edge_dim=...), UniMP,
+ * the Dwivedi-Bresson graph transformer, relative-position encodings of mesh transformers).  Closest thing in the reference: none.
+ *
+ * Ek is (nnz, heads * d) and Ev (nnz, heads * dv), row-major in the entry order of the CSR arrays the matrix was set with
+ * (Ek[e * ldek + h * d + i], 64-bit offsets), as E of sextans_spmm_edge_device_rm.  For the stored entry e = (r, c) and head h
+ *     k_e = K[c,h,:] + Ek[e,h,:]       s_e = scale * (<Q[r,h,:], k_e> + bias_e)
+ *     v_e = V[c,h,:] + Ev[e,h,:]       O[r,h,:] = sum_e softmax_e(s) v_e          lse[r,h] as in sextans_attention_device
+ *     backward   dQ[r,h,:] = sum_e scale ds_e k_e;  dK[c,h,:] = sum_e scale ds_e Q[r,h,:];  dV[c,h,:] = sum_e (m_e p_e) G[r,h,:]
+ *                dEk[e,h,:] = (scale ds_e) * Q[r,h,:];  dEv[e,h,:] = (m_e p_e) * G[r,h,:]   -- one rounded multiply per element
+ *                with ds_e = p_e * (m_e <G[r,h,:], v_e> - delta[r,h]) and m_e the dropout multiplier (1 without dropout)
+ * k_e and v_e are ONE rounded fp32 add per element, formed once per pass; everything after is the arithmetic of
+ * sextans_attention_device (sextans_attention_dropout_device with drop) on k_e, v_e: the same row walking, lane groups, long-row
+ * workgroups, merges and order of every sum, so all three passes recompute the same score bits.  Per (entry, head) the forward and the
+ * row pass read one more 16-byte-piece row of each E given; the column pass (over A^T) reads both E a second time, through the
+ * transpose's entry permutation.  An (entry, head) belongs to one group of lanes in the row pass, which stores its dEk and dEv pieces:
+ * no atomics, no read-modify-write, the same bits on every run and stream; nothing of size nnz exists besides E, dE and the bias.
+ * d_Ek or d_Ev may be NULL: that side has no edge term (k_e = K[c] / v_e = V[c], bit for bit).  Both NULL: the call IS
+ * sextans_attention_dropout_device / _backward_device -- the plain kernels, the plain bits, their sextans_last_kernel.
+ * drop == NULL or p == 0: no dropout, as there.
+ * Backward: d_dEk and d_dEv may each be NULL (gradient not wanted).  d_dEk == d_dEv (one projected edge_attr used for both sides,
+ * as PyG does): the sum dEk + dEv (one rounded add of the two pieces) is stored once -- needs both E, d == dv and lddek == lddev.
+ * Leading dimensions: ldek, lddek >= heads * d, ldev, lddev >= heads * dv, multiples of 4, checked whether or not their pointer is
+ * NULL; every pointer 16-byte aligned.  The outputs must not overlap the inputs or each other (but for d_dEk == d_dEv).
+ * sextans_last_kernel: "attention_edge_fused" / "attention_edge_fused_backward", then "+dropout", then "+long_rows".
+ * SEXTANS_ERR_INVALID: everything sextans_attention_dropout_device rejects, in its order, with the E leading dimensions and pointers
+ * among the others; (backward) a gradient pointer for an absent E; d_dEk == d_dEv unless both E are given, d == dv and
+ * lddek == lddev -- then SEXTANS_ERR_STATE for a handle without a CSR matrix, then SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a
+ * required pointer that is NULL with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- O, delta, dQ, dK, dV are
+ * zeroed, lse is -inf, dEk and dEv have no element. */
+int sextans_attention_edge_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_Ek, int64_t ldek, const float *d_Ev, int64_t ldev,
+    const float *d_bias, float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream);
+int sextans_attention_edge_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale,
+    const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk, const float *d_V, int64_t ldv,
+    const float *d_Ek, int64_t ldek, const float *d_Ev, int64_t ldev,
+    const float *d_bias, const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv,
+    float *d_dEk, int64_t lddek, float *d_dEv, int64_t lddev, float *d_dbias, const sextans_dropout *drop, void *stream);
+
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *
  * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or

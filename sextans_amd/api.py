@@ -93,7 +93,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
-    "sextans_dropout_mask_device", "sextans_dropout_keep_host"))
+    "sextans_dropout_mask_device", "sextans_dropout_keep_host",
+    "sextans_attention_edge_device", "sextans_attention_edge_backward_device"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
@@ -325,6 +326,11 @@ def lib():
                                               C.c_int64, C.c_void_p]
     L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    vp, i64 = C.c_void_p, C.c_int64
+    L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                                vp, vp, i64, vp, dp, vp]
+    L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                                         vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, dp, vp]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -954,6 +960,26 @@ class Engine:
         d_B / d_E may be None where the op's gradient does not read them."""
         _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
                "spmm_edge_backward_device_rm")
+
+    def attention_edge_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias, d_O, ldo, d_lse,
+                              drop=None, stream=None):
+        """Fused attention with a feature vector per stored entry on the key and on the value side (sextans_attention_edge_device):
+        s_e = scale * (<Q[r, h, :], K[c, h, :] + Ek[e, h, :]> + bias_e), O[r, h, :] = sum_e softmax_e(s) (V[c, h, :] + Ev[e, h, :]).
+        Ek is (nnz, heads * d), Ev (nnz, heads * dv), row-major in the CSR entry order; either may be None (no edge term on that side;
+        both None: attention_dropout_device).  drop: a Dropout or None."""
+        _check(lib().sextans_attention_edge_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias,
+                                                   d_O, ldo, d_lse, _drop_ref(drop), stream), "attention_edge_device")
+
+    def attention_edge_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias, d_O, ldo, d_lse,
+                                       d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dEk, lddek, d_dEv, lddev, d_dbias,
+                                       drop=None, stream=None):
+        """dQ, dK, dV, dEk (nnz x heads * d), dEv (nnz x heads * dv) and, d_dbias not None, the bias gradient of attention_edge_device
+        from its O and lse and the upstream gradient G (sextans_attention_edge_backward_device).  d_dEk / d_dEv may each be None; the
+        same address for both (both E given, d == dv, lddek == lddev) stores the sum dEk + dEv once.  drop: the Dropout of the forward."""
+        _check(lib().sextans_attention_edge_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev,
+                                                            d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv,
+                                                            d_dEk, lddek, d_dEv, lddev, d_dbias, _drop_ref(drop), stream),
+               "attention_edge_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -36,6 +36,20 @@ struct AttnArgs {
 // they were before it existed.
 struct AttnDropArgs : AttnArgs { DropArgs drop; };
 
+// Edge features (the *_edge_device entries, engine_attention_edge.hip): a key row Ek[e, h, :] and a value row Ev[e, h, :] per stored entry,
+// (nnz, H d) and (nnz, H dv) row-major in A's entry order, addressed (long long)e * ld as in spmm_edge_kernels.h:
+//   k_e = K[c] + Ek[e],  v_e = V[c] + Ev[e]   (one __fadd_rn per element, formed once per pass), then everything above with k_e, v_e
+//   row pass       dEk[e, h, :] = scale ds Q[r, h, :];  dEv[e, h, :] = m p G[r, h, :]   -- an (entry, head) belongs to one slot: plain stores;
+//                  dEk == dEv: the sum of the two pieces is stored once
+//   column pass    the score and <G[r], v_e> read Ek, Ev a second time, through perm; dK and dV keep their form
+// Ek / Ev absent (NULL): a wavefront-uniform test, that side is the plain one.  A COMPILE-TIME variant of the passes (EDGE), as DROP is.
+struct AttnEdgeArgs : AttnArgs {
+    const float *Ek, *Ev;
+    float *dEk, *dEv;   // row pass; NULL: not wanted
+    long long ldek, ldev, lddek, lddev;
+};
+struct AttnEdgeDropArgs : AttnEdgeArgs { DropArgs drop; };
+
 __device__ __forceinline__ uint64_t drop_key(const DropArgs &d) {
     // (volatile: a vector load of the word a captured graph's caller bumps between replays)
     const uint64_t step = d.step ? *reinterpret_cast<const volatile uint64_t *>(d.step) : 0;
@@ -48,9 +62,9 @@ __device__ __forceinline__ float drop_mult(const DropArgs &d, uint64_t key, int 
 
 // One slot's view of a pass.  "own" is the row of the pattern walked (a row of A; the column pass: a row of A^T = a column of A),
 // "other" the index stored with an entry.
-template <int PASS, int T_, int P_, int U_, bool DROP = false>
-struct AttnPass {
-    using Args = std::conditional_t<DROP, AttnDropArgs, AttnArgs>;
+template <int PASS, int T_, int P_, int U_, bool DROP, bool EDGE>
+struct AttnPassT {
+    using Args = std::conditional_t<EDGE, std::conditional_t<DROP, AttnEdgeDropArgs, AttnEdgeArgs>, std::conditional_t<DROP, AttnDropArgs, AttnArgs>>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 2 + W : PASS == kAttnBackwardRows ? W : 2 * W;   // forward: m, Z, acc; rows: dQ; cols: dK, dV
     static constexpr bool kMerge = true;
@@ -63,7 +77,7 @@ struct AttnPass {
     float lse = 0.f, delta = 0.f;
     uint64_t key = 0;   // DROP: the mask's key
 
-    __device__ __forceinline__ AttnPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {
+    __device__ __forceinline__ AttnPassT(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {
         if constexpr (DROP) key = drop_key(a.drop);
     }
 
@@ -115,9 +129,55 @@ struct AttnPass {
                 bs[u] = (a.bias && valid[u]) ? a.bias[e[u]] : 0.0f;
             }
         }
+        long long pe[EDGE ? U : 1];                                  // EDGE: the entry's position in A's arrays
+        float ke[EDGE && PASS == kAttnBackwardCols ? U : 1][W];      // EDGE, column pass: k_e (the other passes form it in p1)
+        float ve[EDGE && PASS == kAttnBackwardCols ? U : 1][W];
+        if constexpr (EDGE) {
+            float ek[U][W], ev[U][W];
+#pragma unroll
+            for (int u = 0; u < U; ++u) pe[u] = PASS == kAttnBackwardCols ? (valid[u] ? perm[e[u]] : 0) : e[u];
+            if (a.Ek) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) attn_load<T, P>(ek[u], a.Ek + pe[u] * a.ldek + (long long)h * a.d, a.d, t, valid[u]);
+            }
+            if (a.Ev) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) attn_load<T, P>(ev[u], a.Ev + pe[u] * a.ldev + (long long)h * a.dv, a.dv, t, valid[u]);
+            }
+            if (PASS == kAttnBackwardCols) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#pragma unroll
+                    for (int i = 0; i < W; ++i) {
+                        ke[u][i] = a.Ek ? __fadd_rn(x[i], ek[u][i]) : x[i];
+                        ve[u][i] = a.Ev ? __fadd_rn(y[i], ev[u][i]) : y[i];
+                    }
+                }
+            } else {
+                if (a.Ek) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+#pragma unroll
+                        for (int i = 0; i < W; ++i) p1[u][i] = __fadd_rn(p1[u][i], ek[u][i]);
+                    }
+                }
+                if (a.Ev) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+#pragma unroll
+                        for (int i = 0; i < W; ++i) p2[u][i] = __fadd_rn(p2[u][i], ev[u][i]);
+                    }
+                }
+            }
+        }
         float s[U], mk[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) s[u] = __fmul_rn(a.scale, __fadd_rn(attn_dot<T, W>(x, p1[u]), bs[u]));
+        for (int u = 0; u < U; ++u) {
+            float dot;
+            if constexpr (EDGE && PASS == kAttnBackwardCols) dot = attn_dot<T, W>(ke[u], p1[u]);
+            else dot = attn_dot<T, W>(x, p1[u]);
+            s[u] = __fmul_rn(a.scale, __fadd_rn(dot, bs[u]));
+        }
         if constexpr (DROP) {
 #pragma unroll
             for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, valid[u] ? (PASS == kAttnBackwardCols ? perm[e[u]] : e[u]) : 0, a.H, h);
@@ -147,7 +207,9 @@ struct AttnPass {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const float p = valid[u] ? softmax_exp(__fsub_rn(s[u], ls[u])) : 0.0f;
-                float dp = attn_dot<T, W>(y, p2[u]), pm = p;
+                float dp, pm = p;
+                if constexpr (EDGE && PASS == kAttnBackwardCols) dp = attn_dot<T, W>(ve[u], p2[u]);
+                else dp = attn_dot<T, W>(y, p2[u]);
                 if constexpr (DROP) { dp = __fmul_rn(mk[u], dp); pm = __fmul_rn(mk[u], p); }
                 const float ds = valid[u] ? __fmul_rn(a.scale, __fmul_rn(p, __fsub_rn(dp, dl[u]))) : 0.0f;
 #pragma unroll
@@ -158,6 +220,24 @@ struct AttnPass {
                 } else if (a.dbias && valid[u] && t == 0) {
                     // the heads of an entry are taken by this lane one after the other, in ascending order: a plain read-modify-write
                     a.dbias[e[u]] = h == 0 ? ds : __fadd_rn(a.dbias[e[u]], ds);
+                }
+                if constexpr (EDGE && PASS == kAttnBackwardRows) {
+                    if (valid[u] && (a.dEk || a.dEv)) {
+                        float gk[W], gv[W];
+#pragma unroll
+                        for (int i = 0; i < W; ++i) {
+                            gk[i] = __fmul_rn(ds, x[i]);
+                            gv[i] = __fmul_rn(pm, y[i]);
+                        }
+                        if (a.dEk == a.dEv) {   // one shared gradient (d == dv): the sum, stored once
+#pragma unroll
+                            for (int i = 0; i < W; ++i) gk[i] = __fadd_rn(gk[i], gv[i]);
+                            attn_store<T, P>(gk, a.dEk + pe[u] * a.lddek + (long long)h * a.d, a.d, t);
+                        } else {
+                            if (a.dEk) attn_store<T, P>(gk, a.dEk + pe[u] * a.lddek + (long long)h * a.d, a.d, t);
+                            if (a.dEv) attn_store<T, P>(gv, a.dEv + pe[u] * a.lddev + (long long)h * a.dv, a.dv, t);
+                        }
+                    }
                 }
             }
         }
@@ -196,6 +276,16 @@ struct AttnPass {
             attn_store<T, P>(f + W, a.dV + r * a.lddv + (long long)h * a.dv, a.dv, t);
         }
     }
+};
+
+// The two families' pass types.  AttnPass keeps its own name and parameters: its kernels are the instantiations they were before EDGE existed.
+template <int PASS, int T_, int P_, int U_, bool DROP = false>
+struct AttnPass : AttnPassT<PASS, T_, P_, U_, DROP, false> {
+    using AttnPassT<PASS, T_, P_, U_, DROP, false>::AttnPassT;
+};
+template <int PASS, int T_, int P_, int U_, bool DROP = false>
+struct AttnEdgePass : AttnPassT<PASS, T_, P_, U_, DROP, true> {
+    using AttnPassT<PASS, T_, P_, U_, DROP, true>::AttnPassT;
 };
 
 }  // namespace sx

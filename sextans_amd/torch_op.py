@@ -46,6 +46,12 @@ the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_su
                                                    kernel pass per direction, E the only nnz x N tensor, no atomics; "mean": / row length
     A, perm = from_edge_index(edge_index, num_dst, num_src)   the sparse_csr A of a PyG edge list, and perm with E = edge_attr[perm]
 
+Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
+
+    O = sparse_attention_edge(A, Q, K, V, edge_key=None, edge_value=None, scale=None, bias=False, dropout=0.0, seed=None, step=None)
+                                                   softmax(scale * (<Q[r], K[c] + edge_key[e]> [+ A_e])) (V[c] + edge_value[e]) per head;
+                                                   the edge tensors are (nnz, H, d) in A's entry order; edge_key is edge_value: one gradient
+
 S and P are sparse_csr tensors that carry A's own index tensors, so the three ops and spmm() meet in one cache entry and hand each
 other's values to the engine as value refreshes; all are differentiable, their backward passes run on the engine too.
 """
@@ -716,6 +722,127 @@ def _sparse_attention(A, Q, K, V, scale, bias, fast, fused, p, seed, step):
             out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast), p, seed, step)
         else:
             out = _FusedAttentionFunction.apply(A, Q3, K3, V3, float(scale), bool(bias), bool(fast), 0.0, 0, None)
+    return out if V.dim() == 3 else out[:, 0]
+
+
+class _EdgeAttentionFunction(torch.autograd.Function):
+    """sparse_attention_edge(): the fused attention with a key row and a value row per stored entry (sextans_attention_edge_device /
+    sextans_attention_edge_backward_device).  Ek / Ev: (nnz, H, d) / (nnz, H, dv) or None; shared: Ev is Ek itself -- the backward then
+    hands one buffer to the engine as both gradients and gets their sum.  As _FusedAttentionFunction: nothing of size nnz but E, dE and
+    the bias, no value refresh."""
+
+    @staticmethod
+    def forward(ctx, A, Q, K, V, Ek, Ev, shared, scale, bias, fast, p, seed, step):
+        M, Kk = A.shape
+        H, d, dv = Q.shape[1], Q.shape[2], V.shape[2]
+        dp, dvp = -(-d // 8) * 8, -(-dv // 8) * 8
+        dev = A.device.index or 0
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, Kk), dev, fast, values_needed=False)
+        Qr, ldq = _heads_operand(Q.detach(), dp)
+        Kr, ldk = _heads_operand(K.detach(), dp)
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        Ekr, ldek = _heads_operand(Ek.detach(), dp) if Ek is not None else (None, H * dp)
+        Evr, ldev = (Ekr, ldek) if shared else _heads_operand(Ev.detach(), dvp) if Ev is not None else (None, H * dvp)
+        b = _vals32(val) if bias else None
+        O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
+        lse = torch.empty((M, H), dtype=torch.float32, device=A.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ent.eng.attention_edge_device(H, dp, dvp, scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv, ptr(Ekr), ldek, ptr(Evr), ldev,
+                                      ptr(b), O.data_ptr(), H * dvp, lse.data_ptr(), _drop_struct(p, seed, step),
+                                      torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, val, Q, K, V, Ek, Ev, O, lse)
+        ctx.shape, ctx.scale, ctx.bias, ctx.fast, ctx.dev, ctx.shared = (M, Kk), scale, bias, fast, dev, shared
+        ctx.drop = (p, seed, step)   # the backward recomputes the forward's mask
+        return O if dvp == dv else O[:, :, :dv]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        crow, col, val, Q, K, V, Ek, Ev, O, lse = ctx.saved_tensors
+        M, Kk = ctx.shape
+        H, d, dv = Q.shape[1], Q.shape[2], V.shape[2]
+        dp, dvp = -(-d // 8) * 8, O.shape[2]
+        nnz, shared = int(val.numel()), ctx.shared
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        Qr, ldq = _heads_operand(Q.detach(), dp)
+        Kr, ldk = _heads_operand(K.detach(), dp)
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        Ekr, ldek = _heads_operand(Ek.detach(), dp) if Ek is not None else (None, H * dp)
+        Evr, ldev = (Ekr, ldek) if shared else _heads_operand(Ev.detach(), dvp) if Ev is not None else (None, H * dvp)
+        Gr, ldg = _heads_operand(G, dvp)
+        want_bias = ctx.bias and ctx.needs_input_grad[0]
+        b = _vals32(val) if ctx.bias else None
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=G.device)
+        delta, dQ, dK, dV = new(M, H), new(M, H, dp), new(Kk, H, dp), new(Kk, H, dvp)
+        db = new(nnz) if want_bias else None
+        dEk = new(nnz, H, dp) if Ek is not None and ctx.needs_input_grad[4] else None
+        dEv = dEk if shared else new(nnz, H, dvp) if Ev is not None and ctx.needs_input_grad[5] else None   # shared: ONE buffer, the sum
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        ent.eng.attention_edge_backward_device(H, dp, dvp, ctx.scale, Qr.data_ptr(), ldq, Kr.data_ptr(), ldk, Vr.data_ptr(), ldv, ptr(Ekr), ldek,
+                                               ptr(Evr), ldev, ptr(b), O.data_ptr(), H * dvp, lse.data_ptr(), Gr.data_ptr(), ldg,
+                                               delta.data_ptr(), dQ.data_ptr(), H * dp, dK.data_ptr(), H * dp, dV.data_ptr(), H * dvp,
+                                               ptr(dEk), H * dp, ptr(dEv), H * dvp, ptr(db), _drop_struct(*ctx.drop),
+                                               torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, db.to(val.dtype), size=(M, Kk)) if want_bias else None
+        gQ = (dQ if dp == d else dQ[:, :, :d]).to(Q.dtype) if ctx.needs_input_grad[1] else None
+        gK = (dK if dp == d else dK[:, :, :d]).to(K.dtype) if ctx.needs_input_grad[2] else None
+        gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if ctx.needs_input_grad[3] else None
+        gEk = (dEk if dp == d else dEk[:, :, :d]).to(Ek.dtype) if dEk is not None else None
+        gEv = (dEv if dvp == dv else dEv[:, :, :dv]).to(Ev.dtype) if dEv is not None and not shared else None
+        return gA, gQ, gK, gV, gEk, gEv, None, None, None, None, None, None, None
+
+
+def sparse_attention_edge(A, Q, K, V, edge_key=None, edge_value=None, scale=None, bias=False, dropout=0.0, seed=None, step=None, fast=False):
+    """Attention on A's pattern with a feature vector per stored entry inside it (TransformerConv(edge_dim=...), UniMP, relative-position
+    encodings): for the entry e = (r, c) of row r and head h
+        s_e = scale * (<Q[r, h], K[c, h] + edge_key[e, h]> + A_e if bias),   O[r, h] = sum_e softmax_e(s) (V[c, h] + edge_value[e, h])
+    Always fused: one kernel pass forward, a row pass and a column pass backward (sextans_attention_edge_device /
+    sextans_attention_edge_backward_device), all heads at once, the edge rows read where they lie.  Q is (M, d) or (M, H, d), K (Kk, d) /
+    (Kk, H, d), V (Kk, dv) / (Kk, H, dv); edge_key is (nnz, H * d) or (nnz, H, d), edge_value (nnz, H * dv) or (nnz, H, dv), both in A's
+    entry order (from_edge_index's perm brings a PyG edge_attr there); either may be None.  The result has V's rank.  scale=None means
+    1 / sqrt(d); dropout, seed, step as sparse_attention_dropout().  Differentiable in Q, K, V, both edge tensors and (bias=True) A.
+    edge_key is edge_value (one projected edge_attr for both sides, d == dv): the backward stores the sum of the two gradients once and
+    returns it -- no second (nnz, H, d) buffer exists.  One cached engine per pattern, no value refresh."""
+    _check_sparse(A, "sparse_attention_edge")
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (Q, K, V)):
+        raise TypeError("sparse_attention_edge expects CUDA/HIP dense Q, K and V")
+    if any(t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda) for t in (edge_key, edge_value)):
+        raise TypeError("sparse_attention_edge expects CUDA/HIP dense edge_key and edge_value (or None)")
+    if any(t.dim() not in (2, 3) for t in (Q, K, V)):
+        raise ValueError("Q, K and V are (rows, d) or (rows, heads, d)")
+    Q3, K3, V3 = (t if t.dim() == 3 else t.unsqueeze(1) for t in (Q, K, V))
+    M, Kk = A.shape
+    H, d, dv = Q3.shape[1], Q3.shape[2], V3.shape[2]
+    if K3.shape[1] != H or V3.shape[1] != H:
+        raise ValueError("Q, K and V differ in their number of heads")
+    if Q3.shape[0] != M or K3.shape[0] != Kk or V3.shape[0] != Kk or K3.shape[2] != d or H == 0 or d == 0 or dv == 0:
+        raise ValueError("shape mismatch")
+    if d > 128 or dv > 128:
+        raise ValueError("sparse_attention_edge: head dimensions up to 128")
+    nnz = int(A.values().numel())
+    shared = edge_key is not None and edge_key is edge_value
+
+    def edge3(t, w, name):
+        if t is None:
+            return None
+        if t.dim() not in (2, 3) or t.shape[0] != nnz or (tuple(t.shape[1:]) != (H, w) if t.dim() == 3 else t.shape[1] != H * w):
+            raise ValueError("%s is (nnz, heads * d) or (nnz, heads, d) in A's entry order" % name)
+        return t if t.dim() == 3 else t.unflatten(1, (H, w))
+
+    Ek3 = edge3(edge_key, d, "edge_key")
+    Ev3 = None if shared else edge3(edge_value, dv, "edge_value")
+    if shared and d != dv:
+        raise ValueError("edge_key is edge_value needs d == dv")
+    if scale is None:
+        scale = 1.0 / math.sqrt(d)
+    p = _check_dropout(dropout)
+    if p > 0.0:
+        seed, step = _draw_seed(seed), _check_step(step, A.device)
+    else:
+        seed, step = 0, None
+    out = _EdgeAttentionFunction.apply(A, Q3, K3, V3, Ek3, Ev3, shared, float(scale), bool(bias), bool(fast), p, seed, step)
     return out if V.dim() == 3 else out[:, 0]
 
 
