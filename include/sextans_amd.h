@@ -791,6 +791,47 @@ int sextans_spmm_reduce_backward_device_rm(sextans_handle_t h, int N, const floa
                                            const int32_t *d_arg, int64_t ldarg, const float *d_G, int64_t ldg,
                                            float *d_dB, int64_t lddb, float *d_dval, void *stream);
 
+/* ---- Several aggregations of the SAME messages in one pass (PNA's mean / max / min / std, PyG's MultiAggregation, the mean || max
+ * read-outs of GraphSAGE variants).  Closest thing in the reference: none.
+ *
+ * A, B, d_val and the message p_e[n] = val[e] * B[c, n] (ONE rounded fp32 product) are those of sextans_spmm_reduce_device_rm above; one
+ * gathered B row per entry serves every aggregate.  Outputs (each row-major M x N with its OWN pointer and leading dimension, so that they
+ * may be column slices of one (M, k N) buffer -- the concatenation PNA wants is written in place; columns beyond N are never written):
+ *     d_sum      sum_e p_e                       (fp32 adds rounded to nearest)
+ *     d_sumsq    sum_e p_e^2                     (s = fma(p_e, p_e, s))
+ *     d_max / d_argmax, d_min / d_argmin          the values AND BITS of sextans_spmm_reduce_device_rm with SEXTANS_REDUCE_MAX / _MIN
+ *     a row without stored entries: sums +0, max and min +0, args -1
+ * The sums run in an order fixed by the pattern and the launch shape (no atomics: the same bits on every run and stream); that order does
+ * not depend on which outputs are requested.  A NULL output is not computed (sum and sumsq form one group, max and min with their args
+ * the other; a group without any pointer is compiled out) -- at least one of the four values must be given, and an arg needs its value.
+ * Backward, for the upstream gradients that are given (NULL: absent) and the args of the forward:
+ *     t_e[n]   = Gsum[r, n] + 2 p_e[n] Gsq[r, n] + (argmax[r, n] == e ? Gmax[r, n] : 0) + (argmin[r, n] == e ? Gmin[r, n] : 0)
+ *                (evaluated left to right: t = Gsum; t = fma(2 p_e, Gsq, t); t += Gmax where e won; t += Gmin where e won)
+ *     dB[c, n] = sum over the entries of column c of val[e] * t_e[n]   (fma; one GATHER pass over the rows of A^T)
+ *     dval[e]  = sum_n B[c, n] * t_e[n]                                (fma; one row pass over A, one lane owns an entry)
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles (see DESIGN 4.18 for this family's tile).  Leading dimensions:
+ * ldb and lddb always, a struct member's when its pointer is given (ld_arg: when either arg is): >= N and multiples of 4; every pointer
+ * 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * d_val == NULL: the engine's current values.  No value refresh happens and none of the engine's packed forms is read or written.
+ * Backward: d_dB or d_dval may be NULL, not both; d_B may be NULL when neither d_gsumsq nor d_dval is given.  It writes every element
+ * of dB (K x N) and of dval (nnz) it is given.
+ * First calls build the row softmax's tables / A^T as for sextans_spmm_reduce_device_rm and synchronise then; after that a call allocates
+ * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_multi" / "spmm_multi_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, out / g == NULL, a bad N, a bad leading dimension, a misaligned pointer, no output (no gradient)
+ * given, an arg without its value, (backward) d_gmax without d_argmax or d_gmin without d_argmin, d_dB and d_dval both NULL, d_gsumsq
+ * or d_dval without d_B -- then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for
+ * nnz > INT32_MAX and (forward) d_B == NULL with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- the values and
+ * dB are zeroed, the args = -1. */
+typedef struct { float *d_sum, *d_sumsq, *d_max, *d_min; int64_t ld_sum, ld_sumsq, ld_max, ld_min;
+                 int32_t *d_argmax, *d_argmin; int64_t ld_arg; } sextans_multi_out;
+typedef struct { const float *d_gsum, *d_gsumsq, *d_gmax, *d_gmin; int64_t ld_gsum, ld_gsumsq, ld_gmax, ld_gmin;
+                 const int32_t *d_argmax, *d_argmin; int64_t ld_arg; } sextans_multi_grad;
+int sextans_spmm_multi_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb,
+                                 const sextans_multi_out *out, void *stream);
+int sextans_spmm_multi_backward_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb,
+                                          const sextans_multi_grad *g, float *d_dB, int64_t lddb, float *d_dval, void *stream);
+
 /* ---- SpMM with a feature VECTOR per stored entry (edge-feature message passing: continuous-filter convolution / u_mul_e_sum, GINE /
  * relu(u_add_e) summed, edge -> node reduction / copy_e_sum).  Closest thing in the reference: none -- its PEs weight an entry with a
  * scalar.

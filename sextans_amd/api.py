@@ -66,6 +66,21 @@ def _drop_ref(drop):
     return C.byref(drop) if drop is not None else None
 
 
+class MultiOut(C.Structure):
+    """sextans_multi_out: the outputs of spmm_multi_device_rm, each a device address (None: not computed) with its own leading dimension
+    -- they may be column slices of one (M, k N) buffer.  ld_arg serves both args."""
+    _fields_ = [("d_sum", C.c_void_p), ("d_sumsq", C.c_void_p), ("d_max", C.c_void_p), ("d_min", C.c_void_p),
+                ("ld_sum", C.c_int64), ("ld_sumsq", C.c_int64), ("ld_max", C.c_int64), ("ld_min", C.c_int64),
+                ("d_argmax", C.c_void_p), ("d_argmin", C.c_void_p), ("ld_arg", C.c_int64)]
+
+
+class MultiGrad(C.Structure):
+    """sextans_multi_grad: the upstream gradients of spmm_multi_backward_device_rm (None: absent) and the forward's args."""
+    _fields_ = [("d_gsum", C.c_void_p), ("d_gsumsq", C.c_void_p), ("d_gmax", C.c_void_p), ("d_gmin", C.c_void_p),
+                ("ld_gsum", C.c_int64), ("ld_gsumsq", C.c_int64), ("ld_gmax", C.c_int64), ("ld_gmin", C.c_int64),
+                ("d_argmax", C.c_void_p), ("d_argmin", C.c_void_p), ("ld_arg", C.c_int64)]
+
+
 class SextansError(RuntimeError):
     def __init__(self, code, where=""):
         self.code = code
@@ -89,6 +104,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
     "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
     "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm",
+    "sextans_spmm_multi_device_rm", "sextans_spmm_multi_backward_device_rm",
     "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -322,6 +338,9 @@ def lib():
                                                 C.c_void_p, C.c_int64, C.c_void_p]
     L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_spmm_multi_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiOut), C.c_void_p]
+    L.sextans_spmm_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiGrad),
+                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.sextans_spmm_edge_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_int64, C.c_void_p]
     L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -947,6 +966,20 @@ class Engine:
         None (not both); d_B may be None when d_dval is."""
         _check(lib().sextans_spmm_reduce_backward_device_rm(self._h, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream),
                "spmm_reduce_backward_device_rm")
+
+    def spmm_multi_device_rm(self, N, d_val, d_B, ldb, out, stream=None):
+        """Several aggregations of the messages d_val[e] * B[c, n] in one pass (sextans_spmm_multi_device_rm): out is a MultiOut whose
+        given addresses receive the sum, the sum of squares, the max and the min over every row's entries (and the int32 args of the
+        extrema, with the bits of spmm_reduce_device_rm); an empty row gives +0 and -1.  d_val None = the engine's current values."""
+        _check(lib().sextans_spmm_multi_device_rm(self._h, N, d_val, d_B, ldb, C.byref(out) if out is not None else None, stream),
+               "spmm_multi_device_rm")
+
+    def spmm_multi_backward_device_rm(self, N, d_val, d_B, ldb, g, d_dB, lddb, d_dval, stream=None):
+        """dB (K x N) and dval (nnz floats) of spmm_multi_device_rm from the upstream gradients and the args in g, a MultiGrad
+        (sextans_spmm_multi_backward_device_rm): one column pass over A^T, one row pass over A.  d_dB or d_dval may be None (not both);
+        d_B may be None when neither g.d_gsumsq nor d_dval is given."""
+        _check(lib().sextans_spmm_multi_backward_device_rm(self._h, N, d_val, d_B, ldb, C.byref(g) if g is not None else None, d_dB, lddb,
+                                                           d_dval, stream), "spmm_multi_backward_device_rm")
 
     def spmm_edge_device_rm(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
         """SpMM with a feature vector per stored entry (sextans_spmm_edge_device_rm): C[r, n] = sum over row r's entries e = (r, c) of

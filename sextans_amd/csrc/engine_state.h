@@ -13,6 +13,7 @@
 //   engine_gat.hip      fused graph attention (GAT) on A's pattern (sextans_gat_attention_device, ..._backward_device)
 //   engine_gatv2.hip    fused GATv2 graph attention on A's pattern (sextans_gatv2_attention_device, ..._backward_device, the datt sum)
 //   engine_reduce.hip   max / min aggregation SpMM, forward and backward (sextans_spmm_reduce_device_rm, ..._backward_device_rm)
+//   engine_multi.hip    sum, sum of squares, max and min in one pass, forward and backward (sextans_spmm_multi_device_rm, ..._backward_device_rm)
 //   engine_edge.hip     SpMM with a feature vector per entry, forward and backward (sextans_spmm_edge_device_rm, ..._backward_device_rm)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)

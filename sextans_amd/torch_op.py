@@ -37,6 +37,9 @@ in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
     C = spmm_reduce(A, B, reduce="amax")           C[r, n] = max ("amin": min) over row r's stored entries (r, c) of A_e * B[c, n]; an empty
                                                    row gives 0.  One kernel pass, nothing of size nnz x N materialised; return_arg=True
                                                    also returns the winning entries.  "mean" / "sum": spmm() (divided by the row lengths)
+    C = spmm_multi(A, B, aggr=("mean", "max", "min", "std"))   several aggregations of the same messages side by side, (M, len(aggr) N)
+                                                   (PNAConv, MultiAggregation): one kernel pass gathers B's rows once for the sum, the sum
+                                                   of squares, the max and the min; one backward call.  Also "sum", "var", "sumsq"
 
 Edge-feature message passing -- a feature VECTOR per stored entry instead of a scalar weight (SchNet's CFConv / diagonal NNConv, GINEConv,
 the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_sum in DGL), on the cached engine of the pattern:
@@ -1191,6 +1194,183 @@ def spmm_reduce(A, B, reduce="amax", return_arg=False, fast=False):
         if C.shape[1] != N:
             C, arg = C[:, :N], (arg[:, :N] if arg is not None else None)
     return (C, arg) if return_arg else C
+
+
+_MULTI_RAW = ("sum", "sumsq", "max", "min")                       # what the kernel computes, in the order of sextans_multi_out
+_MULTI_NEEDS = {"sum": ("sum",), "mean": ("sum",), "max": ("max",), "min": ("min",), "sumsq": ("sumsq",),
+                "var": ("sum", "sumsq"), "std": ("sum", "sumsq")}   # aggregate -> the raw aggregates it is made of
+
+
+def _multi_raw(A, B, want, place, width, fast, want_arg):
+    """One forward call of the engine's multi-aggregation.  want: the raw aggregates to compute; place: raw name -> the index of its
+    N-column block in an (M, width) output that the kernel writes in place (N % 8 == 0 only; empty: no such output).
+    -> (out or None, {raw name not placed: (M, Np) tensor}, argmax, argmin), Np = N padded up to a multiple of 8."""
+    M, K = A.shape
+    N = B.shape[1]
+    Np = api.round_up_n(N)
+    crow, col = _index_tensors(A)
+    val = A.values()
+    ent = _entry_for_parts(crow, col, val, (M, K), A.device.index or 0, fast, values_needed=False)
+    Brm = _rowmajor(B.detach(), K, N, Np)
+    v = _vals32(val)
+    out = torch.empty((M, width), dtype=torch.float32, device=A.device) if place else None
+    tmp = {name: torch.empty((M, Np), dtype=torch.float32, device=A.device) for name in want if name not in place}
+    args = [torch.empty((M, Np), dtype=torch.int32, device=A.device) if want_arg and name in want else None for name in ("max", "min")]
+    if M:
+        o = api.MultiOut()
+        for name in want:
+            if name in place:
+                ptr, ld = out.data_ptr() + 4 * N * place[name], width
+            else:
+                ptr, ld = tmp[name].data_ptr(), Np
+            setattr(o, "d_" + name, ptr)
+            setattr(o, "ld_" + name, ld)
+        o.d_argmax, o.d_argmin = (t.data_ptr() if t is not None else None for t in args)
+        o.ld_arg = Np
+        ent.eng.spmm_multi_device_rm(Np, v.data_ptr() if v.numel() else None, Brm.data_ptr() if Brm.numel() else None, Brm.stride(0), o,
+                                     torch.cuda.current_stream(A.device).cuda_stream)
+    return out, tmp, args[0], args[1]
+
+
+class _SpmmMultiFunction(torch.autograd.Function):
+    """spmm_multi(): ONE forward call (sextans_spmm_multi_device_rm) for the raw aggregates that are needed and the args of the extrema,
+    ONE backward call (sextans_spmm_multi_backward_device_rm) that takes the upstream gradients that exist -- a column pass over A^T for
+    dB and a row pass over A for dA, each only when autograd asks for it.  A's values enter as an explicit pointer, never through the
+    engine: no value refresh anywhere.  Outputs: the (M, width) tensor with the raw aggregates written in place (or None), then sum,
+    sumsq, max, min as tensors of their own where they are not placed (else None), argmax, argmin.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, B, want, place, width, fast):
+        N = B.shape[1]
+        out, tmp, amax, amin = _multi_raw(A, B, want, place, width, fast, True)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B, *(t for t in (amax, amin) if t is not None))
+        ctx.shape, ctx.fast, ctx.dev, ctx.want, ctx.place = tuple(A.shape), fast, A.device.index or 0, want, place
+        ctx.set_materialize_grads(False)
+        cut = lambda t: t if t is None or t.shape[1] == N else t[:, :N]
+        amax, amin = cut(amax), cut(amin)
+        ctx.mark_non_differentiable(*(t for t in (amax, amin) if t is not None))
+        return (out,) + tuple(cut(tmp.get(name)) for name in _MULTI_RAW) + (amax, amin)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, *g_raw):
+        crow, col, val, B, *args = ctx.saved_tensors
+        M, K = ctx.shape
+        N = B.shape[1]
+        Np = api.round_up_n(N)
+        want_a, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * 6
+        if not (want_a or want_b):
+            return none
+        arg = dict(zip([name for name in ("max", "min") if name in ctx.want], args))
+        g = api.MultiGrad()
+        keep = []                                   # the gradient tensors the kernel reads, kept alive over the call
+        if g_out is not None and ctx.place:
+            g_out = _rowmajor(g_out, M, g_out.shape[1], g_out.shape[1])   # (N % 8 == 0 here: the slices are aligned)
+            keep.append(g_out)
+        for name, gr in zip(_MULTI_RAW, g_raw[:4]):
+            if name in ctx.place:
+                if g_out is None:
+                    continue
+                ptr, ld = g_out.data_ptr() + 4 * N * ctx.place[name], g_out.stride(0)
+            elif gr is not None:
+                gr = _rowmajor(gr, M, N, Np)        # (a copy when the gradient has zero strides, e.g. after .sum(), or N % 8 != 0)
+                keep.append(gr)
+                ptr, ld = gr.data_ptr(), gr.stride(0)
+            else:
+                continue
+            setattr(g, "d_g" + name, ptr)
+            setattr(g, "ld_g" + name, ld)
+            if name in arg:
+                setattr(g, "d_arg" + name, arg[name].data_ptr())
+                g.ld_arg = Np
+        given = any(getattr(g, "d_g" + name) for name in _MULTI_RAW)
+        Brm = _rowmajor(B.detach(), K, N, Np) if (want_a or g.d_gsumsq) else None
+        v = _vals32(val)
+        new = torch.empty if given else torch.zeros   # (no upstream gradient at all: zeros, no call)
+        dB = new((K, Np), dtype=torch.float32, device=val.device) if want_b else None
+        dv = new((val.numel(),), dtype=torch.float32, device=val.device) if want_a else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        if given and M and (ptr(dB) is not None or ptr(dv) is not None):   # (else: no element to write)
+            ctx_eng = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False).eng
+            ctx_eng.spmm_multi_backward_device_rm(Np, ptr(v), ptr(Brm), Brm.stride(0) if Brm is not None else Np, g, ptr(dB), Np, ptr(dv),
+                                                  torch.cuda.current_stream(val.device).cuda_stream)
+        elif given:
+            for t in (dB, dv):
+                if t is not None:
+                    t.zero_()
+        gA = torch.sparse_csr_tensor(crow, col, dv.to(val.dtype), size=(M, K)) if want_a else None
+        gB = (dB if Np == N else dB[:, :N]).to(B.dtype) if want_b else None
+        return (gA, gB) + none[2:]
+
+
+class _MultiAssemble(torch.autograd.Function):
+    """The derived aggregates copied into their N-column blocks of spmm_multi()'s result, in place; backward hands the upstream
+    gradient on as it is (the raw aggregates' node reads its own blocks of it) and its blocks to the derived ones as views -- what
+    out[:, block] = t would do with a copy of the whole gradient per assignment."""
+
+    @staticmethod
+    def forward(ctx, out, blocks, *derived):
+        N = derived[0].shape[1]
+        for j, t in zip(blocks, derived):
+            out[:, j * N:(j + 1) * N] = t
+        ctx.blocks, ctx.N = blocks, N
+        ctx.mark_dirty(out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        N = ctx.N
+        return (g, None) + tuple(g[:, j * N:(j + 1) * N] for j in ctx.blocks)
+
+
+def spmm_multi(A, B, aggr=("mean", "max", "min", "std"), eps=1e-5, fast=False):
+    """Several aggregations of the same messages at once (PNAConv's aggregators, PyG's MultiAggregation, mean || max read-outs): A is an
+    (M, K) sparse_csr matrix, B a dense (K, N) tensor, the result a dense fp32 (M, len(aggr) * N) tensor with the aggregates side by side
+    in aggr's order.  The message of the stored entry e = (r, c) is p_e = A_e * B[c, :] (one rounded fp32 product, as in spmm_reduce()).
+      "sum", "sumsq", "max", "min": the kernel's own outputs -- sum_e p_e, sum_e p_e^2, and the extrema with the bits of spmm_reduce();
+      "mean" = sum / deg, "var" = sumsq / deg - mean^2, "std" = sqrt(relu(var) + eps) (PNA's form), deg the row's stored-entry count
+      clamped to at least 1: plain torch elementwise ops on top, differentiated by autograd.  A row without entries gives 0 (std: sqrt(eps)).
+    ONE kernel pass gathers B's rows once for everything (sextans_spmm_multi_device_rm), one backward call serves all upstream gradients
+    (sextans_spmm_multi_backward_device_rm); differentiable in B and in A (dA: a sparse_csr tensor on A's index tensors); ties send the
+    extrema's gradient to the first entry, as spmm_reduce() does.  With N % 8 == 0 the kernel writes "sum", "sumsq", "max" and "min"
+    straight into their columns of the result; otherwise operands and results are copied with zero padding, as spmm_reduce() does.  A's
+    values are handed over as a pointer: no value refresh of the cached engine.  `fast` only selects the cached engine.  Degree scalers
+    are left to the caller."""
+    aggr = tuple(aggr)
+    if not aggr or any(name not in _MULTI_NEEDS for name in aggr) or len(set(aggr)) != len(aggr):
+        raise ValueError("aggr: a non-empty sequence of distinct names out of 'sum', 'mean', 'max', 'min', 'var', 'std', 'sumsq'")
+    _check_sparse(A, "spmm_multi")
+    if not (isinstance(B, torch.Tensor) and B.is_cuda):
+        raise TypeError("spmm_multi expects a CUDA/HIP dense B")
+    if B.dim() != 2 or B.shape[0] != A.shape[1] or B.shape[1] == 0:
+        raise ValueError("shape mismatch")
+    M, N = A.shape[0], B.shape[1]
+    width = len(aggr) * N
+    want = tuple(name for name in _MULTI_RAW if any(name in _MULTI_NEEDS[x] for x in aggr))
+    place = {name: aggr.index(name) for name in want if name in aggr} if N % 8 == 0 else {}
+    if torch.is_grad_enabled() and (A.requires_grad or B.requires_grad):
+        out, *raw = _SpmmMultiFunction.apply(A, B, want, place, width, bool(fast))[:5]
+        raw = dict(zip(_MULTI_RAW, raw))
+    else:
+        out, raw, _, _ = _multi_raw(A, B, want, place, width, bool(fast), False)
+        raw = {name: (t if t.shape[1] == N else t[:, :N]) for name, t in raw.items()}
+    for name, j in place.items():
+        raw[name] = out[:, j * N:(j + 1) * N]
+    got = dict(raw)   # every aggregate that is asked for or needed on the way, from the raw ones
+    if any(name in aggr for name in ("mean", "var", "std")):
+        crow = _index_tensors(A)[0]
+        deg = (crow[1:] - crow[:-1]).clamp(min=1).to(torch.float32)[:, None]
+        got["mean"] = raw["sum"] / deg
+        if "var" in aggr or "std" in aggr:
+            got["var"] = raw["sumsq"] / deg - got["mean"] ** 2
+        if "std" in aggr:
+            got["std"] = torch.sqrt(torch.relu(got["var"]) + eps)
+    if out is None:
+        return torch.cat([got[name] for name in aggr], dim=1)
+    blocks = tuple(j for j, name in enumerate(aggr) if name not in place)
+    return _MultiAssemble.apply(out, blocks, *(got[aggr[j]] for j in blocks)) if blocks else out
 
 
 _EDGE_OPS = {"mul": api.EDGE_MUL, "add": api.EDGE_ADD, "add_relu": api.EDGE_ADD_RELU, "copy": api.EDGE_COPY}
