@@ -832,6 +832,46 @@ int sextans_spmm_multi_device_rm(sextans_handle_t h, int N, const float *d_val, 
 int sextans_spmm_multi_backward_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb,
                                           const sextans_multi_grad *g, float *d_dB, int64_t lddb, float *d_dval, void *stream);
 
+/* ---- Softmax aggregation: a softmax PER OUTPUT COLUMN over a row's messages themselves, with a temperature per column (PyG's
+ * SoftmaxAggregation(t, learn=True), the aggregator of GENConv / DeeperGCN, an entry of MultiAggregation).  It spans the mean (t = 0), the
+ * max (t -> inf) and the min (t -> -inf).  Closest thing in the reference: none.
+ *
+ * A, B, d_val and the message p_e[n] = val[e] * B[c, n] (ONE rounded fp32 product) are those of sextans_spmm_reduce_device_rm above.  d_t: N
+ * floats, one temperature per column, any finite value; NULL = 1.  All arithmetic fp32:
+ *     s_e[n]    = t[n] * p_e[n]                   (one rounded multiply; d_t == NULL: s_e = p_e)
+ *     lse[r, n] = log sum_e exp(s_e[n])           w_e[n] = exp(s_e[n] - lse[r, n])
+ *     C[r, n]   = sum_e w_e[n] p_e[n]             a row without stored entries: C = +0, lse = -inf
+ * computed online (a running maximum, normaliser and accumulator per (row, column); only differences to the maximum are exponentiated, so
+ * t p beyond +-88 does not overflow), C = acc / z, lse = m + log z.  A row of ONE entry gives C the bits of its product (+0 for -0).  A
+ * non-finite product does what this arithmetic makes of it (two infinite scores: NaN) within its own (row, column) and goes nowhere else.
+ * Backward, G the upstream gradient of C, q_e[n] = (G[r, n] w_e[n]) (1 + t[n] (p_e[n] - C[r, n])):
+ *     dB[c, n] = sum over the entries of column c of val[e] q_e[n]                  (fma; one GATHER pass over the rows of A^T)
+ *     dval[e]  = sum_n B[c, n] q_e[n]                                               (fma; one row pass over A, one lane owns an entry)
+ *     dt[n]    = sum_r sum_e (G[r, n] w_e[n]) (p_e[n] (p_e[n] - C[r, n]))           (the row pass leaves the inner sum per row in d_work;
+ *                rows are then added in a fixed two-level order: 256-row chunks ascending, then the chunks ascending)
+ * The gradients amplify the rounding of s by t (p - C): at |t| of a few hundred they lose digits that the forward keeps.
+ * Every sum runs in an order fixed by the pattern and the launch shape; there are no atomics: the same bits on every run and stream.
+ * Nothing of size nnz x N exists.  No value refresh happens and none of the engine's packed forms is read or written.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 128 floats.  Leading dimensions (all of them, whether or
+ * not their pointer is NULL): >= N and multiples of 4; every pointer 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * d_lse may be NULL in the forward (inference).  In the backward any of d_dB, d_dval, d_dt may be NULL, not all three; d_dt needs d_work,
+ * sextans_spmm_softagg_workspace_floats(h, N) = M * N + ceil(M / 256) * N floats that the call writes (only when d_dt is given).  The
+ * backward writes every element of dB (K x N), dval (nnz) and dt (N) it is given.
+ * First calls build the row softmax's tables / A^T as for sextans_spmm_reduce_device_rm and synchronise then; after that a call allocates
+ * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_softagg" / "spmm_softagg_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, N < 8 or not a multiple of 8, a leading dimension below N or not a multiple of 4, a misaligned pointer,
+ * (backward) d_dB, d_dval and d_dt all NULL, d_dt without d_work -- checked in this order, then the handle's state (SEXTANS_ERR_STATE: no CSR
+ * matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a required pointer (B, C, and in the backward lse and G) that is NULL
+ * with nnz > 0; all before any device is touched.  sextans_spmm_softagg_workspace_floats returns the error code negated.  M == 0 or
+ * nnz == 0: OK -- C, dB, dt and the workspace are zeroed, lse = -inf. */
+int sextans_spmm_softagg_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb, const float *d_t,
+                                   float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream);
+int64_t sextans_spmm_softagg_workspace_floats(sextans_handle_t h, int N);
+int sextans_spmm_softagg_backward_device_rm(sextans_handle_t h, int N, const float *d_val, const float *d_B, int64_t ldb, const float *d_t,
+                                            const float *d_C, int64_t ldc, const float *d_lse, int64_t ldlse, const float *d_G, int64_t ldg,
+                                            float *d_dB, int64_t lddb, float *d_dval, float *d_dt, float *d_work, void *stream);
+
 /* ---- SpMM with a feature VECTOR per stored entry (edge-feature message passing: continuous-filter convolution / u_mul_e_sum, GINE /
  * relu(u_add_e) summed, edge -> node reduction / copy_e_sum).  Closest thing in the reference: none -- its PEs weight an entry with a
  * scalar.

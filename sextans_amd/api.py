@@ -105,6 +105,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
     "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm",
     "sextans_spmm_multi_device_rm", "sextans_spmm_multi_backward_device_rm",
+    "sextans_spmm_softagg_device_rm", "sextans_spmm_softagg_workspace_floats", "sextans_spmm_softagg_backward_device_rm",
     "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -341,6 +342,13 @@ def lib():
     L.sextans_spmm_multi_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiOut), C.c_void_p]
     L.sextans_spmm_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiGrad),
                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.sextans_spmm_softagg_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                 C.c_void_p, C.c_int64, C.c_void_p]
+    L.sextans_spmm_softagg_workspace_floats.argtypes = [C.c_void_p, C.c_int]
+    L.sextans_spmm_softagg_workspace_floats.restype = C.c_int64
+    L.sextans_spmm_softagg_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_spmm_edge_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                               C.c_int64, C.c_void_p]
     L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -980,6 +988,29 @@ class Engine:
         d_B may be None when neither g.d_gsumsq nor d_dval is given."""
         _check(lib().sextans_spmm_multi_backward_device_rm(self._h, N, d_val, d_B, ldb, C.byref(g) if g is not None else None, d_dB, lddb,
                                                            d_dval, stream), "spmm_multi_backward_device_rm")
+
+    def spmm_softagg_device_rm(self, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, stream=None):
+        """Softmax aggregation (sextans_spmm_softagg_device_rm): C[r, n] = sum over row r's stored entries e = (r, c) of
+        softmax_e(t[n] * p_e[n]) * p_e[n], p_e[n] = d_val[e] * B[c, n] -- a softmax per column over the row's messages; lse[r, n] its
+        log-sum-exp (d_lse None: not written).  d_t: N floats, None = 1; d_val None = the engine's current values.  An empty row gives +0
+        and -inf.  B, C and lse row-major, N % 8 == 0."""
+        _check(lib().sextans_spmm_softagg_device_rm(self._h, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, stream), "spmm_softagg_device_rm")
+
+    def spmm_softagg_workspace_floats(self, N):
+        """Floats of workspace spmm_softagg_backward_device_rm needs for dt on this matrix (sextans_spmm_softagg_workspace_floats):
+        M * N for the rows' sums plus ceil(M / 256) * N for the chunk sums."""
+        n = lib().sextans_spmm_softagg_workspace_floats(self._h, N)
+        if n < 0:
+            _check(int(-n), "spmm_softagg_workspace_floats")
+        return int(n)
+
+    def spmm_softagg_backward_device_rm(self, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dval, d_dt, d_work,
+                                        stream=None):
+        """dB (K x N), dval (nnz floats) and dt (N floats, summed over the rows in a fixed two-level order) of spmm_softagg_device_rm from
+        its C and lse and the upstream gradient G (sextans_spmm_softagg_backward_device_rm).  Any of d_dB, d_dval, d_dt may be None (not
+        all three); d_dt needs d_work, spmm_softagg_workspace_floats(N) floats the call writes."""
+        _check(lib().sextans_spmm_softagg_backward_device_rm(self._h, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb,
+                                                             d_dval, d_dt, d_work, stream), "spmm_softagg_backward_device_rm")
 
     def spmm_edge_device_rm(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
         """SpMM with a feature vector per stored entry (sextans_spmm_edge_device_rm): C[r, n] = sum over row r's entries e = (r, c) of

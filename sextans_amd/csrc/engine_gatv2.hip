@@ -32,6 +32,14 @@ void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool h
 int64_t chunks_of(int64_t M) { return (M + sx::kGatv2Chunk - 1) / sx::kGatv2Chunk; }
 
 }  // namespace
+
+// (engine_state.h) the datt sum; engine_softagg.hip's dt goes through it too
+void column_sum_two_level(const float *rows, int64_t M, int hd, float *part, float *out, hipStream_t s) {
+    const int64_t nchunks = chunks_of(M);
+    hipLaunchKernelGGL(sx::gatv2_datt_chunks, dim3((unsigned)nchunks), dim3(256), 0, s, rows, (long long)M, hd, part);
+    hipLaunchKernelGGL(sx::gatv2_datt_total, dim3((unsigned)((hd + 255) / 256)), dim3(256), 0, s, part, (long long)nchunks, hd, out);
+}
+
 }  // namespace sxe
 
 using namespace sxe;
@@ -119,8 +127,7 @@ int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, c
         launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
     });
     name_pass(h, "gatv2_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
-    hipLaunchKernelGGL(sx::gatv2_datt_chunks, dim3((unsigned)nchunks), dim3(256), 0, s, d_work, (long long)h->M, (int)hd, d_part);
-    hipLaunchKernelGGL(sx::gatv2_datt_total, dim3((unsigned)((hd + 255) / 256)), dim3(256), 0, s, d_part, (long long)nchunks, (int)hd, d_datt);
+    column_sum_two_level(d_work, h->M, (int)hd, d_part, d_datt, s);
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }

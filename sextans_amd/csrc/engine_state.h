@@ -436,6 +436,9 @@ int ensure_transpose(sextans_engine *h, hipStream_t s);    // engine_transpose.h
 void free_softmax(sextans_engine *h);                      // engine_softmax.hip: the row-softmax tables and workspace
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
 void attention_fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s);   // engine_attention.hip: rows x cols floats <- value (degenerate calls)
+// engine_gatv2.hip: out[j] = the sum over the M rows of rows[r, j] (hd floats a row) in the two-level fixed order of GATv2's datt -- 256-row
+// chunks into part (ceil(M / 256) x hd floats), then the chunks ascending.  One copy of that kernel pair in the library (softagg's dt uses it)
+void column_sum_two_level(const float *rows, int64_t M, int hd, float *part, float *out, hipStream_t s);
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s);   // engine_transpose.hip: sextans_prepare(..., SEXTANS_LAYOUT_ROWMAJOR_T, ...)
 int transposed_options(sextans_engine *h, const char *key, int64_t value);   // engine.hip: one option (nullptr: all) onto the companion
 int allow_big_lds(sextans_engine *h, const void *kern, int bytes);

@@ -40,6 +40,8 @@ in PyG, copy_u_max in DGL), again on the cached engine of the pattern:
     C = spmm_multi(A, B, aggr=("mean", "max", "min", "std"))   several aggregations of the same messages side by side, (M, len(aggr) N)
                                                    (PNAConv, MultiAggregation): one kernel pass gathers B's rows once for the sum, the sum
                                                    of squares, the max and the min; one backward call.  Also "sum", "var", "sumsq"
+    C = spmm_softagg(A, B, t=1.0)                  softmax aggregation (SoftmaxAggregation(t, learn=True), GENConv): a softmax per column over
+                                                   the row's messages, weighted sum of the same messages; differentiable in A, B and t
 
 Edge-feature message passing -- a feature VECTOR per stored entry instead of a scalar weight (SchNet's CFConv / diagonal NNConv, GINEConv,
 the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_sum in DGL), on the cached engine of the pattern:
@@ -1194,6 +1196,115 @@ def spmm_reduce(A, B, reduce="amax", return_arg=False, fast=False):
         if C.shape[1] != N:
             C, arg = C[:, :N], (arg[:, :N] if arg is not None else None)
     return (C, arg) if return_arg else C
+
+
+def _softagg_forward(A, B, t, fast, want_lse):
+    """(C, lse, tp) of the engine's softmax aggregation: C and lse (M, Np) with N padded up to a multiple of 8 (zero columns of B), lse
+    None unless asked for; tp the (Np,) fp32 temperatures handed to the kernel (padded columns: 1), None for t = 1 everywhere."""
+    M, K = A.shape
+    N = B.shape[1]
+    Np = api.round_up_n(N)
+    crow, col = _index_tensors(A)
+    val = A.values()
+    ent = _entry_for_parts(crow, col, val, (M, K), A.device.index or 0, fast, values_needed=False)
+    Brm = _rowmajor(B.detach(), K, N, Np)
+    v = _vals32(val)
+    tp = None
+    if t is not None:
+        tp = torch.ones((Np,), dtype=torch.float32, device=A.device)
+        tp[:N] = t.detach()
+    C = torch.empty((M, Np), dtype=torch.float32, device=A.device)
+    lse = torch.empty((M, Np), dtype=torch.float32, device=A.device) if want_lse else None
+    ent.eng.spmm_softagg_device_rm(Np, v.data_ptr() if v.numel() else None, Brm.data_ptr() if Brm.numel() else None, Brm.stride(0),
+                                   tp.data_ptr() if tp is not None else None, C.data_ptr() if C.numel() else None, Np,
+                                   lse.data_ptr() if lse is not None and lse.numel() else None, Np,
+                                   torch.cuda.current_stream(A.device).cuda_stream)
+    return C, lse, tp
+
+
+class _SpmmSoftaggFunction(torch.autograd.Function):
+    """spmm_softagg(): ONE forward call (sextans_spmm_softagg_device_rm) that keeps C and the log-sum-exp of every (row, column), ONE
+    backward call (sextans_spmm_softagg_backward_device_rm) for the gradients that are wanted: a column pass over A^T for dB, a row pass
+    for dA and the rows' share of dt, the fixed-order sum over the rows for dt.  t is the (N,) tensor or None (= 1, no gradient); the
+    workspace exists only when t wants a gradient.  A's values enter as an explicit pointer: no value refresh.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, B, t, fast):
+        N = B.shape[1]
+        C, lse, tp = _softagg_forward(A, B, t, fast, True)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B, C, lse, *((tp,) if tp is not None else ()))
+        ctx.shape, ctx.fast, ctx.dev = tuple(A.shape), fast, A.device.index or 0
+        ctx.t_dtype = t.dtype if t is not None else None
+        out_lse = lse if lse.shape[1] == N else lse[:, :N]
+        ctx.mark_non_differentiable(out_lse)
+        return (C if C.shape[1] == N else C[:, :N]), out_lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _):
+        crow, col, val, B, C, lse = ctx.saved_tensors[:6]
+        tp = ctx.saved_tensors[6] if len(ctx.saved_tensors) > 6 else None
+        M, K = ctx.shape
+        N = B.shape[1]
+        Np = C.shape[1]
+        want_a, want_b, want_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1], tp is not None and ctx.needs_input_grad[2]
+        if not (want_a or want_b or want_t):
+            return None, None, None, None
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        Grm = _rowmajor(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
+        Brm = _rowmajor(B.detach(), K, N, Np)
+        v = _vals32(val)
+        dB = torch.empty((K, Np), dtype=torch.float32, device=G.device) if want_b else None
+        dv = torch.empty((val.numel(),), dtype=torch.float32, device=G.device) if want_a else None
+        dt = torch.empty((Np,), dtype=torch.float32, device=G.device) if want_t else None
+        work = torch.empty((max(ent.eng.spmm_softagg_workspace_floats(Np), 1),), dtype=torch.float32, device=G.device) if want_t else None
+        ptr = lambda x: x.data_ptr() if x is not None and x.numel() else None
+        if ptr(dB) is not None or ptr(dv) is not None or dt is not None:   # (else: no element to write)
+            ent.eng.spmm_softagg_backward_device_rm(Np, ptr(v), ptr(Brm), Brm.stride(0), ptr(tp), ptr(C), Np, ptr(lse), Np, ptr(Grm),
+                                                    Grm.stride(0), ptr(dB), Np, ptr(dv), ptr(dt), ptr(work),
+                                                    torch.cuda.current_stream(G.device).cuda_stream)
+        gA = torch.sparse_csr_tensor(crow, col, dv.to(val.dtype), size=(M, K)) if want_a else None
+        gB = (dB if Np == N else dB[:, :N]).to(B.dtype) if want_b else None
+        gt = (dt if Np == N else dt[:N]).to(ctx.t_dtype) if want_t else None
+        return gA, gB, gt, None
+
+
+def spmm_softagg(A, B, t=1.0, return_lse=False, fast=False):
+    """Softmax aggregation (SoftmaxAggregation(t, learn=True) in PyG, the aggregator of GENConv / DeeperGCN): A is an (M, K) sparse_csr
+    matrix, B a dense (K, N) tensor, the result a dense fp32 (M, N) tensor
+        C[r, n] = sum over row r's stored entries e = (r, c) of softmax_e(t[n] * p_e[n]) * p_e[n],    p_e[n] = A_e * B[c, n]
+    -- a softmax per output column over the row's messages themselves (one rounded fp32 product each).  t is the temperature: a Python
+    float, a 0-d tensor or an (N,) tensor, any finite values; 0 gives the mean, large values the max, negative ones a soft minimum.  A row
+    without entries gives 0.  One kernel pass per direction (sextans_spmm_softagg_device_rm / _backward_device_rm): online softmax, nothing
+    of size nnz x N materialised, no atomics -- the same bits on every run.  Differentiable in B, in A (dA: a sparse_csr tensor on A's
+    index tensors, in A's value dtype) and in t when it is a tensor that requires grad (a 0-d t gets the sum over the columns); the
+    gradients lose digits where |t (p - C)| is large.  return_lse=True: also the (M, N) log-sum-exp of the scores t p (-inf in an empty
+    row; not differentiable).  A's values are handed to the kernel as a pointer: no value refresh of the cached engine.  An N that is not
+    a multiple of 8, and a B the kernel cannot read where it lies, are copied with zero padding, as spmm_reduce() does; `fast` only selects
+    the cached engine."""
+    _check_sparse(A, "spmm_softagg")
+    if not (isinstance(B, torch.Tensor) and B.is_cuda):
+        raise TypeError("spmm_softagg expects a CUDA/HIP dense B")
+    if B.dim() != 2 or B.shape[0] != A.shape[1] or B.shape[1] == 0:
+        raise ValueError("shape mismatch")
+    N = B.shape[1]
+    if isinstance(t, torch.Tensor):
+        if t.dim() > 1 or (t.dim() == 1 and t.shape[0] != N):
+            raise ValueError("t must be a float, a 0-d tensor or an (N,) tensor")
+        if not t.is_floating_point():
+            raise TypeError("t must be a floating-point tensor")
+        tv = t.to(B.device).expand(N)   # (autograd sums a scalar's gradient back)
+    elif float(t) == 1.0:
+        tv = None                       # the kernels' t == NULL path
+    else:
+        tv = torch.full((N,), float(t), dtype=torch.float32, device=B.device)
+    if torch.is_grad_enabled() and (A.requires_grad or B.requires_grad or (tv is not None and tv.requires_grad)):
+        C, lse = _SpmmSoftaggFunction.apply(A, B, tv, bool(fast))
+    else:
+        C, lse, _ = _softagg_forward(A, B, tv, bool(fast), bool(return_lse))
+        if C.shape[1] != N:
+            C, lse = C[:, :N], (lse[:, :N] if lse is not None else None)
+    return (C, lse) if return_lse else C
 
 
 _MULTI_RAW = ("sum", "sumsq", "max", "min")                       # what the kernel computes, in the order of sextans_multi_out
