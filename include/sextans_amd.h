@@ -958,6 +958,48 @@ int sextans_attention_edge_backward_device(sextans_handle_t h, int heads, int d,
     float *d_delta, float *d_dQ, int64_t lddq, float *d_dK, int64_t lddk, float *d_dV, int64_t lddv,
     float *d_dEk, int64_t lddek, float *d_dEv, int64_t lddev, float *d_dbias, const sextans_dropout *drop, void *stream);
 
+/* ---- Attention from caller-supplied per-head scores ("score attention"): the softmax of, or the plain weighting by, an (nnz, heads)
+ * tensor S, times V, per head -- DGL's edge_softmax + u_mul_e_sum, PyG's softmax(alpha, index) + propagate; the piece HGT's typed
+ * projections, AGNN's cosine score, SuperGAT, distance / RBF scores, a Graphormer-style per-head bias, an MLP on edge features or
+ * coefficients kept from another layer are written with.  Closest thing in the reference: none.
+ *
+ * S and dS are (nnz, heads) row-major in the entry order of the CSR arrays the matrix was set with: element (e, h) is S[e * lds + h]
+ * (64-bit offsets), read and written one float at a time, so lds, ldds >= heads is the only condition on them (as ldadst).  V, O, G, dV
+ * as in sextans_gat_attention_device; lse is M x heads, dense.  A's own values are neither read nor written.  For the stored entry
+ * e = (r, c), head h and m_e the dropout multiplier (1 without dropout):
+ *   SEXTANS_SCORE_SOFTMAX   s_e = S[e,h];  O[r,h,:] = sum_e softmax_e(s) m_e V[c,h,:];  lse[r,h] = m + log Z
+ *       the arithmetic of sextans_gat_attention_device from s onward (online softmax, exp2-based exp, FMA accumulation, dropped entries
+ *       count in Z): fed the scores GAT computes, O, lse and dV are GAT's bits.
+ *       backward   delta = <O[r,h,:], G[r,h,:]> (in registers: no workspace);  p_e = exp(s_e - lse[r,h])
+ *                  dS[e,h] = p_e * (m_e <G[r,h,:], V[c,h,:]> - delta);  dV[c,h,:] = sum_e (m_e p_e) G[r,h,:]
+ *   SEXTANS_SCORE_WEIGHT    O[r,h,:] = sum_e S[e,h] V[c,h,:], FMA in the slot's entry order.  d_lse is neither read nor written, forward
+ *       and backward, and d_O not in the backward: they may be NULL there (and the backward does not look at ldo).
+ *       backward   dS[e,h] = <G[r,h,:], V[c,h,:]>;  dV[c,h,:] = sum_e S[e,h] G[r,h,:]
+ *       drop must be NULL or have p == 0: the caller holds the weights and can drop them.
+ * The forward and the row pass run over A: one 4-byte load and one gathered V row per (entry, head); the row pass stores dS[e,h] from
+ * one lane of the one group of lanes that owns the entry -- one plain store per element.  The column pass runs over A^T, reads
+ * S[perm e, h] and lse[r,h], gathers G[r,h,:] and writes dV.  d_dS or d_dV may be NULL (not both): that pass is skipped, the other's
+ * bits are unchanged.  Everything written is written in full: rows / columns without entries get +0, their lse -inf.  No atomics, the
+ * same bits on every run and stream, nothing allocated beyond the softmax tables and A^T (after
+ * sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) the calls can be captured).
+ * Special values (SOFTMAX): a -inf score is a mask and contributes exactly 0 everywhere; a row of only -inf scores, or with a +inf or
+ * NaN score, gives NaN in that (row, head).  dv: a multiple of 8 in [8, 128]; ldv, ldo, ldg, lddv >= heads * dv, multiples of 4; every
+ * pointer 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * sextans_last_kernel: "score_softmax_fused" / "score_weight_fused", "..._backward", then "+dropout", then "+long_rows".
+ * SEXTANS_ERR_INVALID, in this order: a NULL handle, a mode that is neither, heads < 1, a bad dv; a bad dropout (p outside [0, 1)) and
+ * p > 0 in SEXTANS_SCORE_WEIGHT; the leading dimensions; alignment -- then SEXTANS_ERR_STATE for a handle without a CSR matrix, then
+ * SEXTANS_ERR_INVALID for d_dS and d_dV both NULL and for a required pointer that is NULL with nnz > 0; all before any device is
+ * touched.  M == 0 or nnz == 0: OK -- O and dV are zeroed, lse is -inf, dS has no element. */
+#define SEXTANS_SCORE_SOFTMAX 1
+#define SEXTANS_SCORE_WEIGHT 2
+int sextans_score_attention_device(sextans_handle_t h, int mode, int heads, int dv,
+    const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
+    float *d_O, int64_t ldo, float *d_lse, const sextans_dropout *drop, void *stream);
+int sextans_score_attention_backward_device(sextans_handle_t h, int mode, int heads, int dv,
+    const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
+    const float *d_O, int64_t ldo, const float *d_lse, const float *d_G, int64_t ldg,
+    float *d_dS, int64_t ldds, float *d_dV, int64_t lddv, const sextans_dropout *drop, void *stream);
+
 /* ---- bf16 DENSE operands on the row-major CSR entry (autocast activations, bf16 feature matrices).
  *
  * C = alpha * A * B + beta * C_in with B in bf16 (16-bit patterns, B[k * ldb + n]) and C_in / C_out BOTH of c_dtype: fp32 (float *) or

@@ -111,11 +111,13 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
     "sextans_dropout_mask_device", "sextans_dropout_keep_host",
-    "sextans_attention_edge_device", "sextans_attention_edge_backward_device"))
+    "sextans_attention_edge_device", "sextans_attention_edge_backward_device",
+    "sextans_score_attention_device", "sextans_score_attention_backward_device"))
 
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
 EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
+SCORE_SOFTMAX, SCORE_WEIGHT = 1, 2  # SEXTANS_SCORE_*: the mode of score_attention_device
 
 
 class _Optional:
@@ -358,6 +360,9 @@ def lib():
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                          vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, dp, vp]
+    L.sextans_score_attention_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, dp, vp]
+    L.sextans_score_attention_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64,
+                                                          dp, vp]
     L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
     L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -1044,6 +1049,21 @@ class Engine:
                                                             d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv,
                                                             d_dEk, lddek, d_dEv, lddev, d_dbias, _drop_ref(drop), stream),
                "attention_edge_backward_device")
+
+    def score_attention_device(self, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, drop=None, stream=None):
+        """Attention from caller-supplied scores (sextans_score_attention_device).  S is (nnz, heads), element (e, h) at S[e * lds + h], in the
+        CSR entry order.  SCORE_SOFTMAX: O[r, h, :] = sum_e softmax_e(S[:, h] over row r) V[c, h, :] and lse (M x heads);
+        SCORE_WEIGHT: O[r, h, :] = sum_e S[e, h] V[c, h, :] (d_lse is not touched and may be None).  drop: a Dropout or None (SOFTMAX only)."""
+        _check(lib().sextans_score_attention_device(self._h, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, _drop_ref(drop), stream),
+               "score_attention_device")
+
+    def score_attention_backward_device(self, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, d_G, ldg, d_dS, ldds, d_dV, lddv,
+                                        drop=None, stream=None):
+        """dS (nnz x heads, element (e, h) at dS[e * ldds + h]: one plain store each) and dV of score_attention_device from the upstream
+        gradient G -- SCORE_SOFTMAX: and its O and lse; SCORE_WEIGHT: d_O and d_lse are not read and may be None
+        (sextans_score_attention_backward_device).  d_dS or d_dV may be None (not both): that pass is skipped.  drop: the forward's."""
+        _check(lib().sextans_score_attention_backward_device(self._h, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, d_G, ldg, d_dS, ldds,
+                                                             d_dV, lddv, _drop_ref(drop), stream), "score_attention_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):

@@ -22,6 +22,11 @@ Attention over a fixed sparsity pattern (graph attention, sparse / sliding-windo
                                                    softmax(leaky_relu(a_dst[r] + a_src[c] [+ A_e])) V per head, fused the same way
     O = gatv2_attention(A, x_dst, x_src, att, negative_slope=0.2, bias=False)   GATv2 (GATv2Conv): the activation inside the projection
                                                    softmax(<att, leaky_relu(x_dst[r] + x_src[c])> [+ A_e]) x_src per head, fused the same way
+    O = score_attention(A, S, V, normalize="softmax", dropout=0.0, seed=None, step=None, return_weights=False)
+                                                   any OTHER score: S is (nnz, H), computed by the caller in A's entry order; softmax over
+                                                   each row per head, times V (edge_softmax + u_mul_e_sum) -- or normalize="none": S holds
+                                                   the weights themselves.  One kernel pass per direction, differentiable in S and V
+    rows = entry_rows(A)                           the (nnz,) row of every stored entry: S = f(x[rows], x[A.col_indices()])
 
 Dropout on the normalised attention coefficients (GATConv / GATv2Conv's dropout, attn_drop), made INSIDE the fused kernels from a hash
 of (seed, step, entry, head) -- the coefficients are never materialised, so it cannot be applied from outside:
@@ -977,6 +982,116 @@ def _gat_attention(A, a_dst, a_src, V, negative_slope, bias, fast, p, seed, step
     else:
         out = _GatAttentionFunction.apply(A, ad2, as2, V3, slope, bool(bias), bool(fast), 0.0, 0, None)
     return out if V.dim() == 3 else out[:, 0]
+
+
+def entry_rows(A):
+    """The row of every stored entry of A, in A's entry order: an (nnz,) int64 tensor on A's device -- with A.col_indices() what a score
+    f(x[row], x[col]) for score_attention() is computed from.  No host synchronisation."""
+    _check_sparse(A, "entry_rows")
+    crow, col = _index_tensors(A)
+    return torch.repeat_interleave((crow[1:] - crow[:-1]).long(), output_size=col.numel())   # (int32 indices would give int32 rows)
+
+
+_SCORE_MODES = {"softmax": api.SCORE_SOFTMAX, "none": api.SCORE_WEIGHT}
+
+
+class _ScoreAttentionFunction(torch.autograd.Function):
+    """score_attention(): one kernel pass forward (sextans_score_attention_device), a row pass and a column pass backward
+    (sextans_score_attention_backward_device), all heads at once.  S and dS are the only tensors of size nnz; A's values are not read:
+    no value refresh anywhere.  Returns (O, lse); lse (softmax mode; else empty) is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, S, V, mode, fast, p=0.0, seed=0, step=None):
+        M, Kk = A.shape
+        H, dv = V.shape[1], V.shape[2]
+        dvp = -(-dv // 8) * 8
+        dev = A.device.index or 0
+        soft = mode == api.SCORE_SOFTMAX
+        crow, col = _index_tensors(A)
+        val = A.values()
+        ent = _entry_for_parts(crow, col, val, (M, Kk), dev, fast, values_needed=False)
+        Sr, lds = _scalars_operand(S.detach())
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        O = torch.empty((M, H, dvp), dtype=torch.float32, device=A.device)
+        lse = torch.empty((M, H) if soft else (0,), dtype=torch.float32, device=A.device)
+        ent.eng.score_attention_device(mode, H, dvp, Sr.data_ptr(), lds, Vr.data_ptr(), ldv, O.data_ptr(), H * dvp,
+                                       lse.data_ptr() if soft else None, _drop_struct(p, seed, step),
+                                       torch.cuda.current_stream(A.device).cuda_stream)
+        ctx.save_for_backward(crow, col, val, S, V, *((O, lse) if soft else ()))
+        ctx.shape, ctx.mode, ctx.fast, ctx.dev, ctx.dvp = (M, Kk), mode, fast, dev, dvp
+        ctx.drop = (p, seed, step)   # the backward recomputes the forward's mask
+        ctx.mark_non_differentiable(lse)
+        return (O if dvp == dv else O[:, :, :dv]), lse
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _):
+        crow, col, val, S, V = ctx.saved_tensors[:5]
+        soft = ctx.mode == api.SCORE_SOFTMAX
+        O, lse = ctx.saved_tensors[5:] if soft else (None, None)
+        M, Kk = ctx.shape
+        H, dv = V.shape[1], V.shape[2]
+        dvp = ctx.dvp
+        ent = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False)
+        Sr, lds = _scalars_operand(S.detach())
+        Vr, ldv = _heads_operand(V.detach(), dvp)
+        Gr, ldg = _heads_operand(G, dvp)           # (a copy when G has zero strides, e.g. after .sum(), or dv % 8 != 0)
+        dS = torch.empty((S.shape[0], H), dtype=torch.float32, device=G.device) if ctx.needs_input_grad[1] else None
+        dV = torch.empty((Kk, H, dvp), dtype=torch.float32, device=G.device) if ctx.needs_input_grad[2] else None
+        ent.eng.score_attention_backward_device(ctx.mode, H, dvp, Sr.data_ptr(), lds, Vr.data_ptr(), ldv, O.data_ptr() if soft else None, H * dvp,
+                                                lse.data_ptr() if soft else None, Gr.data_ptr(), ldg,
+                                                dS.data_ptr() if dS is not None else None, H, dV.data_ptr() if dV is not None else None, H * dvp,
+                                                _drop_struct(*ctx.drop), torch.cuda.current_stream(G.device).cuda_stream)
+        gS = dS.to(S.dtype) if dS is not None else None
+        gV = (dV if dvp == dv else dV[:, :, :dv]).to(V.dtype) if dV is not None else None
+        return None, gS, gV, None, None, None, None, None
+
+
+def score_attention(A, S, V, normalize="softmax", dropout=0.0, seed=None, step=None, return_weights=False, fast=False):
+    """Attention on A's pattern from scores the CALLER computed, per head (DGL's edge_softmax + u_mul_e_sum, PyG's softmax(alpha, index) +
+    propagate): what HGT, AGNN, SuperGAT, distance / RBF scores, a per-head spatial bias or an MLP on edge features are written with.
+        normalize="softmax"   O[r, h, :] = sum over row r's stored entries e = (r, c) of softmax_e(S[:, h] over the row) * V[c, h, :]
+        normalize="none"      O[r, h, :] = sum_e S[e, h] * V[c, h, :]   (S holds the weights themselves)
+    A (M x Kk) gives the pattern only: its values are not read.  S is (nnz,) or (nnz, H), in A's entry order (entry_rows(A) and
+    A.col_indices() give every entry's row and column); V is (Kk, dv) or (Kk, H, dv), the result has V's rank.  One forward call and one
+    backward call on the pattern's cached engine for all heads (sextans_score_attention_device / _backward_device), no value refresh,
+    nothing of size nnz besides S and its gradient.  Differentiable in S and V; gradients come in the operands' dtypes.  A -inf score
+    masks its entry (softmax).  dropout (softmax only), seed and step as in gat_attention_dropout(): made inside the kernels on the
+    normalised coefficients; dropout=0 is the plain call, bit for bit.  With normalize="none" the caller holds the weights and drops them.
+    return_weights=True (softmax only): also returns the detached (nnz, H) coefficients exp(S - lse[row]) before dropout -- ((nnz,) for
+    a 1-D S) -- an elementwise expression on the kernel's log-sum-exp, no kernel of its own.  dv up to 128; a dv that is not a multiple
+    of 8, and operands that do not lie as the kernels read them, are copied (V with zero padding)."""
+    _check_sparse(A, "score_attention")
+    if normalize not in _SCORE_MODES:
+        raise ValueError("normalize is 'softmax' or 'none'")
+    mode = _SCORE_MODES[normalize]
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (S, V)):
+        raise TypeError("score_attention expects CUDA/HIP dense S and V")
+    if V.dim() not in (2, 3) or S.dim() not in (1, 2):
+        raise ValueError("S is (nnz,) or (nnz, heads), V is (rows, dv) or (rows, heads, dv)")
+    V3 = V if V.dim() == 3 else V.unsqueeze(1)
+    S2 = S if S.dim() == 2 else S.unsqueeze(1)
+    M, Kk = A.shape
+    H, dv = V3.shape[1], V3.shape[2]
+    if S2.shape[1] != H:
+        raise ValueError("S and V differ in their number of heads")
+    if S2.shape[0] != A.values().numel() or V3.shape[0] != Kk or H == 0 or dv == 0:
+        raise ValueError("shape mismatch")
+    if dv > 128:
+        raise ValueError("score_attention: dv up to 128")
+    p = _check_dropout(dropout)
+    soft = mode == api.SCORE_SOFTMAX
+    if not soft and (p > 0.0 or return_weights):
+        raise ValueError("normalize='none': the caller holds the weights (no dropout, no return_weights)")
+    if p > 0.0:
+        out, lse = _ScoreAttentionFunction.apply(A, S2, V3, mode, bool(fast), p, _draw_seed(seed), _check_step(step, A.device))
+    else:
+        out, lse = _ScoreAttentionFunction.apply(A, S2, V3, mode, bool(fast), 0.0, 0, None)
+    out = out if V.dim() == 3 else out[:, 0]
+    if not return_weights:
+        return out
+    w = torch.exp(S2.detach().to(torch.float32) - lse[entry_rows(A)])
+    return out, (w if S.dim() == 2 else w[:, 0])
 
 
 class _Gatv2AttentionFunction(torch.autograd.Function):
