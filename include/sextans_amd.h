@@ -918,6 +918,48 @@ int sextans_spmm_edge_device_rm(sextans_handle_t h, int op, int N, const float *
 int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
                                          const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
 
+/* ---- Several aggregations of EDGE-FEATURE messages in one pass: the messages of sextans_spmm_edge_device_rm under the aggregates of
+ * sextans_spmm_multi_device_rm (PNAConv over an edge MLP's messages = COPY under mean / max / min / std; EdgeConv, DGCNN = copy_e_max;
+ * DGL's u_mul_e_max and u_add_e_max; MultiAggregation over any materialised message).  Closest thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used.  B, E, op and the message m[e, n] (ONE rounded fp32 operation, the relu of
+ * ADD_RELU keeping a NaN) are those of sextans_spmm_edge_device_rm above; the outputs, sextans_multi_out and sextans_multi_grad those of
+ * sextans_spmm_multi_device_rm (own pointer and leading dimension each, so that they may be column slices of one (M, k N) buffer):
+ *     d_sum      sum_e m                          (fp32 adds rounded to nearest)
+ *     d_sumsq    sum_e m^2                        (s = fma(m, m, s))
+ *     d_max / d_argmax, d_min / d_argmin           a NaN wins, then the better value, then the smaller entry position; the args are
+ *                                                  positions in the CSR arrays (= rows of E)
+ *     a row without stored entries: sums +0, max and min +0, args -1; a row of one entry: sum has the message's bits
+ * The sums run in an order fixed by the pattern and the launch shape (no atomics: the same bits on every run and stream) that does not
+ * depend on which outputs are requested.  A NULL output is not computed (the groups of sextans_spmm_multi_device_rm); at least one of
+ * the four values must be given, and an arg needs its value.
+ * Backward, for the upstream gradients that are given (NULL: absent) and the args of the forward:
+ *     t_e[n]   = Gsum[r, n] + 2 m[e, n] Gsq[r, n] + (argmax[r, n] == e ? Gmax[r, n] : 0) + (argmin[r, n] == e ? Gmin[r, n] : 0)
+ *                (evaluated left to right as for sextans_spmm_multi_backward_device_rm)
+ *     dB[c, n] = sum over the entries of column c of E[e, n] * t_e[n] (MUL, fused multiply-add) | t_e[n] (ADD) |
+ *                (B[c, n] + E[e, n] > 0 ? t_e[n] : 0) (ADD_RELU); COPY has no dB      (one GATHER pass over the rows of A^T)
+ *     dE[e, n] = t_e[n] * B[c, n] (MUL) | t_e[n] (ADD, COPY) | (B[c, n] + E[e, n] > 0 ? t_e[n] : +0) (ADD_RELU)
+ *                -- one rounded operation per element, stored once: BIT-DETERMINED (ADD / COPY with d_gsum alone: G's bits)
+ * Nothing of size nnz x N exists besides E and dE.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 64 floats.  Leading dimensions: ldb, lde,
+ * lddb and ldde always, a struct member's when its pointer is given (ld_arg: when either arg is): >= N and multiples of 4; every pointer
+ * 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * Needed with nnz > 0: d_E always; d_B unless op is SEXTANS_EDGE_COPY (then d_B may be NULL and d_dB must be).  The pointers are
+ * required by rule; a kernel reads an operand only where its formula does.  Backward: d_dB or d_dE may be NULL, not both; it writes every
+ * element of dB (K x N) and of dE (nnz x N) it is given.
+ * First calls build the row softmax's tables / A^T as for sextans_spmm_edge_device_rm and synchronise then; after that a call allocates
+ * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_edge_multi" / "spmm_edge_multi_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, out / g == NULL, op not one of the four, a bad N, a bad leading dimension, a misaligned pointer, no
+ * output (no gradient) given, an arg without its value, (backward) d_gmax without d_argmax or d_gmin without d_argmin, d_dB and d_dE
+ * both NULL, d_dB with COPY -- then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for
+ * nnz > INT32_MAX and for a required pointer that is NULL with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- the
+ * values and dB are zeroed, the args = -1, dE has no element. */
+int sextans_spmm_edge_multi_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
+                                      const sextans_multi_out *out, void *stream);
+int sextans_spmm_edge_multi_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
+                                               const sextans_multi_grad *g, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
+
 /* ---- Edge features inside the fused attention: a key row and a value row per stored entry (PyG's TransformerConv(edge_dim=...), UniMP,
  * the Dwivedi-Bresson graph transformer, relative-position encodings of mesh transformers).  Closest thing in the reference: none.
  *

@@ -107,6 +107,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_multi_device_rm", "sextans_spmm_multi_backward_device_rm",
     "sextans_spmm_softagg_device_rm", "sextans_spmm_softagg_workspace_floats", "sextans_spmm_softagg_backward_device_rm",
     "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
+    "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -355,6 +356,10 @@ def lib():
                                               C.c_int64, C.c_void_p]
     L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.sextans_spmm_edge_multi_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                    C.POINTER(MultiOut), C.c_void_p]
+    L.sextans_spmm_edge_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                             C.POINTER(MultiGrad), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     vp, i64 = C.c_void_p, C.c_int64
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
@@ -1029,6 +1034,21 @@ class Engine:
         d_B / d_E may be None where the op's gradient does not read them."""
         _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
                "spmm_edge_backward_device_rm")
+
+    def spmm_edge_multi_device_rm(self, op, N, d_B, ldb, d_E, lde, out, stream=None):
+        """Several aggregations of edge-feature messages in one pass (sextans_spmm_edge_multi_device_rm): the message of the stored entry
+        e = (r, c) is that of spmm_edge_device_rm (B[c, n] * E[e, n], B + E, relu(B + E) or E[e, n] by op: EDGE_*; d_B may be None with
+        EDGE_COPY); out is a MultiOut whose given addresses receive the sum, the sum of squares, the max and the min over every row's
+        entries and the int32 entry positions of the extrema; an empty row gives +0 and -1.  Only the pattern is used."""
+        _check(lib().sextans_spmm_edge_multi_device_rm(self._h, op, N, d_B, ldb, d_E, lde, C.byref(out) if out is not None else None, stream),
+               "spmm_edge_multi_device_rm")
+
+    def spmm_edge_multi_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, g, d_dB, lddb, d_dE, ldde, stream=None):
+        """dB (K x N) and dE (nnz x N) of spmm_edge_multi_device_rm from the upstream gradients and the args in g, a MultiGrad
+        (sextans_spmm_edge_multi_backward_device_rm): a column pass over A^T and a row pass over A, no atomics.  d_dB or d_dE may be None
+        (not both; d_dB must be None with EDGE_COPY); d_E is always needed, d_B unless EDGE_COPY."""
+        _check(lib().sextans_spmm_edge_multi_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, C.byref(g) if g is not None else None,
+                                                                d_dB, lddb, d_dE, ldde, stream), "spmm_edge_multi_backward_device_rm")
 
     def attention_edge_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias, d_O, ldo, d_lse,
                               drop=None, stream=None):

@@ -54,6 +54,11 @@ the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_su
     C = spmm_edge(A, B, E, op="mul", reduce="sum") C[r, n] = sum over row r's stored entries e = (r, c) of B[c, n] * E[e, n] ("add": B + E,
                                                    "add_relu": relu(B + E), "copy": E[e, n], B=None); E is (nnz, N) in A's entry order.  One
                                                    kernel pass per direction, E the only nnz x N tensor, no atomics; "mean": / row length
+    C = spmm_edge_multi(A, B, E, op="mul", aggr=("mean", "max", "min", "std"))   spmm_multi()'s aggregates of spmm_edge()'s messages,
+                                                   (M, len(aggr) N): PNAConv over an edge MLP's messages ("copy"), MultiAggregation; one
+                                                   kernel pass, one backward call, nothing of size nnz x N beyond E and dE
+    C = spmm_edge_reduce(A, B, E, op="mul", reduce="amax")   the max ("amin": min) of those messages alone (EdgeConv / DGCNN: copy_e_max,
+                                                   u_mul_e_max, u_add_e_max); return_arg=True also returns the winning entries
     A, perm = from_edge_index(edge_index, num_dst, num_src)   the sparse_csr A of a PyG edge list, and perm with E = edge_attr[perm]
 
 Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
@@ -1427,18 +1432,19 @@ _MULTI_NEEDS = {"sum": ("sum",), "mean": ("sum",), "max": ("max",), "min": ("min
                 "var": ("sum", "sumsq"), "std": ("sum", "sumsq")}   # aggregate -> the raw aggregates it is made of
 
 
-def _multi_raw(A, B, want, place, width, fast, want_arg):
+def _multi_raw(A, B, want, place, width, fast, want_arg, E=None, op=None):
     """One forward call of the engine's multi-aggregation.  want: the raw aggregates to compute; place: raw name -> the index of its
     N-column block in an (M, width) output that the kernel writes in place (N % 8 == 0 only; empty: no such output).
-    -> (out or None, {raw name not placed: (M, Np) tensor}, argmax, argmin), Np = N padded up to a multiple of 8."""
+    -> (out or None, {raw name not placed: (M, Np) tensor}, argmax, argmin), Np = N padded up to a multiple of 8.
+    E (nnz, N) and op (EDGE_*): the edge-feature messages of spmm_edge_multi() instead of A_e * B[c] (B is None for EDGE_COPY)."""
     M, K = A.shape
-    N = B.shape[1]
+    N = (B if E is None else E).shape[1]
     Np = api.round_up_n(N)
     crow, col = _index_tensors(A)
     val = A.values()
     ent = _entry_for_parts(crow, col, val, (M, K), A.device.index or 0, fast, values_needed=False)
-    Brm = _rowmajor(B.detach(), K, N, Np)
-    v = _vals32(val)
+    Brm = _rowmajor(B.detach(), K, N, Np) if B is not None else None
+    v = _vals32(val) if E is None else None
     out = torch.empty((M, width), dtype=torch.float32, device=A.device) if place else None
     tmp = {name: torch.empty((M, Np), dtype=torch.float32, device=A.device) for name in want if name not in place}
     args = [torch.empty((M, Np), dtype=torch.int32, device=A.device) if want_arg and name in want else None for name in ("max", "min")]
@@ -1453,9 +1459,44 @@ def _multi_raw(A, B, want, place, width, fast, want_arg):
             setattr(o, "ld_" + name, ld)
         o.d_argmax, o.d_argmin = (t.data_ptr() if t is not None else None for t in args)
         o.ld_arg = Np
-        ent.eng.spmm_multi_device_rm(Np, v.data_ptr() if v.numel() else None, Brm.data_ptr() if Brm.numel() else None, Brm.stride(0), o,
-                                     torch.cuda.current_stream(A.device).cuda_stream)
+        stream = torch.cuda.current_stream(A.device).cuda_stream
+        if E is None:
+            ent.eng.spmm_multi_device_rm(Np, v.data_ptr() if v.numel() else None, Brm.data_ptr() if Brm.numel() else None, Brm.stride(0), o, stream)
+        else:
+            Erm = _rowmajor(E.detach(), E.shape[0], N, Np)
+            ent.eng.spmm_edge_multi_device_rm(op, Np, Brm.data_ptr() if Brm is not None and Brm.numel() else None,
+                                              Brm.stride(0) if Brm is not None else Np, Erm.data_ptr() if Erm.numel() else None, Erm.stride(0), o,
+                                              stream)
     return out, tmp, args[0], args[1]
+
+
+def _multi_grads(ctx, g_out, g_raw, args, M, N, Np):
+    """The MultiGrad of a backward call from the upstream gradients that exist: g_out, the gradient of the (M, width) output whose blocks
+    ctx.place names, and g_raw, those of the raw aggregates that are tensors of their own; args: the saved args of the extrema in
+    ctx.want.  -> (g, the tensors the kernel reads -- to be kept alive over the call --, whether any gradient is given)."""
+    arg = dict(zip([name for name in ("max", "min") if name in ctx.want], args))
+    g = api.MultiGrad()
+    keep = []
+    if g_out is not None and ctx.place:
+        g_out = _rowmajor(g_out, M, g_out.shape[1], g_out.shape[1])   # (N % 8 == 0 here: the slices are aligned)
+        keep.append(g_out)
+    for name, gr in zip(_MULTI_RAW, g_raw[:4]):
+        if name in ctx.place:
+            if g_out is None:
+                continue
+            ptr, ld = g_out.data_ptr() + 4 * N * ctx.place[name], g_out.stride(0)
+        elif gr is not None:
+            gr = _rowmajor(gr, M, N, Np)        # (a copy when the gradient has zero strides, e.g. after .sum(), or N % 8 != 0)
+            keep.append(gr)
+            ptr, ld = gr.data_ptr(), gr.stride(0)
+        else:
+            continue
+        setattr(g, "d_g" + name, ptr)
+        setattr(g, "ld_g" + name, ld)
+        if name in arg:
+            setattr(g, "d_arg" + name, arg[name].data_ptr())
+            g.ld_arg = Np
+    return g, keep, any(getattr(g, "d_g" + name) for name in _MULTI_RAW)
 
 
 class _SpmmMultiFunction(torch.autograd.Function):
@@ -1488,29 +1529,7 @@ class _SpmmMultiFunction(torch.autograd.Function):
         none = (None,) * 6
         if not (want_a or want_b):
             return none
-        arg = dict(zip([name for name in ("max", "min") if name in ctx.want], args))
-        g = api.MultiGrad()
-        keep = []                                   # the gradient tensors the kernel reads, kept alive over the call
-        if g_out is not None and ctx.place:
-            g_out = _rowmajor(g_out, M, g_out.shape[1], g_out.shape[1])   # (N % 8 == 0 here: the slices are aligned)
-            keep.append(g_out)
-        for name, gr in zip(_MULTI_RAW, g_raw[:4]):
-            if name in ctx.place:
-                if g_out is None:
-                    continue
-                ptr, ld = g_out.data_ptr() + 4 * N * ctx.place[name], g_out.stride(0)
-            elif gr is not None:
-                gr = _rowmajor(gr, M, N, Np)        # (a copy when the gradient has zero strides, e.g. after .sum(), or N % 8 != 0)
-                keep.append(gr)
-                ptr, ld = gr.data_ptr(), gr.stride(0)
-            else:
-                continue
-            setattr(g, "d_g" + name, ptr)
-            setattr(g, "ld_g" + name, ld)
-            if name in arg:
-                setattr(g, "d_arg" + name, arg[name].data_ptr())
-                g.ld_arg = Np
-        given = any(getattr(g, "d_g" + name) for name in _MULTI_RAW)
+        g, keep, given = _multi_grads(ctx, g_out, g_raw, args, M, N, Np)   # (keep: alive over the call)
         Brm = _rowmajor(B.detach(), K, N, Np) if (want_a or g.d_gsumsq) else None
         v = _vals32(val)
         new = torch.empty if given else torch.zeros   # (no upstream gradient at all: zeros, no call)
@@ -1564,24 +1583,39 @@ def spmm_multi(A, B, aggr=("mean", "max", "min", "std"), eps=1e-5, fast=False):
     straight into their columns of the result; otherwise operands and results are copied with zero padding, as spmm_reduce() does.  A's
     values are handed over as a pointer: no value refresh of the cached engine.  `fast` only selects the cached engine.  Degree scalers
     are left to the caller."""
-    aggr = tuple(aggr)
-    if not aggr or any(name not in _MULTI_NEEDS for name in aggr) or len(set(aggr)) != len(aggr):
-        raise ValueError("aggr: a non-empty sequence of distinct names out of 'sum', 'mean', 'max', 'min', 'var', 'std', 'sumsq'")
+    aggr = _multi_names(aggr)
     _check_sparse(A, "spmm_multi")
     if not (isinstance(B, torch.Tensor) and B.is_cuda):
         raise TypeError("spmm_multi expects a CUDA/HIP dense B")
     if B.dim() != 2 or B.shape[0] != A.shape[1] or B.shape[1] == 0:
         raise ValueError("shape mismatch")
-    M, N = A.shape[0], B.shape[1]
-    width = len(aggr) * N
-    want = tuple(name for name in _MULTI_RAW if any(name in _MULTI_NEEDS[x] for x in aggr))
-    place = {name: aggr.index(name) for name in want if name in aggr} if N % 8 == 0 else {}
+    N = B.shape[1]
+    want, place, width = _multi_plan(aggr, N)
     if torch.is_grad_enabled() and (A.requires_grad or B.requires_grad):
         out, *raw = _SpmmMultiFunction.apply(A, B, want, place, width, bool(fast))[:5]
         raw = dict(zip(_MULTI_RAW, raw))
     else:
         out, raw, _, _ = _multi_raw(A, B, want, place, width, bool(fast), False)
         raw = {name: (t if t.shape[1] == N else t[:, :N]) for name, t in raw.items()}
+    return _multi_finish(A, aggr, out, raw, place, N, eps)
+
+
+def _multi_names(aggr):
+    aggr = tuple(aggr)
+    if not aggr or any(name not in _MULTI_NEEDS for name in aggr) or len(set(aggr)) != len(aggr):
+        raise ValueError("aggr: a non-empty sequence of distinct names out of 'sum', 'mean', 'max', 'min', 'var', 'std', 'sumsq'")
+    return aggr
+
+
+def _multi_plan(aggr, N):
+    """-> (the raw aggregates aggr needs, raw name -> its block in the result where the kernel writes it in place, the result's width)"""
+    want = tuple(name for name in _MULTI_RAW if any(name in _MULTI_NEEDS[x] for x in aggr))
+    place = {name: aggr.index(name) for name in want if name in aggr} if N % 8 == 0 else {}
+    return want, place, len(aggr) * N
+
+
+def _multi_finish(A, aggr, out, raw, place, N, eps):
+    """The result of spmm_multi() / spmm_edge_multi() from the kernel's raw aggregates: the derived ones on top, side by side in aggr's order."""
     for name, j in place.items():
         raw[name] = out[:, j * N:(j + 1) * N]
     got = dict(raw)   # every aggregate that is asked for or needed on the way, from the raw ones
@@ -1703,6 +1737,116 @@ def spmm_edge(A, B, E, op="mul", reduce="sum", fast=False):
         crow = _index_tensors(A)[0]
         out = out / (crow[1:] - crow[:-1]).clamp(min=1).to(out.dtype)[:, None]
     return out.reshape((M,) + tail)
+
+
+class _SpmmEdgeMultiFunction(torch.autograd.Function):
+    """spmm_edge_multi() / spmm_edge_reduce(): ONE forward call (sextans_spmm_edge_multi_device_rm) for the raw aggregates that are
+    needed and the args of the extrema, ONE backward call (sextans_spmm_edge_multi_backward_device_rm) that takes the upstream gradients
+    that exist -- a column pass over A^T for dB, a row pass over A that stores dE, each only when autograd asks for it.  A's values never
+    enter: no gradient for A, no value refresh.  Outputs as _SpmmMultiFunction's.  Not twice differentiable."""
+
+    @staticmethod
+    def forward(ctx, A, B, E, op, want, place, width, fast):
+        N = E.shape[1]
+        out, tmp, amax, amin = _multi_raw(A, B, want, place, width, fast, True, E, op)
+        ctx.save_for_backward(*_index_tensors(A), A.values(), B, E, *(t for t in (amax, amin) if t is not None))
+        ctx.shape, ctx.op, ctx.fast, ctx.dev, ctx.want, ctx.place = tuple(A.shape), op, fast, A.device.index or 0, want, place
+        ctx.set_materialize_grads(False)
+        cut = lambda t: t if t is None or t.shape[1] == N else t[:, :N]
+        amax, amin = cut(amax), cut(amin)
+        ctx.mark_non_differentiable(*(t for t in (amax, amin) if t is not None))
+        return (out,) + tuple(cut(tmp.get(name)) for name in _MULTI_RAW) + (amax, amin)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, *g_raw):
+        crow, col, val, B, E, *args = ctx.saved_tensors
+        M, K = ctx.shape
+        nnz, N = E.shape
+        Np = api.round_up_n(N)
+        want_b, want_e = B is not None and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        none = (None,) * 8
+        if not (want_b or want_e):
+            return none
+        g, keep, given = _multi_grads(ctx, g_out, g_raw, args, M, N, Np)   # (keep: alive over the call)
+        new = torch.empty if given else torch.zeros   # (no upstream gradient at all: zeros, no call)
+        dB = new((K, Np), dtype=torch.float32, device=E.device) if want_b else None
+        dE = new((nnz, Np), dtype=torch.float32, device=E.device) if want_e else None
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        if given and M and (ptr(dB) is not None or ptr(dE) is not None):   # (else: no element to write)
+            eng = _entry_for_parts(crow, col, val, ctx.shape, ctx.dev, ctx.fast, values_needed=False).eng
+            Brm = _rowmajor(B.detach(), K, N, Np) if B is not None else None
+            Erm = _rowmajor(E.detach(), nnz, N, Np)
+            eng.spmm_edge_multi_backward_device_rm(ctx.op, Np, ptr(Brm), Brm.stride(0) if Brm is not None else Np, ptr(Erm), Erm.stride(0), g,
+                                                   ptr(dB), Np, ptr(dE), Np, torch.cuda.current_stream(E.device).cuda_stream)
+        elif given:
+            for t in (dB, dE):
+                if t is not None:
+                    t.zero_()
+        gB = (dB if Np == N else dB[:, :N]).to(B.dtype) if want_b else None
+        gE = (dE if Np == N else dE[:, :N]).to(E.dtype) if want_e else None
+        return (None, gB, gE) + none[3:]
+
+
+def _check_edge_operands(A, B, E, op, name):
+    """The misuse spmm_edge() refuses, for the 2-D operands of spmm_edge_multi() / spmm_edge_reduce()."""
+    if op not in _EDGE_OPS:
+        raise ValueError("op must be 'mul', 'add', 'add_relu' or 'copy'")
+    _check_sparse(A, name)
+    if (B is None) != (op == "copy"):
+        raise ValueError(name + ": B=None goes with op='copy', and only with it")
+    if not (isinstance(E, torch.Tensor) and E.is_cuda and (B is None or (isinstance(B, torch.Tensor) and B.is_cuda))):
+        raise TypeError(name + " expects CUDA/HIP dense B and E")
+    if E.dim() != 2 or (B is not None and (B.dim() != 2 or B.shape[1] != E.shape[1])):
+        raise ValueError(name + ": B is (K, N), E (nnz, N)")
+    if E.shape[0] != A.values().numel() or (B is not None and B.shape[0] != A.shape[1]) or E.shape[1] == 0:
+        raise ValueError("shape mismatch")
+
+
+def _edge_multi(A, B, E, op, want, place, width, fast, want_arg):
+    """-> (out or None, {raw name: (M, N) tensor}, argmax, argmin) of the edge-feature multi-aggregation, through autograd when a
+    gradient can be asked for (the args are then always computed)."""
+    N = E.shape[1]
+    code = _EDGE_OPS[op]
+    if torch.is_grad_enabled() and ((B is not None and B.requires_grad) or E.requires_grad):
+        out, *rest = _SpmmEdgeMultiFunction.apply(A, B, E, code, want, place, width, bool(fast))
+        return out, {name: t for name, t in zip(_MULTI_RAW, rest[:4]) if t is not None}, rest[4], rest[5]
+    out, raw, amax, amin = _multi_raw(A, B, want, place, width, bool(fast), want_arg, E, code)
+    cut = lambda t: t if t is None or t.shape[1] == N else t[:, :N]
+    return out, {name: cut(t) for name, t in raw.items()}, cut(amax), cut(amin)
+
+
+def spmm_edge_multi(A, B, E, op="mul", aggr=("mean", "max", "min", "std"), eps=1e-5, fast=False):
+    """Several aggregations of EDGE-FEATURE messages at once: spmm_multi()'s aggregates of spmm_edge()'s messages (PNAConv, whose message
+    is an MLP of x_i, x_j and e_ij: op="copy"; MultiAggregation over any materialised message; u_mul_e / u_add_e under several
+    reducers).  A is an (M, K) sparse_csr matrix of which only the PATTERN is used, B (K, N) -- None with "copy" --, E (nnz, N) in A's
+    CSR entry order; the message of the stored entry e = (r, c) is m_e = B[c] * E[e] ("mul"), B[c] + E[e] ("add"), relu(B[c] + E[e])
+    ("add_relu") or E[e] ("copy"), one rounded fp32 operation.  The result is a dense fp32 (M, len(aggr) * N) tensor with the
+    aggregates side by side in aggr's order; the names, the derived "mean" / "var" / "std" (eps), the in-place placement for N % 8 == 0
+    and the zero padding otherwise are spmm_multi()'s.  ONE kernel pass (sextans_spmm_edge_multi_device_rm), one backward call
+    (sextans_spmm_edge_multi_backward_device_rm): nothing of size nnz x N exists besides E and its gradient, no atomics, the same bits on
+    every run.  Differentiable in B and E; ties send the extrema's gradient to the first entry.  A gets no gradient and the cached
+    engine no value refresh.  `fast` only selects the cached engine."""
+    aggr = _multi_names(aggr)
+    _check_edge_operands(A, B, E, op, "spmm_edge_multi")
+    N = E.shape[1]
+    want, place, width = _multi_plan(aggr, N)
+    out, raw, _, _ = _edge_multi(A, B, E, op, want, place, width, fast, False)
+    return _multi_finish(A, aggr, out, raw, place, N, eps)
+
+
+def spmm_edge_reduce(A, B, E, op="mul", reduce="amax", return_arg=False, fast=False):
+    """The max ("amin": the min) over a row's entries of spmm_edge()'s messages: C[r, n] = max over row r's stored entries e = (r, c)
+    of m_e[n] (EdgeConv / DGCNN: copy_e_max; DGL's u_mul_e_max, u_add_e_max).  Operands, ops and messages as spmm_edge_multi(), of which
+    this is the extrema group with one output: a dense fp32 (M, N) tensor; a row without entries gives 0, a NaN message wins, the first
+    of equal messages wins.  return_arg=True: also the int32 (M, N) tensor of the winning entries' positions in A's CSR arrays (= rows
+    of E; -1 in an empty row; not differentiable).  Differentiable in B and E: each position's gradient goes to the entry that won it."""
+    if reduce not in _REDUCE_OPS:
+        raise ValueError("reduce must be 'amax' or 'amin'")
+    _check_edge_operands(A, B, E, op, "spmm_edge_reduce")
+    name = "max" if reduce == "amax" else "min"
+    _, raw, amax, amin = _edge_multi(A, B, E, op, (name,), {}, E.shape[1], fast, bool(return_arg))
+    return (raw[name], amax if name == "max" else amin) if return_arg else raw[name]
 
 
 def from_edge_index(edge_index, num_dst, num_src, values=None):
