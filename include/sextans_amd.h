@@ -960,6 +960,56 @@ int sextans_spmm_edge_multi_device_rm(sextans_handle_t h, int op, int N, const f
 int sextans_spmm_edge_multi_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
                                                const sextans_multi_grad *g, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
 
+/* ---- Gated aggregation: a per-channel sigmoid gate on every stored entry, computed from both endpoints and, optionally, the entry's own
+ * features (PyG's ResGatedGraphConv; GatedGCN of Bresson & Laurent, the MPNN of GraphGPS and of the LRGB / "Benchmarking GNNs" suites).
+ * Closest thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * xdst is row-major M x N fp32, xsrc and V K x N, E (optional: d_e == NULL) nnz x N IN THE CSR ENTRY ORDER the matrix was set with, as E of
+ * sextans_spmm_edge_device_rm (64-bit offsets).  For the stored entry e = (r, c) and column n, all arithmetic fp32:
+ *     z_e[n]   = (xdst[r, n] + xsrc[c, n]) + E[e, n]       two rounded adds in this order; without E the first one alone
+ *     g_e[n]   = 1 / (1 + exp(-z_e[n]))                    the division rounded to nearest: exactly 1 for large z, exactly +0 for very
+ *                                                          negative z (z = +-200 included), never inf; a NaN stays a NaN
+ *     num[r,n] = sum_e fma(g_e[n], V[c, n], num)           den[r, n] = sum_e g_e[n]          (partial sums merged by rounded adds)
+ *     SEXTANS_GATE_SUM    C[r, n] = num[r, n]                              (ResGatedGraphConv)
+ *     SEXTANS_GATE_NORM   C[r, n] = num[r, n] / (den[r, n] + eps)          (GatedGCN; one rounded add, one rounded division)
+ *     a row without stored entries: C = +0 and den = +0 in either mode
+ * d_den (optional) receives den (M x N) in either mode; d_z (optional) receives z (nnz x N, in the entry order, one plain store per
+ * element): the layer's new edge features.  Without d_z nothing of size nnz x N is written, without d_e none is read.
+ * Backward, G the upstream gradient of C and Gz (optional) that of z; gn = G (SUM) or G / (den + eps) (NORM), C read as 0 in SUM:
+ *     dg_e[n]  = gn[r, n] (V[c, n] - C[r, n])              dz_e[n] = fma(dg_e[n], g_e[n] (1 - g_e[n]), Gz[e, n])
+ *     dxdst[r, n] = sum_e dz_e[n]      dE[e, n] = dz_e[n]  (one store per element)                       -- a row pass over A
+ *     dxsrc[c, n] = sum over the entries of column c of dz_e[n]      dV[c, n] = sum of fma(g_e[n], gn[r, n], dV)   -- a GATHER pass over A^T
+ * z and g are RECOMPUTED with the forward's expressions (the same bits), not stored.  In NORM mode a small elementwise kernel writes gn
+ * once into d_work, sextans_spmm_gated_workspace_floats(h, mode, N) floats (NORM: M * N; SUM: 0, d_work is not read and may be NULL);
+ * both passes read it.  The row pass runs only when d_dxdst or d_de is given, the column pass (and with it A^T) only when d_dxsrc or
+ * d_dv is; a gradient has the same bits whichever others are asked for.  d_de without d_e is allowed: the gradient of z.
+ * There are no atomics anywhere; every sum runs in an order fixed by the pattern and the launch shape: the same bits on every run and stream.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 64 floats.  Leading dimensions: ld_xdst,
+ * ld_xsrc, ld_v, ldc (forward) and ldg always, every other one when its pointer is given: >= N and multiples of 4; every pointer 16-byte
+ * aligned.  The outputs must not overlap the inputs or each other.
+ * eps: finite and > 0 in NORM mode; ignored in SUM mode.  d_C and d_den of the backward: required in NORM mode, ignored in SUM mode.
+ * The backward writes every element of the gradients it is given (dxdst M x N, dxsrc and dV K x N, dE nnz x N).
+ * First calls build the row softmax's tables / A^T as for sextans_spmm_edge_device_rm and synchronise then; after that a call allocates
+ * nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_gated" / "spmm_gated_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, in / out == NULL, mode not one of the two, a bad eps in NORM mode, a bad N, a bad leading dimension, a
+ * misaligned pointer, (backward) no gradient pointer given -- then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then
+ * SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a required pointer (xdst, xsrc, V, C; backward: G and, in NORM mode, C, den and d_work)
+ * that is NULL with nnz > 0; all before any device is touched.  sextans_spmm_gated_workspace_floats returns the error code negated.
+ * M == 0 or nnz == 0: OK -- C, den, dxdst, dxsrc and dV are zeroed; z and dE have no element. */
+#define SEXTANS_GATE_SUM 1
+#define SEXTANS_GATE_NORM 2
+typedef struct { const float *d_xdst, *d_xsrc, *d_v, *d_e; int64_t ld_xdst, ld_xsrc, ld_v, ld_e; } sextans_gated_in;     /* d_e may be NULL */
+typedef struct { float *d_dxdst, *d_dxsrc, *d_dv, *d_de; int64_t ld_dxdst, ld_dxsrc, ld_dv, ld_de; } sextans_gated_grad; /* any subset, not none */
+int sextans_spmm_gated_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in,
+                                 float *d_C, int64_t ldc, float *d_den, int64_t ldden, float *d_z, int64_t ldz, void *stream);
+int64_t sextans_spmm_gated_workspace_floats(sextans_handle_t h, int mode, int N);
+int sextans_spmm_gated_backward_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in,
+                                          const float *d_C, int64_t ldc, const float *d_den, int64_t ldden,
+                                          const float *d_G, int64_t ldg, const float *d_Gz, int64_t ldgz,
+                                          const sextans_gated_grad *out, float *d_work, void *stream);
+
 /* ---- Edge features inside the fused attention: a key row and a value row per stored entry (PyG's TransformerConv(edge_dim=...), UniMP,
  * the Dwivedi-Bresson graph transformer, relative-position encodings of mesh transformers).  Closest thing in the reference: none.
  *

@@ -81,6 +81,19 @@ class MultiGrad(C.Structure):
                 ("d_argmax", C.c_void_p), ("d_argmin", C.c_void_p), ("ld_arg", C.c_int64)]
 
 
+class GatedIn(C.Structure):
+    """sextans_gated_in: the operands of spmm_gated_device_rm as device addresses with their leading dimensions -- xdst (M x N), xsrc and
+    V (K x N), E (nnz x N in the CSR entry order; None: no edge features)."""
+    _fields_ = [("d_xdst", C.c_void_p), ("d_xsrc", C.c_void_p), ("d_v", C.c_void_p), ("d_e", C.c_void_p),
+                ("ld_xdst", C.c_int64), ("ld_xsrc", C.c_int64), ("ld_v", C.c_int64), ("ld_e", C.c_int64)]
+
+
+class GatedGrad(C.Structure):
+    """sextans_gated_grad: the gradients spmm_gated_backward_device_rm writes (None: not computed; not all four)."""
+    _fields_ = [("d_dxdst", C.c_void_p), ("d_dxsrc", C.c_void_p), ("d_dv", C.c_void_p), ("d_de", C.c_void_p),
+                ("ld_dxdst", C.c_int64), ("ld_dxsrc", C.c_int64), ("ld_dv", C.c_int64), ("ld_de", C.c_int64)]
+
+
 class SextansError(RuntimeError):
     def __init__(self, code, where=""):
         self.code = code
@@ -107,6 +120,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_multi_device_rm", "sextans_spmm_multi_backward_device_rm",
     "sextans_spmm_softagg_device_rm", "sextans_spmm_softagg_workspace_floats", "sextans_spmm_softagg_backward_device_rm",
     "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
+    "sextans_spmm_gated_device_rm", "sextans_spmm_gated_workspace_floats", "sextans_spmm_gated_backward_device_rm",
     "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -118,6 +132,7 @@ _OPTIONAL_SYMBOLS = frozenset((
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
 EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
+GATE_SUM, GATE_NORM = 1, 2  # SEXTANS_GATE_*: the mode of spmm_gated_device_rm
 SCORE_SOFTMAX, SCORE_WEIGHT = 1, 2  # SEXTANS_SCORE_*: the mode of score_attention_device
 
 
@@ -361,6 +376,11 @@ def lib():
     L.sextans_spmm_edge_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                                              C.POINTER(MultiGrad), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     vp, i64 = C.c_void_p, C.c_int64
+    L.sextans_spmm_gated_device_rm.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.POINTER(GatedIn), vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_spmm_gated_workspace_floats.argtypes = [vp, C.c_int, C.c_int]
+    L.sextans_spmm_gated_workspace_floats.restype = i64
+    L.sextans_spmm_gated_backward_device_rm.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.POINTER(GatedIn), vp, i64, vp, i64, vp, i64, vp, i64,
+                                                        C.POINTER(GatedGrad), vp, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1034,6 +1054,31 @@ class Engine:
         d_B / d_E may be None where the op's gradient does not read them."""
         _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
                "spmm_edge_backward_device_rm")
+
+    def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
+        """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and
+        g_e = sigmoid(z_e) per column; C[r] = sum_e g_e * V[c] (GATE_SUM) or that sum / (sum_e g_e + eps) (GATE_NORM).  gin: a GatedIn
+        (d_e None: no edge features).  d_den (M x N; the gates' sums) and d_z (nnz x N in the CSR entry order; the new edge features)
+        may be None.  Only the pattern is used; everything row-major, N % 8 == 0; an empty row gives +0."""
+        _check(lib().sextans_spmm_gated_device_rm(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den, ldden,
+                                                  d_z, ldz, stream), "spmm_gated_device_rm")
+
+    def spmm_gated_workspace_floats(self, mode, N):
+        """Floats of workspace spmm_gated_backward_device_rm needs on this matrix (sextans_spmm_gated_workspace_floats): M * N in
+        GATE_NORM mode (gn = G / (den + eps)), 0 in GATE_SUM mode."""
+        n = lib().sextans_spmm_gated_workspace_floats(self._h, mode, N)
+        if n < 0:
+            _check(int(-n), "spmm_gated_workspace_floats")
+        return int(n)
+
+    def spmm_gated_backward_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_G, ldg, d_Gz, ldgz, out, d_work, stream=None):
+        """The gradients of spmm_gated_device_rm named in out, a GatedGrad (sextans_spmm_gated_backward_device_rm): dxdst (M x N) and dE
+        (nnz x N) from a row pass over A, dxsrc and dV (K x N) from a column pass over A^T; the gates are recomputed, no atomics.  d_G is
+        the upstream gradient of C, d_Gz (None: absent) that of z.  d_C and d_den: the forward's, needed in GATE_NORM mode only, as is
+        d_work, spmm_gated_workspace_floats(mode, N) floats the call writes."""
+        _check(lib().sextans_spmm_gated_backward_device_rm(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den,
+                                                           ldden, d_G, ldg, d_Gz, ldgz, C.byref(out) if out is not None else None, d_work,
+                                                           stream), "spmm_gated_backward_device_rm")
 
     def spmm_edge_multi_device_rm(self, op, N, d_B, ldb, d_E, lde, out, stream=None):
         """Several aggregations of edge-feature messages in one pass (sextans_spmm_edge_multi_device_rm): the message of the stored entry

@@ -61,6 +61,9 @@ the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_su
                                                    u_mul_e_max, u_add_e_max); return_arg=True also returns the winning entries
     A, perm = from_edge_index(edge_index, num_dst, num_src)   the sparse_csr A of a PyG edge list, and perm with E = edge_attr[perm]
 
+The gated aggregation of ResGatedGraphConv / GatedGCN (a per-channel sigmoid gate per entry from both endpoints and the entry's features)
+lives in a module of its own, on the same cached engines: sextans_amd.gated.spmm_gated(A, x_dst, x_src, V, E=None, normalize=False, ...).
+
 Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
 
     O = sparse_attention_edge(A, Q, K, V, edge_key=None, edge_value=None, scale=None, bias=False, dropout=0.0, seed=None, step=None)
