@@ -960,6 +960,57 @@ int sextans_spmm_edge_multi_device_rm(sextans_handle_t h, int op, int N, const f
 int sextans_spmm_edge_multi_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
                                                const sextans_multi_grad *g, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, void *stream);
 
+/* ---- Softmax aggregation of EDGE-FEATURE messages: the messages of sextans_spmm_edge_device_rm under the per-column softmax of
+ * sextans_spmm_softagg_device_rm (GENConv / DeeperGCN on graphs with edge features, whose message is relu(x_j + e_ij) + eps: ADD_RELU;
+ * PyG's SoftmaxAggregation over any materialised message: COPY).  Closest thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * B, E, op and the message m_e[n] (ONE rounded fp32 operation, the relu of ADD_RELU keeping a NaN) are those of
+ * sextans_spmm_edge_device_rm above; d_t, C and lse those of sextans_spmm_softagg_device_rm.  All arithmetic fp32:
+ *     s_e[n]    = t[n] * m_e[n]                   (one rounded multiply, never fused; d_t == NULL: s_e = m_e)
+ *     lse[r, n] = log sum_e exp(s_e[n])           w_e[n] = exp(s_e[n] - lse[r, n])
+ *     C[r, n]   = sum_e w_e[n] m_e[n]             a row without stored entries: C = +0, lse = -inf
+ * computed online exactly as sextans_spmm_softagg_device_rm does (running maximum, normaliser and accumulator per (row, column); t m may be
+ * anything finite): with SEXTANS_EDGE_MUL and E[e, :] = val[e] the call returns that function's bits for N <= 64.  A row of ONE entry gives
+ * C the bits of its message (+0 for -0).  A non-finite message does what this arithmetic makes of it within its own (row, column) and goes
+ * nowhere else.  A shift common to a row's messages (GENConv's + eps) cancels in the weights: add it to C on the rows that have entries.
+ * Backward, G the upstream gradient of C, q_e[n] = (G[r, n] w_e[n]) fma(t[n], m_e[n] - C[r, n], 1)   (= dL/dm_e; all three passes
+ * recompute m_e and s_e with the same operations, so they see the same bits):
+ *     dE[e, n] = q_e[n] * B[c, n] (MUL) | q_e[n] (ADD, COPY) | (B[c, n] + E[e, n] > 0 ? q_e[n] : +0) (ADD_RELU)
+ *                (one row pass over A; every element stored once by the lanes that own its (entry, tile))
+ *     dt[n]    = sum_r G[r, n] sum_e w_e[n] m_e[n] (m_e[n] - C[r, n])   (the row pass leaves the inner sum per row in d_work; rows are then
+ *                added in a fixed two-level order: 256-row chunks ascending, then the chunks ascending)
+ *     dB[c, n] = sum over the entries of column c of q_e[n] * E[e, n] (MUL, fused multiply-add) | q_e[n] (ADD) |
+ *                (B[c, n] + E[e, n] > 0 ? q_e[n] : 0) (ADD_RELU); COPY has no dB        (one GATHER pass over the rows of A^T)
+ * The gradients amplify the rounding of s by t (m - C): at |t| of a few hundred they lose digits that the forward keeps.
+ * Every sum runs in an order fixed by the pattern and the launch shape; there are no atomics: the same bits on every run and stream.
+ * Nothing of size nnz x N exists besides E and dE.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 64 floats.  Leading dimensions: >= N and
+ * multiples of 4 -- lde, ldc, ldg and (backward) ldlse always; ldb unless d_B is NULL with SEXTANS_EDGE_COPY; ldlse in the forward, lddb
+ * and ldde when their pointer is given.  Every pointer 16-byte aligned.  The outputs must not overlap the inputs or each other.
+ * Needed with nnz > 0: d_E and d_C always; d_B unless op is SEXTANS_EDGE_COPY (then d_B may be NULL and d_dB must be); in the backward
+ * also d_lse and d_G.  d_lse may be NULL in the forward (inference).  In the backward any of d_dB, d_dE, d_dt may be NULL, not all three;
+ * d_dt needs d_work, sextans_spmm_edge_softagg_workspace_floats(h, N) = M * N + ceil(M / 256) * N floats that the call writes (only when
+ * d_dt is given).  The backward writes every element of dB (K x N), dE (nnz x N) and dt (N) it is given; the column pass runs only for
+ * d_dB, the row pass for d_dE or d_dt.
+ * The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call with d_dB also builds A^T
+ * (its arrays and the companion engine's tables only); both synchronise then.  After that a call allocates nothing, reads nothing back
+ * and does not synchronise: it can be captured into a hipGraph.
+ * sextans_last_kernel: "spmm_edge_softagg" / "spmm_edge_softagg_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, op not one of the four, N < 8 or not a multiple of 8 or more than 65535 tiles, a leading dimension
+ * below N or not a multiple of 4, a misaligned pointer, (backward) d_dB, d_dE and d_dt all NULL, d_dt without d_work, d_dB with COPY --
+ * checked in this order, then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX
+ * and for a required pointer that is NULL with nnz > 0; all before any device is touched.
+ * sextans_spmm_edge_softagg_workspace_floats returns the error code negated.  M == 0 or nnz == 0: OK -- C, dB, dt and the workspace are
+ * zeroed, lse = -inf, dE has no element. */
+int sextans_spmm_edge_softagg_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
+                                        const float *d_t, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream);
+int64_t sextans_spmm_edge_softagg_workspace_floats(sextans_handle_t h, int N);
+int sextans_spmm_edge_softagg_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E,
+                                                 int64_t lde, const float *d_t, const float *d_C, int64_t ldc, const float *d_lse,
+                                                 int64_t ldlse, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE,
+                                                 int64_t ldde, float *d_dt, float *d_work, void *stream);
+
 /* ---- Gated aggregation: a per-channel sigmoid gate on every stored entry, computed from both endpoints and, optionally, the entry's own
  * features (PyG's ResGatedGraphConv; GatedGCN of Bresson & Laurent, the MPNN of GraphGPS and of the LRGB / "Benchmarking GNNs" suites).
  * Closest thing in the reference: none.

@@ -122,6 +122,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
     "sextans_spmm_gated_device_rm", "sextans_spmm_gated_workspace_floats", "sextans_spmm_gated_backward_device_rm",
     "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
+    "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -381,6 +382,11 @@ def lib():
     L.sextans_spmm_gated_workspace_floats.restype = i64
     L.sextans_spmm_gated_backward_device_rm.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.POINTER(GatedIn), vp, i64, vp, i64, vp, i64, vp, i64,
                                                         C.POINTER(GatedGrad), vp, vp]
+    L.sextans_spmm_edge_softagg_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp]
+    L.sextans_spmm_edge_softagg_workspace_floats.argtypes = [vp, C.c_int]
+    L.sextans_spmm_edge_softagg_workspace_floats.restype = i64
+    L.sextans_spmm_edge_softagg_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64,
+                                                               vp, i64, vp, vp, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1054,6 +1060,33 @@ class Engine:
         d_B / d_E may be None where the op's gradient does not read them."""
         _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
                "spmm_edge_backward_device_rm")
+
+    def spmm_edge_softagg_device_rm(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream=None):
+        """Softmax aggregation of edge-feature messages (sextans_spmm_edge_softagg_device_rm): C[r, n] = sum over row r's stored entries
+        e = (r, c) of softmax_e(t[n] * m_e[n]) * m_e[n], with the message m_e of spmm_edge_device_rm (B[c, n] * E[e, n], B + E, relu(B + E)
+        or E[e, n] by op: EDGE_*; d_B may be None with EDGE_COPY) and the softmax per output column of spmm_softagg_device_rm; d_lse (may
+        be None) gets log sum_e exp(t[n] m_e[n]).  Only A's pattern is read.  d_t: N temperatures, or None for 1.  An empty row: 0 and
+        -inf.  N: a multiple of 8."""
+        _check(lib().sextans_spmm_edge_softagg_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream),
+               "spmm_edge_softagg_device_rm")
+
+    def spmm_edge_softagg_workspace_floats(self, N):
+        """Floats of workspace spmm_edge_softagg_backward_device_rm needs for dt on this matrix
+        (sextans_spmm_edge_softagg_workspace_floats): M * N + ceil(M / 256) * N."""
+        n = lib().sextans_spmm_edge_softagg_workspace_floats(self._h, N)
+        if n < 0:
+            _check(int(-n), "spmm_edge_softagg_workspace_floats")
+        return int(n)
+
+    def spmm_edge_softagg_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dE, ldde,
+                                             d_dt, d_work, stream=None):
+        """dB (K x N), dE (nnz x N) and dt (N floats, summed over the rows in a fixed two-level order) of spmm_edge_softagg_device_rm from
+        its C and lse and the upstream gradient G (sextans_spmm_edge_softagg_backward_device_rm): a column pass over A^T for dB, a row pass
+        over A that stores dE and the rows' share of dt, no atomics.  Any of d_dB, d_dE, d_dt may be None (not all three; d_dB must be
+        with EDGE_COPY); d_dt needs d_work, spmm_edge_softagg_workspace_floats(N) floats the call writes."""
+        _check(lib().sextans_spmm_edge_softagg_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg,
+                                                                  d_dB, lddb, d_dE, ldde, d_dt, d_work, stream),
+               "spmm_edge_softagg_backward_device_rm")
 
     def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and
