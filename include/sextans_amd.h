@@ -1011,6 +1011,59 @@ int sextans_spmm_edge_softagg_backward_device_rm(sextans_handle_t h, int op, int
                                                  int64_t ldlse, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE,
                                                  int64_t ldde, float *d_dt, float *d_work, void *stream);
 
+/* ---- Channel-wise ("vector") attention from caller-supplied PER-CHANNEL scores: the per-column softmax of
+ * sextans_spmm_edge_softagg_device_rm with the score decoupled from the message (PointTransformerConv:
+ * x_i' = sum_j softmax_j(gamma(phi(x_i) - psi(x_j) + delta_ij)) * (W x_j + delta_ij), the score an (nnz, N) tensor out of an MLP; DGL's
+ * edge_softmax on multi-channel edge data followed by u_mul_e_sum / e_mul_e; PyG's softmax(alpha, index) with a per-channel alpha;
+ * AttentionalAggregation with a per-channel gate).  Closest thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * S, D, dS and dD are (nnz, N) row-major IN THE CSR ENTRY ORDER (element [e * ld + n], 64-bit offsets); V and dV are (K, N); C, lse and G
+ * are (M, N).  For the stored entry e = (r, c) and column n, all arithmetic fp32:
+ *     SEXTANS_VATT_NODE   m_e = V[c, n]                 (d_D is ignored)
+ *     SEXTANS_VATT_ADD    m_e = V[c, n] + D[e, n]       (ONE rounded add)
+ *     SEXTANS_VATT_EDGE   m_e = D[e, n]                 (d_V is ignored)
+ *     s_e = S[e, n]                                     (read, never computed)
+ *     lse[r, n] = log sum_e exp(s_e)      w_e = exp(s_e - lse[r, n])      C[r, n] = sum_e w_e m_e
+ * computed online exactly as sextans_spmm_edge_softagg_device_rm does (running maximum, normaliser and accumulator per (row, column); the
+ * scores may be anything finite): fed S = t[n] m_e formed as one rounded product, ADD and EDGE return the bits of that function's ADD
+ * and COPY and NODE those of sextans_spmm_softagg_device_rm on values of 1, for N <= 64.  A row without stored entries: C = +0,
+ * lse = -inf.  A row of ONE entry gives C the bits of its message (+0 for -0) and lse = s.  A score of -inf MASKS its (entry, column): the
+ * weight is exactly +0 and dS is +0 there; a (row, column) whose scores are all -inf ends as 0 / 0: C is NaN there, lse -inf, and the NaN
+ * stays in that (row, column).  Any other non-finite score or message stays in its own (row, column) as well.
+ * Backward, G the upstream gradient of C, gw_e = G[r, n] w_e (both passes recompute w_e with the same operations: the same bits):
+ *     dS[e, n] = gw_e (m_e - C[r, n])   (+0 where S[e, n] = -inf)       dD[e, n] = gw_e   (ADD, EDGE)
+ *                (one row pass over A; every element stored once by the lanes that own its (entry, tile))
+ *     dV[c, n] = sum over the entries of column c of gw_e   (NODE, ADD)      (one GATHER pass over the rows of A^T, which reads S through
+ *                the transpose's permutation and gathers lse and G; neither C, V nor D)
+ * Every sum runs in an order fixed by the pattern and the launch shape; there are no atomics: the same bits on every run and stream.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 64 floats.  Leading dimensions: >= N and
+ * multiples of 4 -- lds, ldc, ldg and (backward) ldlse always; ldv unless msg is EDGE, ldd unless msg is NODE; ldlse in the forward,
+ * ldds, lddv and lddd when their pointer is given.  Every pointer that is read or written 16-byte aligned.  An operand the mode does not
+ * read (d_V with EDGE, d_D with NODE) is ignored with its leading dimension.  The outputs must not overlap the inputs or each other; in
+ * ADD mode dS and dD are two distinct buffers.
+ * Needed with nnz > 0: d_S, d_C and the operands the mode reads; in the backward also d_lse and d_G.  d_lse may be NULL in the forward
+ * (inference).  In the backward any of d_dS, d_dV, d_dD may be NULL, not all three; the row pass runs when d_dS or d_dD is given, the
+ * column pass when d_dV is given; every element of a gradient that is given is written.
+ * The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call with d_dV also builds A^T
+ * (its arrays and the companion engine's tables only); both synchronise then.  After that a call allocates nothing, reads nothing back
+ * and does not synchronise: it can be captured into a hipGraph.  The caller's stream is used.
+ * sextans_last_kernel: "vector_attention" / "vector_attention_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, msg not one of the three, N < 8 or not a multiple of 8 or more than 65535 tiles, a leading dimension
+ * below N or not a multiple of 4, a misaligned pointer, (backward) d_dS, d_dV and d_dD all NULL, d_dV with EDGE, d_dD with NODE --
+ * checked in this order, then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX
+ * and for a required pointer that is NULL with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- C and dV are
+ * zeroed, lse = -inf, dS and dD have no element. */
+#define SEXTANS_VATT_NODE 1
+#define SEXTANS_VATT_ADD 2
+#define SEXTANS_VATT_EDGE 3
+int sextans_vector_attention_device_rm(sextans_handle_t h, int msg, int N, const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
+                                       const float *d_D, int64_t ldd, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream);
+int sextans_vector_attention_backward_device_rm(sextans_handle_t h, int msg, int N, const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
+                                                const float *d_D, int64_t ldd, const float *d_C, int64_t ldc, const float *d_lse, int64_t ldlse,
+                                                const float *d_G, int64_t ldg, float *d_dS, int64_t ldds, float *d_dV, int64_t lddv,
+                                                float *d_dD, int64_t lddd, void *stream);
+
 /* ---- Gated aggregation: a per-channel sigmoid gate on every stored entry, computed from both endpoints and, optionally, the entry's own
  * features (PyG's ResGatedGraphConv; GatedGCN of Bresson & Laurent, the MPNN of GraphGPS and of the LRGB / "Benchmarking GNNs" suites).
  * Closest thing in the reference: none.

@@ -123,6 +123,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_gated_device_rm", "sextans_spmm_gated_workspace_floats", "sextans_spmm_gated_backward_device_rm",
     "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
     "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
+    "sextans_vector_attention_device_rm", "sextans_vector_attention_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -134,6 +135,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on th
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
 EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
 GATE_SUM, GATE_NORM = 1, 2  # SEXTANS_GATE_*: the mode of spmm_gated_device_rm
+VATT_NODE, VATT_ADD, VATT_EDGE = 1, 2, 3  # SEXTANS_VATT_*: the message of vector_attention_device_rm
 SCORE_SOFTMAX, SCORE_WEIGHT = 1, 2  # SEXTANS_SCORE_*: the mode of score_attention_device
 
 
@@ -387,6 +389,9 @@ def lib():
     L.sextans_spmm_edge_softagg_workspace_floats.restype = i64
     L.sextans_spmm_edge_softagg_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64,
                                                                vp, i64, vp, vp, vp]
+    L.sextans_vector_attention_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_vector_attention_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                                              vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1087,6 +1092,25 @@ class Engine:
         _check(lib().sextans_spmm_edge_softagg_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg,
                                                                   d_dB, lddb, d_dE, ldde, d_dt, d_work, stream),
                "spmm_edge_softagg_backward_device_rm")
+
+    def vector_attention_device_rm(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream=None):
+        """Channel-wise attention from per-channel scores (sextans_vector_attention_device_rm): C[r, n] = sum over row r's stored entries
+        e = (r, c) of softmax_e(S[e, n]) * m_e[n], a softmax per output column over the row's scores, which are READ from the (nnz, N)
+        tensor S in A's entry order; the message m_e is V[c, n] (VATT_NODE), V[c, n] + D[e, n] (VATT_ADD) or D[e, n] (VATT_EDGE); the
+        operand a mode does not read is ignored and may be None.  d_lse (may be None) gets log sum_e exp(S[e, n]).  Only A's pattern is
+        read.  A score of -inf masks its (entry, column).  An empty row: 0 and -inf.  N: a multiple of 8."""
+        _check(lib().sextans_vector_attention_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream),
+               "vector_attention_device_rm")
+
+    def vector_attention_backward_device_rm(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dS, ldds, d_dV,
+                                            lddv, d_dD, lddd, stream=None):
+        """dS (nnz x N), dV (K x N) and dD (nnz x N) of vector_attention_device_rm from its C and lse and the upstream gradient G
+        (sextans_vector_attention_backward_device_rm): a row pass over A that stores dS and dD when either is given, a column pass over
+        A^T for dV when it is given, no atomics.  Any of the three may be None, not all; d_dV must be None with VATT_EDGE, d_dD with
+        VATT_NODE."""
+        _check(lib().sextans_vector_attention_backward_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg,
+                                                                 d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
+               "vector_attention_backward_device_rm")
 
     def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and

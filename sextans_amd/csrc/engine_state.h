@@ -17,6 +17,8 @@
 //   engine_edge.hip     SpMM with a feature vector per entry, forward and backward (sextans_spmm_edge_device_rm, ..._backward_device_rm)
 //   engine_edge_softagg.hip  softmax aggregation of edge-feature messages, forward and backward (sextans_spmm_edge_softagg_device_rm,
 //                       ..._backward_device_rm)
+//   engine_vector_attention.hip  channel-wise attention from per-channel scores, forward and backward (sextans_vector_attention_device_rm,
+//                       ..._backward_device_rm)
 //   engine_bell.hip     blocked-ELL bf16 MFMA path (BASELINE config 5) and the dense-tile extraction
 //   engine_dist.hip     native multi-GPU entry (RCCL all-gather of C slabs) and its clustered-order chunks (cc_*)
 //   engine_transpose.hip  the backward pass: A^T behind a companion engine (sextans_spmm_t_device_rm) and the SDDMM

@@ -1,0 +1,189 @@
+// vector_attention_kernels.h -- channel-wise ("vector") attention from caller-supplied per-channel scores over a CSR pattern
+// (sextans_vector_attention_device_rm / sextans_vector_attention_backward_device_rm): PointTransformerConv's
+// x_i' = sum_j softmax_j(gamma(..))[n] * (W x_j + delta_ij)[n], DGL's edge_softmax on multi-channel edge data followed by u_mul_e_sum /
+// e_mul_e, PyG's softmax(alpha, index) with a per-channel alpha.  The softmax of spmm_edge_softagg_kernels.h with the score DECOUPLED
+// from the message: it is read from an (nnz, N) tensor of its own, never computed.  No counterpart in the reference.
+//
+//   m_e = V[c, n] (NODE) | V[c, n] + D[e, n] (ADD, ONE rounded add) | D[e, n] (EDGE, V is not read)
+//   s_e = S[e, n]
+//   forward        lse[r, n] = log sum_e exp(s_e);  w_e = exp(s_e - lse[r, n]);  C[r, n] = sum_e w_e m_e.  Empty row: C = +0, lse = -inf
+//   backward, G the upstream gradient, gw_e = G[r, n] w_e:
+//     rows             dS[e, n] = gw_e (m_e - C[r, n]) (+0 where s_e = -inf);  dD[e, n] = gw_e (ADD, EDGE), each stored once per (entry, tile)
+//     cols (over A^T)  dV[c, n] = sum over the entries of column c of gw_e (NODE, ADD); EDGE has none
+//
+// Only A's PATTERN is read; S, D, dS and dD are (nnz, N) row-major in A's entry order, addressed as (long long)e * ld.  The passes plug
+// into the row walking of pattern_pass.h as EdgeSoftaggPass does: COLUMN TILES of at most 64 floats play the heads' part, a slot of T
+// lanes owns one (row, tile), the last tile of a row may be partial.
+// The forward is SoftaggPass's online softmax with the score loaded instead of multiplied out: the state (m, z, acc) per float, the same
+// batch and combine arithmetic, __fdiv_rn and softagg_log in finish -- fed S = t[n] m_e (one rounded product) it returns the bits of
+// spmm_edge_softagg (ADD, EDGE) and of spmm_softagg on values of 1 (NODE).  A score of -inf masks its (entry, column): weight +0.
+// The row pass keeps NO state (EdgePass's row pass): every (entry, tile) piece of dS and dD is stored by the slot that owns it, each
+// store predicated on its pointer.  The column pass reads S through the transpose's permutation and gathers lse[r] and G[r]; it needs
+// neither C, V nor D: the weight alone is dV's term.
+// No atomics; sums in an order fixed by the pattern and the launch shape.
+#pragma once
+#include "spmm_softagg_kernels.h"
+
+namespace sx {
+
+enum { kVattNode = 1, kVattAdd = 2, kVattEdge = 3 };   // SEXTANS_VATT_*
+
+struct VectorAttnArgs {
+    const float *S, *V, *D;     // V: not read by EDGE; D: not read by NODE
+    const float *C, *lse, *G;   // backward
+    float *out, *out_lse;       // forward; out_lse may be null
+    float *dS, *dV, *dD;        // backward, each may be null
+    long long lds, ldv, ldd, ldc, ldlse, ldg, ldds, lddv, lddd;
+    int H;                      // column tiles (the bodies' "heads")
+    int N, tile;                // tile: floats per tile = 4 T P
+};
+
+// the message: at most one rounded operation (the operand a mode does not read comes in as 0 and is not used)
+template <int MSG>
+__device__ __forceinline__ float vatt_message(float v, float d) {
+    return MSG == kVattNode ? v : MSG == kVattAdd ? __fadd_rn(v, d) : d;
+}
+
+// One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
+template <int PASS, int MSG, int T_, int P_, int U_>
+struct VectorAttnPass {
+    using Args = VectorAttnArgs;
+    static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
+    static constexpr int NF = PASS == kAttnForward ? 3 * W : PASS == kAttnBackwardCols ? W : 1;   // forward: m, z, acc per float; cols: dV
+    static constexpr bool kMerge = PASS != kAttnBackwardRows;                                     // rows: nothing to merge
+    static constexpr bool kV = MSG != kVattEdge, kD = MSG != kVattNode;                           // the message reads V / D
+    const VectorAttnArgs &a;
+    const int *ci, *perm;
+    const int t;
+    int h = 0, n = 0;        // the tile and its valid floats
+    float x[W], y[W], z[W];  // rows: the own row's C, lse and G
+    float f[NF];
+
+    __device__ __forceinline__ VectorAttnPass(const VectorAttnArgs &a_, const int *ci_, const int *perm_, int t_)
+        : a(a_), ci(ci_), perm(perm_), t(t_) {}
+
+    __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
+        h = tile;
+        n = min(a.tile, a.N - h * a.tile);
+        const long long r = act ? own : 0, c0 = (long long)h * a.tile;
+        if (PASS == kAttnForward) {
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                f[i] = -INFINITY;
+                f[W + i] = 0.0f;
+                f[2 * W + i] = 0.0f;
+            }
+        } else {
+            if (PASS == kAttnBackwardRows) {
+                attn_load<T, P>(x, a.C + r * a.ldc + c0, n, t, act);
+                attn_load<T, P>(y, a.lse + r * a.ldlse + c0, n, t, act);
+                attn_load<T, P>(z, a.G + r * a.ldg + c0, n, t, act);
+            }
+#pragma unroll
+            for (int i = 0; i < NF; ++i) f[i] = 0.0f;
+        }
+    }
+
+    __device__ __forceinline__ void batch(const int (&e)[U_], const bool (&valid)[U_]) {
+        constexpr bool COLS = PASS == kAttnBackwardCols;
+        constexpr bool kGather = !COLS && kV;   // forward, rows: the entry's V row
+        constexpr bool kEdge = !COLS && kD;     // forward, rows: the entry's D row
+        long long oth[U], pe[U];
+        float s2[U][W], v2[U][kGather ? W : 1], d2[U][kEdge ? W : 1], l2[U][COLS ? W : 1], g2[U][COLS ? W : 1];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            oth[u] = ((kGather || COLS) && valid[u]) ? ci[e[u]] : 0;
+            pe[u] = COLS ? (valid[u] ? perm[e[u]] : 0) : e[u];   // the entry's position in A's arrays
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long c0 = (long long)h * a.tile;
+            attn_load<T, P>(s2[u], a.S + pe[u] * a.lds + c0, n, t, valid[u]);
+            if constexpr (COLS) {
+                attn_load<T, P>(l2[u], a.lse + oth[u] * a.ldlse + c0, n, t, valid[u]);
+                attn_load<T, P>(g2[u], a.G + oth[u] * a.ldg + c0, n, t, valid[u]);
+            }
+            if constexpr (kGather) attn_load<T, P>(v2[u], a.V + oth[u] * a.ldv + c0, n, t, valid[u]);
+            if constexpr (kEdge) attn_load<T, P>(d2[u], a.D + pe[u] * a.ldd + c0, n, t, valid[u]);
+        }
+        if constexpr (PASS == kAttnForward) {
+            float m2[U][W];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    m2[u][i] = vatt_message<MSG>(kGather ? v2[u][i] : 0.0f, kEdge ? d2[u][i] : 0.0f);   // (an entry the slot does not have: 0)
+                    s2[u][i] = valid[u] ? s2[u][i] : -INFINITY;                                           // (exp gives those +0)
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                float mn = f[i];
+#pragma unroll
+                for (int u = 0; u < U; ++u) mn = fmaxf(mn, s2[u][i]);
+                const float mref = mn == -INFINITY ? 0.0f : mn;          // only -inf so far: everything stays +0
+                const float al = softmax_exp(__fsub_rn(f[i], mref));   // 1 when m did not grow
+                float zz = __fmul_rn(f[W + i], al), acc = __fmul_rn(f[2 * W + i], al);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const float w = softmax_exp(__fsub_rn(s2[u][i], mref));
+                    zz = __fadd_rn(zz, w);
+                    acc = __fmaf_rn(w, m2[u][i], acc);
+                }
+                f[i] = mn; f[W + i] = zz; f[2 * W + i] = acc;
+            }
+        } else if constexpr (COLS) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!valid[u]) continue;
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    // floats beyond the tile read s = lse = 0 and G = 0: the term is +0
+                    f[i] = __fadd_rn(f[i], __fmul_rn(g2[u][i], softmax_exp(__fsub_rn(s2[u][i], l2[u][i]))));
+                }
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                float ds[W], dd[W];
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    const float m = vatt_message<MSG>(kGather ? v2[u][i] : 0.0f, kEdge ? d2[u][i] : 0.0f);
+                    const float gw = __fmul_rn(z[i], softmax_exp(__fsub_rn(s2[u][i], y[i])));
+                    dd[i] = gw;
+                    ds[i] = s2[u][i] == -INFINITY ? 0.0f : __fmul_rn(gw, __fsub_rn(m, x[i]));   // a masked (entry, column): +0, not G's sign
+                }
+                if (!valid[u]) continue;
+                const long long c0 = (long long)h * a.tile;
+                if (a.dS) attn_store<T, P>(ds, a.dS + pe[u] * a.ldds + c0, n, t);
+                if (kD && a.dD) attn_store<T, P>(dd, a.dD + pe[u] * a.lddd + c0, n, t);
+            }
+        }
+    }
+
+    // g <- g (+) o: SoftaggPass's own merge (the forward's state has its layout; the column pass adds) -- commutative operations only, so
+    // both sides of a butterfly exchange compute the same bits
+    static __device__ __forceinline__ void combine(float *g, const float *o) {
+        if constexpr (PASS != kAttnBackwardRows) SoftaggPass<PASS, T_, P_, U_>::combine(g, o);
+    }
+
+    // cnt: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
+    __device__ __forceinline__ void finish(bool writer, int own, int cnt) {
+        if (!writer || PASS == kAttnBackwardRows) return;
+        const long long r = own, c0 = (long long)h * a.tile;
+        if (PASS == kAttnForward) {
+            float c[W], l[W];
+#pragma unroll
+            for (int i = 0; i < W; ++i) {
+                c[i] = cnt > 0 ? __fdiv_rn(f[2 * W + i], f[W + i]) : 0.0f;
+                l[i] = cnt > 0 ? __fadd_rn(f[i], softagg_log(f[W + i])) : -INFINITY;
+            }
+            attn_store<T, P>(c, a.out + r * a.ldc + c0, n, t);
+            if (a.out_lse) attn_store<T, P>(l, a.out_lse + r * a.ldlse + c0, n, t);
+        } else {
+            attn_store<T, P>(f, a.dV + r * a.lddv + c0, n, t);
+        }
+    }
+};
+
+}  // namespace sx

@@ -65,6 +65,7 @@ The gated aggregation of ResGatedGraphConv / GatedGCN (a per-channel sigmoid gat
 lives in a module of its own, on the same cached engines: sextans_amd.gated.spmm_gated(A, x_dst, x_src, V, E=None, normalize=False, ...).
 So does the softmax aggregation of edge-feature messages (GENConv / DeeperGCN with edge features: relu(x_j + e_ij) + eps under a softmax
 with a learnable temperature): sextans_amd.edge_softagg.spmm_edge_softagg(A, B, E, op="mul", t=1.0, eps=0.0, return_lse=False).
+And Point Transformer's channel-wise attention from per-channel scores: sextans_amd.vector_attention.vector_attention(A, S, V=None, D=None).
 
 Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
 
