@@ -1064,6 +1064,63 @@ int sextans_vector_attention_backward_device_rm(sextans_handle_t h, int msg, int
                                                 const float *d_G, int64_t ldg, float *d_dS, int64_t ldds, float *d_dV, int64_t lddv,
                                                 float *d_dD, int64_t lddd, void *stream);
 
+/* ---- Edge-OUTPUT ops from both endpoints of every stored entry (DGL's gSDDMM next to gSpMM: u_add_v, u_sub_v, u_mul_v, copy_u, copy_v,
+ * each optionally + e): the (nnz, N) tensors that sextans_score_attention_device, sextans_vector_attention_device_rm,
+ * sextans_spmm_edge*_device_rm and sextans_spmm_edge_softagg_device_rm READ -- Point Transformer's phi(x_i) - psi(x_j) + delta_ij,
+ * EdgeConv's x_j - x_i, the halves of MeshGraphNets' concat(e, x_i, x_j) (ldz places them), the argument of an MLP on x_i * x_j, GatedGCN's
+ * pre-activations without the aggregation -- without two materialised gathers and without an atomic scatter in the backward.  Closest
+ * thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * xdst and dxdst are row-major M x N fp32, xsrc and dxsrc K x N; Z, E and Gz are (nnz, N) row-major IN THE CSR ENTRY ORDER the matrix was
+ * set with, as E of sextans_spmm_edge_device_rm (element [e * ld + n], 64-bit offsets).  For the stored entry e = (r, c) and column n
+ * every result is ONE rounded fp32 operation:
+ *     SEXTANS_EDGEOP_ADD   z = xdst[r, n] + xsrc[c, n]
+ *     SEXTANS_EDGEOP_SUB   z = xdst[r, n] - xsrc[c, n]
+ *     SEXTANS_EDGEOP_MUL   z = xdst[r, n] * xsrc[c, n]
+ *     SEXTANS_EDGEOP_DST   z = xdst[r, n]                 (d_xsrc is ignored)
+ *     SEXTANS_EDGEOP_SRC   z = xsrc[c, n]                 (d_xdst is ignored)
+ *     Z[e, n] = z                  when d_E == NULL
+ *     Z[e, n] = z + E[e, n]        otherwise: a second rounded add, in this order, never contracted
+ * The forward is bit-determined: the bits of the same float32 expression anywhere.  MUL returns the bits of
+ * sextans_spmm_edge_backward_device_rm's dE (G := xdst, B := xsrc), ADD with E those of sextans_spmm_gated_device_rm's z.
+ * Backward, Gz the upstream gradient of Z (dE = Gz: no kernel and no argument):
+ *     dxdst[r, n] = sum over row r's entries of Gz[e, n] (ADD, SUB, DST) | fma(Gz[e, n], xsrc[c, n], .) (MUL)
+ *                   (one pass over the rows of A)
+ *     dxsrc[c, n] = sum over column c's entries of Gz[e, n] (ADD, SRC) | fma(Gz[e, n], xdst[r, n], .) (MUL); SUB subtracts Gz[e, n] from an
+ *                   accumulator that starts at +0: ADD's bits negated, except that a zero sum is +0
+ *                   (the same pass over the rows of A^T, which reads Gz through the transpose's permutation)
+ * d_dxdst or d_dxsrc may be NULL, not both: its pass is skipped, and with d_dxsrc == NULL A^T is never built.  The backward reads xsrc
+ * only for MUL's dxdst and xdst only for MUL's dxsrc; otherwise they are ignored with their leading dimensions.  No atomics, no
+ * workspace, no value refresh; every sum runs in an order fixed by the pattern and the launch shape: the same bits on every run and
+ * stream.  Everything handed in is written in full: a row or column without entries gets +0.  NaN and +-inf reach only the entries,
+ * rows and columns that hold them.
+ * N: a multiple of 8, at least 8, no upper limit but 65535 column tiles of up to 128 floats.  Leading dimensions: >= N and
+ * multiples of 4 -- ldz and ldgz always, those of the operands a call reads, lde, lddxdst and lddxsrc when their pointer is given.  Every
+ * pointer that is read or written 16-byte aligned.  An operand the op does not read is ignored together with its leading dimension and
+ * alignment.  The outputs must not overlap the inputs or each other; ldz > N writes Z into a wider buffer (a concatenation).
+ * Needed with nnz > 0: d_Z, d_Gz and the operands the call reads.
+ * The first forward call on a matrix validates it and builds the row softmax's tables; the first backward call with d_dxsrc also builds
+ * A^T (its arrays and the companion engine's tables only); both synchronise then.  After that -- in particular after
+ * sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) -- a call allocates nothing, reads nothing back and does not synchronise: it
+ * can be captured into a hipGraph.  The caller's stream is used.
+ * sextans_last_kernel: "edge_op" / "edge_op_backward", "+long_rows" appended when the workgroup path ran.
+ * SEXTANS_ERR_INVALID: h == NULL, op not one of the five, N < 8 or not a multiple of 8 or more than 65535 tiles, a leading dimension
+ * below N or not a multiple of 4, a misaligned pointer, (backward) d_dxdst and d_dxsrc both NULL, d_dxdst with SRC, d_dxsrc with DST --
+ * checked in this order, then the handle's state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX
+ * and for a required pointer that is NULL with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- Z has no element,
+ * dxdst and dxsrc are zeroed. */
+#define SEXTANS_EDGEOP_ADD 1
+#define SEXTANS_EDGEOP_SUB 2
+#define SEXTANS_EDGEOP_MUL 3
+#define SEXTANS_EDGEOP_DST 4
+#define SEXTANS_EDGEOP_SRC 5
+int sextans_edge_op_device_rm(sextans_handle_t h, int op, int N, const float *d_xdst, int64_t ldxdst, const float *d_xsrc, int64_t ldxsrc,
+                              const float *d_E, int64_t lde, float *d_Z, int64_t ldz, void *stream);
+int sextans_edge_op_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_xdst, int64_t ldxdst, const float *d_xsrc,
+                                       int64_t ldxsrc, const float *d_Gz, int64_t ldgz, float *d_dxdst, int64_t lddxdst, float *d_dxsrc,
+                                       int64_t lddxsrc, void *stream);
+
 /* ---- Gated aggregation: a per-channel sigmoid gate on every stored entry, computed from both endpoints and, optionally, the entry's own
  * features (PyG's ResGatedGraphConv; GatedGCN of Bresson & Laurent, the MPNN of GraphGPS and of the LRGB / "Benchmarking GNNs" suites).
  * Closest thing in the reference: none.

@@ -124,6 +124,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
     "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
     "sextans_vector_attention_device_rm", "sextans_vector_attention_backward_device_rm",
+    "sextans_edge_op_device_rm", "sextans_edge_op_backward_device_rm",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -136,6 +137,7 @@ REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_
 EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
 GATE_SUM, GATE_NORM = 1, 2  # SEXTANS_GATE_*: the mode of spmm_gated_device_rm
 VATT_NODE, VATT_ADD, VATT_EDGE = 1, 2, 3  # SEXTANS_VATT_*: the message of vector_attention_device_rm
+EDGEOP_ADD, EDGEOP_SUB, EDGEOP_MUL, EDGEOP_DST, EDGEOP_SRC = 1, 2, 3, 4, 5  # SEXTANS_EDGEOP_*: the op of edge_op_device_rm
 SCORE_SOFTMAX, SCORE_WEIGHT = 1, 2  # SEXTANS_SCORE_*: the mode of score_attention_device
 
 
@@ -392,6 +394,8 @@ def lib():
     L.sextans_vector_attention_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_vector_attention_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                               vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_edge_op_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_edge_op_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1111,6 +1115,21 @@ class Engine:
         _check(lib().sextans_vector_attention_backward_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg,
                                                                  d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
                "vector_attention_backward_device_rm")
+
+    def edge_op_device_rm(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream=None):
+        """Edge-output op from both endpoints (sextans_edge_op_device_rm): for every stored entry e = (r, c), in the CSR entry order,
+        Z[e, n] = xdst[r, n] + / - / * xsrc[c, n] (EDGEOP_ADD / EDGEOP_SUB / EDGEOP_MUL), xdst[r, n] (EDGEOP_DST) or xsrc[c, n]
+        (EDGEOP_SRC), one rounded fp32 operation, plus E[e, n] (a second rounded add) when d_E is given.  The operand an op does not read
+        is ignored and may be None.  Only A's pattern is read.  N: a multiple of 8."""
+        _check(lib().sextans_edge_op_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream), "edge_op_device_rm")
+
+    def edge_op_backward_device_rm(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc, lddxsrc, stream=None):
+        """dxdst (M x N) and dxsrc (K x N) of edge_op_device_rm from the upstream gradient Gz of Z (sextans_edge_op_backward_device_rm):
+        a sum over every row's entries and the same pass over A^T's rows, no atomics; dE is Gz itself.  Either may be None (not both;
+        d_dxdst must be None with EDGEOP_SRC, d_dxsrc with EDGEOP_DST): its pass is skipped, and without d_dxsrc A^T is never built.
+        xsrc is read only for EDGEOP_MUL's dxdst, xdst only for EDGEOP_MUL's dxsrc."""
+        _check(lib().sextans_edge_op_backward_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc,
+                                                        lddxsrc, stream), "edge_op_backward_device_rm")
 
     def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and

@@ -1,5 +1,5 @@
 // pattern_launch.h -- the host side of the pattern passes (pattern_pass.h), shared by engine_attention.hip, engine_attention_edge.hip,
-// engine_gat.hip, engine_gatv2.hip, engine_reduce.hip, engine_multi.hip, engine_softagg.hip, engine_edge.hip, engine_gated.hip, engine_edge_softagg.hip, engine_vector_attention.hip and (through edge_multi_launch.h, the
+// engine_gat.hip, engine_gatv2.hip, engine_reduce.hip, engine_multi.hip, engine_softagg.hip, engine_edge.hip, engine_gated.hip, engine_edge_softagg.hip, engine_vector_attention.hip, engine_edge_op.hip and (through edge_multi_launch.h, the
 // launcher that engine_edge_multi.hip and its per-op sources engine_edge_multi_*.hip share) the edge multi-aggregation, and included by nothing else: the launch of a pass, the width table, the
 // argument checks, the degenerate-call fill, the backward's tables and the dropout variant.  What a family keeps: its Args, its entry
 // points and the entries in flight per slot (U) of each of its passes.

@@ -66,6 +66,8 @@ lives in a module of its own, on the same cached engines: sextans_amd.gated.spmm
 So does the softmax aggregation of edge-feature messages (GENConv / DeeperGCN with edge features: relu(x_j + e_ij) + eps under a softmax
 with a learnable temperature): sextans_amd.edge_softagg.spmm_edge_softagg(A, B, E, op="mul", t=1.0, eps=0.0, return_lse=False).
 And Point Transformer's channel-wise attention from per-channel scores: sextans_amd.vector_attention.vector_attention(A, S, V=None, D=None).
+The opposite direction, node to edge -- the (nnz, N) tensors those ops read, from both endpoints of every entry (u_add_v, u_sub_v, u_mul_v,
+copy_u, copy_v, each optionally + e), with a backward without atomics: sextans_amd.edge_op.edge_op(A, x_dst=None, x_src=None, E=None, op="add").
 
 Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
 
