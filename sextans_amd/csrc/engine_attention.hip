@@ -3,9 +3,8 @@
 //   sextans_attention_backward_device   dQ, dK, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
 //   sextans_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
 //   sextans_dropout_mask_device, sextans_dropout_keep_host        the mask itself: nnz * heads multipliers on the device, keep flags on the host
-// Passes: attention_kernels.h on the row walking of pattern_pass.h, launched through pattern_launch.h.  The row pass uses the row
-// softmax's tables of this engine, the column pass those of the companion engine that holds A^T (engine_transpose.hip) -- no table of
-// its own, and A's values are never read.
+// Passes: attention_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  No table of its own,
+// and A's values are never read.
 #include "attention_kernels.h"
 #include "pattern_launch.h"
 
@@ -64,25 +63,22 @@ int attention_forward(sextans_handle_t h, int heads, int d, int dv, float scale,
     if (bad_ld(ldq, (int64_t)heads * d) || bad_ld(ldk, (int64_t)heads * d) || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv))
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_Q, d_K, d_V, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
-        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_Q || !d_K || !d_V || !d_O || !d_lse, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, call.s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::AttnArgs a{};
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
-    with_dropout<sx::AttnDropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
-    name_pass(h, "attention_fused", drop != nullptr, h->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    with_dropout<sx::AttnDropArgs>(a, drop, [&](const auto &args) {
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, args, perm, false, call.s); });
+    });
+    return call.close("attention_fused", drop != nullptr);
 }
 
 int attention_backward(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K, int64_t ldk,
@@ -98,31 +94,26 @@ int attention_backward(sextans_handle_t h, int heads, int d, int dv, float scale
         bad_ld(lddv, hdv))
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_Q, d_K, d_V, d_bias, d_O, d_lse, d_G, d_delta, d_dQ, d_dK, d_dV, d_dbias)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {
-        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
-        attention_fill(d_dQ, h->M, (int)hd, lddq, 0.0f, s);
-        attention_fill(d_dK, h->K, (int)hd, lddk, 0.0f, s);
-        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV, stream)) return rc;
+    if (call.degenerate()) {
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, call.s);
+        attention_fill(d_dQ, h->M, (int)hd, lddq, 0.0f, call.s);
+        attention_fill(d_dK, h->K, (int)hd, lddk, 0.0f, call.s);
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_backward_tables(h, s)) return rc;
+    if (int rc = call.tables(true)) return rc;
     sx::AttnArgs a{};
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dQ = d_dQ; a.dK = d_dK; a.dV = d_dV; a.dbias = d_dbias;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
     with_dropout<sx::AttnDropArgs>(a, drop, [&](const auto &args) {
-        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, args, perm, d_dbias != nullptr, call.s); });
+        call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, args, perm, false, call.s); });
     });
-    name_pass(h, "attention_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    return call.close("attention_fused_backward", drop != nullptr);
 }
 
 }  // namespace

@@ -3,8 +3,8 @@
 //   sextans_attention_edge_device            s_e = scale * (<Q[r], K[c] + Ek[e]> + bias_e);  O[r] = sum_e softmax_e(s) (V[c] + Ev[e])
 //   sextans_attention_edge_backward_device   dQ, dK, dV, dEk, dEv (and dbias): a row pass over A, a column pass over A^T
 // Passes: the EDGE variant of attention_kernels.h (AttnEdgePass), with and without dropout, in a translation unit of its own so that the
-// build stays parallel; the kernels of engine_attention.hip are not touched.  Tables as there: the row softmax's of this engine, those
-// of the companion engine that holds A^T for the column pass.  Ek == NULL and Ev == NULL: the plain entries serve the call.
+// build stays parallel; the kernels of engine_attention.hip are not touched.  The entry points' frame: pattern_launch.h.
+// Ek == NULL and Ev == NULL: the plain entries serve the call.
 #include "attention_kernels.h"
 #include "pattern_launch.h"
 
@@ -45,27 +45,23 @@ int sextans_attention_edge_device(sextans_handle_t h, int heads, int d, int dv, 
     if (dropout_mode(drop) == Dropout::kPlain) drop = nullptr;
     if (misaligned(d_Q, d_K, d_V, d_Ek, d_Ev, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
     if (!d_Ek && !d_Ev) return sextans_attention_dropout_device(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, drop, stream);
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
-        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_Q || !d_K || !d_V || !d_O || !d_lse, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, call.s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::AttnEdgeArgs a{};
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
     a.Ek = d_Ek; a.Ev = d_Ev; a.ldek = ldek; a.ldev = ldev;
-    with_dropout<sx::AttnEdgeDropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
-    name_pass(h, "attention_edge_fused", drop != nullptr, h->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    with_dropout<sx::AttnEdgeDropArgs>(a, drop, [&](const auto &args) {
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, args, perm, false, call.s); });
+    });
+    return call.close("attention_edge_fused", drop != nullptr);
 }
 
 int sextans_attention_edge_backward_device(sextans_handle_t h, int heads, int d, int dv, float scale, const float *d_Q, int64_t ldq, const float *d_K,
@@ -83,20 +79,16 @@ int sextans_attention_edge_backward_device(sextans_handle_t h, int heads, int d,
     if (!d_Ek && !d_Ev)
         return sextans_attention_dropout_backward_device(h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta,
                                                          d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, drop, stream);
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // (dEk and dEv have no element)
-        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
-        attention_fill(d_dQ, h->M, (int)hd, lddq, 0.0f, s);
-        attention_fill(d_dK, h->K, (int)hd, lddk, 0.0f, s);
-        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_Q || !d_K || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dQ || !d_dK || !d_dV, stream)) return rc;
+    if (call.degenerate()) {   // (dEk and dEv have no element)
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, call.s);
+        attention_fill(d_dQ, h->M, (int)hd, lddq, 0.0f, call.s);
+        attention_fill(d_dK, h->K, (int)hd, lddk, 0.0f, call.s);
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_backward_tables(h, s)) return rc;
+    if (int rc = call.tables(true)) return rc;
     sx::AttnEdgeArgs a{};
     a.Q = d_Q; a.K = d_K; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dQ = d_dQ; a.dK = d_dK; a.dV = d_dV; a.dbias = d_dbias;
@@ -104,12 +96,10 @@ int sextans_attention_edge_backward_device(sextans_handle_t h, int heads, int d,
     a.H = heads; a.d = d; a.dv = dv; a.scale = scale;
     a.Ek = d_Ek; a.Ev = d_Ev; a.dEk = d_dEk; a.dEv = d_dEv; a.ldek = ldek; a.ldev = ldev; a.lddek = lddek; a.lddev = lddev;
     with_dropout<sx::AttnEdgeDropArgs>(a, drop, [&](const auto &args) {
-        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, args, perm, d_dbias != nullptr, call.s); });
+        call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, args, perm, false, call.s); });
     });
-    name_pass(h, "attention_edge_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    return call.close("attention_edge_fused_backward", drop != nullptr);
 }
 
 }  // extern "C"

@@ -1,9 +1,8 @@
 // engine_edge.hip -- SpMM with a feature vector per stored entry over the CSR pattern on an engine handle (include/sextans_amd.h):
 //   sextans_spmm_edge_device_rm            C[r, :] = sum over row r's entries of B[c, :] (op) E[e, :]   (mul / add / relu(add) / copy)
 //   sextans_spmm_edge_backward_device_rm   dB and dE from the upstream gradient: a column pass over A^T, a row pass over A
-// Kernels: spmm_edge_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_reduce.hip: the row softmax's of this
-// engine for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  Only the pattern is read:
-// neither the engine's values nor any of its packed forms is read or touched.
+// Kernels: spmm_edge_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the pattern is
+// read: neither the engine's values nor any of its packed forms is read or touched.
 #include "pattern_launch.h"
 #include "spmm_edge_kernels.h"
 
@@ -44,24 +43,18 @@ int sextans_spmm_edge_device_rm(sextans_handle_t h, int op, int N, const float *
     if (!h || bad_op(op) || bad_n(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_ld(ldb, N) || bad_ld(lde, N) || bad_ld(ldc, N)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_B, d_E, d_C)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && ((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::EdgeArgs a{};
     a.B = d_B; a.E = d_E; a.C = d_C;
     a.ldb = ldb; a.lde = lde; a.ldc = ldc; a.N = N;
-    launch_op<sx::kAttnForward>(op, h, a, nullptr, s);
-    SX_HIP(hipGetLastError());
-    h->last_kernel = h->softmax.nchunks > 0 ? "spmm_edge+long_rows" : "spmm_edge";
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnForward>(op, e, a, perm, call.s); });
+    return call.close("spmm_edge");
 }
 
 int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
@@ -71,37 +64,22 @@ int sextans_spmm_edge_backward_device_rm(sextans_handle_t h, int op, int N, cons
     if (misaligned(d_B, d_E, d_G, d_dB, d_dE)) return SEXTANS_ERR_INVALID;
     if (!d_dB && !d_dE) return SEXTANS_ERR_INVALID;
     if (d_dB && op == SEXTANS_EDGE_COPY) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0) {
-        bool need_b = false, need_e = false;   // MUL: E for dB, B for dE; ADD_RELU: both for either; ADD and COPY: neither
-        if (op == SEXTANS_EDGE_MUL) { need_e = d_dB != nullptr; need_b = d_dE != nullptr; }
-        else if (op == SEXTANS_EDGE_ADD_RELU) need_b = need_e = true;
-        if (!d_G || (need_b && !d_B) || (need_e && !d_E)) return SEXTANS_ERR_INVALID;
+    bool need_b = false, need_e = false;   // MUL: E for dB, B for dE; ADD_RELU: both for either; ADD and COPY: neither
+    if (op == SEXTANS_EDGE_MUL) { need_e = d_dB != nullptr; need_b = d_dE != nullptr; }
+    else if (op == SEXTANS_EDGE_ADD_RELU) need_b = need_e = true;
+    PatternCall call{h};
+    if (int rc = call.open(!d_G || (need_b && !d_B) || (need_e && !d_E), stream)) return rc;
+    if (call.degenerate()) {   // (dE has no element)
+        attention_fill(d_dB, h->K, N, lddb, 0.0f, call.s);
+        return call.done();
     }
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // (dE has no element)
-        attention_fill(d_dB, h->K, N, lddb, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
-    }
-    if (int rc = d_dB ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dB != nullptr)) return rc;
     sx::EdgeArgs a{};
     a.B = d_B; a.E = d_E; a.G = d_G; a.dB = d_dB; a.dE = d_dE;
     a.ldb = ldb; a.lde = lde; a.ldg = ldg; a.lddb = lddb; a.ldde = ldde; a.N = N;
-    bool long_rows = false;
-    if (d_dB) {
-        launch_op<sx::kAttnBackwardCols>(op, h->tr, a, h->at.d_tperm, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
-    }
-    if (d_dE) {
-        launch_op<sx::kAttnBackwardRows>(op, h, a, nullptr, s);
-        long_rows |= h->softmax.nchunks > 0;
-    }
-    SX_HIP(hipGetLastError());
-    h->last_kernel = long_rows ? "spmm_edge_backward+long_rows" : "spmm_edge_backward";
-    return SEXTANS_OK;
+    if (d_dB) call.cols([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnBackwardCols>(op, e, a, perm, call.s); });
+    if (d_dE) call.rows([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnBackwardRows>(op, e, a, perm, call.s); });
+    return call.close("spmm_edge_backward");
 }
 
 }  // extern "C"

@@ -4,9 +4,8 @@
 //                                        (add / sub / mul / dst / src)
 //   sextans_edge_op_backward_device_rm   dx_dst and dx_src from the upstream gradient Gz of Z: an endpoint sum over A's rows, the same
 //                                        pass over A^T's rows through the transpose's permutation
-// Kernels: edge_op_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_edge.hip: the row softmax's of this engine for
-// the forward and dx_dst, those of the companion engine that holds A^T for dx_src.  Only the pattern is read: neither the engine's
-// values nor any of its packed forms is read or touched.  dE = Gz needs no kernel.
+// Kernels: edge_op_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the pattern is read:
+// neither the engine's values nor any of its packed forms is read or touched.  dE = Gz needs no kernel.
 // 5 ops x with / without E x 5 widths x 2 kernels forward (100), 3 terms x 2 directions x 5 widths x 2 kernels backward (60).
 #include "edge_op_kernels.h"
 #include "pattern_launch.h"
@@ -65,7 +64,6 @@ void launch_sum_term(int term, const sextans_engine *e, const sx::EdgeOpArgs &a,
 bool bad_op(int op) { return op < SEXTANS_EDGEOP_ADD || op > SEXTANS_EDGEOP_SRC; }
 bool reads_dst(int op) { return op != SEXTANS_EDGEOP_SRC; }
 bool reads_src(int op) { return op != SEXTANS_EDGEOP_DST; }
-bool bad_ld_of(const void *p, int64_t ld, int N) { return p && bad_ld(ld, N); }   // an optional operand: its leading dimension counts when it is given
 
 }  // namespace
 }  // namespace sxe
@@ -82,20 +80,15 @@ int sextans_edge_op_device_rm(sextans_handle_t h, int op, int N, const float *d_
     if ((reads_dst(op) && bad_ld(ldxdst, N)) || (reads_src(op) && bad_ld(ldxsrc, N)) || bad_ld_of(d_E, lde, N) || bad_ld(ldz, N))
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_xdst, d_xsrc, d_E, d_Z)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && ((reads_dst(op) && !d_xdst) || (reads_src(op) && !d_xsrc) || !d_Z)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) return SEXTANS_OK;   // Z has no element
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    PatternCall call{h};
+    if (int rc = call.open((reads_dst(op) && !d_xdst) || (reads_src(op) && !d_xsrc) || !d_Z, stream)) return rc;
+    if (call.degenerate()) return SEXTANS_OK;   // Z has no element
+    if (int rc = call.tables(false)) return rc;
     sx::EdgeOpArgs a{};
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.E = d_E; a.Z = d_Z;
     a.ldxdst = ldxdst; a.ldxsrc = ldxsrc; a.lde = lde; a.ldz = ldz; a.N = N;
-    launch_forward_op(op, h, a, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "edge_op", false, h->softmax.nchunks > 0);
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *) { launch_forward_op(op, e, a, call.s); });
+    return call.close("edge_op");
 }
 
 int sextans_edge_op_backward_device_rm(sextans_handle_t h, int op, int N, const float *d_xdst, int64_t ldxdst, const float *d_xsrc,
@@ -113,35 +106,27 @@ int sextans_edge_op_backward_device_rm(sextans_handle_t h, int op, int N, const 
     if (!d_dxdst && !d_dxsrc) return SEXTANS_ERR_INVALID;                    // nothing to compute
     if (d_dxdst && !reads_dst(op)) return SEXTANS_ERR_INVALID;               // a gradient of an operand the op does not read
     if (d_dxsrc && !reads_src(op)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_Gz || (need_dst && !d_xdst) || (need_src && !d_xsrc))) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row and column is empty
-        attention_fill(d_dxdst, h->M, N, lddxdst, 0.0f, s);
-        attention_fill(d_dxsrc, h->K, N, lddxsrc, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_Gz || (need_dst && !d_xdst) || (need_src && !d_xsrc), stream)) return rc;
+    if (call.degenerate()) {   // every row and column is empty
+        attention_fill(d_dxdst, h->M, N, lddxdst, 0.0f, call.s);
+        attention_fill(d_dxsrc, h->K, N, lddxsrc, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = d_dxsrc ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dxsrc != nullptr)) return rc;
     sx::EdgeOpArgs a{};
     a.Gz = d_Gz; a.ldgz = ldgz; a.N = N;
-    bool long_rows = false;
+    const int mul = op == SEXTANS_EDGEOP_MUL ? sx::kEndSumMul : sx::kEndSumPlain;
     if (d_dxsrc) {   // over A^T: own = c, the other endpoint r
         a.x = d_xdst; a.ldx = ldxdst; a.out = d_dxsrc; a.ldout = lddxsrc;
-        launch_sum_term(op == SEXTANS_EDGEOP_MUL ? sx::kEndSumMul : op == SEXTANS_EDGEOP_SUB ? sx::kEndSumNeg : sx::kEndSumPlain, h->tr, a,
-                        h->at.d_tperm, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
+        const int term = op == SEXTANS_EDGEOP_SUB ? sx::kEndSumNeg : mul;
+        call.cols([&](const sextans_engine *e, const int *perm) { launch_sum_term(term, e, a, perm, call.s); });
     }
     if (d_dxdst) {   // over A: own = r, the other endpoint c
         a.x = d_xsrc; a.ldx = ldxsrc; a.out = d_dxdst; a.ldout = lddxdst;
-        launch_sum_term(op == SEXTANS_EDGEOP_MUL ? sx::kEndSumMul : sx::kEndSumPlain, h, a, nullptr, s);
-        long_rows |= h->softmax.nchunks > 0;
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_sum_term(mul, e, a, perm, call.s); });
     }
-    SX_HIP(hipGetLastError());
-    name_pass(h, "edge_op_backward", false, long_rows);
-    return SEXTANS_OK;
+    return call.close("edge_op_backward");
 }
 
 }  // extern "C"

@@ -4,9 +4,8 @@
 //   sextans_spmm_edge_softagg_workspace_floats     the floats of workspace dt needs (dt_rows, then the chunk sums)
 //   sextans_spmm_edge_softagg_backward_device_rm   dB, dE and dt from C, lse and the upstream gradient: a column pass over A^T, a row pass
 //                                                  over A, the two-level dt sum
-// Kernels: spmm_edge_softagg_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_edge.hip: the row softmax's of this
-// engine for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  Only the pattern is read:
-// neither the engine's values nor any of its packed forms is read or touched.
+// Kernels: spmm_edge_softagg_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the
+// pattern is read: neither the engine's values nor any of its packed forms is read or touched.
 // The row pass runs when dE or dt is asked for.  It keeps the dt sum whether or not dt is asked for, as engine_softagg.hip's does and for
 // its reason, and its dE store is PREDICATED on the pointer, not a compile-time switch: a variant without the store would add 4 ops x
 // 4 widths x 2 kernels for the call that wants dt alone, and what the predicate saves there -- the stores, not the E stream, which the
@@ -47,11 +46,8 @@ void launch_op(int op, const sextans_engine *e, const sx::EdgeSoftaggArgs &a, co
 }
 
 bool bad_op(int op) { return op < SEXTANS_EDGE_MUL || op > SEXTANS_EDGE_COPY; }
-bool bad_ld_of(const void *p, int64_t ld, int N) { return p && bad_ld(ld, N); }   // an optional operand: its leading dimension counts when it is given
-bool too_many_tiles(int N) { return (N + kMaxTile - 1) / kMaxTile > kMaxTiles; }
 // B is optional with COPY only
 bool bad_ldb(int op, const float *d_B, int64_t ldb, int N) { return op == SEXTANS_EDGE_COPY ? bad_ld_of(d_B, ldb, N) : bad_ld(ldb, N); }
-int64_t chunks_of(int64_t M) { return (M + 255) / 256; }   // the chunks of column_sum_two_level
 
 }  // namespace
 }  // namespace sxe
@@ -62,32 +58,26 @@ extern "C" {
 
 int sextans_spmm_edge_softagg_device_rm(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const float *d_E, int64_t lde,
                                         const float *d_t, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream) {
-    if (!h || bad_op(op) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (!h || bad_op(op) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_ldb(op, d_B, ldb, N) || bad_ld(lde, N) || bad_ld(ldc, N) || bad_ld_of(d_lse, ldlse, N)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_B, d_E, d_t, d_C, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && ((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
+        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::EdgeSoftaggArgs a{};
     a.B = d_B; a.E = d_E; a.t = d_t; a.out = d_C; a.out_lse = d_lse;
     a.ldb = ldb; a.lde = lde; a.ldc = ldc; a.ldlse = ldlse; a.N = N;
-    launch_op<sx::kAttnForward>(op, h, a, nullptr, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_edge_softagg", false, h->softmax.nchunks > 0);
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnForward>(op, e, a, perm, call.s); });
+    return call.close("spmm_edge_softagg");
 }
 
 int64_t sextans_spmm_edge_softagg_workspace_floats(sextans_handle_t h, int N) {
-    if (!h || bad_n(N) || too_many_tiles(N)) return -(int64_t)SEXTANS_ERR_INVALID;
+    if (!h || bad_n(N) || too_many_tiles(N, kMaxTile)) return -(int64_t)SEXTANS_ERR_INVALID;
     if (!h->d_rp) return -(int64_t)SEXTANS_ERR_STATE;
     return (int64_t)h->M * N + chunks_of(h->M) * N;
 }
@@ -96,7 +86,7 @@ int sextans_spmm_edge_softagg_backward_device_rm(sextans_handle_t h, int op, int
                                                  const float *d_t, const float *d_C, int64_t ldc, const float *d_lse, int64_t ldlse,
                                                  const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, float *d_dE, int64_t ldde, float *d_dt,
                                                  float *d_work, void *stream) {
-    if (!h || bad_op(op) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;
+    if (!h || bad_op(op) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;
     if (bad_ldb(op, d_B, ldb, N) || bad_ld(lde, N) || bad_ld(ldc, N) || bad_ld(ldlse, N) || bad_ld(ldg, N) || bad_ld_of(d_dB, lddb, N) ||
         bad_ld_of(d_dE, ldde, N))
         return SEXTANS_ERR_INVALID;
@@ -104,39 +94,26 @@ int sextans_spmm_edge_softagg_backward_device_rm(sextans_handle_t h, int op, int
     if (!d_dB && !d_dE && !d_dt) return SEXTANS_ERR_INVALID;   // nothing to compute
     if (d_dt && !d_work) return SEXTANS_ERR_INVALID;
     if (d_dB && op == SEXTANS_EDGE_COPY) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && ((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C || !d_lse || !d_G)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
+    PatternCall call{h};
+    if (int rc = call.open((!d_B && op != SEXTANS_EDGE_COPY) || !d_E || !d_C || !d_lse || !d_G, stream)) return rc;
     float *d_rows = d_dt ? d_work : nullptr;   // the workspace is written only for dt
     float *d_part = d_rows ? d_rows + (int64_t)h->M * N : nullptr;
-    if (h->M == 0 || h->nnz == 0) {   // (dE has no element)
-        attention_fill(d_dB, h->K, N, lddb, 0.0f, s);
-        attention_fill(d_rows, h->M, N, N, 0.0f, s);   // dt_rows and the chunk sums: what the passes would have left
-        attention_fill(d_part, chunks_of(h->M), N, N, 0.0f, s);
-        attention_fill(d_dt, 1, N, N, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    if (call.degenerate()) {   // (dE has no element)
+        attention_fill(d_dB, h->K, N, lddb, 0.0f, call.s);
+        attention_fill(d_rows, h->M, N, N, 0.0f, call.s);   // dt_rows and the chunk sums: what the passes would have left
+        attention_fill(d_part, chunks_of(h->M), N, N, 0.0f, call.s);
+        attention_fill(d_dt, 1, N, N, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = d_dB ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dB != nullptr)) return rc;
     sx::EdgeSoftaggArgs a{};
     a.B = d_B; a.E = d_E; a.t = d_t; a.C = d_C; a.lse = d_lse; a.G = d_G;
     a.dB = d_dB; a.dE = d_dE; a.dt_rows = d_rows;
     a.ldb = ldb; a.lde = lde; a.ldc = ldc; a.ldlse = ldlse; a.ldg = ldg; a.lddb = lddb; a.ldde = ldde; a.N = N;
-    bool long_rows = false;
-    if (d_dB) {
-        launch_op<sx::kAttnBackwardCols>(op, h->tr, a, h->at.d_tperm, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
-    }
-    if (d_dE || d_dt) {
-        launch_op<sx::kAttnBackwardRows>(op, h, a, nullptr, s);
-        long_rows |= h->softmax.nchunks > 0;
-    }
-    if (d_dt) column_sum_two_level(d_rows, h->M, N, d_part, d_dt, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_edge_softagg_backward", false, long_rows);
-    return SEXTANS_OK;
+    if (d_dB) call.cols([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnBackwardCols>(op, e, a, perm, call.s); });
+    if (d_dE || d_dt) call.rows([&](const sextans_engine *e, const int *perm) { launch_op<sx::kAttnBackwardRows>(op, e, a, perm, call.s); });
+    if (d_dt) column_sum_two_level(d_rows, h->M, N, d_part, d_dt, call.s);
+    return call.close("spmm_edge_softagg_backward");
 }
 
 }  // extern "C"

@@ -2,8 +2,8 @@
 //   sextans_gat_attention_device            O = softmax(LeakyReLU(adst[r] + asrc[c] + bias) on A's pattern) V per head, and the rows' log-sum-exp
 //   sextans_gat_attention_backward_device   dadst, dasrc, dV (and dbias) from O, lse and the upstream gradient: a row pass over A, a column pass over A^T
 //   sextans_gat_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
-// Kernels: gat_kernels.h (the additive score) on the row walking of pattern_pass.h.  Tables as in engine_attention.hip: the row
-// softmax's of this engine for the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
+// Kernels: gat_kernels.h (the additive score) on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  A's
+// values are never read.
 #include "gat_kernels.h"
 #include "pattern_launch.h"
 
@@ -43,25 +43,22 @@ int gat_forward(sextans_handle_t h, int heads, int dv, float negative_slope, con
     if (mode == Dropout::kPlain) drop = nullptr;
     if (ldadst < heads || ldasrc < heads || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_adst, d_asrc, d_V, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
-        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_adst || !d_asrc || !d_V || !d_O || !d_lse, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, call.s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::GatArgs a{};
     a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
-    with_dropout<sx::GatDropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
-    name_pass(h, "gat_fused", drop != nullptr, h->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    with_dropout<sx::GatDropArgs>(a, drop, [&](const auto &args) {
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, args, perm, false, call.s); });
+    });
+    return call.close("gat_fused", drop != nullptr);
 }
 
 int gat_backward(sextans_handle_t h, int heads, int dv, float negative_slope, const float *d_adst, int64_t ldadst, const float *d_asrc, int64_t ldasrc,
@@ -77,31 +74,26 @@ int gat_backward(sextans_handle_t h, int heads, int dv, float negative_slope, co
         bad_ld(lddv, hdv))
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_adst, d_asrc, d_V, d_bias, d_O, d_lse, d_G, d_delta, d_dadst, d_dasrc, d_dV, d_dbias)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_adst || !d_asrc || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dadst || !d_dasrc || !d_dV)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {
-        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
-        attention_fill(d_dadst, h->M, heads, lddadst, 0.0f, s);
-        attention_fill(d_dasrc, h->K, heads, lddasrc, 0.0f, s);
-        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_adst || !d_asrc || !d_V || !d_O || !d_lse || !d_G || !d_delta || !d_dadst || !d_dasrc || !d_dV, stream)) return rc;
+    if (call.degenerate()) {
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, call.s);
+        attention_fill(d_dadst, h->M, heads, lddadst, 0.0f, call.s);
+        attention_fill(d_dasrc, h->K, heads, lddasrc, 0.0f, call.s);
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_backward_tables(h, s)) return rc;
+    if (int rc = call.tables(true)) return rc;
     sx::GatArgs a{};
     a.adst = d_adst; a.asrc = d_asrc; a.V = d_V; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dadst = d_dadst; a.dasrc = d_dasrc; a.dV = d_dV; a.dbias = d_dbias;
     a.ldadst = ldadst; a.ldasrc = ldasrc; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.lddadst = lddadst; a.lddasrc = lddasrc; a.lddv = lddv;
     a.H = heads; a.dv = dv; a.slope = negative_slope;
     with_dropout<sx::GatDropArgs>(a, drop, [&](const auto &args) {
-        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, args, perm, d_dbias != nullptr, call.s); });
+        call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, args, perm, false, call.s); });
     });
-    name_pass(h, "gat_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    return call.close("gat_fused_backward", drop != nullptr);
 }
 
 }  // namespace

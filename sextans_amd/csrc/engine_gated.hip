@@ -3,9 +3,8 @@
 //                                           divided by the sum of the gates + eps (NORM); optionally the gates' sum and the pre-activations z
 //   sextans_spmm_gated_workspace_floats     the floats of workspace the backward needs (NORM: gn = G / (den + eps), M x N; SUM: none)
 //   sextans_spmm_gated_backward_device_rm   dxdst and dE (a row pass over A), dxsrc and dV (a column pass over A^T), each only when asked for
-// Kernels: spmm_gated_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_edge.hip: the row softmax's of this engine for
-// the forward and the row pass, those of the companion engine that holds A^T for the column pass.  Only the pattern is read: neither the
-// engine's values nor any of its packed forms is read or touched.
+// Kernels: spmm_gated_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the pattern is
+// read: neither the engine's values nor any of its packed forms is read or touched.
 #include "pattern_launch.h"
 #include "spmm_gated_kernels.h"
 
@@ -29,8 +28,6 @@ void launch_pass(const sextans_engine *e, const sx::GatedArgs &a, const int *per
     });
 }
 
-bool bad_ld_of(const void *p, int64_t ld, int N) { return p && bad_ld(ld, N); }
-bool too_many_tiles(int N) { return (N + kMaxTile - 1) / kMaxTile > kMaxTiles; }
 bool bad_mode(int mode) { return mode != SEXTANS_GATE_SUM && mode != SEXTANS_GATE_NORM; }
 bool bad_eps(int mode, float eps) { return mode == SEXTANS_GATE_NORM && (!(eps > 0.0f) || std::isinf(eps)); }
 // the operand struct: xdst, xsrc and V with their leading dimensions always, E's when it is given
@@ -48,34 +45,28 @@ extern "C" {
 
 int sextans_spmm_gated_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in, float *d_C, int64_t ldc,
                                  float *d_den, int64_t ldden, float *d_z, int64_t ldz, void *stream) {
-    if (!h || !in || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (!h || !in || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_in(in, N) || bad_ld(ldc, N) || bad_ld_of(d_den, ldden, N) || bad_ld_of(d_z, ldz, N)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_C, d_den, d_z)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!in->d_xdst || !in->d_xsrc || !in->d_v || !d_C)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty (z has no element)
-        attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        attention_fill(d_den, h->M, N, ldden, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!in->d_xdst || !in->d_xsrc || !in->d_v || !d_C, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty (z has no element)
+        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
+        attention_fill(d_den, h->M, N, ldden, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::GatedArgs a{};
     a.xdst = in->d_xdst; a.xsrc = in->d_xsrc; a.V = in->d_v; a.E = in->d_e;
     a.ld_xdst = in->ld_xdst; a.ld_xsrc = in->ld_xsrc; a.ld_v = in->ld_v; a.ld_e = in->ld_e;
     a.out = d_C; a.den = d_den; a.z = d_z; a.ldc = ldc; a.ldden = ldden; a.ldz = ldz;
     a.norm = mode == SEXTANS_GATE_NORM; a.eps = eps; a.N = N;
-    launch_pass<sx::kAttnForward>(h, a, nullptr, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_gated", false, h->softmax.nchunks > 0);
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, a, perm, call.s); });
+    return call.close("spmm_gated");
 }
 
 int64_t sextans_spmm_gated_workspace_floats(sextans_handle_t h, int mode, int N) {
-    if (!h || bad_mode(mode) || bad_n(N) || too_many_tiles(N)) return -(int64_t)SEXTANS_ERR_INVALID;
+    if (!h || bad_mode(mode) || bad_n(N) || too_many_tiles(N, kMaxTile)) return -(int64_t)SEXTANS_ERR_INVALID;
     if (!h->d_rp) return -(int64_t)SEXTANS_ERR_STATE;
     return mode == SEXTANS_GATE_NORM ? (int64_t)h->M * N : 0;
 }
@@ -83,7 +74,7 @@ int64_t sextans_spmm_gated_workspace_floats(sextans_handle_t h, int mode, int N)
 int sextans_spmm_gated_backward_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in, const float *d_C, int64_t ldc,
                                           const float *d_den, int64_t ldden, const float *d_G, int64_t ldg, const float *d_Gz, int64_t ldgz,
                                           const sextans_gated_grad *out, float *d_work, void *stream) {
-    if (!h || !in || !out || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;
+    if (!h || !in || !out || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;
     const bool norm = mode == SEXTANS_GATE_NORM;
     if (!norm) d_C = d_den = nullptr;   // SUM ignores them
     if (bad_in(in, N) || bad_ld_of(d_C, ldc, N) || bad_ld_of(d_den, ldden, N) || bad_ld(ldg, N) || bad_ld_of(d_Gz, ldgz, N)) return SEXTANS_ERR_INVALID;
@@ -92,20 +83,16 @@ int sextans_spmm_gated_backward_device_rm(sextans_handle_t h, int mode, float ep
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_C, d_den, d_G, d_Gz, out->d_dxdst, out->d_dxsrc, out->d_dv, out->d_de, d_work)) return SEXTANS_ERR_INVALID;
     if (!out->d_dxdst && !out->d_dxsrc && !out->d_dv && !out->d_de) return SEXTANS_ERR_INVALID;   // nothing to compute
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!in->d_xdst || !in->d_xsrc || !in->d_v || !d_G || (norm && (!d_C || !d_den || !d_work)))) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // (dE has no element)
-        attention_fill(out->d_dxdst, h->M, N, out->ld_dxdst, 0.0f, s);
-        attention_fill(out->d_dxsrc, h->K, N, out->ld_dxsrc, 0.0f, s);
-        attention_fill(out->d_dv, h->K, N, out->ld_dv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!in->d_xdst || !in->d_xsrc || !in->d_v || !d_G || (norm && (!d_C || !d_den || !d_work)), stream)) return rc;
+    if (call.degenerate()) {   // (dE has no element)
+        attention_fill(out->d_dxdst, h->M, N, out->ld_dxdst, 0.0f, call.s);
+        attention_fill(out->d_dxsrc, h->K, N, out->ld_dxsrc, 0.0f, call.s);
+        attention_fill(out->d_dv, h->K, N, out->ld_dv, 0.0f, call.s);
+        return call.done();
     }
     const bool rows = out->d_dxdst || out->d_de, cols = out->d_dxsrc || out->d_dv;
-    if (int rc = cols ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(cols)) return rc;
     sx::GatedArgs a{};
     a.xdst = in->d_xdst; a.xsrc = in->d_xsrc; a.V = in->d_v; a.E = in->d_e;
     a.ld_xdst = in->ld_xdst; a.ld_xsrc = in->ld_xsrc; a.ld_v = in->ld_v; a.ld_e = in->ld_e;
@@ -116,22 +103,13 @@ int sextans_spmm_gated_backward_device_rm(sextans_handle_t h, int mode, float ep
     a.norm = norm; a.eps = eps; a.N = N;
     if (norm) {   // gn once, for both passes
         const long long items = (long long)h->M * (N / 4);
-        hipLaunchKernelGGL(sx::gated_gn, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (long long)h->M, N / 4, d_G, (long long)ldg, d_den,
-                           (long long)ldden, eps, d_work);
+        hipLaunchKernelGGL(sx::gated_gn, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, call.s, (long long)h->M, N / 4, d_G, (long long)ldg,
+                           d_den, (long long)ldden, eps, d_work);
         a.gn = d_work; a.ldgn = N;
     }
-    bool long_rows = false;
-    if (cols) {
-        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
-    }
-    if (rows) {
-        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, s);
-        long_rows |= h->softmax.nchunks > 0;
-    }
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_gated_backward", false, long_rows);
-    return SEXTANS_OK;
+    if (cols) call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, a, perm, call.s); });
+    if (rows) call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, a, perm, call.s); });
+    return call.close("spmm_gated_backward");
 }
 
 }  // extern "C"

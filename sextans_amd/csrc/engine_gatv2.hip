@@ -3,8 +3,7 @@
 //   sextans_gatv2_attention_device            O = softmax(att . LeakyReLU(x_dst[r] + x_src[c]) + bias on A's pattern) x_src per head, and lse
 //   sextans_gatv2_attention_backward_device   dx_dst, dx_src, datt (and dbias): a row pass over A, a column pass over A^T, the two-level datt sum
 //   sextans_gatv2_attention_dropout_device / _dropout_backward_device   the same with dropout on the attention coefficients (dropout_hash.h)
-// Kernels: gatv2_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_gat.hip: the row softmax's of this engine for
-// the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
+// Kernels: gatv2_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  A's values are never read.
 #include "gatv2_kernels.h"
 #include "pattern_launch.h"
 
@@ -29,7 +28,7 @@ void launch_pass(const sextans_engine *e, const Args &a, const int *perm, bool h
     });
 }
 
-int64_t chunks_of(int64_t M) { return (M + sx::kGatv2Chunk - 1) / sx::kGatv2Chunk; }
+static_assert(sx::kGatv2Chunk == 256, "chunks_of (pattern_launch.h) counts the chunks of gatv2_datt_chunks");
 
 }  // namespace
 
@@ -67,25 +66,22 @@ int gatv2_forward(sextans_handle_t h, int heads, int d, float negative_slope, co
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_xdst, d_xsrc, d_att, d_bias, d_O, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_O, h->M, (int)hd, ldo, 0.0f, s);
-        attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_O, h->M, (int)hd, ldo, 0.0f, call.s);
+        attention_fill(d_lse, h->M, heads, heads, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::Gatv2Args a{};
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.att = d_att; a.bias = d_bias; a.out = d_O; a.out_lse = d_lse;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo;
     a.H = heads; a.d = d; a.slope = negative_slope;
-    with_dropout<sx::Gatv2DropArgs>(a, drop, [&](const auto &args) { launch_pass<sx::kAttnForward>(h, args, nullptr, false, s); });
-    name_pass(h, "gatv2_fused", drop != nullptr, h->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    with_dropout<sx::Gatv2DropArgs>(a, drop, [&](const auto &args) {
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, args, perm, false, call.s); });
+    });
+    return call.close("gatv2_fused", drop != nullptr);
 }
 
 int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, const float *d_xdst, int64_t ldxd, const float *d_xsrc, int64_t ldxs,
@@ -99,37 +95,31 @@ int gatv2_backward(sextans_handle_t h, int heads, int d, float negative_slope, c
     const int64_t hd = (int64_t)heads * d;
     if (bad_ld(ldxd, hd) || bad_ld(ldxs, hd) || bad_ld(ldo, hd) || bad_ld(ldg, hd) || bad_ld(lddxd, hd) || bad_ld(lddxs, hd)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_xdst, d_xsrc, d_att, d_bias, d_O, d_lse, d_G, d_delta, d_dxdst, d_dxsrc, d_datt, d_work, d_dbias)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse || !d_G || !d_delta || !d_dxdst || !d_dxsrc || !d_datt || !d_work))
-        return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t nchunks = chunks_of(h->M);
+    PatternCall call{h};
+    if (int rc = call.open(!d_xdst || !d_xsrc || !d_att || !d_O || !d_lse || !d_G || !d_delta || !d_dxdst || !d_dxsrc || !d_datt || !d_work, stream))
+        return rc;
     float *d_part = d_work ? d_work + (int64_t)h->M * hd : nullptr;
-    if (h->M == 0 || h->nnz == 0) {
-        attention_fill(d_delta, h->M, heads, heads, 0.0f, s);
-        attention_fill(d_dxdst, h->M, (int)hd, lddxd, 0.0f, s);
-        attention_fill(d_dxsrc, h->K, (int)hd, lddxs, 0.0f, s);
-        attention_fill(d_work, h->M, (int)hd, hd, 0.0f, s);   // datt_rows and the chunk sums: what the passes would have left
-        attention_fill(d_part, nchunks, (int)hd, hd, 0.0f, s);
-        attention_fill(d_datt, 1, (int)hd, hd, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    if (call.degenerate()) {
+        attention_fill(d_delta, h->M, heads, heads, 0.0f, call.s);
+        attention_fill(d_dxdst, h->M, (int)hd, lddxd, 0.0f, call.s);
+        attention_fill(d_dxsrc, h->K, (int)hd, lddxs, 0.0f, call.s);
+        attention_fill(d_work, h->M, (int)hd, hd, 0.0f, call.s);   // datt_rows and the chunk sums: what the passes would have left
+        attention_fill(d_part, chunks_of(h->M), (int)hd, hd, 0.0f, call.s);
+        attention_fill(d_datt, 1, (int)hd, hd, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = ensure_backward_tables(h, s)) return rc;
+    if (int rc = call.tables(true)) return rc;
     sx::Gatv2Args a{};
     a.xdst = d_xdst; a.xsrc = d_xsrc; a.att = d_att; a.bias = d_bias; a.O = d_O; a.lse = d_lse; a.G = d_G; a.delta = d_delta;
     a.out_delta = d_delta; a.dxdst = d_dxdst; a.dxsrc = d_dxsrc; a.datt_rows = d_work; a.dbias = d_dbias;
     a.ldxd = ldxd; a.ldxs = ldxs; a.ldo = ldo; a.ldg = ldg; a.lddxd = lddxd; a.lddxs = lddxs;
     a.H = heads; a.d = d; a.slope = negative_slope;
     with_dropout<sx::Gatv2DropArgs>(a, drop, [&](const auto &args) {
-        launch_pass<sx::kAttnBackwardRows>(h, args, nullptr, d_dbias != nullptr, s);
-        launch_pass<sx::kAttnBackwardCols>(h->tr, args, h->at.d_tperm, false, s);
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, args, perm, d_dbias != nullptr, call.s); });
+        call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, args, perm, false, call.s); });
     });
-    name_pass(h, "gatv2_fused_backward", drop != nullptr, h->softmax.nchunks > 0 || h->tr->softmax.nchunks > 0);
-    column_sum_two_level(d_work, h->M, (int)hd, d_part, d_datt, s);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    column_sum_two_level(d_work, h->M, (int)hd, d_part, d_datt, call.s);
+    return call.close("gatv2_fused_backward", drop != nullptr);
 }
 
 }  // namespace

@@ -3,8 +3,7 @@
 //   sextans_score_attention_device            SOFTMAX: O = softmax(S on A's pattern) V per head and the rows' log-sum-exp; WEIGHT: O = S V per head
 //   sextans_score_attention_backward_device   dS (nnz x heads, stored per element) and dV from the upstream gradient: a row pass over A, a
 //                                             column pass over A^T; either may be skipped
-// Kernels: score_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_gat.hip: the row softmax's of this engine for the
-// forward and the row pass, those of the companion engine that holds A^T for the column pass; A's values are never read.
+// Kernels: score_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  A's values are never read.
 #include "score_kernels.h"
 #include "pattern_launch.h"
 
@@ -58,25 +57,22 @@ int sextans_score_attention_device(sextans_handle_t h, int mode, int heads, int 
     if (dmode == Dropout::kPlain) drop = nullptr;
     if (lds < heads || bad_ld(ldv, (int64_t)heads * dv) || bad_ld(ldo, (int64_t)heads * dv)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_S, d_V, d_O, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > 0 && (!d_S || !d_V || !d_O || (soft && !d_lse))) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, s);
-        if (soft) attention_fill(d_lse, h->M, heads, heads, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_S || !d_V || !d_O || (soft && !d_lse), stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_O, h->M, heads * dv, ldo, 0.0f, call.s);
+        if (soft) attention_fill(d_lse, h->M, heads, heads, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::ScoreArgs a{};
     a.S = d_S; a.V = d_V; a.out = d_O; a.out_lse = d_lse;
     a.lds = lds; a.ldv = ldv; a.ldo = ldo;
     a.H = heads; a.dv = dv;
-    with_dropout<sx::ScoreDropArgs>(a, drop, [&](const auto &args) { launch_mode<sx::kAttnForward>(mode, h, args, nullptr, s); });
-    name_pass(h, base_name(mode, false), drop != nullptr, h->softmax.nchunks > 0);
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    with_dropout<sx::ScoreDropArgs>(a, drop, [&](const auto &args) {
+        call.rows([&](const sextans_engine *e, const int *perm) { launch_mode<sx::kAttnForward>(mode, e, args, perm, call.s); });
+    });
+    return call.close(base_name(mode, false), drop != nullptr);
 }
 
 int sextans_score_attention_backward_device(sextans_handle_t h, int mode, int heads, int dv, const float *d_S, int64_t lds, const float *d_V,
@@ -91,28 +87,24 @@ int sextans_score_attention_backward_device(sextans_handle_t h, int mode, int he
     // (WEIGHT reads no O: its ldo is not looked at)
     if (lds < heads || ldds < heads || bad_ld(ldv, hdv) || (soft && bad_ld(ldo, hdv)) || bad_ld(ldg, hdv) || bad_ld(lddv, hdv)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_S, d_V, d_O, d_lse, d_G, d_dS, d_dV)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
+    if (!h->d_rp) return SEXTANS_ERR_STATE;            // this family documents "nothing to compute" after STATE: both stay here
     if (!d_dS && !d_dV) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_S || !d_V || !d_G || (soft && (!d_O || !d_lse)))) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // (no entries: dS has no element)
-        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_S || !d_V || !d_G || (soft && (!d_O || !d_lse)), stream)) return rc;
+    if (call.degenerate()) {   // (no entries: dS has no element)
+        attention_fill(d_dV, h->K, (int)hdv, lddv, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = d_dV ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dV != nullptr)) return rc;
     sx::ScoreArgs a{};
     a.S = d_S; a.V = d_V; a.O = d_O; a.lse = d_lse; a.G = d_G; a.dS = d_dS; a.dV = d_dV;
     a.lds = lds; a.ldv = ldv; a.ldo = ldo; a.ldg = ldg; a.ldds = ldds; a.lddv = lddv;
     a.H = heads; a.dv = dv;
     with_dropout<sx::ScoreDropArgs>(a, drop, [&](const auto &args) {
-        if (d_dS) launch_mode<sx::kAttnBackwardRows>(mode, h, args, nullptr, s);
-        if (d_dV) launch_mode<sx::kAttnBackwardCols>(mode, h->tr, args, h->at.d_tperm, s);
+        if (d_dS) call.rows([&](const sextans_engine *e, const int *perm) { launch_mode<sx::kAttnBackwardRows>(mode, e, args, perm, call.s); });
+        if (d_dV) call.cols([&](const sextans_engine *e, const int *perm) { launch_mode<sx::kAttnBackwardCols>(mode, e, args, perm, call.s); });
     });
-    name_pass(h, base_name(mode, true), drop != nullptr, (d_dS && h->softmax.nchunks > 0) || (d_dV && h->tr->softmax.nchunks > 0));
-    SX_HIP(hipGetLastError());
-    return SEXTANS_OK;
+    return call.close(base_name(mode, true), drop != nullptr);
 }
 
 }  // extern "C"

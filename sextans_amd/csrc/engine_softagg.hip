@@ -3,9 +3,8 @@
 //   sextans_spmm_softagg_workspace_floats     the floats of workspace dt needs (dt_rows, then the chunk sums)
 //   sextans_spmm_softagg_backward_device_rm   dB, dval and dt from C, lse and the upstream gradient: a column pass over A^T, a row pass
 //                                             over A, the two-level dt sum
-// Kernels: spmm_softagg_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_reduce.hip: the row softmax's of this engine
-// for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  The values come through an
-// explicit pointer (NULL: the engine's current ones); none of the engine's packed forms is read or touched.
+// Kernels: spmm_softagg_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  The values come
+// through an explicit pointer (NULL: the engine's current ones); none of the engine's packed forms is read or touched.
 #include "pattern_launch.h"
 #include "spmm_softagg_kernels.h"
 
@@ -31,8 +30,6 @@ void launch_pass(const sextans_engine *e, const sx::SoftaggArgs &a, const int *p
     });
 }
 
-int64_t chunks_of(int64_t M) { return (M + 255) / 256; }   // the chunks of column_sum_two_level
-
 }  // namespace
 }  // namespace sxe
 
@@ -45,25 +42,19 @@ int sextans_spmm_softagg_device_rm(sextans_handle_t h, int N, const float *d_val
     if (!h || bad_n(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (bad_ld(ldb, N) || bad_ld(ldc, N) || bad_ld(ldlse, N)) return SEXTANS_ERR_INVALID;
     if (misaligned(d_val, d_B, d_t, d_C, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_B || !d_C)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_B || !d_C, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
+        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::SoftaggArgs a{};
     a.val = d_val ? d_val : h->d_v; a.B = d_B; a.t = d_t; a.out = d_C; a.out_lse = d_lse;
     a.ldb = ldb; a.ldc = ldc; a.ldlse = ldlse; a.N = N;
-    launch_pass<sx::kAttnForward>(h, a, nullptr, false, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_softagg", false, h->softmax.nchunks > 0);
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, a, perm, false, call.s); });
+    return call.close("spmm_softagg");
 }
 
 int64_t sextans_spmm_softagg_workspace_floats(sextans_handle_t h, int N) {
@@ -80,39 +71,26 @@ int sextans_spmm_softagg_backward_device_rm(sextans_handle_t h, int N, const flo
     if (misaligned(d_val, d_B, d_t, d_C, d_lse, d_G, d_dB, d_dval, d_dt, d_work)) return SEXTANS_ERR_INVALID;
     if (!d_dB && !d_dval && !d_dt) return SEXTANS_ERR_INVALID;   // nothing to compute
     if (d_dt && !d_work) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_B || !d_C || !d_lse || !d_G)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
+    PatternCall call{h};
+    if (int rc = call.open(!d_B || !d_C || !d_lse || !d_G, stream)) return rc;
     float *d_rows = d_dt ? d_work : nullptr;   // the workspace is written only for dt
     float *d_part = d_rows ? d_rows + (int64_t)h->M * N : nullptr;
-    if (h->M == 0 || h->nnz == 0) {   // (dval has no element)
-        attention_fill(d_dB, h->K, N, lddb, 0.0f, s);
-        attention_fill(d_rows, h->M, N, N, 0.0f, s);   // dt_rows and the chunk sums: what the passes would have left
-        attention_fill(d_part, chunks_of(h->M), N, N, 0.0f, s);
-        attention_fill(d_dt, 1, N, N, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    if (call.degenerate()) {   // (dval has no element)
+        attention_fill(d_dB, h->K, N, lddb, 0.0f, call.s);
+        attention_fill(d_rows, h->M, N, N, 0.0f, call.s);   // dt_rows and the chunk sums: what the passes would have left
+        attention_fill(d_part, chunks_of(h->M), N, N, 0.0f, call.s);
+        attention_fill(d_dt, 1, N, N, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = d_dB ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dB != nullptr)) return rc;
     sx::SoftaggArgs a{};
     a.val = d_val ? d_val : h->d_v; a.B = d_B; a.t = d_t; a.C = d_C; a.lse = d_lse; a.G = d_G;
     a.dB = d_dB; a.dval = d_dval; a.dt_rows = d_rows;
     a.ldb = ldb; a.ldc = ldc; a.ldlse = ldlse; a.ldg = ldg; a.lddb = lddb; a.N = N;
-    bool long_rows = false;
-    if (d_dB) {
-        launch_pass<sx::kAttnBackwardCols>(h->tr, a, h->at.d_tperm, false, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
-    }
-    if (d_dval || d_dt) {
-        launch_pass<sx::kAttnBackwardRows>(h, a, nullptr, true, s);
-        long_rows |= h->softmax.nchunks > 0;
-    }
-    if (d_dt) column_sum_two_level(d_rows, h->M, N, d_part, d_dt, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "spmm_softagg_backward", false, long_rows);
-    return SEXTANS_OK;
+    if (d_dB) call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, a, perm, false, call.s); });
+    if (d_dval || d_dt) call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, a, perm, true, call.s); });
+    if (d_dt) column_sum_two_level(d_rows, h->M, N, d_part, d_dt, call.s);
+    return call.close("spmm_softagg_backward");
 }
 
 }  // extern "C"

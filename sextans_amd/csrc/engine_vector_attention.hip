@@ -4,9 +4,8 @@
 //                                                 V[c, n] + D[e, n] | D[e, n] (msg: SEXTANS_VATT_*), and lse
 //   sextans_vector_attention_backward_device_rm   dS, dD and dV from C, lse and the upstream gradient: a row pass over A that stores dS and
 //                                                 dD, a column pass over A^T for dV
-// Kernels: vector_attention_kernels.h on the row walking of pattern_pass.h.  Tables as in engine_edge_softagg.hip: the row softmax's of
-// this engine for the forward and the row pass, those of the companion engine that holds A^T for the column pass.  Only the pattern is
-// read: neither the engine's values nor any of its packed forms is read or touched.
+// Kernels: vector_attention_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the pattern
+// is read: neither the engine's values nor any of its packed forms is read or touched.
 // The row pass runs when dS or dD is asked for, the column pass (and the transpose) only for dV.  The row pass's two stores are
 // PREDICATED on their pointers, not compile-time switches, as engine_edge_softagg.hip's dE store is and for its reason.
 // All 3 passes x 3 messages x 4 widths x 2 kernels (less EDGE's column pass: 64) are instantiated here.
@@ -45,8 +44,6 @@ void launch_msg(int msg, const sextans_engine *e, const sx::VectorAttnArgs &a, c
 bool bad_msg(int msg) { return msg < SEXTANS_VATT_NODE || msg > SEXTANS_VATT_EDGE; }
 bool reads_v(int msg) { return msg != SEXTANS_VATT_EDGE; }
 bool reads_d(int msg) { return msg != SEXTANS_VATT_NODE; }
-bool bad_ld_of(const void *p, int64_t ld, int N) { return p && bad_ld(ld, N); }   // an optional operand: its leading dimension counts when it is given
-bool too_many_tiles(int N) { return (N + kMaxTile - 1) / kMaxTile > kMaxTiles; }
 
 }  // namespace
 }  // namespace sxe
@@ -57,38 +54,32 @@ extern "C" {
 
 int sextans_vector_attention_device_rm(sextans_handle_t h, int msg, int N, const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
                                        const float *d_D, int64_t ldd, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream) {
-    if (!h || bad_msg(msg) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
+    if (!h || bad_msg(msg) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
     if (!reads_v(msg)) d_V = nullptr;   // an operand the mode does not read is ignored, with its leading dimension
     if (!reads_d(msg)) d_D = nullptr;
     if (bad_ld(lds, N) || (reads_v(msg) && bad_ld(ldv, N)) || (reads_d(msg) && bad_ld(ldd, N)) || bad_ld(ldc, N) || bad_ld_of(d_lse, ldlse, N))
         return SEXTANS_ERR_INVALID;
     if (misaligned(d_S, d_V, d_D, d_C, d_lse)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_S || (reads_v(msg) && !d_V) || (reads_d(msg) && !d_D) || !d_C)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // every row is empty
-        attention_fill(d_C, h->M, N, ldc, 0.0f, s);
-        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_S || (reads_v(msg) && !d_V) || (reads_d(msg) && !d_D) || !d_C, stream)) return rc;
+    if (call.degenerate()) {   // every row is empty
+        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
+        attention_fill(d_lse, h->M, N, ldlse, -INFINITY, call.s);
+        return call.done();
     }
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(false)) return rc;
     sx::VectorAttnArgs a{};
     a.S = d_S; a.V = d_V; a.D = d_D; a.out = d_C; a.out_lse = d_lse;
     a.lds = lds; a.ldv = ldv; a.ldd = ldd; a.ldc = ldc; a.ldlse = ldlse; a.N = N;
-    launch_msg<sx::kAttnForward>(msg, h, a, nullptr, s);
-    SX_HIP(hipGetLastError());
-    name_pass(h, "vector_attention", false, h->softmax.nchunks > 0);
-    return SEXTANS_OK;
+    call.rows([&](const sextans_engine *e, const int *perm) { launch_msg<sx::kAttnForward>(msg, e, a, perm, call.s); });
+    return call.close("vector_attention");
 }
 
 int sextans_vector_attention_backward_device_rm(sextans_handle_t h, int msg, int N, const float *d_S, int64_t lds, const float *d_V, int64_t ldv,
                                                 const float *d_D, int64_t ldd, const float *d_C, int64_t ldc, const float *d_lse, int64_t ldlse,
                                                 const float *d_G, int64_t ldg, float *d_dS, int64_t ldds, float *d_dV, int64_t lddv,
                                                 float *d_dD, int64_t lddd, void *stream) {
-    if (!h || bad_msg(msg) || bad_n(N) || too_many_tiles(N)) return SEXTANS_ERR_INVALID;
+    if (!h || bad_msg(msg) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;
     if (!reads_v(msg)) d_V = nullptr;
     if (!reads_d(msg)) d_D = nullptr;
     if (bad_ld(lds, N) || (reads_v(msg) && bad_ld(ldv, N)) || (reads_d(msg) && bad_ld(ldd, N)) || bad_ld(ldc, N) || bad_ld(ldlse, N) ||
@@ -98,33 +89,20 @@ int sextans_vector_attention_backward_device_rm(sextans_handle_t h, int msg, int
     if (!d_dS && !d_dV && !d_dD) return SEXTANS_ERR_INVALID;   // nothing to compute
     if (d_dV && !reads_v(msg)) return SEXTANS_ERR_INVALID;     // a gradient of an operand the mode does not read
     if (d_dD && !reads_d(msg)) return SEXTANS_ERR_INVALID;
-    if (!h->d_rp) return SEXTANS_ERR_STATE;
-    if (h->nnz > INT32_MAX) return SEXTANS_ERR_INVALID;
-    if (h->nnz > 0 && (!d_S || (reads_v(msg) && !d_V) || (reads_d(msg) && !d_D) || !d_C || !d_lse || !d_G)) return SEXTANS_ERR_INVALID;
-    SX_HIP(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    if (h->M == 0 || h->nnz == 0) {   // (dS and dD have no element)
-        attention_fill(d_dV, h->K, N, lddv, 0.0f, s);
-        SX_HIP(hipGetLastError());
-        return SEXTANS_OK;
+    PatternCall call{h};
+    if (int rc = call.open(!d_S || (reads_v(msg) && !d_V) || (reads_d(msg) && !d_D) || !d_C || !d_lse || !d_G, stream)) return rc;
+    if (call.degenerate()) {   // (dS and dD have no element)
+        attention_fill(d_dV, h->K, N, lddv, 0.0f, call.s);
+        return call.done();
     }
-    if (int rc = d_dV ? ensure_backward_tables(h, s) : ensure_softmax_tables(h, s)) return rc;
+    if (int rc = call.tables(d_dV != nullptr)) return rc;
     sx::VectorAttnArgs a{};
     a.S = d_S; a.V = d_V; a.D = d_D; a.C = d_C; a.lse = d_lse; a.G = d_G;
     a.dS = d_dS; a.dV = d_dV; a.dD = d_dD;
     a.lds = lds; a.ldv = ldv; a.ldd = ldd; a.ldc = ldc; a.ldlse = ldlse; a.ldg = ldg; a.ldds = ldds; a.lddv = lddv; a.lddd = lddd; a.N = N;
-    bool long_rows = false;
-    if (d_dV) {
-        launch_msg<sx::kAttnBackwardCols>(msg, h->tr, a, h->at.d_tperm, s);
-        long_rows |= h->tr->softmax.nchunks > 0;
-    }
-    if (d_dS || d_dD) {
-        launch_msg<sx::kAttnBackwardRows>(msg, h, a, nullptr, s);
-        long_rows |= h->softmax.nchunks > 0;
-    }
-    SX_HIP(hipGetLastError());
-    name_pass(h, "vector_attention_backward", false, long_rows);
-    return SEXTANS_OK;
+    if (d_dV) call.cols([&](const sextans_engine *e, const int *perm) { launch_msg<sx::kAttnBackwardCols>(msg, e, a, perm, call.s); });
+    if (d_dS || d_dD) call.rows([&](const sextans_engine *e, const int *perm) { launch_msg<sx::kAttnBackwardRows>(msg, e, a, perm, call.s); });
+    return call.close("vector_attention_backward");
 }
 
 }  // extern "C"

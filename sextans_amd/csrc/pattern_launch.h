@@ -1,8 +1,7 @@
-// pattern_launch.h -- the host side of the pattern passes (pattern_pass.h), shared by engine_attention.hip, engine_attention_edge.hip,
-// engine_gat.hip, engine_gatv2.hip, engine_reduce.hip, engine_multi.hip, engine_softagg.hip, engine_edge.hip, engine_gated.hip, engine_edge_softagg.hip, engine_vector_attention.hip, engine_edge_op.hip and (through edge_multi_launch.h, the
-// launcher that engine_edge_multi.hip and its per-op sources engine_edge_multi_*.hip share) the edge multi-aggregation, and included by nothing else: the launch of a pass, the width table, the
-// argument checks, the degenerate-call fill, the backward's tables and the dropout variant.  What a family keeps: its Args, its entry
-// points and the entries in flight per slot (U) of each of its passes.
+// pattern_launch.h -- the host side of the pattern passes (pattern_pass.h): included by the engine_*.hip of every pattern-pass family
+// and by nothing else.  The argument checks, the degenerate-call fill, the dropout variant, the frame of an entry point (PatternCall),
+// the width table and the launch of a pass.  What a family keeps: its Args, the entries in flight per slot (U) of each of its passes,
+// its tile cap, and its entry points -- their own argument checks, the fills of a degenerate call, and what each pass launches.
 #pragma once
 #include <cmath>
 #include <string>
@@ -30,6 +29,9 @@ constexpr int kMaxTiles = 65535;   // the long-row kernel's grid has one y per c
 inline bool bad_dim(int d) { return d < 8 || d > 128 || (d % 8) != 0; }                              // a head dimension
 inline bool bad_n(int N) { return N < 8 || (N % 8) != 0 || (N + 127) / 128 > kMaxTiles; }            // the columns of a tiled family
 inline bool bad_ld(int64_t ld, int64_t need) { return ld < need || (ld % 4) != 0; }
+inline bool bad_ld_of(const void *p, int64_t ld, int64_t need) { return p && bad_ld(ld, need); }    // an optional operand: its leading dimension counts when it is given
+inline bool too_many_tiles(int N, int max_tile) { return (N + max_tile - 1) / max_tile > kMaxTiles; }   // a family that caps its tile below 128
+inline int64_t chunks_of(int64_t M) { return (M + 255) / 256; }                                      // the chunks of column_sum_two_level (engine_state.h)
 inline bool bad_slope(float s) { return !(s >= 0.0f) || std::isinf(s); }
 template <class... Ptr>
 bool misaligned(const Ptr *...p) { return ((reinterpret_cast<uintptr_t>(p) | ... | 0) & 15) != 0; }   // some pointer is not 16-byte aligned (NULL is)
@@ -39,13 +41,6 @@ template <class T>
 void fill(T *out, int64_t rows, int cols, int64_t ld, T value, hipStream_t s) {
     if (!out || rows <= 0 || cols <= 0) return;
     hipLaunchKernelGGL(sx::pattern_fill<T>, dim3((unsigned)((rows * cols + 255) / 256)), dim3(256), 0, s, (long long)rows, cols, (long long)ld, value, out);
-}
-
-// what a backward with a column pass walks: the softmax tables of h, A^T behind the companion h->tr, and the companion's tables
-inline int ensure_backward_tables(sextans_engine *h, hipStream_t s) {
-    if (int rc = ensure_softmax_tables(h, s)) return rc;
-    if (int rc = ensure_transpose(h, s)) return rc;
-    return ensure_softmax_tables(h->tr, s);   // A^T's rows: the tables of the column pass
 }
 
 // --- dropout -------------------------------------------------------------------------------------------------------------------------
@@ -65,11 +60,60 @@ void with_dropout(const Args &a, const sextans_dropout *drop, F &&f) {
     ad.drop = sx::dropout_args(drop->p, drop->seed, drop->d_step);
     f(ad);
 }
-// last_kernel = base [+dropout] [+long_rows]
-inline void name_pass(sextans_engine *h, const char *base, bool dropout, bool long_rows) {
-    h->last_kernel_buf = std::string(base) + (dropout ? "+dropout" : "") + (long_rows ? "+long_rows" : "");
-    h->last_kernel = h->last_kernel_buf.c_str();
-}
+
+// --- the frame of an entry point -----------------------------------------------------------------------------------------------------
+// What every entry point does between its own argument checks and its return, in the order of its calls:
+//     PatternCall call{h};
+//     if (int rc = call.open(<a required operand is NULL>, stream)) return rc;
+//     if (call.degenerate()) { <fill the outputs on call.s>; return call.done(); }
+//     if (int rc = call.tables(<a column pass runs>)) return rc;
+//     <Args>;  call.cols(f) and / or call.rows(f), f(engine, perm) launching the family's pass;
+//     return call.close("name", dropout);
+// Nothing before open's STATE return touches a non-trivial member of *h (the ABI tests hand in a zeroed buffer).
+struct PatternCall {
+    sextans_engine *h;
+    hipStream_t s = nullptr;
+    bool long_rows = false;   // some pass so far walked an engine with rows beyond kSoftmaxChunk
+
+    // STATE without a matrix; INVALID for more entries than an int indexes and for a missing operand when there are entries; the device
+    int open(bool operand_missing, void *stream) {
+        if (!h->d_rp) return SEXTANS_ERR_STATE;
+        if (h->nnz > INT32_MAX || (h->nnz > 0 && operand_missing)) return SEXTANS_ERR_INVALID;
+        SX_HIP(hipSetDevice(h->device));
+        s = (hipStream_t)stream;
+        return SEXTANS_OK;
+    }
+    // no rows or no entries: the family fills its outputs, then done() -- last_kernel stays what it was
+    bool degenerate() const { return h->M == 0 || h->nnz == 0; }
+    int done() const {
+        SX_HIP(hipGetLastError());
+        return SEXTANS_OK;
+    }
+    // the softmax tables of h; cols: also A^T behind the companion h->tr and the companion's tables, what a column pass walks
+    int tables(bool cols) {
+        if (int rc = ensure_softmax_tables(h, s)) return rc;
+        if (!cols) return SEXTANS_OK;
+        if (int rc = ensure_transpose(h, s)) return rc;
+        return ensure_softmax_tables(h->tr, s);
+    }
+    // f(e, perm): e the engine whose CSR arrays and tables the pass walks, perm NULL over A, the transpose's permutation over A^T
+    template <class F>
+    void walk(const sextans_engine *e, const int *perm, F &&f) {
+        f(e, perm);
+        long_rows |= e->softmax.nchunks > 0;
+    }
+    template <class F>
+    void rows(F &&f) { walk(h, nullptr, f); }
+    template <class F>
+    void cols(F &&f) { walk(h->tr, h->at.d_tperm, f); }
+    // last_kernel = name [+dropout] [+long_rows], once every launch went through
+    int close(const char *name, bool dropout = false) {
+        SX_HIP(hipGetLastError());
+        h->last_kernel_buf = std::string(name) + (dropout ? "+dropout" : "") + (long_rows ? "+long_rows" : "");
+        h->last_kernel = h->last_kernel_buf.c_str();
+        return SEXTANS_OK;
+    }
+};
 
 // --- launch --------------------------------------------------------------------------------------------------------------------------
 // The slot widths: T lanes hold P 16-byte pieces each, 4 T P floats.
