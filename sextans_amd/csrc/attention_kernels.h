@@ -18,7 +18,7 @@
 #include <type_traits>
 
 #include "dropout_hash.h"
-#include "pattern_pass.h"
+#include "online_softmax.h"
 
 namespace sx {
 
@@ -87,9 +87,7 @@ struct AttnPassT {
         const long long r = act ? own : 0;
         if (PASS == kAttnForward) {
             attn_load<T, P>(x, a.Q + r * a.ldq + (long long)h * a.d, a.d, t, act);
-            f[0] = -INFINITY;
-#pragma unroll
-            for (int i = 1; i < NF; ++i) f[i] = 0.0f;
+            HeadSoftmax<W>::init(f);
         } else if (PASS == kAttnBackwardRows) {
             float o[W];
             attn_load<T, P>(x, a.Q + r * a.ldq + (long long)h * a.d, a.d, t, act);
@@ -183,14 +181,15 @@ struct AttnPassT {
             for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, valid[u] ? (PASS == kAttnBackwardCols ? perm[e[u]] : e[u]) : 0, a.H, h);
         }
         if (PASS == kAttnForward) {
+            // HeadSoftmax<W>::absorb (online_softmax.h), kept inline: the call changes this family's wide kernels (profiles/online_softmax_device_code.txt)
             float mn = f[0];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                s[u] = valid[u] ? s[u] : -INFINITY;   // (exp gives those +0, and their V pieces are zero)
-                mn = fmaxf(mn, s[u]);                 // (a NaN does not reach m; it reaches Z through its own exp)
+                s[u] = valid[u] ? s[u] : -INFINITY;
+                mn = fmaxf(mn, s[u]);
             }
-            const float mref = mn == -INFINITY ? 0.0f : mn;   // only -inf so far: everything stays +0; a ROW of only -inf ends as 0 / 0
-            const float al = softmax_exp(__fsub_rn(f[0], mref));   // 1 when m did not grow
+            const float mref = mn == -INFINITY ? 0.0f : mn;
+            const float al = softmax_exp(__fsub_rn(f[0], mref));
 #pragma unroll
             for (int i = 1; i < NF; ++i) f[i] = __fmul_rn(f[i], al);
 #pragma unroll
@@ -246,15 +245,9 @@ struct AttnPassT {
     // g <- g (+) o: commutative operations only, so both sides of a butterfly exchange compute the same bits
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnForward) {
-            const float mn = fmaxf(g[0], o[0]);
-            const float mref = mn == -INFINITY ? 0.0f : mn;
-            const float ca = softmax_exp(__fsub_rn(g[0], mref)), cb = softmax_exp(__fsub_rn(o[0], mref));
-#pragma unroll
-            for (int i = 1; i < NF; ++i) g[i] = __fadd_rn(__fmul_rn(g[i], ca), __fmul_rn(o[i], cb));
-            g[0] = mn;
+            HeadSoftmax<W>::combine(g, o);
         } else {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
+            state_add<NF>(g, o);
         }
     }
 
@@ -268,7 +261,7 @@ struct AttnPassT {
 #pragma unroll
             for (int i = 0; i < W; ++i) o[i] = n > 0 ? __fmul_rn(f[2 + i], inv) : 0.0f;
             attn_store<T, P>(o, a.out + r * a.ldo + (long long)h * a.dv, a.dv, t);
-            if (t == 0) a.out_lse[r * a.H + h] = n > 0 ? __fadd_rn(f[0], __fmul_rn(__builtin_amdgcn_logf(f[1]), 0.6931471805599453f)) : -INFINITY;
+            if (t == 0) a.out_lse[r * a.H + h] = HeadSoftmax<W>::lse(f, n);
         } else if (PASS == kAttnBackwardRows) {
             attn_store<T, P>(f, a.dQ + r * a.lddq + (long long)h * a.d, a.d, t);
         } else {

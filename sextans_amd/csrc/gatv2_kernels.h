@@ -58,9 +58,7 @@ struct Gatv2Pass {
         attn_load<T, P>(w, a.att + (long long)h * a.d, a.d, t, true);
         if (PASS == kAttnForward) {
             attn_load<T, P>(x, a.xdst + r * a.ldxd + (long long)h * a.d, a.d, t, act);
-            f[0] = -INFINITY;
-#pragma unroll
-            for (int i = 1; i < NF; ++i) f[i] = 0.0f;
+            HeadSoftmax<W>::init(f);
         } else if (PASS == kAttnBackwardRows) {
             float o[W];
             attn_load<T, P>(x, a.xdst + r * a.ldxd + (long long)h * a.d, a.d, t, act);
@@ -115,26 +113,7 @@ struct Gatv2Pass {
                 }
                 s[u] = __fadd_rn(attn_dot<T, W>(w, l), bs[u]);
             }
-            float mn = f[0];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                s[u] = valid[u] ? s[u] : -INFINITY;   // (exp gives those +0, and their x_src pieces are zero)
-                mn = fmaxf(mn, s[u]);                 // (a NaN does not reach m; it reaches Z through its own exp)
-            }
-            const float mref = mn == -INFINITY ? 0.0f : mn;   // only -inf so far: everything stays +0; a ROW of only -inf ends as 0 / 0
-            const float al = softmax_exp(__fsub_rn(f[0], mref));   // 1 when m did not grow
-#pragma unroll
-            for (int i = 1; i < NF; ++i) f[i] = __fmul_rn(f[i], al);
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float p = softmax_exp(__fsub_rn(s[u], mref));
-                f[1] = __fadd_rn(f[1], p);
-                float pm = p;
-                if constexpr (DROP) pm = __fmul_rn(mk[u], p);
-#pragma unroll
-                for (int i = 0; i < W; ++i) f[2 + i] = __fmaf_rn(pm, p1[u][i], f[2 + i]);
-            }
-            f[0] = mn;
+            HeadSoftmax<W>::template absorb<U, DROP>(f, s, valid, mk, p1);
         } else {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -173,15 +152,9 @@ struct Gatv2Pass {
     // g <- g (+) o: commutative operations only, so both sides of a butterfly exchange compute the same bits
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnForward) {
-            const float mn = fmaxf(g[0], o[0]);
-            const float mref = mn == -INFINITY ? 0.0f : mn;
-            const float ca = softmax_exp(__fsub_rn(g[0], mref)), cb = softmax_exp(__fsub_rn(o[0], mref));
-#pragma unroll
-            for (int i = 1; i < NF; ++i) g[i] = __fadd_rn(__fmul_rn(g[i], ca), __fmul_rn(o[i], cb));
-            g[0] = mn;
+            HeadSoftmax<W>::combine(g, o);
         } else {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
+            state_add<NF>(g, o);
         }
     }
 
@@ -195,7 +168,7 @@ struct Gatv2Pass {
 #pragma unroll
             for (int i = 0; i < W; ++i) o[i] = n > 0 ? __fmul_rn(f[2 + i], inv) : 0.0f;
             attn_store<T, P>(o, a.out + r * a.ldo + (long long)h * a.d, a.d, t);
-            if (t == 0) a.out_lse[r * a.H + h] = n > 0 ? __fadd_rn(f[0], __fmul_rn(__builtin_amdgcn_logf(f[1]), 0.6931471805599453f)) : -INFINITY;
+            if (t == 0) a.out_lse[r * a.H + h] = HeadSoftmax<W>::lse(f, n);
         } else if (PASS == kAttnBackwardRows) {
             attn_store<T, P>(f, a.dxdst + r * a.lddxd + (long long)h * a.d, a.d, t);
             attn_store<T, P>(f + W, a.datt_rows + (r * a.H + h) * (long long)a.d, a.d, t);

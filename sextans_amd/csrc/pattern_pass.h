@@ -1,5 +1,12 @@
-// pattern_pass.h -- the row-walking engine under every pass over the pattern of a CSR matrix: fused attention (attention_kernels.h), GAT
-// (gat_kernels.h), GATv2 (gatv2_kernels.h), max / min aggregation (spmm_reduce_kernels.h) and edge-feature SpMM (spmm_edge_kernels.h).
+// pattern_pass.h -- the row-walking engine under every pass over the pattern of a CSR matrix.  The fourteen families:
+//   softmax per head     fused attention and its edge-feature variant (attention_kernels.h), GAT (gat_kernels.h), GATv2 (gatv2_kernels.h),
+//                        attention from supplied scores (score_kernels.h)
+//   softmax per channel  softmax aggregation (spmm_softagg_kernels.h), of edge messages (spmm_edge_softagg_kernels.h), channel-wise
+//                        attention (vector_attention_kernels.h)
+//   no softmax           max / min aggregation (spmm_reduce_kernels.h), multi-aggregation (spmm_multi_kernels.h), edge-feature SpMM
+//                        (spmm_edge_kernels.h), edge-feature multi-aggregation (spmm_edge_multi_kernels.h), gated aggregation
+//                        (spmm_gated_kernels.h), edge-output ops (edge_op_kernels.h)
+// The seven softmax families keep their running softmax with the one definition of online_softmax.h.
 // A family is a Pass struct (the contract: DESIGN 4.16); this header deals rows to slots, walks their entries, merges the slots' partial
 // states and is the ONLY place with a __global__ of this layer: pattern_rows<Pass> and pattern_long<Pass>.
 //

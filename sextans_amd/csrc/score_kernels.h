@@ -9,7 +9,8 @@
 //            backward rows  dS[e,h] = <G[r,h,:], V[c,h,:]>
 //            backward cols  dV[c,h,:] = sum_e S[perm e, h] G[r,h,:]
 // fp32 throughout, FMA in the dot products and the V / G accumulations, exp as in the softmax kernels.  From s onward the SOFTMAX forward
-// and column pass make GatPass's roundings in GatPass's order: fed the scores GAT computes, they give its bits (tests/test_score_attention_gpu.py).
+// and column pass make GatPass's roundings in GatPass's order (the forward's are HeadSoftmax's, online_softmax.h): fed the scores GAT
+// computes, they give its bits (tests/test_score_attention_gpu.py).
 //
 // S and dS are (nnz, H) row-major in A's entry order, element (e, h) at (long long)e * ld + h, read and written one float at a time (the
 // same address in all T lanes of the slot).  The passes plug into the row walking of pattern_pass.h as GatPass does.  The ROW pass has no
@@ -59,7 +60,7 @@ struct ScorePass {
 #pragma unroll
         for (int i = 0; i < NF; ++i) f[i] = 0.0f;
         if (PASS == kAttnForward) {
-            if (kSoft) f[0] = -INFINITY;
+            if (kSoft) f[0] = -INFINITY;   // HeadSoftmax<W>::init's values (online_softmax.h); the call in a branch of its own changes three kernels
         } else if (PASS == kAttnBackwardRows) {
             attn_load<T, P>(y, a.G + r * a.ldg + (long long)h * a.dv, a.dv, t, act);
             if (kSoft) {
@@ -95,14 +96,15 @@ struct ScorePass {
             for (int u = 0; u < U; ++u) mk[u] = drop_mult(a.drop, key, (int)pe[u], a.H, h);
         }
         if (PASS == kAttnForward && kSoft) {
+            // HeadSoftmax<W>::absorb (online_softmax.h), kept inline: the call changes this family's wide kernels (profiles/online_softmax_device_code.txt)
             float mn = f[0];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                s[u] = valid[u] ? s[u] : -INFINITY;   // (exp gives those +0, and their V pieces are zero)
-                mn = fmaxf(mn, s[u]);                 // (a NaN does not reach m; it reaches Z through its own exp)
+                s[u] = valid[u] ? s[u] : -INFINITY;
+                mn = fmaxf(mn, s[u]);
             }
-            const float mref = mn == -INFINITY ? 0.0f : mn;   // only -inf so far: everything stays +0; a ROW of only -inf ends as 0 / 0
-            const float al = softmax_exp(__fsub_rn(f[0], mref));   // 1 when m did not grow
+            const float mref = mn == -INFINITY ? 0.0f : mn;
+            const float al = softmax_exp(__fsub_rn(f[0], mref));
 #pragma unroll
             for (int i = 1; i < NF; ++i) f[i] = __fmul_rn(f[i], al);
 #pragma unroll
@@ -144,15 +146,9 @@ struct ScorePass {
     static __device__ __forceinline__ void combine(float *g, const float *o) {
         if (PASS == kAttnBackwardRows) return;
         if (PASS == kAttnForward && kSoft) {
-            const float mn = fmaxf(g[0], o[0]);
-            const float mref = mn == -INFINITY ? 0.0f : mn;
-            const float ca = softmax_exp(__fsub_rn(g[0], mref)), cb = softmax_exp(__fsub_rn(o[0], mref));
-#pragma unroll
-            for (int i = 1; i < NF; ++i) g[i] = __fadd_rn(__fmul_rn(g[i], ca), __fmul_rn(o[i], cb));
-            g[0] = mn;
+            HeadSoftmax<W>::combine(g, o);
         } else {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
+            state_add<NF>(g, o);
         }
     }
 
@@ -166,7 +162,7 @@ struct ScorePass {
 #pragma unroll
             for (int i = 0; i < W; ++i) o[i] = n > 0 ? __fmul_rn(f[2 + i], inv) : 0.0f;
             attn_store<T, P>(o, a.out + r * a.ldo + (long long)h * a.dv, a.dv, t);
-            if (t == 0) a.out_lse[r * a.H + h] = n > 0 ? __fadd_rn(f[0], __fmul_rn(__builtin_amdgcn_logf(f[1]), 0.6931471805599453f)) : -INFINITY;
+            if (t == 0) a.out_lse[r * a.H + h] = HeadSoftmax<W>::lse(f, n);
         } else if (PASS == kAttnForward) {
             attn_store<T, P>(f, a.out + r * a.ldo + (long long)h * a.dv, a.dv, t);
         } else {

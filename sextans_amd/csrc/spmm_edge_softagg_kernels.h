@@ -16,8 +16,8 @@
 // row walking of pattern_pass.h as SoftaggPass and EdgePass do: COLUMN TILES of at most 64 floats play the heads' part, a slot of T lanes
 // owns one (row, tile), the last tile of a row may be partial.  All three passes compute m_e and s_e with the same two functions
 // (edge_message, score): they see the same bits.
-// The forward is SoftaggPass's online softmax with another source of the message: the state (m, z, acc) per float, the same batch and
-// combine arithmetic, __fdiv_rn and softagg_log in finish -- with E[e, :] = val[e] and MUL it returns spmm_softagg's bits.
+// The forward is SoftaggPass's online softmax with another source of the message: both passes are SoftaggFrame (online_softmax.h) plus
+// a batch() that hands its scores and messages to the one ChannelSoftmax -- so with E[e, :] = val[e] and MUL it returns spmm_softagg's bits.
 // The row pass does NOT take the tiles inside the slot (there is no dval to add up over tiles): every (entry, tile) piece of dE is stored
 // by the slot that owns it, as in EdgePass; its state is the tile's dt sum (W floats, merged by adds), kept whether or not dt is asked
 // for and stored when dt_rows is given; the dE store is predicated on its pointer (engine_edge_softagg.hip says why).
@@ -45,62 +45,14 @@ __device__ __forceinline__ float edge_message(float b, float x) {
 }
 
 // One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
+// begin, score, grad, combine and finish are SoftaggFrame's (online_softmax.h), the ones SoftaggPass has.
 template <int PASS, int OP, int T_, int P_, int U_>
-struct EdgeSoftaggPass {
-    using Args = EdgeSoftaggArgs;
+struct EdgeSoftaggPass : SoftaggFrame<PASS, EdgeSoftaggArgs, T_, P_> {
+    using Frame = SoftaggFrame<PASS, EdgeSoftaggArgs, T_, P_>;
+    using Frame::Frame;
+    using Frame::a, Frame::ci, Frame::perm, Frame::t, Frame::h, Frame::n, Frame::x, Frame::y, Frame::z, Frame::f, Frame::score, Frame::grad;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
-    static constexpr int NF = PASS == kAttnForward ? 3 * W : W;   // forward: m, z, acc per float; rows: the dt sum; cols: dB
-    static constexpr bool kMerge = true;
     static constexpr bool kB = OP != kEdgeCopy;   // the message reads B
-    const EdgeSoftaggArgs &a;
-    const int *ci, *perm;
-    const int t;
-    int h = 0, n = 0;        // the tile and its valid floats
-    float tt[W];             // the tile's temperatures
-    float x[W], y[W], z[W];  // backward: the own column's B (cols) or the own row's C (rows); rows: the own row's lse and G
-    float f[NF];
-
-    __device__ __forceinline__ EdgeSoftaggPass(const EdgeSoftaggArgs &a_, const int *ci_, const int *perm_, int t_)
-        : a(a_), ci(ci_), perm(perm_), t(t_) {}
-
-    __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
-        h = tile;
-        n = min(a.tile, a.N - h * a.tile);
-        const long long r = act ? own : 0, c0 = (long long)h * a.tile;
-        if (a.t) {
-            attn_load<T, P>(tt, a.t + c0, n, t, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i) tt[i] = 1.0f;
-        }
-        if (PASS == kAttnForward) {
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                f[i] = -INFINITY;
-                f[W + i] = 0.0f;
-                f[2 * W + i] = 0.0f;
-            }
-        } else {
-            if (PASS == kAttnBackwardRows) {
-                attn_load<T, P>(x, a.C + r * a.ldc + c0, n, t, act);
-                attn_load<T, P>(y, a.lse + r * a.ldlse + c0, n, t, act);
-                attn_load<T, P>(z, a.G + r * a.ldg + c0, n, t, act);
-            } else {
-                attn_load<T, P>(x, a.B + r * a.ldb + c0, n, t, act);
-            }
-#pragma unroll
-            for (int i = 0; i < NF; ++i) f[i] = 0.0f;
-        }
-    }
-
-    __device__ __forceinline__ float score(float m, int i) const { return a.t ? __fmul_rn(tt[i], m) : m; }
-    // q_e from the row's C, lse and G at this float: w = exp(s - lse), gw = G w, d = m - C, q = gw fma(t, d, 1)
-    __device__ __forceinline__ float grad(float m, float c, float l, float g, int i, float &gw, float &d) const {
-        const float w = softmax_exp(__fsub_rn(score(m, i), l));
-        d = __fsub_rn(m, c);
-        gw = __fmul_rn(g, w);
-        return a.t ? __fmul_rn(gw, __fmaf_rn(tt[i], d, 1.0f)) : __fmul_rn(gw, __fadd_rn(d, 1.0f));
-    }
 
     __device__ __forceinline__ void batch(const int (&e)[U_], const bool (&valid)[U_]) {
         constexpr bool COLS = PASS == kAttnBackwardCols;
@@ -134,22 +86,7 @@ struct EdgeSoftaggPass {
                     s[u][i] = valid[u] ? score(e2[u][i], i) : -INFINITY;                // (exp gives those +0, and their messages are zero)
                 }
             }
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                float mn = f[i];
-#pragma unroll
-                for (int u = 0; u < U; ++u) mn = fmaxf(mn, s[u][i]);
-                const float mref = mn == -INFINITY ? 0.0f : mn;          // only -inf so far: everything stays +0
-                const float al = softmax_exp(__fsub_rn(f[i], mref));   // 1 when m did not grow
-                float zz = __fmul_rn(f[W + i], al), acc = __fmul_rn(f[2 * W + i], al);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float w = softmax_exp(__fsub_rn(s[u][i], mref));
-                    zz = __fadd_rn(zz, w);
-                    acc = __fmaf_rn(w, e2[u][i], acc);
-                }
-                f[i] = mn; f[W + i] = zz; f[2 * W + i] = acc;
-            }
+            ChannelSoftmax<W>::template absorb<U>(f, s, e2);
         } else if constexpr (COLS) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -181,34 +118,6 @@ struct EdgeSoftaggPass {
                 }
                 if (a.dE && valid[u]) attn_store<T, P>(de, a.dE + pe[u] * a.ldde + (long long)h * a.tile, n, t);
             }
-        }
-    }
-
-    // g <- g (+) o: SoftaggPass's own merge (the states have its layout) -- commutative operations only, so both sides of a butterfly
-    // exchange compute the same bits
-    static __device__ __forceinline__ void combine(float *g, const float *o) { SoftaggPass<PASS, T_, P_, U_>::combine(g, o); }
-
-    // cnt: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
-    __device__ __forceinline__ void finish(bool writer, int own, int cnt) {
-        if (!writer) return;
-        const long long r = own, c0 = (long long)h * a.tile;
-        if (PASS == kAttnForward) {
-            float c[W], l[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                c[i] = cnt > 0 ? __fdiv_rn(f[2 * W + i], f[W + i]) : 0.0f;
-                l[i] = cnt > 0 ? __fadd_rn(f[i], softagg_log(f[W + i])) : -INFINITY;
-            }
-            attn_store<T, P>(c, a.out + r * a.ldc + c0, n, t);
-            if (a.out_lse) attn_store<T, P>(l, a.out_lse + r * a.ldlse + c0, n, t);
-        } else if (PASS == kAttnBackwardRows) {
-            if (!a.dt_rows) return;
-            float d[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) d[i] = cnt > 0 ? f[i] : 0.0f;
-            attn_store<T, P>(d, a.dt_rows + r * a.N + c0, n, t);
-        } else {
-            attn_store<T, P>(f, a.dB + r * a.lddb + c0, n, t);
         }
     }
 };

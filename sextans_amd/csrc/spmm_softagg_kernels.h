@@ -12,8 +12,8 @@
 //
 // The passes plug into the row walking of pattern_pass.h as ReducePass does: COLUMN TILES play the heads' part, a slot of T lanes owns
 // one (row, tile), the last tile of a row may be partial.  The forward is the online softmax of attention_kernels.h per float instead of
-// per head: its state is (m, z, acc) for every float, 3 W floats, and merging two states takes the larger m, rescales both sides and
-// adds -- commutative operations only, so both sides of a butterfly end with the same bits.  A row of one entry ends with z = 1 and
+// per head (ChannelSoftmax, online_softmax.h): its state is (m, z, acc) for every float, 3 W floats, and merging two states takes the
+// larger m, rescales both sides and adds -- commutative operations only, so both sides of a butterfly end with the same bits.  A row of one entry ends with z = 1 and
 // acc = p: C has the product's bits (a -0 product gives +0).  t p may be anything finite: only differences to the running maximum are
 // exponentiated.  A non-finite product does what this arithmetic makes of it (inf - inf = NaN in its own (row, column)); it does not
 // leave that (row, column).
@@ -21,7 +21,7 @@
 // order.  It ALWAYS keeps the row's dt sum in its state (W floats, merged by adds) and stores it when dt_rows is given: see
 // engine_softagg.hip.  No atomics; sums in an order fixed by the pattern and the launch shape.
 #pragma once
-#include "pattern_pass.h"
+#include "online_softmax.h"
 
 namespace sx {
 
@@ -35,63 +35,13 @@ struct SoftaggArgs {
     int N, tile;                // tile: floats per tile = 4 T P
 };
 
-__device__ __forceinline__ float softagg_log(float z) { return __fmul_rn(__builtin_amdgcn_logf(z), 0.6931471805599453f); }
-
-// One slot's view of a pass: the interface of AttnPass.
+// One slot's view of a pass: the interface of AttnPass.  begin, score, grad, combine and finish are SoftaggFrame's (online_softmax.h).
 template <int PASS, int T_, int P_, int U_>
-struct SoftaggPass {
-    using Args = SoftaggArgs;
+struct SoftaggPass : SoftaggFrame<PASS, SoftaggArgs, T_, P_> {
+    using Frame = SoftaggFrame<PASS, SoftaggArgs, T_, P_>;
+    using Frame::Frame;
+    using Frame::a, Frame::ci, Frame::perm, Frame::t, Frame::h, Frame::n, Frame::x, Frame::y, Frame::z, Frame::f, Frame::score, Frame::grad;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
-    static constexpr int NF = PASS == kAttnForward ? 3 * W : W;   // forward: m, z, acc per float; rows: the dt sum; cols: dB
-    static constexpr bool kMerge = true;
-    const SoftaggArgs &a;
-    const int *ci, *perm;
-    const int t;
-    int h = 0, n = 0;        // the tile and its valid floats
-    float tt[W];             // the tile's temperatures
-    float x[W], y[W], z[W];  // backward: the own row's B (cols) or C (rows); rows: the own row's lse and G
-    float f[NF];
-
-    __device__ __forceinline__ SoftaggPass(const SoftaggArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
-
-    __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
-        h = tile;
-        n = min(a.tile, a.N - h * a.tile);
-        const long long r = act ? own : 0, c0 = (long long)h * a.tile;
-        if (a.t) {
-            attn_load<T, P>(tt, a.t + c0, n, t, true);
-        } else {
-#pragma unroll
-            for (int i = 0; i < W; ++i) tt[i] = 1.0f;
-        }
-        if (PASS == kAttnForward) {
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                f[i] = -INFINITY;
-                f[W + i] = 0.0f;
-                f[2 * W + i] = 0.0f;
-            }
-        } else {
-            if (PASS == kAttnBackwardRows) {
-                attn_load<T, P>(x, a.C + r * a.ldc + c0, n, t, act);
-                attn_load<T, P>(y, a.lse + r * a.ldlse + c0, n, t, act);
-                attn_load<T, P>(z, a.G + r * a.ldg + c0, n, t, act);
-            } else {
-                attn_load<T, P>(x, a.B + r * a.ldb + c0, n, t, act);
-            }
-#pragma unroll
-            for (int i = 0; i < NF; ++i) f[i] = 0.0f;
-        }
-    }
-
-    __device__ __forceinline__ float score(float p, int i) const { return a.t ? __fmul_rn(tt[i], p) : p; }
-    // q_e / (its p), from the row's C, lse and G at this float: w = exp(s - lse), gw = G w, q = gw (1 + t (p - C))
-    __device__ __forceinline__ float grad(float p, float c, float l, float g, int i, float &gw, float &d) const {
-        const float w = softmax_exp(__fsub_rn(score(p, i), l));
-        d = __fsub_rn(p, c);
-        gw = __fmul_rn(g, w);
-        return a.t ? __fmul_rn(gw, __fmaf_rn(tt[i], d, 1.0f)) : __fmul_rn(gw, __fadd_rn(d, 1.0f));
-    }
 
     __device__ __forceinline__ void batch(const int (&e)[U_], const bool (&valid)[U_]) {
         constexpr bool COLS = PASS == kAttnBackwardCols;
@@ -125,22 +75,7 @@ struct SoftaggPass {
                     s[u][i] = valid[u] ? score(p2[u][i], i) : -INFINITY;   // (exp gives those +0, and their products are zero)
                 }
             }
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                float mn = f[i];
-#pragma unroll
-                for (int u = 0; u < U; ++u) mn = fmaxf(mn, s[u][i]);
-                const float mref = mn == -INFINITY ? 0.0f : mn;          // only -inf so far: everything stays +0
-                const float al = softmax_exp(__fsub_rn(f[i], mref));   // 1 when m did not grow
-                float zz = __fmul_rn(f[W + i], al), acc = __fmul_rn(f[2 * W + i], al);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float w = softmax_exp(__fsub_rn(s[u][i], mref));
-                    zz = __fadd_rn(zz, w);
-                    acc = __fmaf_rn(w, p2[u][i], acc);
-                }
-                f[i] = mn; f[W + i] = zz; f[2 * W + i] = acc;
-            }
+            ChannelSoftmax<W>::template absorb<U>(f, s, p2);
         } else if constexpr (COLS) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -173,48 +108,6 @@ struct SoftaggPass {
                     if (valid[u] && t == 0) a.dval[pe[u]] = h == 0 ? s : __fadd_rn(a.dval[pe[u]], s);
                 }
             }
-        }
-    }
-
-    // g <- g (+) o: commutative operations only, so both sides of a butterfly exchange compute the same bits
-    static __device__ __forceinline__ void combine(float *g, const float *o) {
-        if (PASS == kAttnForward) {
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                const float mn = fmaxf(g[i], o[i]);
-                const float mref = mn == -INFINITY ? 0.0f : mn;
-                const float ca = softmax_exp(__fsub_rn(g[i], mref)), cb = softmax_exp(__fsub_rn(o[i], mref));
-                g[W + i] = __fadd_rn(__fmul_rn(g[W + i], ca), __fmul_rn(o[W + i], cb));
-                g[2 * W + i] = __fadd_rn(__fmul_rn(g[2 * W + i], ca), __fmul_rn(o[2 * W + i], cb));
-                g[i] = mn;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < NF; ++i) g[i] = __fadd_rn(g[i], o[i]);
-        }
-    }
-
-    // cnt: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
-    __device__ __forceinline__ void finish(bool writer, int own, int cnt) {
-        if (!writer) return;
-        const long long r = own, c0 = (long long)h * a.tile;
-        if (PASS == kAttnForward) {
-            float c[W], l[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                c[i] = cnt > 0 ? __fdiv_rn(f[2 * W + i], f[W + i]) : 0.0f;
-                l[i] = cnt > 0 ? __fadd_rn(f[i], softagg_log(f[W + i])) : -INFINITY;
-            }
-            attn_store<T, P>(c, a.out + r * a.ldc + c0, n, t);
-            if (a.out_lse) attn_store<T, P>(l, a.out_lse + r * a.ldlse + c0, n, t);
-        } else if (PASS == kAttnBackwardRows) {
-            if (!a.dt_rows) return;
-            float d[W];
-#pragma unroll
-            for (int i = 0; i < W; ++i) d[i] = cnt > 0 ? f[i] : 0.0f;
-            attn_store<T, P>(d, a.dt_rows + r * a.N + c0, n, t);
-        } else {
-            attn_store<T, P>(f, a.dB + r * a.lddb + c0, n, t);
         }
     }
 };

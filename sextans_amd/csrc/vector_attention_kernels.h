@@ -14,15 +14,15 @@
 // Only A's PATTERN is read; S, D, dS and dD are (nnz, N) row-major in A's entry order, addressed as (long long)e * ld.  The passes plug
 // into the row walking of pattern_pass.h as EdgeSoftaggPass does: COLUMN TILES of at most 64 floats play the heads' part, a slot of T
 // lanes owns one (row, tile), the last tile of a row may be partial.
-// The forward is SoftaggPass's online softmax with the score loaded instead of multiplied out: the state (m, z, acc) per float, the same
-// batch and combine arithmetic, __fdiv_rn and softagg_log in finish -- fed S = t[n] m_e (one rounded product) it returns the bits of
-// spmm_edge_softagg (ADD, EDGE) and of spmm_softagg on values of 1 (NODE).  A score of -inf masks its (entry, column): weight +0.
+// The forward is SoftaggPass's online softmax with the score loaded instead of multiplied out: both call the one ChannelSoftmax of
+// online_softmax.h (state, batch update, merge, the two results per float) -- so, fed S = t[n] m_e (one rounded product), it returns the
+// bits of spmm_edge_softagg (ADD, EDGE) and of spmm_softagg on values of 1 (NODE).  A score of -inf masks its (entry, column): weight +0.
 // The row pass keeps NO state (EdgePass's row pass): every (entry, tile) piece of dS and dD is stored by the slot that owns it, each
 // store predicated on its pointer.  The column pass reads S through the transpose's permutation and gathers lse[r] and G[r]; it needs
 // neither C, V nor D: the weight alone is dV's term.
 // No atomics; sums in an order fixed by the pattern and the launch shape.
 #pragma once
-#include "spmm_softagg_kernels.h"
+#include "online_softmax.h"
 
 namespace sx {
 
@@ -64,15 +64,10 @@ struct VectorAttnPass {
 
     __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
         h = tile;
-        n = min(a.tile, a.N - h * a.tile);
+        n = tile_floats(a, h);
         const long long r = act ? own : 0, c0 = (long long)h * a.tile;
         if (PASS == kAttnForward) {
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                f[i] = -INFINITY;
-                f[W + i] = 0.0f;
-                f[2 * W + i] = 0.0f;
-            }
+            ChannelSoftmax<W>::init(f);
         } else {
             if (PASS == kAttnBackwardRows) {
                 attn_load<T, P>(x, a.C + r * a.ldc + c0, n, t, act);
@@ -116,22 +111,7 @@ struct VectorAttnPass {
                     s2[u][i] = valid[u] ? s2[u][i] : -INFINITY;                                           // (exp gives those +0)
                 }
             }
-#pragma unroll
-            for (int i = 0; i < W; ++i) {
-                float mn = f[i];
-#pragma unroll
-                for (int u = 0; u < U; ++u) mn = fmaxf(mn, s2[u][i]);
-                const float mref = mn == -INFINITY ? 0.0f : mn;          // only -inf so far: everything stays +0
-                const float al = softmax_exp(__fsub_rn(f[i], mref));   // 1 when m did not grow
-                float zz = __fmul_rn(f[W + i], al), acc = __fmul_rn(f[2 * W + i], al);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const float w = softmax_exp(__fsub_rn(s2[u][i], mref));
-                    zz = __fadd_rn(zz, w);
-                    acc = __fmaf_rn(w, m2[u][i], acc);
-                }
-                f[i] = mn; f[W + i] = zz; f[2 * W + i] = acc;
-            }
+            ChannelSoftmax<W>::template absorb<U>(f, s2, m2);
         } else if constexpr (COLS) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -161,22 +141,22 @@ struct VectorAttnPass {
         }
     }
 
-    // g <- g (+) o: SoftaggPass's own merge (the forward's state has its layout; the column pass adds) -- commutative operations only, so
-    // both sides of a butterfly exchange compute the same bits
+    // g <- g (+) o: the forward's state is ChannelSoftmax's, the column pass adds
     static __device__ __forceinline__ void combine(float *g, const float *o) {
-        if constexpr (PASS != kAttnBackwardRows) SoftaggPass<PASS, T_, P_, U_>::combine(g, o);
+        if constexpr (PASS == kAttnForward) ChannelSoftmax<W>::combine(g, o);
+        else if constexpr (PASS == kAttnBackwardCols) state_add<NF>(g, o);
     }
 
     // cnt: entries of the own row.  An empty row / column: +0 everywhere, lse = -inf
     __device__ __forceinline__ void finish(bool writer, int own, int cnt) {
         if (!writer || PASS == kAttnBackwardRows) return;
         const long long r = own, c0 = (long long)h * a.tile;
-        if (PASS == kAttnForward) {
+        if (PASS == kAttnForward) {   // SoftaggFrame::finish's forward branch (online_softmax.h), kept inline: a helper around the two stores changes the kernels
             float c[W], l[W];
 #pragma unroll
             for (int i = 0; i < W; ++i) {
-                c[i] = cnt > 0 ? __fdiv_rn(f[2 * W + i], f[W + i]) : 0.0f;
-                l[i] = cnt > 0 ? __fadd_rn(f[i], softagg_log(f[W + i])) : -INFINITY;
+                c[i] = ChannelSoftmax<W>::value(f, i, cnt);
+                l[i] = ChannelSoftmax<W>::lse(f, i, cnt);
             }
             attn_store<T, P>(c, a.out + r * a.ldc + c0, n, t);
             if (a.out_lse) attn_store<T, P>(l, a.out_lse + r * a.ldlse + c0, n, t);

@@ -1,12 +1,14 @@
-"""Is the device code of two trees the same?  For a host-side refactor: compiles translation units of both trees to gfx950 assembly
-with the flags of sextans_amd/build.py (no GPU needed) and compares them kernel by kernel:
+"""Is the device code of two trees the same?  For a refactor that must leave the kernels alone -- of the host side (the entry points'
+frame, profiles/entry_frame_device_code.txt) or of the device side itself (code moved into shared __device__ helpers,
+profiles/online_softmax_device_code.txt): compiles translation units of both trees to gfx950 assembly with the flags of
+sextans_amd/build.py (no GPU needed) and compares them kernel by kernel:
 
     git worktree add --detach ../parent HEAD~1
     python tools/device_code_diff.py ../parent . > profiles/entry_frame_device_code.txt
-    python tools/device_code_diff.py ../parent . sextans_amd/csrc/engine_gat.hip      # chosen units only
+    python tools/device_code_diff.py ../parent . sextans_amd/csrc/engine_gat.hip      # chosen units only: a device-side change is tried per unit
 
-Without units: every sextans_amd/csrc/*.hip of the second tree that includes pattern_launch.h or edge_multi_launch.h.  Host changes
-may reorder template instantiation, so the functions are compared per symbol, not in file order, after the function's index is taken
+Without units: every sextans_amd/csrc/*.hip of the second tree that includes pattern_launch.h or edge_multi_launch.h.  Either kind of
+change may reorder template instantiation, so the functions are compared per symbol, not in file order, after the function's index is taken
 out of its local labels (.LBB<k>_<n>, .Lfunc_end<k>).  What is compared per symbol: the instructions, the kernel descriptor, the
 resource figures and the code-object metadata entry.  Exit status 1 when anything differs."""
 import os
