@@ -1121,6 +1121,47 @@ int sextans_edge_op_backward_device_rm(sextans_handle_t h, int op, int N, const 
                                        int64_t ldxsrc, const float *d_Gz, int64_t ldgz, float *d_dxdst, int64_t lddxdst, float *d_dxsrc,
                                        int64_t lddxsrc, void *stream);
 
+/* ---- Per-head dot product of both endpoints of every stored entry (DGL's u_dot_v, the last member of its gSDDMM set): the (nnz, heads)
+ * scores that sextans_score_attention_device reads -- AGNN's cosine score, HGT's K W Q, SuperGAT's dot-product mode, any clamped,
+ * tempered or MLP-adjusted transformer score written as u_dot_v, elementwise ops, score_attention -- in ONE launch for all heads, without
+ * gathered (nnz, heads, d) temporaries and without an atomic scatter in the backward.  Closest thing in the reference: none.
+ *
+ * Only the PATTERN of the engine's M x K CSR matrix is used: its values are neither read nor touched, and no value refresh happens.
+ * X and dX are row-major M x heads*d fp32 (head h of row r at [r * ld + h * d]), Y and dY K x heads*d -- the operands of
+ * sextans_score_attention_device; S and Gs are (nnz, heads) row-major IN THE CSR ENTRY ORDER the matrix was set with (element
+ * [e * ld + h], 64-bit offsets).  For the stored entry e = (r, c) and head h:
+ *     acc = +0;  acc = acc + X[r, h, n] * Y[c, h, n]  for n = 0 .. d-1 in this order;  S[e, h] = acc
+ * every product and every sum rounded to fp32, never contracted, the same in STRICT and FAST: bit for bit a sequential float32 loop, and
+ * bit for bit what sextans_sddmm_device_rm(h, d, 1.0f, X + h * d, ldx, Y + h * d, ldy, 0, NULL, out, ...) writes for head h.  There is
+ * no alpha: a scale belongs on X or on S.  The work is dealt by non-zeros (a wavefront owns 256 consecutive entries whatever rows they
+ * belong to), so a hub row spreads over hundreds of wavefronts.
+ * Backward, Gs the upstream gradient of S:
+ *     dX[r, h, :] = sum over row r's entries of Gs[e, h] * Y[c, h, :]       the bits of sextans_score_attention_device(SEXTANS_SCORE_WEIGHT)'s
+ *                                                                           O with S := Gs, V := Y (one pass over the rows of A)
+ *     dY[c, h, :] = sum over column c's entries of Gs[e, h] * X[r, h, :]    the bits of sextans_score_attention_backward_device(
+ *                                                                           SEXTANS_SCORE_WEIGHT)'s dV with S := Gs, G := X (the rows of A^T)
+ * d_dX or d_dY may be NULL, not both: its pass is skipped, and with d_dY == NULL A^T is never built.  The backward reads X only for dY
+ * and Y only for dX; otherwise they are ignored with their leading dimensions.  No atomics, no workspace, no value refresh: the same
+ * bits on every run and stream.  Everything handed in is written in full: a row or column without entries gets +0.  NaN and +-inf
+ * reach only the entries, rows and columns that hold them.
+ * heads: 1 .. 65535.  d: a multiple of 8 in [8, 128].  ldx, ldy, lddx, lddy: >= heads * d and multiples of 4 (those of the operands a
+ * call reads or writes); lds, ldgs: >= heads (lds == heads: S leaves as 16-byte stores; wider: one store per element, the columns
+ * beyond heads are left alone).  Every pointer that is read or written 16-byte aligned.  The outputs must not overlap the inputs or each
+ * other.  Needed with nnz > 0: d_S, d_Gs and the operands the call reads.
+ * The first forward call on a matrix validates it and builds the table of the 256-entry ranges' first rows; the first backward call
+ * builds the row softmax's tables and, with d_dY, A^T; both synchronise then.  After sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T,
+ * stream) a call allocates nothing, reads nothing back and does not synchronise: it can be captured into a hipGraph.  The caller's
+ * stream is used.
+ * sextans_last_kernel: "edge_dot" / "edge_dot_backward", the latter with "+long_rows" appended when a pass ran the workgroup path.
+ * SEXTANS_ERR_INVALID: h == NULL, heads < 1 or > 65535, d not a multiple of 8 in [8, 128], a leading dimension too small or (ldx, ldy,
+ * lddx, lddy) not a multiple of 4, a misaligned pointer, (backward) d_dX and d_dY both NULL -- checked in this order, then the handle's
+ * state (SEXTANS_ERR_STATE: no CSR matrix set), then SEXTANS_ERR_INVALID for nnz > INT32_MAX and for a required pointer that is NULL
+ * with nnz > 0; all before any device is touched.  M == 0 or nnz == 0: OK -- S has no element, dX and dY are zeroed. */
+int sextans_edge_dot_device(sextans_handle_t h, int heads, int d, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy, float *d_S,
+                            int64_t lds, void *stream);
+int sextans_edge_dot_backward_device(sextans_handle_t h, int heads, int d, const float *d_X, int64_t ldx, const float *d_Y, int64_t ldy,
+                                     const float *d_Gs, int64_t ldgs, float *d_dX, int64_t lddx, float *d_dY, int64_t lddy, void *stream);
+
 /* ---- Gated aggregation: a per-channel sigmoid gate on every stored entry, computed from both endpoints and, optionally, the entry's own
  * features (PyG's ResGatedGraphConv; GatedGCN of Bresson & Laurent, the MPNN of GraphGPS and of the LRGB / "Benchmarking GNNs" suites).
  * Closest thing in the reference: none.

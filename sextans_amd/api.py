@@ -125,6 +125,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
     "sextans_vector_attention_device_rm", "sextans_vector_attention_backward_device_rm",
     "sextans_edge_op_device_rm", "sextans_edge_op_backward_device_rm",
+    "sextans_edge_dot_device", "sextans_edge_dot_backward_device",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
     "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
@@ -396,6 +397,8 @@ def lib():
                                                               vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_op_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_op_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_edge_dot_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp]
+    L.sextans_edge_dot_backward_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                                 vp, vp, i64, vp, dp, vp]
     L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1130,6 +1133,21 @@ class Engine:
         xsrc is read only for EDGEOP_MUL's dxdst, xdst only for EDGEOP_MUL's dxsrc."""
         _check(lib().sextans_edge_op_backward_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc,
                                                         lddxsrc, stream), "edge_op_backward_device_rm")
+
+    def edge_dot_device(self, heads, d, d_X, ldx, d_Y, ldy, d_S, lds, stream=None):
+        """Per-head dot product of both endpoints (sextans_edge_dot_device, DGL's u_dot_v): for every stored entry e = (r, c), in the CSR
+        entry order, and every head h, S[e * lds + h] = sum_n X[r, h, n] * Y[c, h, n], every product and sum rounded to fp32 in column
+        order (sddmm_device_rm's bits on the head's slice), all heads in one launch dealt by non-zeros.  X is M x heads*d, Y K x heads*d
+        (score_attention_device's operands), d a multiple of 8 in [8, 128].  Only A's pattern is read."""
+        _check(lib().sextans_edge_dot_device(self._h, heads, d, d_X, ldx, d_Y, ldy, d_S, lds, stream), "edge_dot_device")
+
+    def edge_dot_backward_device(self, heads, d, d_X, ldx, d_Y, ldy, d_Gs, ldgs, d_dX, lddx, d_dY, lddy, stream=None):
+        """dX (M x heads*d) and dY (K x heads*d) of edge_dot_device from the upstream gradient Gs of S (sextans_edge_dot_backward_device):
+        score_attention_device(SCORE_WEIGHT)'s O with S := Gs, V := Y, and score_attention_backward_device(SCORE_WEIGHT)'s dV with S := Gs,
+        G := X, no atomics.  Either may be None (not both): its pass is skipped, and without d_dY A^T is never built.  X is read only
+        for dY, Y only for dX."""
+        _check(lib().sextans_edge_dot_backward_device(self._h, heads, d, d_X, ldx, d_Y, ldy, d_Gs, ldgs, d_dX, lddx, d_dY, lddy, stream),
+               "edge_dot_backward_device")
 
     def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and

@@ -3,6 +3,7 @@
   sextans_amd/lib/libsextans_amd.so   C-ABI shared library (include/sextans_amd.h)
   sextans_amd/bin/sextans             CLI with the reference's call surface
   sextans_amd/bin/dist_spmm           examples/dist_spmm.cpp: multi-GPU SpMM through the C ABI alone (one thread per GPU)
+  sextans_amd/bin/edge_dot_attention  examples/edge_dot_attention.cpp: u_dot_v -> score_attention in one captured graph, C ABI alone
 
 hipcc cross-compiles without a GPU.  Artefacts are git-ignored but travel to the GPU box.
 """
@@ -18,7 +19,7 @@ BINDIR = os.path.join(ROOT, "sextans_amd", "bin")
 LIB = os.path.join(LIBDIR, "libsextans_amd.so")
 CLI = os.path.join(BINDIR, "sextans")
 
-LIB_SOURCES = ["engine_launch.hip", "engine.hip", "engine_spmm.hip", "engine_rowmajor.hip", "engine_host.hip", "engine_plan.hip", "engine_bell.hip", "engine_dist.hip", "plan_device.hip", "row_cluster.hip", "graph_cluster.hip", "csr_transpose.hip", "engine_transpose.hip", "engine_softmax.hip", "engine_attention.hip", "engine_attention_edge.hip", "engine_gat.hip", "engine_gatv2.hip", "engine_score.hip", "engine_reduce.hip", "engine_multi.hip", "engine_softagg.hip", "engine_edge.hip", "engine_gated.hip", "engine_edge_multi.hip", "engine_edge_multi_mul.hip", "engine_edge_multi_add.hip", "engine_edge_multi_add_relu.hip", "engine_edge_multi_copy.hip", "engine_edge_softagg.hip", "engine_vector_attention.hip", "engine_edge_op.hip", "engine_refresh.hip", "synth.hip", "host_mtx.cpp", "panel_plan.cpp", "window_plan.cpp", "pack_api.cpp",
+LIB_SOURCES = ["engine_launch.hip", "engine.hip", "engine_spmm.hip", "engine_rowmajor.hip", "engine_host.hip", "engine_plan.hip", "engine_bell.hip", "engine_dist.hip", "plan_device.hip", "row_cluster.hip", "graph_cluster.hip", "csr_transpose.hip", "engine_transpose.hip", "engine_softmax.hip", "engine_attention.hip", "engine_attention_edge.hip", "engine_gat.hip", "engine_gatv2.hip", "engine_score.hip", "engine_reduce.hip", "engine_multi.hip", "engine_softagg.hip", "engine_edge.hip", "engine_gated.hip", "engine_edge_multi.hip", "engine_edge_multi_mul.hip", "engine_edge_multi_add.hip", "engine_edge_multi_add_relu.hip", "engine_edge_multi_copy.hip", "engine_edge_softagg.hip", "engine_vector_attention.hip", "engine_edge_op.hip", "engine_edge_dot.hip", "engine_refresh.hip", "synth.hip", "host_mtx.cpp", "panel_plan.cpp", "window_plan.cpp", "pack_api.cpp",
                "edge_stream.cpp"]
 # every header of csrc/ (a header that is not listed here would change without anything being recompiled -- round 6 measured two
 # "new" kernels that were never built that way)
@@ -84,13 +85,14 @@ def build(force=False, verbose=False):
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    ex_src = os.path.join(ROOT, "examples", "dist_spmm.cpp")
-    ex_bin = os.path.join(BINDIR, "dist_spmm")
-    if os.path.exists(ex_src) and (force or _stale(ex_bin, [ex_src, LIB])):
-        cmd = [hipcc()] + FLAGS + ["-o", ex_bin, ex_src, "-L", LIBDIR, "-lsextans_amd", "-Wl,-rpath,$ORIGIN/../lib"]
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.run(cmd, check=True)
+    for example in ("dist_spmm", "edge_dot_attention"):
+        ex_src = os.path.join(ROOT, "examples", example + ".cpp")
+        ex_bin = os.path.join(BINDIR, example)
+        if os.path.exists(ex_src) and (force or _stale(ex_bin, [ex_src, LIB])):
+            cmd = [hipcc()] + FLAGS + ["-o", ex_bin, ex_src, "-L", LIBDIR, "-lsextans_amd", "-Wl,-rpath,$ORIGIN/../lib"]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            subprocess.run(cmd, check=True)
     return LIB, CLI
 
 

@@ -437,6 +437,7 @@ void free_matrix(sextans_engine *h);
 void free_backward(sextans_engine *h);                     // engine_transpose.hip: A^T, its companion and the SDDMM row table
 int validate_matrix(sextans_engine *h);                    // engine_transpose.hip: row_ptr / columns of a caller-provided device matrix, once
 int ensure_transpose(sextans_engine *h, hipStream_t s);    // engine_transpose.hip: A^T's arrays (h->at) and the companion engine h->tr, once per matrix
+int ensure_sddmm_rows(sextans_engine *h, hipStream_t s);   // engine_transpose.hip: d_sddmm_row0, the first row of every 256-entry range, once per matrix
 void free_softmax(sextans_engine *h);                      // engine_softmax.hip: the row-softmax tables and workspace
 int ensure_softmax_tables(sextans_engine *h, hipStream_t s);   // engine_softmax.hip: ... built (synchronises s the first time)
 void attention_fill(float *out, int64_t rows, int cols, int64_t ld, float value, hipStream_t s);   // engine_attention.hip: rows x cols floats <- value (degenerate calls)

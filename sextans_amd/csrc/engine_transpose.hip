@@ -64,10 +64,8 @@ int ensure_transpose(sextans_engine *h, hipStream_t s) {
     return SEXTANS_OK;
 }
 
-namespace {
-
-// The row of the first entry of every wavefront range of the SDDMM kernel, once per matrix: the kernel reads two ints per wavefront
-// instead of searching row_ptr (a 64-ary search per wavefront made 2 scattered row_ptr requests per entry: 4x the L2 requests of the
+// The row of the first entry of every wavefront range of the SDDMM kernel, once per matrix (engine_edge_dot.hip's forward walks the same
+// ranges through the same table): the kernel reads two ints per wavefront instead of searching row_ptr (a 64-ary search per wavefront made 2 scattered row_ptr requests per entry: 4x the L2 requests of the
 // row-group gather kernel on the FEM, profiles/train_step_pmc_fem_N16.txt)
 int ensure_sddmm_rows(sextans_engine *h, hipStream_t s) {
     if (h->d_sddmm_row0 || h->nnz == 0) return SEXTANS_OK;
@@ -83,8 +81,6 @@ int ensure_sddmm_rows(sextans_engine *h, hipStream_t s) {
     SX_HIP(hipGetLastError());
     return SEXTANS_OK;
 }
-
-}  // namespace
 
 int prepare_transposed(sextans_engine *h, int N, hipStream_t s) {
     if (int rc = ensure_sddmm_rows(h, s)) return rc;

@@ -68,6 +68,8 @@ with a learnable temperature): sextans_amd.edge_softagg.spmm_edge_softagg(A, B, 
 And Point Transformer's channel-wise attention from per-channel scores: sextans_amd.vector_attention.vector_attention(A, S, V=None, D=None).
 The opposite direction, node to edge -- the (nnz, N) tensors those ops read, from both endpoints of every entry (u_add_v, u_sub_v, u_mul_v,
 copy_u, copy_v, each optionally + e), with a backward without atomics: sextans_amd.edge_op.edge_op(A, x_dst=None, x_src=None, E=None, op="add").
+And the (nnz, H) scores score_attention() reads, the per-head dot product of both endpoints (u_dot_v), all heads in one launch dealt by
+non-zeros: sextans_amd.edge_dot.edge_dot(A, x_dst, x_src).
 
 Edge features INSIDE the fused attention (TransformerConv(edge_dim=...), UniMP, relative-position encodings), one kernel pass per direction:
 
