@@ -4,8 +4,7 @@
     python tools/attention_bench.py --matrix fem --steps 16,64
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/attention_bench.py --matrix fem --kernels-only
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
+Matrices and "spread": tools/compare_bench.py (this tool takes a fixed --reps, and has no verdict of its own).
 
 Kernel records: sextans_row_softmax_device / _backward_device, median us over --rounds rounds of --reps calls between HIP events, bytes
 from shapes (8 nnz + 4 (M + 1) forward, 12 nnz + 4 (M + 1) backward) and their share of the 8 TB/s the project's rooflines use (the
@@ -17,18 +16,14 @@ of each side's rounds.
 Whole-step records (--steps d,...): forward + backward of torch_op.sparse_attention at head dimension d against the same pipeline with
 the torch composition in place of row_softmax."""
 import argparse
-import json
-import os
 import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    ap.add_argument("--matrix", choices=list(cb.MATRICES), default="small")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", default="", help="comma-separated head dimensions for the whole-step record (none: kernels only)")
@@ -38,20 +33,7 @@ def main():
     import torch
     from sextans_amd import api, torch_op
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
+    crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)[1:]
     gen = torch.Generator(device=dev).manual_seed(1)
     x = torch.rand(nnz, device=dev, generator=gen) * 8 - 4
     g = torch.rand(nnz, device=dev, generator=gen) * 2 - 1
@@ -59,18 +41,7 @@ def main():
     stream = torch.cuda.current_stream(dev).cuda_stream
     scale = 0.25
 
-    def timed(fn):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(args.reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / args.reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
+    stats, reps = cb.stats, args.reps
 
     eng = api.Engine(0)
     eng.set_matrix_csr_device(M, K, nnz, crow.data_ptr(), col.data_ptr(), val.data_ptr())
@@ -81,9 +52,9 @@ def main():
            "softmax_long_rows": eng.get_stat("softmax_long_rows")}
     rec["kernel"] = eng.last_kernel()
     if args.kernels_only:
-        rec["forward"] = stats([timed(e_fwd) for _ in range(args.rounds)])
-        rec["backward"] = stats([timed(e_bwd) for _ in range(args.rounds)])
-        print(json.dumps(rec))
+        rec["forward"] = stats([cb.timed(e_fwd, reps) for _ in range(args.rounds)])
+        rec["backward"] = stats([cb.timed(e_bwd, reps) for _ in range(args.rounds)])
+        cb.emit(rec, "")
         return
 
     rows = torch.repeat_interleave(torch.arange(M, device=dev), (crow[1:] - crow[:-1]).long())   # outside every timed region
@@ -115,7 +86,7 @@ def main():
     rec["max_abs_difference_from_composition"] = float((pbuf - want).abs().max())
     ef, eb, bf, bb = [], [], [], []
     for _ in range(args.rounds):   # alternating rounds
-        ef.append(timed(e_fwd)); bf.append(timed(b_fwd)); eb.append(timed(e_bwd)); bb.append(timed(b_bwd))
+        ef.append(cb.timed(e_fwd, reps)); bf.append(cb.timed(b_fwd, reps)); eb.append(cb.timed(e_bwd, reps)); bb.append(cb.timed(b_bwd, reps))
     for name, e, b, nbytes in (("forward", ef, bf, 8 * nnz + 4 * (M + 1)), ("backward", eb, bb, 12 * nnz + 4 * (M + 1))):
         r = stats(e)
         r["bytes"] = nbytes
@@ -156,16 +127,11 @@ def main():
         step_engine(); step_composed(); torch.cuda.synchronize()
         se, sb = [], []
         for _ in range(args.rounds):
-            se.append(timed(step_engine)); sb.append(timed(step_composed))
+            se.append(cb.timed(step_engine, reps)); sb.append(cb.timed(step_composed, reps))
         rec["step_d%d" % d] = {"engine": stats(se), "composed": stats(sb), "ratio": statistics.median(sb) / statistics.median(se)}
         torch_op.clear_cache()
         del A, Q, Kk, V, G, rws
-    line = json.dumps(rec)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
+    cb.emit(rec, args.out)
 
 
 if __name__ == "__main__":

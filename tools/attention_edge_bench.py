@@ -8,56 +8,27 @@ The composition, once per head h (S and P materialised, the edge terms as (nnz,)
     S  = sddmm(A, Q_h, K_h) with (Q_h[row] * Ek_h).sum(-1) added to its values      the key term: a gathered (nnz, d) product
     P  = row_softmax(S, scale)
     O_h = spmm(P, V_h) + spmm_edge(A, None, P.values()[:, None] * Ev_h, op="copy")  the value term: an (nnz, d) message tensor
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
-Per (H, d = dv): the forward alone (no autograd graph) and forward + backward (gradients of Q, K, V, edge_key and edge_value), each side
-timed between HIP events over --rounds rounds of `reps` calls, the two sides in ALTERNATING rounds after one untimed warm-up step per
-side; reps is chosen per record so that a round lasts about --round-ms.  "ratio" = composition median / fused median (> 1: the fused
-path is faster), "spread" = (max - min) / median of a side's rounds, "verdict": "fused" / "composition" when that side's slowest round
-beats the other's fastest -- a difference larger than the spread between repeats -- else "undecided".  "peak_bytes":
-torch.cuda.max_memory_allocated over one forward + backward step of a side, above what was allocated before it.  A case whose operands
-(the two (nnz, H, d) edge tensors) or whose step do not fit the device is recorded with "could not be allocated" for that side."""
+Matrices, rounds, "ratio", "spread", "verdict" and "peak_bytes": tools/compare_bench.py.
+Per (H, d = dv): the forward alone and forward + backward (gradients of Q, K, V, edge_key and edge_value).  A case whose operands (the
+two (nnz, H, d) edge tensors) or whose step do not fit the device is recorded with "could not be allocated" for that side."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 NO_MEMORY = "could not be allocated"
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap, tag=False)
     ap.add_argument("--heads", default="1,8")
     ap.add_argument("--dims", default="16,64")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
     from torch.autograd.function import once_differentiable
-    from sextans_amd import api, torch_op
+    from sextans_amd import torch_op
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, val, size=(M, K))
+    A, crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)
     row = torch.repeat_interleave(torch.arange(M, device=dev, dtype=torch.int32), (crow[1:] - crow[:-1]).long()).long()   # the composition's gather index
     gen = torch.Generator(device=dev).manual_seed(1)
 
@@ -111,36 +82,9 @@ def main():
             outs.append(torch_op.spmm(P, V[:, h]) + torch_op.spmm_edge(A, None, pv[:, None] * Ev[:, h], op="copy"))
         return torch.stack(outs, dim=1)
 
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c):
-        r = {"fused": stats(f), "composition": stats(c)}
-        r["ratio"] = r["composition"]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else "composition" if max(c) < min(f) else "undecided"
-        return r
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as fh:
-                fh.write(line + "\n")
-
     for H in [int(t) for t in args.heads.split(",") if t]:
         for d in [int(t) for t in args.dims.split(",") if t]:
-            rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": int(nnz), "H": H, "d": d, "rounds": args.rounds}
+            rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "H": H, "d": d, "rounds": args.rounds}
             torch_op.clear_cache()
             try:
                 # (filled in place: no temporaries of the operands' size)
@@ -151,78 +95,55 @@ def main():
                 Q = Kk = V = Ek = Ev = G = None
                 torch.cuda.empty_cache()
                 rec["operands"] = NO_MEMORY
-                emit(rec)
+                cb.emit(rec, args.out)
                 continue
             leaves = (Q, Kk, V, Ek, Ev)
             scale = d ** -0.5
 
-            def run(fused):
-                if fused:
+            def run(side):
+                if side == "fused":
                     return torch_op.sparse_attention_edge(A, Q, Kk, V, edge_key=Ek, edge_value=Ev, scale=scale)
                 return composed(Q, Kk, V, Ek, Ev, scale)
 
-            def forward(fused):
+            def forward(side):
                 with torch.no_grad():
-                    run(fused)
+                    run(side)
 
-            def step(fused):
+            def step(side):
                 for t in leaves:
                     t.grad = None
-                run(fused).backward(G)
+                run(side).backward(G)
 
-            peak, fits = {}, {}
-            for fused in (True, False):   # warm-up, and the peak of one step
-                side = "fused" if fused else "composition"
-                try:
-                    step(fused)
-                    for t in leaves:
-                        t.grad = None
-                    torch.cuda.synchronize()
-                    torch.cuda.reset_peak_memory_stats(dev)
-                    base = torch.cuda.memory_allocated(dev)
-                    step(fused)
-                    torch.cuda.synchronize()
-                    peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
-                    fits[side] = True
-                except torch.cuda.OutOfMemoryError:
-                    for t in leaves:
-                        t.grad = None
-                    torch.cuda.empty_cache()
-                    peak[side], fits[side] = NO_MEMORY, False
+            both = ("fused", "composition")
+            peak = {side: NO_MEMORY if nbytes is None else nbytes for side, nbytes in cb.warm_up_peaks(step, leaves, both, may_fail=both)}
             rec["peak_bytes"] = peak
             for name, fn in (("forward", forward), ("forward_backward", step)):
-                sides = [s for s in (True, False) if fits["fused" if s else "composition"] or name == "forward"]
+                sides = [s for s in both if peak[s] != NO_MEMORY or name == "forward"]
                 if not sides:
                     rec[name] = NO_MEMORY
                     continue
                 try:
-                    once = max(timed(lambda: fn(s), 1) for s in sides)
-                    reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-                    ts = {s: [] for s in sides}
-                    for _ in range(args.rounds):   # alternating rounds
-                        for s in sides:
-                            ts[s].append(timed(lambda: fn(s), reps))
+                    ts, reps = cb.alternating_rounds(fn, sides, args)
                 except torch.cuda.OutOfMemoryError:
                     torch.cuda.empty_cache()
                     rec[name] = NO_MEMORY
                     continue
                 if len(sides) == 2:
-                    rec[name] = compare(ts[True], ts[False])
+                    rec[name] = cb.two_sided(ts["fused"], ts["composition"])
                 else:   # one side alone fits: its times, no ratio
-                    rec[name] = {("fused" if s else "composition"): stats(t) for s, t in ts.items()}
-                    rec[name].update({("composition" if s else "fused"): NO_MEMORY for s in sides}, verdict="fused" if sides == [True] else "composition")
+                    rec[name] = {s: cb.stats(t) for s, t in ts.items()}
+                    rec[name].update({s: NO_MEMORY for s in both if s not in sides}, verdict=sides[0])
                 rec[name]["reps"] = reps
-            emit(rec)
+            cb.emit(rec, args.out)
             torch_op.clear_cache()
             del Q, Kk, V, Ek, Ev, G, leaves
             torch.cuda.empty_cache()
-    if args.out:   # per workload: does the fused path beat the composition by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix]
-        for name in ("forward", "forward_backward"):
-            verdicts = ["H%d d%d %s" % (r["H"], r["d"], ("%s x%.2f" % (r[name]["verdict"], r[name]["ratio"])) if isinstance(r.get(name), dict) and "ratio" in r[name]
-                        else r.get("operands") or (r[name]["verdict"] + " alone fits" if isinstance(r.get(name), dict) else r.get(name))) for r in recs]
-            print("%s %s: %s" % (args.matrix, name, "; ".join(str(x) for x in verdicts)))
+    if args.out:
+        recs = cb.read_records(args.out, args.matrix)
+        for name in cb.PASSES:
+            cb.summary_line(recs, args.matrix, name, lambda r: "H%d d%d" % (r["H"], r["d"]),
+                            lambda r: r[name] if isinstance(r.get(name), dict) and "ratio" in r[name] else None,
+                            lambda r: r.get("operands") or (r[name]["verdict"] + " alone fits" if isinstance(r.get(name), dict) else r.get(name)))
 
 
 if __name__ == "__main__":

@@ -11,64 +11,34 @@
     python tools/score_attention_bench.py --matrix config4 --out profiles/score_attention.jsonl     (appends one record per (H, dv))
     python tools/score_attention_bench.py --matrix small --heads 1,8 --dims 16,64
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
+Matrices, rounds, "ratio", "spread", "verdict", "peak_bytes" and --tag: tools/compare_bench.py; each other side is compared with the fused
+op in rounds of its own, with "fused" / the other side's name as the verdict's words, and reps is chosen per comparison.
 The nnz-long row-index vector and the scores are built once, outside every timed region.  Per (H, dv) and other side: the forward alone
-(no autograd graph) and forward + backward (gradients of S -- for (c) of a_dst and a_src -- and V), each side timed between HIP events
-over --rounds rounds of `reps` calls, fused and other side in ALTERNATING rounds after one untimed warm-up step per side (engine, A^T and
-tables are built there); reps is chosen per comparison so that a round lasts about --round-ms.  "ratio" = other median / fused median
-(> 1: the fused path is faster), "spread" = (max - min) / median of a side's rounds, "verdict": "fused" / the other side's name when that
-side's slowest round beats the other's fastest -- a difference larger than the spread between repeats -- else "undecided".
-"peak_bytes": torch.cuda.max_memory_allocated over one forward + backward step of a side, above what was allocated before it.
+and forward + backward (gradients of S -- for (c) of a_dst and a_src -- and V).
 --passes times the kernels alone through the C ABI -- the forward, the backward's row pass (d_dV NULL), its column pass (d_dS NULL) and
 both -- and writes records of "kind": "passes" (keep them in a file of their own: profiles/score_attention_passes.jsonl)."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 SIDES = ("per_head", "torch", "gat")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap)
     ap.add_argument("--heads", default="1,8")
     ap.add_argument("--dims", default="16,64")
     ap.add_argument("--sides", default=",".join(SIDES))
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
     ap.add_argument("--slope", type=float, default=0.2)
     ap.add_argument("--passes", action="store_true", help="time the forward, the row pass, the column pass and the backward on the C ABI: no other side")
-    ap.add_argument("--tag", default="", help="written into every record as \"tag\" (names the build that was timed)")
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     sides = [s for s in args.sides.split(",") if s]
     assert all(s in SIDES for s in sides), sides
     import torch
     from sextans_amd import api, torch_op
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    nnz = int(nnz)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, val, size=(M, K))
+    A, crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)
     gen = torch.Generator(device=dev).manual_seed(1)
     row = torch_op.entry_rows(A)   # built once, untimed
     col64 = col.long()
@@ -101,25 +71,6 @@ def main():
         msg = (P[:, :, None] * V[col64]).flatten(1)
         return torch.segment_reduce(msg, "sum", lengths=lengths, axis=0, unsafe=True).unflatten(1, V.shape[1:])
 
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c, other):
-        r = {"fused": stats(f), other: stats(c)}
-        r["ratio"] = r[other]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else other if max(c) < min(f) else "undecided"
-        return r
-
     def passes(H, d):
         """the C ABI directly: the forward, the row pass alone (d_dV NULL), the column pass alone (d_dS NULL) and the whole backward"""
         S = torch.rand((nnz, H), device=dev, generator=gen) * 2 - 1
@@ -144,20 +95,15 @@ def main():
         rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "H": H, "dv": d, "rounds": args.rounds, "kind": "passes"}
         for name, fn in (("forward", fwd), ("row_pass", lambda: bwd(True, False)), ("column_pass", lambda: bwd(False, True)),
                          ("backward", lambda: bwd(True, True))):
-            reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / timed(fn, 1))))
-            rec[name] = stats([timed(fn, reps) for _ in range(args.rounds)])
+            ts, _ = cb.alternating_rounds(lambda f: f(), [fn], args)   # (one side, itself the call)
+            rec[name] = cb.stats(ts[fn])
         torch_op.clear_cache()
         return rec
 
     if args.passes:
         for H in [int(t) for t in args.heads.split(",") if t]:
             for d in [int(t) for t in args.dims.split(",") if t]:
-                line = json.dumps(passes(H, d))
-                print(line, flush=True)
-                if args.out:
-                    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-                    with open(args.out, "a") as fh:
-                        fh.write(line + "\n")
+                cb.emit(passes(H, d), args.out)
         return
 
     for H in [int(t) for t in args.heads.split(",") if t]:
@@ -208,17 +154,9 @@ def main():
                             t.grad = None
                         torch.cuda.empty_cache()
                         continue
-                step(side)
+                peak[side] = cb.peak_of_step(lambda: step(side), params[side])
                 for t in params[side]:
                     t.grad = None
-                torch.cuda.synchronize()
-                torch.cuda.reset_peak_memory_stats(dev)
-                base = torch.cuda.memory_allocated(dev)
-                step(side)
-                for t in params[side]:
-                    t.grad = None
-                torch.cuda.synchronize()
-                peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
                 torch.cuda.empty_cache()
                 if side != "fused":
                     run.append(side)
@@ -227,30 +165,19 @@ def main():
             for name, fn in (("forward", forward), ("forward_backward", step)):
                 rec[name] = {}
                 for side in run:
-                    once = max(timed(lambda: fn("fused"), 1), timed(lambda: fn(side), 1))
-                    reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-                    f, c = [], []
-                    for _ in range(args.rounds):   # alternating rounds
-                        f.append(timed(lambda: fn("fused"), reps)); c.append(timed(lambda: fn(side), reps))
-                    rec[name][side] = compare(f, c, side)
+                    ts, reps = cb.alternating_rounds(fn, ["fused", side], args)
+                    rec[name][side] = cb.two_sided(ts["fused"], ts[side], "fused", side)
                     rec[name][side]["reps"] = reps
-            line = json.dumps(rec)
-            print(line, flush=True)
-            if args.out:
-                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-                with open(args.out, "a") as fh:
-                    fh.write(line + "\n")
+            cb.emit(rec, args.out)
             torch_op.clear_cache()
             del ad, as_, V, G, S, params
             torch.cuda.empty_cache()
-    if args.out:   # per workload: does the fused path beat each other side by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix]
-        for name in ("forward", "forward_backward"):
+    if args.out:
+        recs = cb.read_records(args.out, args.matrix)
+        for name in cb.PASSES:
             for side in sides:
-                verdicts = ["H%d dv%d %s x%.2f" % (r["H"], r["dv"], r[name][side]["verdict"], r[name][side]["ratio"]) for r in recs
-                            if side in r[name]]
-                print("%s %s vs %s: %s" % (args.matrix, name, side, "; ".join(verdicts)))
+                cb.summary_line([r for r in recs if side in r[name]], args.matrix, "%s vs %s" % (name, side),
+                                lambda r: "H%d dv%d" % (r["H"], r["dv"]), lambda r: r[name][side])
 
 
 if __name__ == "__main__":

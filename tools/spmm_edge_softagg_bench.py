@@ -6,63 +6,31 @@ on one GPU.
     python tools/spmm_edge_softagg_bench.py --matrix config4 --out profiles/spmm_edge_softagg.jsonl     (appends one record per N and op)
     python tools/spmm_edge_softagg_bench.py --matrix small --dims 16,64 --ops add_relu,copy
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
-The composition's row lengths and 64-bit column indices are built once, outside every timed region.  Per N and op: the forward alone (no
-autograd graph) and forward + backward (the gradients of B -- not for "copy" --, of E and of the (N,) temperature t), each side timed
-between HIP events over --rounds rounds of `reps` calls, the sides in ALTERNATING rounds after one untimed warm-up step per side (engine,
-A^T and tables are built there); reps is chosen per record so that a round lasts about --round-ms.  "ratio" = composition median / fused
-median (> 1: the fused path is faster), "spread" = (max - min) / median of a side's rounds, "verdict": "fused" / "composition" when that
-side's slowest round beats the other's fastest -- a difference larger than the spread between repeats -- else "undecided".
-"peak_bytes": torch.cuda.max_memory_allocated over one forward + backward step of a side, above what was allocated before it (B, E, G, t
-and the matrix are allocated before it on every side).  A composition case that cannot be allocated is recorded as such
-("composition": "out of memory") and the fused side is timed alone; an E that cannot be allocated ends the record ("E": "out of memory").
+Matrices, rounds, "ratio", "spread", "verdict", "peak_bytes" and --tag: tools/compare_bench.py.
+The composition's row lengths and 64-bit column indices are built once, outside every timed region.  Per N and op: the forward alone and
+forward + backward (the gradients of B -- not for "copy" --, of E and of the (N,) temperature t); B, E, G, t and the matrix are allocated
+before a side's peak is taken.  A composition case that cannot be allocated is recorded as such ("composition": "out of memory") and the
+fused side is timed alone; an E that cannot be allocated ends the record ("E": "out of memory").
 For information, on the same matrix and N: "spmm_softagg" = torch_op.spmm_softagg(A, B, t), the scalar-weighted messages val[e] * B[c]
 under the same softmax (its backward: the gradients of B and t) -- the fused op without the E stream, i.e. what E and dE cost.
 "bytes_per_entry": what the fused forward must at least move per stored entry (4 + 8 N: the column index, a gathered B row and the E
-row; 4 + 4 N for "copy"), for reading the times against.
---tag NAME is written into every record and says which build it timed."""
+row; 4 + 4 N for "copy"), for reading the times against."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap)
     ap.add_argument("--dims", default="16,64")
     ap.add_argument("--ops", default="add_relu,copy")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
-    ap.add_argument("--tag", default="", help="written into every record as \"tag\" (names the build that was timed)")
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
-    from sextans_amd import api, torch_op
+    from sextans_amd import torch_op
     from sextans_amd.edge_softagg import spmm_edge_softagg
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    nnz = int(nnz)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, val, size=(M, K))
+    A, crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)
     gen = torch.Generator(device=dev).manual_seed(1)
     lens = (crow[1:] - crow[:-1]).long()       # built once, untimed
     col64 = col.long()
@@ -76,33 +44,6 @@ def main():
         acc = torch.segment_reduce(W * P, "sum", lengths=lens, axis=0)
         return acc / z.clamp(min=1e-30)
 
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c):
-        r = {"fused": stats(f), "composition": stats(c)}
-        r["ratio"] = r["composition"]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else "composition" if max(c) < min(f) else "undecided"
-        return r
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as fh:
-                fh.write(line + "\n")
-
     extras = ["spmm_softagg"]
     for N in [int(x) for x in args.dims.split(",") if x]:
         B = (torch.rand((K, N), device=dev, generator=gen) * 2 - 1).requires_grad_()
@@ -112,7 +53,7 @@ def main():
             E = torch.rand((nnz, N), device=dev, generator=gen).mul_(2).sub_(1).requires_grad_()
         except torch.OutOfMemoryError:
             torch.cuda.empty_cache()
-            emit({"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "N": N, "E": "out of memory", "E_bytes": 4 * nnz * N})
+            cb.emit({"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "N": N, "E": "out of memory", "E_bytes": 4 * nnz * N}, args.out)
             continue
         for op in [x for x in args.ops.split(",") if x]:
             leaves = (E, t) if op == "copy" else (B, E, t)
@@ -142,58 +83,37 @@ def main():
                 rec["tag"] = args.tag
             sides = ["fused", "composition"]
             peak = {}
-            for side in list(sides) + extras:   # warm-up, and the peak of one step
-                try:
-                    step(side)
-                    for x in (B, E, t):
-                        x.grad = None
-                    torch.cuda.synchronize()
-                    torch.cuda.reset_peak_memory_stats(dev)
-                    base = torch.cuda.memory_allocated(dev)
-                    step(side)
-                    torch.cuda.synchronize()
-                    peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
-                except torch.OutOfMemoryError:
-                    if side != "composition":
-                        raise
+            for side, nbytes in cb.warm_up_peaks(step, (B, E, t), sides + extras, may_fail=["composition"]):
+                if nbytes is None:
                     sides.remove("composition")
                     rec["composition"] = "out of memory"
+                else:
+                    peak[side] = nbytes
                 for x in (B, E, t):
                     x.grad = None
                 torch.cuda.empty_cache()
             rec["peak_bytes"] = peak
             rec["value_refreshes"] = torch_op.cache_info()["value_refreshes"]
             for name, fn in (("forward", forward), ("forward_backward", step)):
-                try:
-                    once = max(timed(lambda: fn(s), 1) for s in sides)
-                except torch.OutOfMemoryError:   # (the step fitted once, or the other way round)
-                    torch.cuda.empty_cache()
-                    sides.remove("composition")
+                once, lost = cb.slowest_once_dropping(fn, sides)
+                if lost:
                     rec["composition"] = "out of memory"
-                    once = timed(lambda: fn("fused"), 1)
-                reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-                ts = {s: [] for s in sides + extras}
-                for _ in range(args.rounds):   # alternating rounds
-                    for s in ts:
-                        ts[s].append(timed(lambda: fn(s), reps))
-                rec[name] = compare(ts["fused"], ts["composition"]) if "composition" in ts else {"fused": stats(ts["fused"])}
+                ts, reps = cb.rounds_at(fn, sides + extras, once, args)
+                rec[name] = cb.pass_block(ts)
                 for s in extras:
-                    rec[name][s] = stats(ts[s])
+                    rec[name][s] = cb.stats(ts[s])
                 rec[name]["reps"] = reps
                 for x in (B, E, t):
                     x.grad = None
                 torch.cuda.empty_cache()
-            emit(rec)
+            cb.emit(rec, args.out)
             torch_op.clear_cache()
         del B, E, G, t, leaves
         torch.cuda.empty_cache()
-    if args.out:   # per workload: does the fused path beat the composition by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix and "op" in r]
-        for name in ("forward", "forward_backward"):
-            verdicts = ["N%d %s %s" % (r["N"], r["op"], "%s x%.2f" % (r[name]["verdict"], r[name]["ratio"]) if "verdict" in r[name]
-                                       else "composition: out of memory") for r in recs]
-            print("%s %s: %s" % (args.matrix, name, "; ".join(verdicts)))
+    if args.out:
+        recs = [r for r in cb.read_records(args.out, args.matrix) if "op" in r]
+        for name in cb.PASSES:
+            cb.summary_line(recs, args.matrix, name, lambda r: "N%d %s" % (r["N"], r["op"]), lambda r: r[name])
 
 
 if __name__ == "__main__":

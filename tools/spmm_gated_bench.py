@@ -6,58 +6,28 @@ same tensors, on one GPU.
     python tools/spmm_gated_bench.py --matrix config4 --out profiles/spmm_gated.jsonl     (appends one record per N, mode and E / no E)
     python tools/spmm_gated_bench.py --matrix small --dims 16,64
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
-The composition's 64-bit row and column indices are built once, outside every timed region.  Per record: the forward alone (no autograd
-graph) and forward + backward (the gradients of x_dst, x_src, V and, when present, E), each side timed between HIP events over --rounds
-rounds of `reps` calls, the sides in ALTERNATING rounds after one untimed warm-up step per side (engine, A^T and tables are built there);
-reps is chosen per record so that a round lasts about --round-ms.  "ratio" = composition median / fused median (> 1: the fused path is
-faster), "spread" = (max - min) / median of a side's rounds, "verdict": "fused" / "composition" when that side's slowest round beats the
-other's fastest -- a difference larger than the spread between repeats -- else "undecided".
-"peak_bytes": torch.cuda.max_memory_allocated over one forward + backward step of a side, above what was allocated before it (the
-operands, E among them, are allocated before).  A case whose operands or whose composition cannot be allocated is recorded as such
-("operands": "out of memory" / "composition": "out of memory"); in the second case the fused side is timed alone."""
+Matrices, rounds, "ratio", "spread", "verdict" and "peak_bytes": tools/compare_bench.py.
+The composition's 64-bit row and column indices are built once, outside every timed region.  Per record: the forward alone and forward +
+backward (the gradients of x_dst, x_src, V and, when present, E); the operands, E among them, are allocated before a side's peak is taken.
+A case whose operands or whose composition cannot be allocated is recorded as such ("operands": "out of memory" / "composition": "out of
+memory"); in the second case the fused side is timed alone."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap, tag=False)
     ap.add_argument("--dims", default="16,64")
     ap.add_argument("--modes", default="sum,norm")
     ap.add_argument("--edge", default="0,1", help="0: without E, 1: with E")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
-    from sextans_amd import api, torch_op
+    from sextans_amd import torch_op
     from sextans_amd.gated import spmm_gated
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    nnz = int(nnz)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, val, size=(M, K))
+    A, crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)
     gen = torch.Generator(device=dev).manual_seed(1)
     lens = (crow[1:] - crow[:-1]).long()       # built once, untimed
     row64 = torch.repeat_interleave(torch.arange(M, device=dev), lens, output_size=nnz)
@@ -73,33 +43,6 @@ def main():
         if not norm:
             return num
         return num / (torch_op.spmm_edge(A, None, g, "copy") + eps)
-
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c):
-        r = {"fused": stats(f), "composition": stats(c)}
-        r["ratio"] = r["composition"]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else "composition" if max(c) < min(f) else "undecided"
-        return r
-
-    def emit(rec):
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as fh:
-                fh.write(line + "\n")
 
     cases = [(int(n), m, e == "1") for n in args.dims.split(",") if n for m in args.modes.split(",") if m for e in args.edge.split(",") if e]
     for N, mode, with_e in cases:
@@ -117,7 +60,7 @@ def main():
             xd = xs = V = E = G = None
             torch.cuda.empty_cache()
             rec["operands"] = "out of memory"
-            emit(rec)
+            cb.emit(rec, args.out)
             continue
         leaves = [t for t in (xd, xs, V, E) if t is not None]
 
@@ -137,56 +80,31 @@ def main():
 
         sides = ["fused", "composition"]
         peak = {}
-        for side in list(sides):   # warm-up, and the peak of one step
-            try:
-                step(side)
-                for x in leaves:
-                    x.grad = None
-                torch.cuda.synchronize()
-                torch.cuda.reset_peak_memory_stats(dev)
-                base = torch.cuda.memory_allocated(dev)
-                step(side)
-                torch.cuda.synchronize()
-                peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
-            except torch.OutOfMemoryError:
-                if side != "composition":
-                    raise
-                for x in leaves:
-                    x.grad = None
-                torch.cuda.empty_cache()
+        for side, nbytes in cb.warm_up_peaks(step, leaves, tuple(sides), may_fail=["composition"]):
+            if nbytes is None:
                 sides.remove("composition")
                 rec["composition"] = "out of memory"
+            else:
+                peak[side] = nbytes
         rec["peak_bytes"] = peak
         rec["value_refreshes"] = torch_op.cache_info()["value_refreshes"]
         for name, fn in (("forward", forward), ("forward_backward", step)):
             for x in leaves:
                 x.grad = None
-            try:
-                once = max(timed(lambda: fn(s), 1) for s in sides)
-            except torch.OutOfMemoryError:   # (the forward alone fitted, or the other way round)
-                torch.cuda.empty_cache()
-                sides.remove("composition")
+            once, lost = cb.slowest_once_dropping(fn, sides)
+            if lost:
                 rec["composition"] = "out of memory"
-                once = timed(lambda: fn("fused"), 1)
-            reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-            ts = {s: [] for s in sides}
-            for _ in range(args.rounds):   # alternating rounds
-                for s in ts:
-                    ts[s].append(timed(lambda: fn(s), reps))
-            rec[name] = compare(ts["fused"], ts["composition"]) if "composition" in ts else {"fused": stats(ts["fused"])}
+            ts, reps = cb.rounds_at(fn, sides, once, args)
+            rec[name] = cb.pass_block(ts)
             rec[name]["reps"] = reps
-        emit(rec)
+        cb.emit(rec, args.out)
         torch_op.clear_cache()
         del xd, xs, V, E, G, leaves
         torch.cuda.empty_cache()
-    if args.out:   # per workload: does the fused path beat the composition by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix and "forward" in r]
-        for name in ("forward", "forward_backward"):
-            verdicts = ["N%d %s%s %s" % (r["N"], r["mode"], "+E" if r["edge_features"] else "",
-                                         "%s x%.2f" % (r[name]["verdict"], r[name]["ratio"]) if "verdict" in r[name] else "composition: out of memory")
-                        for r in recs]
-            print("%s %s: %s" % (args.matrix, name, "; ".join(verdicts)))
+    if args.out:
+        recs = [r for r in cb.read_records(args.out, args.matrix) if "forward" in r]
+        for name in cb.PASSES:
+            cb.summary_line(recs, args.matrix, name, lambda r: "N%d %s%s" % (r["N"], r["mode"], "+E" if r["edge_features"] else ""), lambda r: r[name])
 
 
 if __name__ == "__main__":

@@ -6,55 +6,26 @@ spmm_reduce(A, B, "amin") -- those of them the aggregate set needs -- and the sa
     python tools/spmm_multi_bench.py --matrix config4 --out profiles/spmm_multi.jsonl     (appends one record per N and aggregate set)
     python tools/spmm_multi_bench.py --matrix small --dims 16,64
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
-Per N and aggregate set ("mean,max,min,std" and "mean,std"): the forward alone (no autograd graph) and forward + backward (the gradient
-of B), each side timed between HIP events over --rounds rounds of `reps` calls, the two sides in ALTERNATING rounds after one untimed
-warm-up step per side (engines, A^T and tables are built there); reps is chosen per record so that a round lasts about --round-ms.
-"ratio" = composition median / fused median (> 1: the fused path is faster), "spread" = (max - min) / median of a side's rounds,
-"verdict": "fused" / "composition" when that side's slowest round beats the other's fastest -- a difference larger than the spread
-between repeats -- else "undecided".  "peak_bytes": torch.cuda.max_memory_allocated over one forward + backward step of a side, above
-what was allocated before it.  "reduce_amax": one spmm_reduce(A, B, "amax") pass on the same matrix and N, for information: the fused
+Matrices, rounds, "ratio", "spread", "verdict", "peak_bytes" and --tag: tools/compare_bench.py.
+Per N and aggregate set ("mean,max,min,std" and "mean,std"): the forward alone and forward + backward (the gradient of B).
+"reduce_amax": one spmm_reduce(A, B, "amax") pass on the same matrix and N, for information: the fused
 forward does the same gathers."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap)
     ap.add_argument("--dims", default="16,64")
     ap.add_argument("--aggr", default="mean,max,min,std;mean,std", help="aggregate sets, ';' between sets")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
-    ap.add_argument("--tag", default="", help="written into every record as \"tag\" (names the build that was timed)")
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
-    from sextans_amd import api, torch_op
+    from sextans_amd import torch_op
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-    for src in (p, i, v):
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, torch.ones(nnz, dtype=torch.float32, device=dev), size=(M, K))   # unit values
+    crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)[1:]
+    A = torch.sparse_csr_tensor(crow, col, val.fill_(1.0), size=(M, K))   # unit values
     deg = (crow[1:] - crow[:-1]).clamp(min=1).to(torch.float32)[:, None]
     gen = torch.Generator(device=dev).manual_seed(1)
     eps = 1e-5
@@ -75,25 +46,6 @@ def main():
             raw["var"] = raw["sumsq"] / deg - raw["mean"] ** 2
             raw["std"] = torch.sqrt(torch.relu(raw["var"]) + eps)
         return torch.cat([raw[x] for x in aggr], dim=1)
-
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c):
-        r = {"fused": stats(f), "composition": stats(c)}
-        r["ratio"] = r["composition"]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else "composition" if max(c) < min(f) else "undecided"
-        return r
 
     for N in [int(t) for t in args.dims.split(",") if t]:
         for aggr in [tuple(s.split(",")) for s in args.aggr.split(";") if s]:
@@ -117,51 +69,29 @@ def main():
                 out.backward(G if side != "reduce_amax" else G[:, :N])
 
             torch_op.clear_cache()
-            rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": int(nnz), "N": N, "aggr": list(aggr), "rounds": args.rounds,
+            rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "N": N, "aggr": list(aggr), "rounds": args.rounds,
                    "composition_form": "spmm x2 + spmm_reduce x2, unit values"}
             if args.tag:
                 rec["tag"] = args.tag
             sides = ["fused", "composition"]
-            peak = {}
-            for side in sides + ["reduce_amax"]:   # warm-up, and the peak of one step
-                step(side)
-                B.grad = None
-                torch.cuda.synchronize()
-                torch.cuda.reset_peak_memory_stats(dev)
-                base = torch.cuda.memory_allocated(dev)
-                step(side)
-                torch.cuda.synchronize()
-                peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
-            rec["peak_bytes"] = peak
+            rec["peak_bytes"] = dict(cb.warm_up_peaks(step, (B,), sides + ["reduce_amax"]))
             rec["value_refreshes"] = torch_op.cache_info()["value_refreshes"]
             with torch.no_grad():   # the two sides compute the same thing
                 diff = (apply("fused") - apply("composition")).abs().max().item()
             rec["max_abs_diff"] = diff
             for name, fn in (("forward", forward), ("forward_backward", step)):
-                once = max(timed(lambda: fn(s), 1) for s in sides)
-                reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-                ts = {s: [] for s in sides + ["reduce_amax"]}
-                for _ in range(args.rounds):   # alternating rounds
-                    for s in ts:
-                        ts[s].append(timed(lambda: fn(s), reps))
-                rec[name] = compare(ts["fused"], ts["composition"])
-                rec[name]["reduce_amax"] = stats(ts["reduce_amax"])
+                ts, reps = cb.alternating_rounds(fn, sides, args, also=["reduce_amax"])
+                rec[name] = cb.two_sided(ts["fused"], ts["composition"])
+                rec[name]["reduce_amax"] = cb.stats(ts["reduce_amax"])
                 rec[name]["reps"] = reps
-            line = json.dumps(rec)
-            print(line, flush=True)
-            if args.out:
-                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-                with open(args.out, "a") as fh:
-                    fh.write(line + "\n")
+            cb.emit(rec, args.out)
             torch_op.clear_cache()
             del B, G
             torch.cuda.empty_cache()
-    if args.out:   # per workload: does the fused path beat the composition by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix]
-        for name in ("forward", "forward_backward"):
-            verdicts = ["N%d %s %s x%.2f" % (r["N"], "+".join(r["aggr"]), r[name]["verdict"], r[name]["ratio"]) for r in recs]
-            print("%s %s: %s" % (args.matrix, name, "; ".join(verdicts)))
+    if args.out:
+        recs = cb.read_records(args.out, args.matrix)
+        for name in cb.PASSES:
+            cb.summary_line(recs, args.matrix, name, lambda r: "N%d %s" % (r["N"], "+".join(r["aggr"])), lambda r: r[name])
 
 
 if __name__ == "__main__":

@@ -5,68 +5,37 @@ through it -- on the same commit, the same process and the same tensors, on one 
     python tools/spmm_reduce_bench.py --matrix config4 --out profiles/spmm_reduce.jsonl     (appends one record per N)
     python tools/spmm_reduce_bench.py --matrix small --dims 16,64
 
-Matrices: "config4" = gen_csr_device(4 M, 4 M, Poisson(40)), "fem" = gen_fem3d_device(110, 110, 110, 3) (3.99 M rows, 318 M non-zeros),
-"powerlaw" = gen_powerlaw_device(1 M, 1 M, 6, 1.2, 400 000), "small" = a 200 k-row config-4 for trying the tool out.
+Matrices, rounds, "ratio", "spread", "verdict", "peak_bytes" and --tag: tools/compare_bench.py.
 The composition's nnz-long row-index vector (and the row lengths) are built once, outside every timed region.  Per N: the forward alone
-(no autograd graph) and forward + backward (the gradient of B; --grad-a: of A's values too), each side timed between HIP events over
---rounds rounds of `reps` calls, the two sides in ALTERNATING rounds after one untimed warm-up step per side (engine, A^T and tables are
-built there); reps is chosen per record so that a round lasts about --round-ms.  "ratio" = composition median / fused median (> 1: the
-fused path is faster), "spread" = (max - min) / median of a side's rounds, "verdict": "fused" / "composition" when that side's slowest
-round beats the other's fastest -- a difference larger than the spread between repeats -- else "undecided".
-"peak_bytes": torch.cuda.max_memory_allocated over one forward + backward step of a side, above what was allocated before it.
+and forward + backward (the gradient of B; --grad-a: of A's values too).
 A composition case that cannot be allocated is recorded as such ("composition": "out of memory") and the fused side is timed alone.
 "spmm_sum": torch_op.spmm (the strict sum product) on the same matrix and N, for information: it does the same gathers.
 "torch_sparse_mm_gpu": what torch.sparse.mm(A, B, "amax") of the installed GPU build does on a 1000-row corner of the matrix.
---fused-only times spmm_reduce alone (kernel tuning between two builds): no composition, no verdict; --tag NAME is written into every
-record and says which build it timed."""
+--fused-only times spmm_reduce alone (kernel tuning between two builds): no composition, no verdict."""
 import argparse
-import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import compare_bench as cb
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrix", choices=["config4", "fem", "powerlaw", "small"], default="small")
+    cb.add_protocol_args(ap)
     ap.add_argument("--dims", default="16,64")
     ap.add_argument("--reduce", choices=["amax", "amin"], default="amax")
     ap.add_argument("--composition", choices=["scatter", "segment"], default="scatter", help="scatter_reduce over the row index, or segment_reduce")
     ap.add_argument("--grad-a", action="store_true", help="forward + backward also takes the gradient of A's values")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--round-ms", type=float, default=200.0)
-    ap.add_argument("--max-reps", type=int, default=8)
     ap.add_argument("--fused-only", action="store_true", help="time spmm_reduce alone (kernel tuning): no composition, no verdict")
-    ap.add_argument("--tag", default="", help="written into every record as \"tag\" (names the build that was timed)")
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
-    from sextans_amd import api, torch_op
+    from sextans_amd import torch_op
     dev = torch.device("cuda", 0)
-    if args.matrix == "fem":
-        M = K = 110 ** 3 * 3
-        p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
-    elif args.matrix == "powerlaw":
-        M = K = 1_000_000
-        p, i, v, nnz = api.gen_powerlaw_device(0, M, K, 6, 120, 400_000, 7)
-    else:
-        M = K = 4_000_000 if args.matrix == "config4" else 200_000
-        p, i, v, nnz = api.gen_csr_device(0, M, K, 40.0, 4)
-    crow = torch.empty(M + 1, dtype=torch.int32, device=dev); col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    val = torch.empty(nnz, dtype=torch.float32, device=dev)
-    for dst, src, n in ((crow, p, (M + 1) * 4), (col, i, nnz * 4), (val, v, nnz * 4)):
-        api.device_copy(0, dst.data_ptr(), src, n)
-        api.device_free(0, src)
-    A = torch.sparse_csr_tensor(crow, col, val, size=(M, K))
+    A, crow, col, val, M, K, nnz = cb.load_matrix(args.matrix)
     vleaf = val.detach().clone()               # the composition's values: a dense leaf
     if args.grad_a:
         A.requires_grad_(); vleaf.requires_grad_()
     gen = torch.Generator(device=dev).manual_seed(1)
     lens = (crow[1:] - crow[:-1]).long()
-    row = torch.repeat_interleave(torch.arange(M, device=dev), lens, output_size=int(nnz))   # built once, untimed
+    row = torch.repeat_interleave(torch.arange(M, device=dev), lens, output_size=nnz)   # built once, untimed
     col64 = col.long()
     red = args.reduce
 
@@ -86,25 +55,6 @@ def main():
             return torch.segment_reduce(P, "max" if red == "amax" else "min", lengths=lens, axis=0)
         out = torch.zeros((M, B.shape[1]), dtype=P.dtype, device=dev)
         return out.scatter_reduce(0, row[:, None].expand(-1, B.shape[1]), P, red, include_self=False)
-
-    def timed(fn, reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps   # us per call
-
-    def stats(ts):
-        med = statistics.median(ts)
-        return {"median_us": med, "min_us": min(ts), "max_us": max(ts), "spread": (max(ts) - min(ts)) / med}
-
-    def compare(f, c):
-        r = {"fused": stats(f), "composition": stats(c)}
-        r["ratio"] = r["composition"]["median_us"] / r["fused"]["median_us"]
-        r["verdict"] = "fused" if max(f) < min(c) else "composition" if max(c) < min(f) else "undecided"
-        return r
 
     for N in [int(t) for t in args.dims.split(",") if t]:
         B = (torch.rand((K, N), device=dev, generator=gen) * 2 - 1).requires_grad_()
@@ -128,59 +78,33 @@ def main():
             apply(side).backward(G)
 
         torch_op.clear_cache()
-        rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": int(nnz), "N": N, "reduce": red, "rounds": args.rounds,
+        rec = {"matrix": args.matrix, "M": M, "K": K, "nnz": nnz, "N": N, "reduce": red, "rounds": args.rounds,
                "composition_form": args.composition + "_reduce", "grad_a": bool(args.grad_a), "torch_sparse_mm_gpu": sparse_mm}
         if args.tag:
             rec["tag"] = args.tag
         sides = ["fused"] if args.fused_only else ["fused", "composition"]
         peak = {}
-        for side in list(sides) + ["sum"]:   # warm-up, and the peak of one step
-            try:
-                step(side)
-                for t in leaves:
-                    t.grad = None
-                torch.cuda.synchronize()
-                torch.cuda.reset_peak_memory_stats(dev)
-                base = torch.cuda.memory_allocated(dev)
-                step(side)
-                torch.cuda.synchronize()
-                peak[side] = int(torch.cuda.max_memory_allocated(dev) - base)
-            except torch.OutOfMemoryError:
-                if side != "composition":
-                    raise
-                for t in leaves:
-                    t.grad = None
-                torch.cuda.empty_cache()
+        for side, nbytes in cb.warm_up_peaks(step, leaves, sides + ["sum"], may_fail=["composition"]):
+            if nbytes is None:
                 sides.remove("composition")
                 rec["composition"] = "out of memory"
+            else:
+                peak[side] = nbytes
         rec["peak_bytes"] = peak
         rec["value_refreshes"] = torch_op.cache_info()["value_refreshes"]
         for name, fn in (("forward", forward), ("forward_backward", step)):
-            once = max(timed(lambda: fn(s), 1) for s in sides)
-            reps = int(max(1, min(args.max_reps, args.round_ms * 1e3 / once)))
-            ts = {s: [] for s in sides + ["sum"]}
-            for _ in range(args.rounds):   # alternating rounds
-                for s in ts:
-                    ts[s].append(timed(lambda: fn(s), reps))
-            rec[name] = compare(ts["fused"], ts["composition"]) if "composition" in ts else {"fused": stats(ts["fused"])}
-            rec[name]["spmm_sum"] = stats(ts["sum"])
+            ts, reps = cb.alternating_rounds(fn, sides, args, also=["sum"])
+            rec[name] = cb.pass_block(ts)
+            rec[name]["spmm_sum"] = cb.stats(ts["sum"])
             rec[name]["reps"] = reps
-        line = json.dumps(rec)
-        print(line, flush=True)
-        if args.out:
-            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-            with open(args.out, "a") as fh:
-                fh.write(line + "\n")
+        cb.emit(rec, args.out)
         torch_op.clear_cache()
         del B, G, leaves
         torch.cuda.empty_cache()
-    if args.out and not args.fused_only:   # per workload: does the fused path beat the composition by more than the spread between repeats?
-        with open(args.out) as fh:
-            recs = [r for r in map(json.loads, fh) if r["matrix"] == args.matrix]
-        for name in ("forward", "forward_backward"):
-            verdicts = ["N%d %s" % (r["N"], "%s x%.2f" % (r[name]["verdict"], r[name]["ratio"]) if "verdict" in r[name] else "composition: out of memory")
-                        for r in recs]
-            print("%s %s: %s" % (args.matrix, name, "; ".join(verdicts)))
+    if args.out and not args.fused_only:
+        recs = cb.read_records(args.out, args.matrix)
+        for name in cb.PASSES:
+            cb.summary_line(recs, args.matrix, name, lambda r: "N%d" % r["N"], lambda r: r[name])
 
 
 if __name__ == "__main__":
