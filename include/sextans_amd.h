@@ -1332,6 +1332,41 @@ int sextans_spmm_t_device_rm_bf16(sextans_handle_t h, int N, float alpha, const 
                                   int64_t ldc_in, void *d_C_out, int64_t ldc, int c_dtype, void *stream);
 int sextans_prepare_rm_bf16(sextans_handle_t h, int N, int c_dtype, int transposed, void *stream);
 
+/* ---- bf16 EDGE tensors for the edge-output ops and the edge-feature SpMM: the (nnz, N) tensors of a call -- E, Z and Gz of
+ * sextans_edge_op*_device_rm, E and dE of sextans_spmm_edge*_device_rm -- in bf16 (16-bit patterns, uint16_t), read and written by the
+ * kernels where they lie.  They are the binding traffic of both families (the node operands are 1 / degree of it); under autocast the
+ * edge projection arrives in bf16 and the next layer wants bf16.  Closest thing in the reference: none.
+ *
+ * Storage changes, arithmetic does not.  The node tensors (xdst, xsrc, B, C, G, dxdst, dxsrc, dB) are fp32 as in the fp32 entry points,
+ * so is every operation and every sum, in the same order (same tiles, slots and dealing).  ONE dtype for all edge tensors of a call:
+ * there are no mixed forms.
+ *     read    a bf16 value is widened exactly (16 zero bits appended)
+ *     write   the fp32 result the fp32 entry point would have stored, rounded ONCE to nearest even: a NaN stays a quiet NaN, +-inf and
+ *             -0 stay what they are, a finite fp32 value at or above the rounding boundary (0x7f7f8000) becomes inf
+ * so for every op and pass
+ *     a bf16 output (Z, dE) is round_bf16(the fp32 entry point's output on the widened inputs), bit for bit;
+ *     an fp32 output (C, dxdst, dxsrc, dB) is the fp32 entry point's output on the widened inputs, bit for bit.
+ * Arguments, ops, what a call reads and ignores, NULL rules, pass skipping ("no A^T without d_dxsrc" / "without d_dB"), degenerate
+ * matrices and determinism are those of the fp32 twin (above).  No atomics, no workspace, no value refresh; after the first call on a
+ * matrix -- in particular after sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream) -- a call allocates nothing, reads nothing back
+ * and does not synchronise: it can be captured into a hipGraph.
+ * Leading dimensions are counted in ELEMENTS of their tensor: >= N and multiples of 4 for the bf16 tensors too (a piece of 4 columns is
+ * one 8-byte access), under the fp32 twin's rules for which of them count.  Every pointer 16-byte aligned.
+ * sextans_last_kernel: "edge_op_bf16" / "edge_op_backward_bf16" / "spmm_edge_bf16" / "spmm_edge_backward_bf16", "+long_rows" appended
+ * when the workgroup path ran.
+ * Errors: the fp32 twin's, in its order (SEXTANS_ERR_INVALID for the arguments, then SEXTANS_ERR_STATE without a CSR matrix, then
+ * SEXTANS_ERR_INVALID for nnz > INT32_MAX or a required pointer that is NULL with nnz > 0), all before any device is touched. */
+int sextans_edge_op_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_xdst, int64_t ldxdst, const float *d_xsrc, int64_t ldxsrc,
+                                   const uint16_t *d_E, int64_t lde, uint16_t *d_Z, int64_t ldz, void *stream);
+int sextans_edge_op_backward_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_xdst, int64_t ldxdst, const float *d_xsrc,
+                                            int64_t ldxsrc, const uint16_t *d_Gz, int64_t ldgz, float *d_dxdst, int64_t lddxdst,
+                                            float *d_dxsrc, int64_t lddxsrc, void *stream);
+int sextans_spmm_edge_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const uint16_t *d_E, int64_t lde,
+                                     float *d_C, int64_t ldc, void *stream);
+int sextans_spmm_edge_backward_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const uint16_t *d_E,
+                                              int64_t lde, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, uint16_t *d_dE,
+                                              int64_t ldde, void *stream);
+
 /* Row-range form: computes rows [row_begin, row_end) only.  d_C_in / d_C_out address row_begin as
  * their row 0 (ldc_in, ldc_out >= row_end - row_begin).  Used to pipeline a rank's slab in chunks so the
  * all-gather of chunk i overlaps the SpMM of chunk i+1.  flags: SEXTANS_ROWS_REUSE_B_PANELS = the B

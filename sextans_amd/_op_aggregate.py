@@ -10,7 +10,7 @@ from torch.autograd.function import once_differentiable
 
 from . import api
 from ._op_cache import (_check_sparse, _cut, _cut_grad, _f32, _index_tensors, _keep_pattern, _kept_pattern_entry, _pattern_entry_of,
-                        _pattern_grad, _ptr, _ptr_nonempty, _row_degrees, _rowmajor, _vals32)
+                        _pattern_grad, _ptr, _ptr_nonempty, _qualifies, _row_degrees, _rowmajor, _vals32)
 from ._op_product import spmm
 
 
@@ -22,13 +22,18 @@ def _tiled_entry(A, N, fast):
     return M, K, api.round_up_n(N), ent, stream, val
 
 
-def _rowmajor_ld(t, rows, N, Np):
+def _rowmajor_ld(t, rows, N, Np, dtype=torch.float32):
     """an optional (rows, N) operand as the kernels read it, zero-padded to Np columns where it must be copied -> (tensor, its leading
-    dimension); None -> (None, Np)"""
+    dimension); None -> (None, Np).  dtype: the element type the kernel reads (bf16: an edge tensor of the bf16 entry points)."""
     if t is None:
         return None, Np
-    t = _rowmajor(t.detach(), rows, N, Np)
+    t = _rowmajor(t.detach(), rows, N, Np, dtype)
     return t, t.stride(0)
+
+
+def _edge_bf16(E, N):
+    """does the edge tensor E (nnz, N) go to the bf16 entry points as it lies: bf16, N % 8 == 0, row-major, aligned"""
+    return E is not None and E.dtype == torch.bfloat16 and _qualifies(E, N, api.round_up_n(N), torch.bfloat16)
 
 
 def _any_elements(*outputs):
@@ -435,21 +440,26 @@ def spmm_multi(A, B, aggr=("mean", "max", "min", "std"), eps=1e-5, fast=False):
 
 # --- edge-feature SpMM ---------------------------------------------------------------------------------------------------------------
 def _edge_forward(A, B, E, op, fast):
-    """C (M, Np) of the engine's edge-feature SpMM, N padded up to a multiple of 8 (zero columns of B and E); B is None for EDGE_COPY."""
+    """C (M, Np) of the engine's edge-feature SpMM, N padded up to a multiple of 8 (zero columns of B and E); B is None for EDGE_COPY.
+    A bf16 E that the kernel can read where it lies goes to the bf16 entry point as it is: the same bits, no fp32 copy of E."""
     nnz, N = E.shape
     M, K, Np, ent, stream, _ = _tiled_entry(A, N, fast)
+    bf16 = _edge_bf16(E, N)
     Brm, ldb = _rowmajor_ld(B, K, N, Np)
-    Erm, lde = _rowmajor_ld(E, nnz, N, Np)
+    Erm, lde = _rowmajor_ld(E, nnz, N, Np, torch.bfloat16 if bf16 else torch.float32)
     C = _f32(A.device, M, Np)
     if _any_elements(C):
-        ent.eng.spmm_edge_device_rm(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(C), Np, stream)
+        call = ent.eng.spmm_edge_device_rm_bf16 if bf16 else ent.eng.spmm_edge_device_rm
+        call(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(C), Np, stream)
     return C
 
 
 class _SpmmEdgeFunction(torch.autograd.Function):
     """spmm_edge(): one kernel pass forward (sextans_spmm_edge_device_rm); backward a column pass over A^T for dB and a row pass over A
     that stores dE (sextans_spmm_edge_backward_device_rm).  Only the gradients autograd asks for are computed, and only the operands
-    their formulas read are handed over.  A's values never enter: no gradient for A, no value refresh.  Not twice differentiable."""
+    their formulas read are handed over.  A's values never enter: no gradient for A, no value refresh.  Not twice differentiable.
+    A bf16 E that went to the bf16 forward as it lies goes to sextans_spmm_edge_backward_device_rm_bf16 the same way, and the kernel
+    writes dE in bf16: the bits of the fp32 dE rounded to E's dtype, without the fp32 tensors."""
 
     @staticmethod
     def forward(ctx, A, B, E, op, fast):
@@ -473,14 +483,17 @@ class _SpmmEdgeFunction(torch.autograd.Function):
         ent, stream = _kept_pattern_entry(ctx, crow, col, val)
         need_b = op == api.EDGE_ADD_RELU or (op == api.EDGE_MUL and want_e)
         need_e = op == api.EDGE_ADD_RELU or (op == api.EDGE_MUL and want_b)
+        bf16 = _edge_bf16(E, N)                            # (the forward's route: one dtype for E and dE)
+        e_dtype = torch.bfloat16 if bf16 else torch.float32
         Grm, ldg = _rowmajor_ld(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
         Brm, ldb = _rowmajor_ld(B if need_b else None, K, N, Np)
-        Erm, lde = _rowmajor_ld(E if need_e else None, nnz, N, Np)
+        Erm, lde = _rowmajor_ld(E if need_e else None, nnz, N, Np, e_dtype)
         dB = _f32(G.device, K, Np) if want_b else None
-        dE = _f32(G.device, nnz, Np) if want_e else None
+        dE = torch.empty((nnz, Np), dtype=e_dtype, device=G.device) if want_e else None
         if _any_elements(dB, dE):
-            ent.eng.spmm_edge_backward_device_rm(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(Grm), ldg,
-                                                 _ptr_nonempty(dB), Np, _ptr_nonempty(dE), Np, stream)
+            call = ent.eng.spmm_edge_backward_device_rm_bf16 if bf16 else ent.eng.spmm_edge_backward_device_rm
+            call(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(Grm), ldg, _ptr_nonempty(dB), Np, _ptr_nonempty(dE), Np,
+                 stream)
         return None, _cut_grad(dB, N, B), _cut_grad(dE, N, E), None, None
 
 
@@ -517,7 +530,9 @@ def spmm_edge(A, B, E, op="mul", reduce="sum", fast=False):
     order fixed by the pattern -- no atomics, the same bits on every run; an empty row gives 0.  reduce="mean": the sum divided by the
     row's entry count clamped to >= 1, a composition.  Differentiable in B and E; only the gradients asked for are computed (a column
     pass over A^T for dB, a row pass that writes dE once).  `fast` only selects the cached engine.  An N that is not a multiple of 8, and
-    operands the kernel cannot read where they lie, are copied with zero padding, as spmm() does."""
+    operands the kernel cannot read where they lie, are copied with zero padding, as spmm() does.  A bf16 E (autocast) with N % 8 == 0
+    that is row-major and 16-byte aligned is read as it lies and its gradient written in bf16 by the kernel
+    (sextans_spmm_edge_device_rm_bf16 / _backward_device_rm_bf16): the bits of the fp32 route, without an fp32 (nnz, N) tensor."""
     _check_edge_op(op)
     if reduce not in ("sum", "mean"):
         raise ValueError("reduce must be 'sum' or 'mean'")

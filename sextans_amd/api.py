@@ -125,6 +125,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
     "sextans_vector_attention_device_rm", "sextans_vector_attention_backward_device_rm",
     "sextans_edge_op_device_rm", "sextans_edge_op_backward_device_rm",
+    "sextans_edge_op_device_rm_bf16", "sextans_edge_op_backward_device_rm_bf16",
+    "sextans_spmm_edge_device_rm_bf16", "sextans_spmm_edge_backward_device_rm_bf16",
     "sextans_edge_dot_device", "sextans_edge_dot_backward_device",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -397,6 +399,11 @@ def lib():
                                                               vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_op_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_op_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
+    # the bf16 twins take the same frames: only the element type behind the (nnz, N) pointers differs
+    L.sextans_edge_op_device_rm_bf16.argtypes = L.sextans_edge_op_device_rm.argtypes
+    L.sextans_edge_op_backward_device_rm_bf16.argtypes = L.sextans_edge_op_backward_device_rm.argtypes
+    L.sextans_spmm_edge_device_rm_bf16.argtypes = L.sextans_spmm_edge_device_rm.argtypes
+    L.sextans_spmm_edge_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_backward_device_rm.argtypes
     L.sextans_edge_dot_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_dot_backward_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1073,6 +1080,17 @@ class Engine:
         _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
                "spmm_edge_backward_device_rm")
 
+    def spmm_edge_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
+        """spmm_edge_device_rm with E in bf16 (sextans_spmm_edge_device_rm_bf16): B and C fp32, E widened exactly -- the bits of
+        spmm_edge_device_rm on the widened E.  lde counts bf16 elements (a multiple of 4)."""
+        _check(lib().sextans_spmm_edge_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream), "spmm_edge_device_rm_bf16")
+
+    def spmm_edge_backward_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream=None):
+        """spmm_edge_backward_device_rm with E and dE in bf16 (sextans_spmm_edge_backward_device_rm_bf16): B, G and dB fp32; dB the bits
+        of spmm_edge_backward_device_rm on the widened E, dE its dE rounded once to nearest even.  lde and ldde count bf16 elements."""
+        _check(lib().sextans_spmm_edge_backward_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
+               "spmm_edge_backward_device_rm_bf16")
+
     def spmm_edge_softagg_device_rm(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream=None):
         """Softmax aggregation of edge-feature messages (sextans_spmm_edge_softagg_device_rm): C[r, n] = sum over row r's stored entries
         e = (r, c) of softmax_e(t[n] * m_e[n]) * m_e[n], with the message m_e of spmm_edge_device_rm (B[c, n] * E[e, n], B + E, relu(B + E)
@@ -1133,6 +1151,20 @@ class Engine:
         xsrc is read only for EDGEOP_MUL's dxdst, xdst only for EDGEOP_MUL's dxsrc."""
         _check(lib().sextans_edge_op_backward_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc,
                                                         lddxsrc, stream), "edge_op_backward_device_rm")
+
+    def edge_op_device_rm_bf16(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream=None):
+        """edge_op_device_rm with E (optional) and Z in bf16 (sextans_edge_op_device_rm_bf16): xdst and xsrc fp32, E widened exactly, the
+        same fp32 operations, Z rounded once to nearest even -- round_bf16 of edge_op_device_rm's Z on the widened E.  lde and ldz count
+        bf16 elements (multiples of 4)."""
+        _check(lib().sextans_edge_op_device_rm_bf16(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream),
+               "edge_op_device_rm_bf16")
+
+    def edge_op_backward_device_rm_bf16(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc, lddxsrc,
+                                        stream=None):
+        """edge_op_backward_device_rm with Gz in bf16 (sextans_edge_op_backward_device_rm_bf16): dxdst and dxsrc fp32, the bits of
+        edge_op_backward_device_rm on the widened Gz.  ldgz counts bf16 elements (a multiple of 4)."""
+        _check(lib().sextans_edge_op_backward_device_rm_bf16(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst,
+                                                             d_dxsrc, lddxsrc, stream), "edge_op_backward_device_rm_bf16")
 
     def edge_dot_device(self, heads, d, d_X, ldx, d_Y, ldy, d_S, lds, stream=None):
         """Per-head dot product of both endpoints (sextans_edge_dot_device, DGL's u_dot_v): for every stored entry e = (r, c), in the CSR

@@ -23,32 +23,38 @@ namespace sx {
 enum { kEdgeOpAdd = 1, kEdgeOpSub = 2, kEdgeOpMul = 3, kEdgeOpDst = 4, kEdgeOpSrc = 5 };   // SEXTANS_EDGEOP_*
 enum { kEndSumPlain = 0, kEndSumNeg = 1, kEndSumMul = 2 };                                  // the endpoint sum's term
 
-struct EdgeOpArgs {
-    const float *xdst, *xsrc, *E;   // forward
-    float *Z;
-    const float *Gz, *x;            // endpoint sum; x: the OTHER endpoint's rows (MUL)
+// ET: the element type of the (nnz, N) tensors E, Z and Gz in memory -- float, or uint16_t for bf16 (pattern_pass.h's typed attn_load /
+// attn_store: fp32 in the registers either way).  The node tensors are fp32.
+template <class ET>
+struct EdgeOpArgsT {
+    const float *xdst, *xsrc;       // forward
+    const ET *E;
+    ET *Z;
+    const ET *Gz;                   // endpoint sum
+    const float *x;                 //   x: the OTHER endpoint's rows (MUL)
     float *out;
     long long ldxdst, ldxsrc, lde, ldz, ldgz, ldx, ldout;
     int H;                          // column tiles (the bodies' "heads")
     int N, tile;                    // tile: floats per tile = 4 T P
 };
+using EdgeOpArgs = EdgeOpArgsT<float>;
 
 // The forward: "own" is the row r of A, ci[e] the column c.  HAS_E: E is given.
-template <int OP, bool HAS_E, int T_, int P_, int U_>
+template <int OP, bool HAS_E, int T_, int P_, int U_, class ET = float>
 struct EdgeOpPass {
-    using Args = EdgeOpArgs;
+    using Args = EdgeOpArgsT<ET>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = 1;           // nothing to merge
     static constexpr bool kMerge = false;
     static constexpr bool kDst = OP != kEdgeOpSrc, kSrc = OP != kEdgeOpDst;   // what the op reads
-    const EdgeOpArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0, n = 0;   // the tile and its valid floats
     float y[W];         // the own row's x_dst
     float f[NF];
 
-    __device__ __forceinline__ EdgeOpPass(const EdgeOpArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ EdgeOpPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
 
     __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
         h = tile;
@@ -89,20 +95,20 @@ struct EdgeOpPass {
 
 // The endpoint sum: "own" is the row walked (with PERM: a column of A, walked as a row of A^T), ci[e] the other index, perm[e] the
 // entry's position in A's arrays.
-template <int TERM, bool PERM, int T_, int P_, int U_>
+template <int TERM, bool PERM, int T_, int P_, int U_, class ET = float>
 struct EndpointSumPass {
-    using Args = EdgeOpArgs;
+    using Args = EdgeOpArgsT<ET>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = W;
     static constexpr bool kMerge = true;
     static constexpr bool kGather = TERM == kEndSumMul;   // the other endpoint's row
-    const EdgeOpArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0, n = 0;   // the tile and its valid floats
     float f[NF];
 
-    __device__ __forceinline__ EndpointSumPass(const EdgeOpArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ EndpointSumPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
 
     __device__ __forceinline__ void begin(bool, int, int tile, bool) {
         h = tile;

@@ -27,7 +27,9 @@
 
 #include <climits>
 #include <cmath>
+#include <cstdint>
 
+#include "bf16_convert.h"
 #include "row_softmax_common.h"
 
 namespace sx {
@@ -51,6 +53,27 @@ __device__ __forceinline__ void attn_store(const float *x, float *row, int n, in
     for (int k = 0; k < P; ++k) {
         const int col = 4 * (t + T * k);
         if (col < n) *reinterpret_cast<float4 *>(row + col) = make_float4(x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]);
+    }
+}
+// The same pieces of a row that lies in memory as bf16 (16-bit patterns): fp32 in the registers, the same 4 consecutive columns per
+// piece -- one 8-byte access -- so a lane holds the columns it holds of an fp32 row.  A read widens exactly, a write rounds once to
+// nearest even (bf16_convert.h).  row + col is 8-byte aligned: a 16-byte aligned base, a leading dimension that is a multiple of 4.
+template <int T, int P>
+__device__ __forceinline__ void attn_load(float *x, const uint16_t *row, int n, int t, bool ok) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+        const int col = 4 * (t + T * k);
+        uint2 v = make_uint2(0u, 0u);
+        if (ok && col < n) v = *reinterpret_cast<const uint2 *>(row + col);
+        x[4 * k] = bf16_lo(v.x); x[4 * k + 1] = bf16_hi(v.x); x[4 * k + 2] = bf16_lo(v.y); x[4 * k + 3] = bf16_hi(v.y);
+    }
+}
+template <int T, int P>
+__device__ __forceinline__ void attn_store(const float *x, uint16_t *row, int n, int t) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+        const int col = 4 * (t + T * k);
+        if (col < n) *reinterpret_cast<uint2 *>(row + col) = make_uint2(bf16_round2_select(x[4 * k], x[4 * k + 1]), bf16_round2_select(x[4 * k + 2], x[4 * k + 3]));
     }
 }
 template <int T, int W>

@@ -9,20 +9,10 @@
 // per output element, a row's products added in ascending CSR order, each product rounded before the add when EXACT -- and the fp32
 // result is bit for bit that kernel's.  A bf16 C_in is widened the same way; a bf16 C_out is the fp32 result rounded to nearest even.
 #pragma once
+#include "bf16_convert.h"   // bf16_round, bf16_round2, bf16_lo, bf16_hi
 #include "spmm_csr_kernels.h"
 
 namespace sx {
-
-// fp32 -> bf16 bit pattern, round to nearest even; a NaN stays a (quiet) NaN.  The integer form: the carry of the rounding add runs
-// into the exponent, which is what makes the largest finite values round to infinity.
-__device__ __forceinline__ unsigned bf16_round(float f) {
-    const unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ unsigned bf16_round2(float lo, float hi) { return bf16_round(lo) | (bf16_round(hi) << 16); }
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }          // the bf16 in bits 0..15, widened
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }  // the bf16 in bits 16..31
 
 // Between two rows of a batch: the accumulators are final and the next row is still raw at this point.  Without it the compiler widens
 // all four rows of a batch up front (32 registers of widened copies, 72-80 VGPRs, 6-7 waves per SIMD); with it a row is widened just

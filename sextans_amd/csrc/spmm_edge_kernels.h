@@ -20,21 +20,28 @@ namespace sx {
 
 enum { kEdgeMul = 1, kEdgeAdd = 2, kEdgeAddRelu = 3, kEdgeCopy = 4 };   // SEXTANS_EDGE_*
 
-struct EdgeArgs {
-    const float *B, *E, *G;
-    float *C, *dB, *dE;
+// ET: the element type of the (nnz, N) tensors E and dE in memory -- float, or uint16_t for bf16 (pattern_pass.h's typed attn_load /
+// attn_store: fp32 in the registers either way).  The node tensors are fp32.
+template <class ET>
+struct EdgeArgsT {
+    const float *B;
+    const ET *E;
+    const float *G;
+    float *C, *dB;
+    ET *dE;
     long long ldb, lde, ldc, ldg, lddb, ldde;
     int H;                      // column tiles (the bodies' "heads")
     int N, tile;                // tile: floats per tile = 4 T P
 };
+using EdgeArgs = EdgeArgsT<float>;
 
 // relu that keeps a NaN and gives +0 for everything else that is not positive
 __device__ __forceinline__ float edge_relu(float s) { return s > 0.0f ? s : (s != s ? s : 0.0f); }
 
 // One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
-template <int PASS, int OP, int T_, int P_, int U_>
+template <int PASS, int OP, int T_, int P_, int U_, class ET = float>
 struct EdgePass {
-    using Args = EdgeArgs;
+    using Args = EdgeArgsT<ET>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnBackwardRows ? 1 : W;   // forward: C's sums; cols: dB's; rows: nothing to merge
     static constexpr bool kMerge = PASS != kAttnBackwardRows;
@@ -43,14 +50,14 @@ struct EdgePass {
                                   : PASS == kAttnBackwardCols ? true                                       // G[r]
                                   : (OP == kEdgeMul || OP == kEdgeAddRelu);                                // B[c]
     static constexpr bool kEdge = PASS == kAttnForward ? true : PASS == kAttnBackwardCols ? OP != kEdgeAdd : OP == kEdgeAddRelu;   // E[e]
-    const EdgeArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0, n = 0;   // the tile and its valid floats
     float y[W];         // rows: the own row's G; cols with ADD_RELU: the own column's B
     float f[NF];
 
-    __device__ __forceinline__ EdgePass(const EdgeArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ EdgePass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
 
     __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
         h = tile;

@@ -67,7 +67,8 @@ So does the softmax aggregation of edge-feature messages (GENConv / DeeperGCN wi
 with a learnable temperature): sextans_amd.edge_softagg.spmm_edge_softagg(A, B, E, op="mul", t=1.0, eps=0.0, return_lse=False).
 And Point Transformer's channel-wise attention from per-channel scores: sextans_amd.vector_attention.vector_attention(A, S, V=None, D=None).
 The opposite direction, node to edge -- the (nnz, N) tensors those ops read, from both endpoints of every entry (u_add_v, u_sub_v, u_mul_v,
-copy_u, copy_v, each optionally + e), with a backward without atomics: sextans_amd.edge_op.edge_op(A, x_dst=None, x_src=None, E=None, op="add").
+copy_u, copy_v, each optionally + e), with a backward without atomics: sextans_amd.edge_op.edge_op(A, x_dst=None, x_src=None, E=None, op="add")
+(with the (nnz, N) tensors in bf16: sextans_amd.edge_op_bf16.edge_op_bf16).
 And the (nnz, H) scores score_attention() reads, the per-head dot product of both endpoints (u_dot_v), all heads in one launch dealt by
 non-zeros: sextans_amd.edge_dot.edge_dot(A, x_dst, x_src).
 

@@ -6,8 +6,12 @@ sextans_amd/build.py (no GPU needed) and compares them kernel by kernel:
     git worktree add --detach ../parent HEAD~1
     python tools/device_code_diff.py ../parent . > profiles/entry_frame_device_code.txt
     python tools/device_code_diff.py ../parent . sextans_amd/csrc/engine_gat.hip      # chosen units only: a device-side change is tried per unit
+    python tools/device_code_diff.py --rename '(Li\d+)EfEEEE' '\1EEEEE' ../parent . sextans_amd/csrc/engine_edge.hip
+                                       # a template gained a defaulted argument: the second tree's symbols are renamed (a regular expression and
+                                       # its replacement, applied to the whole assembly text) before they are matched with the first tree's
 
-Without units: every sextans_amd/csrc/*.hip of the second tree that includes pattern_launch.h or edge_multi_launch.h.  Either kind of
+Without units: every sextans_amd/csrc/*.hip of the second tree that includes pattern_launch.h or one of the family launch headers over it
+(edge_multi_launch.h, edge_op_launch.h, edge_launch.h).  Either kind of
 change may reorder template instantiation, so the functions are compared per symbol, not in file order, after the function's index is taken
 out of its local labels (.LBB<k>_<n>, .Lfunc_end<k>).  What is compared per symbol: the instructions, the kernel descriptor, the
 resource figures and the code-object metadata entry.  Exit status 1 when anything differs."""
@@ -78,9 +82,14 @@ def metadata(rest):
     return {next(l.split()[-1] for l in e if l.strip().startswith(".name:")): "\n".join(e) for e in entries}
 
 
+RENAME = None   # (compiled pattern, replacement) for the second tree's assembly: --rename
+
+
 def compare(parent, branch, unit):
     with ThreadPoolExecutor(2) as pool:
         a, c = pool.map(lambda t: assembly(t, unit), (parent, branch))
+    if RENAME:
+        c = RENAME[0].sub(RENAME[1], c)
     (fa, ra), (fc, rc) = functions(a), functions(c)
     ma, mc = metadata(ra), metadata(rc)
     only_a, only_c = sorted(set(fa) - set(fc)), sorted(set(fc) - set(fa))
@@ -89,10 +98,14 @@ def compare(parent, branch, unit):
 
 
 def main():
-    parent, branch, units = sys.argv[1], sys.argv[2], sys.argv[3:]
+    global RENAME
+    argv = sys.argv[1:]
+    if argv and argv[0] == "--rename":
+        RENAME, argv = (re.compile(argv[1]), argv[2]), argv[3:]
+    parent, branch, units = argv[0], argv[1], argv[2:]
     if not units:
         for f in sorted(os.listdir(os.path.join(branch, CSRC))):
-            if f.endswith(".hip") and re.search(r'#include "(pattern|edge_multi)_launch\.h"', open(os.path.join(branch, CSRC, f)).read()):
+            if f.endswith(".hip") and re.search(r'#include "(pattern|edge_multi|edge_op|edge)_launch\.h"', open(os.path.join(branch, CSRC, f)).read()):
                 units.append(os.path.join(CSRC, f))
     bad = 0
     print("# unit: functions compared, differing, only in the first tree, only in the second")
