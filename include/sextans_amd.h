@@ -374,7 +374,9 @@ int sextans_export_row_order(sextans_handle_t h, int *order, int *clustered);
  * region like the reference's scheduling/packing, sextans-host.cpp:114-148), "window_padded_entries",
  * "window_state" (0 not evaluated, 1 built, -1 rejected), "panel_fraction", "panel_blocks", "piece_path_rows",
  * "reassociated_rows", "bucket_threshold", "split_threshold", "dense_tiles", "dense_tile_fraction",
- * "dense_tiles_on_mfma", "row_cluster" and the other clustering figures listed with that option, "device_bytes" (bytes of
+ * "dense_tiles_on_mfma", "bell_share", "bell_variant" (the matrix-core kernel that the last blocked-ELL call, or the last dense-tile
+ * launch of a CSR call with "mfma_dense_tiles" = 1, ran: 1 / 2 / 4 = spmm_bell_mfma<NSUB>, 8 = spmm_bell_mfma_n256, 9 =
+ * spmm_bell_mfma_shared, 0 = none so far; sextans_last_kernel names only the family), "row_cluster" and the other clustering figures listed with that option, "device_bytes" (bytes of
  * device memory the engine has asked the runtime for and holds right now: matrix copies, packed plans, tables, workspaces), "col_range_lo" / "col_range_hi" (the rows
  * of B the matrix has columns in: only those are repacked -- a rank of a row-partitioned SpMM over a banded matrix touches
  * 1 / world of B plus a halo), "cluster_decline" (why the graph clustering was not used: 1 not square and "row_similarity" = 0, 2 long-row paths,
@@ -1480,7 +1482,12 @@ int sextans_spmm_csr(int M, int N, int K, int NNZ, float ALPHA, const int *CSRRo
  * block_col[br*ell_width + s] is the block column of slot s (or -1 = empty slot), block_val holds the
  * slots' 32x32 bf16 values row-major (1024 values per slot).  B is bf16 COLUMN MAJOR K x N (ldb % 8 == 0),
  * C fp32 column major, C = alpha*A*B + beta*C with fp32 accumulation on v_mfma_f32_32x32x16_bf16.
- * M, K, N must be multiples of 32.  bf16 values are passed as their 16-bit patterns (uint16_t). */
+ * M, K, N must be multiples of 32.  bf16 values are passed as their 16-bit patterns (uint16_t).
+ * beta = 0 does NOT mask C_in: every kernel variant evaluates (alpha * acc) + (beta * C_in) as written, so a NaN or an infinity in
+ * C_in arrives in C_out as NaN at beta = 0 too (0 * NaN = 0 * inf = NaN) -- cpu_spmm_CSR's contract (sparse_helper.h:287), the
+ * same on spmm_bell_mfma<1|2|4>, _n256 and _shared and on the dense-tile route; pass a finite C_in (it may alias C_out).
+ * Leading dimensions: only rows [0, K) of each column of B are read and only rows [0, M) of each column of C_out are written --
+ * whatever lies between K and ldb, or M and ldc, is neither read nor touched.  (tests/test_bell_exact_gpu.py pins both.) */
 int sextans_set_matrix_bell(sextans_handle_t h, int M, int K, int ell_width, const int *block_col,
                             const uint16_t *block_val);
 int sextans_set_matrix_bell_device(sextans_handle_t h, int M, int K, int ell_width,

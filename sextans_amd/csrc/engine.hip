@@ -359,6 +359,7 @@ int sextans_get_stat(sextans_handle_t h, const char *key, double *value) {
     else if (!strcmp(key, "dense_tile_fraction")) *value = h->nnz > 0 ? (double)h->dense.nnz / (double)h->nnz : 0.0;
     else if (!strcmp(key, "dense_tiles_on_mfma")) *value = h->dense.W > 0 ? 1.0 : 0.0;
     else if (!strcmp(key, "bell_share")) *value = h->bell_share;
+    else if (!strcmp(key, "bell_variant")) *value = (double)h->bell_variant;   // 1 / 2 / 4 = spmm_bell_mfma<NSUB>, 8 = _n256, 9 = _shared, 0 = none yet
     else if (!strcmp(key, "row_cluster")) *value = (double)h->cluster.state;          // 1 grid bricks / 2 graph clustering in use, -1 declined, 0 not evaluated yet
     else if (!strcmp(key, "cluster_shared_fraction")) *value = h->cluster.shared;
     else if (!strcmp(key, "cluster_decline")) *value = (double)h->cluster.decline;

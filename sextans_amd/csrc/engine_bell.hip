@@ -372,14 +372,17 @@ int ensure_dense(sextans_engine *h) {
     return SEXTANS_OK;
 }
 
-// One wavefront per block row and group of NSUB column tiles: as many tiles per wavefront (4, 2 or 1) as divide their number
-static void launch_bell_mfma(const int *col, const sx::bf16x8 *Af, const sx::bf16x8 *Bf, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, int mblocks,
+// One wavefront per block row and group of NSUB column tiles: as many tiles per wavefront (4, 2 or 1) as divide their number.
+// Returns NSUB (stat "bell_variant").
+static int launch_bell_mfma(const int *col, const sx::bf16x8 *Af, const sx::bf16x8 *Bf, const float *d_C_in, int64_t ldc_in, float *d_C_out, int64_t ldc, int mblocks,
                       int W, int ntiles, float alpha, float beta, hipStream_t s) {
-    with_value<4, 2, 1>(ntiles % 4 == 0 ? 4 : ntiles % 2 == 0 ? 2 : 1, [&](auto NS) {
+    const int nsub = ntiles % 4 == 0 ? 4 : ntiles % 2 == 0 ? 2 : 1;
+    with_value<4, 2, 1>(nsub, [&](auto NS) {
         constexpr int NSUB = decltype(NS)::value;
         const int64_t waves = (int64_t)mblocks * (ntiles / NSUB);
         hipLaunchKernelGGL((sx::spmm_bell_mfma<NSUB>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, W, ntiles, alpha, beta);
     });
+    return nsub;
 }
 
 int launch_dense_tiles(sextans_engine *h, int N, const Operands &o) {
@@ -399,8 +402,9 @@ int launch_dense_tiles(sextans_engine *h, int N, const Operands &o) {
             hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((h->dense.mb + sx::kShRows - 1) / sx::kShRows)),
                                dim3(sx::kShThreads), lds, s, h->dense.d_dense_col, Af, Bf, o.C_in, o.ldc_in, o.C_out, o.ldc, h->dense.mb, h->dense.W,
                                o.alpha, o.beta, 0);
+            h->bell_variant = 9;
         } else {
-            launch_bell_mfma(h->dense.d_dense_col, Af, Bf, o.C_in, o.ldc_in, o.C_out, o.ldc, h->dense.mb, h->dense.W, ntiles, o.alpha, o.beta, s);
+            h->bell_variant = launch_bell_mfma(h->dense.d_dense_col, Af, Bf, o.C_in, o.ldc_in, o.C_out, o.ldc, h->dense.mb, h->dense.W, ntiles, o.alpha, o.beta, s);
         }
         const int row0 = h->dense.mb * 32;
         if (row0 < h->M) {
@@ -503,6 +507,7 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
             hipLaunchKernelGGL(sx::spmm_bell_mfma_shared, dim3((unsigned)((mblocks + sx::kShRows - 1) / sx::kShRows)), dim3(sx::kShThreads), lds,
                                s, h->bell.d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell.W, alpha, beta, (int)h->opt_bell_debug);
             h->last_kernel = "spmm_bell_mfma_shared";
+            h->bell_variant = 9;
             SX_HIP(hipGetLastError());
             return SEXTANS_OK;
         } else if (ntiles == 8 && h->opt_bell_wide) {
@@ -514,8 +519,9 @@ int sextans_spmm_bell_device2(sextans_handle_t h, int N, float alpha, const uint
                 hipLaunchKernelGGL(sx::spmm_bell_mfma_n256, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, h->bell.d_bell_col, Af,
                                    Bf, d_C_in, ldc_in, d_C_out, ldc, std::min(mblocks, b0 + nb), h->bell.W, alpha, beta, b0);
             }
+            h->bell_variant = 8;
         } else {
-            launch_bell_mfma(h->bell.d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell.W, ntiles, alpha, beta, s);
+            h->bell_variant = launch_bell_mfma(h->bell.d_bell_col, Af, Bf, d_C_in, ldc_in, d_C_out, ldc, mblocks, h->bell.W, ntiles, alpha, beta, s);
         }
         h->last_kernel = "spmm_bell_mfma";
     }

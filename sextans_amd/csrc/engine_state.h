@@ -259,6 +259,7 @@ struct sextans_engine {
     Bell bell;
     int bell_max_union = 0;         // largest number of distinct block columns inside a group of 8 block rows
     double bell_share = 0.0;        // blocks per distinct block column inside groups of 8 block rows (1 = no sharing, 8 = identical rows)
+    int bell_variant = 0;           // matrix-core kernel of the last blocked-ELL call / dense-tile launch: NSUB 1 / 2 / 4, 8 = n256, 9 = shared, 0 = none
     DevBuf<unsigned char> d_bell_Bf;   // B in fragment order (workspace)
     // Long rows leave the "main" matrix -- the CSR arrays every kernel and plan works on, equal to the arrays
     // above when there are none -- and go through the piece path (rows sorted by length, one row group per piece):

@@ -158,3 +158,101 @@ def test_random_shapes_thresholds_kernels(engine, seed):
     finally:
         for k, val in dict(kernel=0, lanes_per_row=0, mfma_dense_tiles=0, dense_tile_fill_x100=50, bucket_rows=-1).items():
             engine.set_option(k, val)
+
+
+# ---- exact: integer operands through both routes ------------------------------------------------------------------------------------
+# Integers of magnitude <= 4 are exact in bf16 and their products in fp32; with every row's sum of |a b| below 2^24 the fp32 sums are
+# exact in any order (MFMA, CSR kernels, the re-associated hub row alike), and with power-of-two alpha / beta and an integer C_in so is the
+# epilogue -- applied once (mfma_dense_tiles = 0) or in two passes (dense tiles, then the CSR kernels on top with beta = 1).  So
+# mfma_dense_tiles = 1 must give the BITS of mfma_dense_tiles = 0, and both the integer result.
+def _integer_result(M, K, N, rp, ci, v, B, C0, alpha, beta):
+    A = np.zeros((M, K))
+    A[np.repeat(np.arange(M), np.diff(rp)), ci] = v
+    Bm = B.reshape(N, K).T.astype(np.float64)
+    Cm = C0.reshape(N, M).T.astype(np.float64)
+    asum = np.abs(A) @ np.abs(Bm)
+    # the precondition, for these inputs: partial sums below 2^24 in any order; the epilogue's multiples of 0.5 below 2^23
+    assert asum.max() < 2 ** 24 and 4 * asum.max() + 4 * np.abs(Cm).max() < 2 ** 23
+    want = alpha * (A @ Bm + 0.0) + beta * Cm
+    w32 = want.astype(np.float32)
+    assert np.array_equal(w32.astype(np.float64), want)
+    return np.ascontiguousarray(w32.T).reshape(-1)
+
+
+_RESTORE = dict(kernel=0, lanes_per_row=0, mfma_dense_tiles=0, dense_tile_fill_x100=50, bucket_rows=-1, bell_shared=-1)
+
+
+@pytest.mark.parametrize("M,K,N,alpha,beta,variant", [(2048 + 17, 2048 + 40, 64, -2.0, 0.5, 2), (333, 257, 96, 0.5, 4.0, 1),
+                                                        (1024 + 5, 1024, 256, 4.0, -2.0, 4)])
+def test_integer_operands_are_exact_on_both_routes(engine, M, K, N, alpha, beta, variant):
+    """Tail rows below the last full block row (scale_tail_rows), K not a multiple of 32 (the zero fill of bell_repack_b_f32), the hub
+    row's piece path in the first shape; N = 64 / 96 / 256 run spmm_bell_mfma<2 / 1 / 4> (no sharing between these block rows)."""
+    rs = np.random.RandomState(M + N)
+    hub = M > 2000
+    rp, ci, _ = block_diagonal_plus_noise(rs, M, K, hub_row=M - 3 if hub else None)
+    v = rs.choice([-4, -3, -2, -1, 1, 2, 3, 4], len(ci)).astype(np.float32)
+    B = rs.randint(-4, 5, K * N).astype(np.float32)
+    C0 = (rs.randint(1, 1025, M * N) * rs.choice([-1, 1], M * N)).astype(np.float32)
+    want = _integer_result(M, K, N, rp, ci, v, B, C0, alpha, beta)
+    assert M % 32 != 0                                                      # tail rows in every shape
+    try:
+        for k, val in dict(kernel=0, lanes_per_row=4, exact=1, split_rows=-1, bucket_rows=-1, mfma_dense_tiles=0, dense_tile_fill_x100=50,
+                           bell_shared=-1).items():
+            engine.set_option(k, val)
+        engine.set_matrix_csr(M, K, rp, ci, v)
+        plain = C0.copy()
+        engine.spmm(N, alpha, B, beta, plain)
+        assert "dense_tiles" not in engine.last_kernel() and engine.get_stat("dense_tiles_on_mfma") == 0
+        engine.set_option("mfma_dense_tiles", 1)
+        out = C0.copy()
+        engine.spmm(N, alpha, B, beta, out)
+        assert engine.last_kernel().endswith("+dense_tiles_mfma") and engine.get_stat("dense_tiles_on_mfma") == 1
+        assert ("+hub_pieces" in engine.last_kernel()) == hub
+        assert engine.get_stat("bell_variant") == variant
+        assert np.array_equal(plain.view(np.uint32), want.view(np.uint32))
+        assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    finally:
+        for k, val in _RESTORE.items():
+            engine.set_option(k, val)
+
+
+@pytest.mark.parametrize("shared", [1, -1])
+def test_shared_tile_kernel_from_the_dense_tile_route_is_exact(engine, shared):
+    """A block-banded CSR matrix of full 32x32 tiles (half-width 2), N = 256: launch_dense_tiles has its own rule for
+    spmm_bell_mfma_shared -- asked for (bell_shared = 1) or chosen by the sharing of the tile columns (-1: 8 block rows x 5 tiles over
+    12 tile columns) -- and the last_kernel string does not name it; the stat does.  Nothing is left for the CSR kernels."""
+    mb, hw, N = 24, 2, 256
+    M = K = 32 * mb
+    rs = np.random.RandomState(8 + shared)
+    rows, cols = [], []
+    r, c = np.meshgrid(np.arange(32), np.arange(32), indexing="ij")
+    for br in range(mb):
+        for bc in range(max(0, br - hw), min(mb, br + hw + 1)):
+            rows.append(br * 32 + r.ravel()); cols.append(bc * 32 + c.ravel())
+    key = np.sort(np.concatenate(rows).astype(np.int64) * K + np.concatenate(cols))
+    ri, ci = (key // K).astype(np.int32), (key % K).astype(np.int32)
+    rp = np.zeros(M + 1, np.int32)
+    rp[1:] = np.cumsum(np.bincount(ri, minlength=M))
+    v = rs.choice([-4, -3, -2, -1, 1, 2, 3, 4], len(ci)).astype(np.float32)
+    B = rs.randint(-4, 5, K * N).astype(np.float32)
+    C0 = (rs.randint(1, 1025, M * N) * rs.choice([-1, 1], M * N)).astype(np.float32)
+    alpha, beta = (0.5, -2.0) if shared == 1 else (-2.0, 4.0)
+    want = _integer_result(M, K, N, rp, ci, v, B, C0, alpha, beta)
+    try:
+        for k, val in dict(kernel=0, lanes_per_row=0, exact=1, mfma_dense_tiles=1, dense_tile_fill_x100=50, bell_shared=shared).items():
+            engine.set_option(k, val)
+        engine.set_matrix_csr(M, K, rp, ci, v)
+        out = C0.copy()
+        engine.spmm(N, alpha, B, beta, out)
+        assert engine.last_kernel().endswith("+dense_tiles_mfma") and engine.get_stat("dense_tiles_on_mfma") == 1
+        assert engine.get_stat("dense_tiles") == len(key) // 1024
+        assert engine.get_stat("bell_variant") == 9
+        assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+        engine.set_option("bell_shared", 0)                                     # the per-wavefront kernel on the same tiles: the same bits
+        out = C0.copy()
+        engine.spmm(N, alpha, B, beta, out)
+        assert engine.get_stat("bell_variant") == 4
+        assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    finally:
+        for k, val in _RESTORE.items():
+            engine.set_option(k, val)
