@@ -1369,6 +1369,37 @@ int sextans_spmm_edge_backward_device_rm_bf16(sextans_handle_t h, int op, int N,
                                               int64_t lde, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, uint16_t *d_dE,
                                               int64_t ldde, void *stream);
 
+/* The same for the two per-channel softmax families, the consumers of those tensors: S, D, dS and dD of
+ * sextans_vector_attention*_device_rm, E and dE of sextans_spmm_edge_softagg*_device_rm in bf16, read and written where they lie.
+ * The contract above, unchanged: ONE dtype for all edge tensors of a call; the node tensors (V, B, t, C, lse, G, dV, dB, dt and the dt
+ * workspace), every operation, the online-softmax state and its merges are fp32, in the fp32 twin's order (same tiles, slots, entries in
+ * flight and dealing).  A bf16 value is widened exactly -- a bf16 -inf score is still a mask: weight +0, dS = +0 --, a bf16 output is
+ * the fp32 value the twin would have stored, rounded ONCE to nearest even (NaN stays a quiet NaN, +-inf and -0 stay, a value at or
+ * above 0x7f7f8000 becomes inf).  So for every mode / op and pass
+ *     a bf16 output (dS, dD, dE) is round_bf16(the fp32 entry point's output on the widened inputs), bit for bit;
+ *     an fp32 output (C, lse, dV, dB, dt) is the fp32 entry point's output on the widened inputs, bit for bit.
+ * Arguments, modes / ops, what a call reads and ignores, NULL rules, pass skipping, degenerate matrices and determinism are the fp32
+ * twin's.  No atomics, no value refresh, no workspace beyond the twin's: sextans_spmm_edge_softagg_workspace_floats serves both dtypes.
+ * Capturable into a hipGraph after sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream), as the twins are.
+ * Leading dimensions are counted in ELEMENTS of their tensor: >= N and multiples of 4 for the bf16 tensors too, under the twin's rules
+ * for which of them count.  Every pointer 16-byte aligned.
+ * sextans_last_kernel: "vector_attention_bf16" / "vector_attention_backward_bf16" / "spmm_edge_softagg_bf16" /
+ * "spmm_edge_softagg_backward_bf16", "+long_rows" appended when the workgroup path ran.
+ * Errors: the fp32 twin's, in its order, all before any device is touched. */
+int sextans_vector_attention_device_rm_bf16(sextans_handle_t h, int msg, int N, const uint16_t *d_S, int64_t lds, const float *d_V, int64_t ldv,
+                                            const uint16_t *d_D, int64_t ldd, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse,
+                                            void *stream);
+int sextans_vector_attention_backward_device_rm_bf16(sextans_handle_t h, int msg, int N, const uint16_t *d_S, int64_t lds, const float *d_V,
+                                                     int64_t ldv, const uint16_t *d_D, int64_t ldd, const float *d_C, int64_t ldc,
+                                                     const float *d_lse, int64_t ldlse, const float *d_G, int64_t ldg, uint16_t *d_dS,
+                                                     int64_t ldds, float *d_dV, int64_t lddv, uint16_t *d_dD, int64_t lddd, void *stream);
+int sextans_spmm_edge_softagg_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const uint16_t *d_E, int64_t lde,
+                                             const float *d_t, float *d_C, int64_t ldc, float *d_lse, int64_t ldlse, void *stream);
+int sextans_spmm_edge_softagg_backward_device_rm_bf16(sextans_handle_t h, int op, int N, const float *d_B, int64_t ldb, const uint16_t *d_E,
+                                                      int64_t lde, const float *d_t, const float *d_C, int64_t ldc, const float *d_lse,
+                                                      int64_t ldlse, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, uint16_t *d_dE,
+                                                      int64_t ldde, float *d_dt, float *d_work, void *stream);
+
 /* Row-range form: computes rows [row_begin, row_end) only.  d_C_in / d_C_out address row_begin as
  * their row 0 (ldc_in, ldc_out >= row_end - row_begin).  Used to pipeline a rank's slab in chunks so the
  * all-gather of chunk i overlaps the SpMM of chunk i+1.  flags: SEXTANS_ROWS_REUSE_B_PANELS = the B

@@ -127,6 +127,8 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_edge_op_device_rm", "sextans_edge_op_backward_device_rm",
     "sextans_edge_op_device_rm_bf16", "sextans_edge_op_backward_device_rm_bf16",
     "sextans_spmm_edge_device_rm_bf16", "sextans_spmm_edge_backward_device_rm_bf16",
+    "sextans_vector_attention_device_rm_bf16", "sextans_vector_attention_backward_device_rm_bf16",
+    "sextans_spmm_edge_softagg_device_rm_bf16", "sextans_spmm_edge_softagg_backward_device_rm_bf16",
     "sextans_edge_dot_device", "sextans_edge_dot_backward_device",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -404,6 +406,10 @@ def lib():
     L.sextans_edge_op_backward_device_rm_bf16.argtypes = L.sextans_edge_op_backward_device_rm.argtypes
     L.sextans_spmm_edge_device_rm_bf16.argtypes = L.sextans_spmm_edge_device_rm.argtypes
     L.sextans_spmm_edge_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_backward_device_rm.argtypes
+    L.sextans_vector_attention_device_rm_bf16.argtypes = L.sextans_vector_attention_device_rm.argtypes
+    L.sextans_vector_attention_backward_device_rm_bf16.argtypes = L.sextans_vector_attention_backward_device_rm.argtypes
+    L.sextans_spmm_edge_softagg_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_device_rm.argtypes
+    L.sextans_spmm_edge_softagg_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_backward_device_rm.argtypes
     L.sextans_edge_dot_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_dot_backward_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1136,6 +1142,37 @@ class Engine:
         _check(lib().sextans_vector_attention_backward_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg,
                                                                  d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
                "vector_attention_backward_device_rm")
+
+    def vector_attention_device_rm_bf16(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream=None):
+        """vector_attention_device_rm with S and D in bf16 (sextans_vector_attention_device_rm_bf16): V, C and lse fp32, S and D widened
+        exactly (a bf16 -inf score still masks) -- the bits of vector_attention_device_rm on the widened S and D.  lds and ldd count bf16
+        elements (multiples of 4)."""
+        _check(lib().sextans_vector_attention_device_rm_bf16(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream),
+               "vector_attention_device_rm_bf16")
+
+    def vector_attention_backward_device_rm_bf16(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dS, ldds,
+                                                 d_dV, lddv, d_dD, lddd, stream=None):
+        """vector_attention_backward_device_rm with S, D, dS and dD in bf16 (sextans_vector_attention_backward_device_rm_bf16): V, C, lse,
+        G and dV fp32; dV the bits of vector_attention_backward_device_rm on the widened S and D, dS and dD its dS and dD rounded once to
+        nearest even.  lds, ldd, ldds and lddd count bf16 elements."""
+        _check(lib().sextans_vector_attention_backward_device_rm_bf16(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse,
+                                                                      d_G, ldg, d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
+               "vector_attention_backward_device_rm_bf16")
+
+    def spmm_edge_softagg_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream=None):
+        """spmm_edge_softagg_device_rm with E in bf16 (sextans_spmm_edge_softagg_device_rm_bf16): B, t, C and lse fp32, E widened exactly
+        -- the bits of spmm_edge_softagg_device_rm on the widened E.  lde counts bf16 elements (a multiple of 4)."""
+        _check(lib().sextans_spmm_edge_softagg_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream),
+               "spmm_edge_softagg_device_rm_bf16")
+
+    def spmm_edge_softagg_backward_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dE,
+                                                  ldde, d_dt, d_work, stream=None):
+        """spmm_edge_softagg_backward_device_rm with E and dE in bf16 (sextans_spmm_edge_softagg_backward_device_rm_bf16): everything else
+        fp32, the workspace that of spmm_edge_softagg_workspace_floats(N); dB and dt the bits of spmm_edge_softagg_backward_device_rm on
+        the widened E, dE its dE rounded once to nearest even.  lde and ldde count bf16 elements."""
+        _check(lib().sextans_spmm_edge_softagg_backward_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G,
+                                                                       ldg, d_dB, lddb, d_dE, ldde, d_dt, d_work, stream),
+               "spmm_edge_softagg_backward_device_rm_bf16")
 
     def edge_op_device_rm(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream=None):
         """Edge-output op from both endpoints (sextans_edge_op_device_rm): for every stored entry e = (r, c), in the CSR entry order,

@@ -20,7 +20,7 @@
 // a batch() that hands its scores and messages to the one ChannelSoftmax -- so with E[e, :] = val[e] and MUL it returns spmm_softagg's bits.
 // The row pass does NOT take the tiles inside the slot (there is no dval to add up over tiles): every (entry, tile) piece of dE is stored
 // by the slot that owns it, as in EdgePass; its state is the tile's dt sum (W floats, merged by adds), kept whether or not dt is asked
-// for and stored when dt_rows is given; the dE store is predicated on its pointer (engine_edge_softagg.hip says why).
+// for and stored when dt_rows is given; the dE store is predicated on its pointer (edge_softagg_launch.h says why).
 // No atomics; sums in an order fixed by the pattern and the launch shape.
 #pragma once
 #include "spmm_edge_kernels.h"
@@ -28,15 +28,23 @@
 
 namespace sx {
 
-struct EdgeSoftaggArgs {
-    const float *B, *E, *t;     // t: N floats or null (= 1)
+// ET: the element type of the (nnz, N) tensors E and dE in memory -- float, or uint16_t for bf16 (pattern_pass.h's typed attn_load /
+// attn_store: fp32 in the registers either way).  The node tensors, t and dt_rows are fp32.
+template <class ET>
+struct EdgeSoftaggArgsT {
+    const float *B;
+    const ET *E;
+    const float *t;             // N floats or null (= 1)
     const float *C, *lse, *G;   // backward
     float *out, *out_lse;       // forward; out_lse may be null
-    float *dB, *dE, *dt_rows;   // backward, each may be null; dt_rows: M x N floats, leading dimension N
+    float *dB;                  // backward, each may be null
+    ET *dE;
+    float *dt_rows;             // M x N floats, leading dimension N
     long long ldb, lde, ldc, ldlse, ldg, lddb, ldde;
     int H;                      // column tiles (the bodies' "heads")
     int N, tile;                // tile: floats per tile = 4 T P
 };
+using EdgeSoftaggArgs = EdgeSoftaggArgsT<float>;
 
 // the message of spmm_edge_kernels.h: one rounded operation (b is not read for COPY)
 template <int OP>
@@ -46,9 +54,9 @@ __device__ __forceinline__ float edge_message(float b, float x) {
 
 // One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
 // begin, score, grad, combine and finish are SoftaggFrame's (online_softmax.h), the ones SoftaggPass has.
-template <int PASS, int OP, int T_, int P_, int U_>
-struct EdgeSoftaggPass : SoftaggFrame<PASS, EdgeSoftaggArgs, T_, P_> {
-    using Frame = SoftaggFrame<PASS, EdgeSoftaggArgs, T_, P_>;
+template <int PASS, int OP, int T_, int P_, int U_, class ET = float>
+struct EdgeSoftaggPass : SoftaggFrame<PASS, EdgeSoftaggArgsT<ET>, T_, P_> {
+    using Frame = SoftaggFrame<PASS, EdgeSoftaggArgsT<ET>, T_, P_>;
     using Frame::Frame;
     using Frame::a, Frame::ci, Frame::perm, Frame::t, Frame::h, Frame::n, Frame::x, Frame::y, Frame::z, Frame::f, Frame::score, Frame::grad;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;

@@ -28,15 +28,23 @@ namespace sx {
 
 enum { kVattNode = 1, kVattAdd = 2, kVattEdge = 3 };   // SEXTANS_VATT_*
 
-struct VectorAttnArgs {
-    const float *S, *V, *D;     // V: not read by EDGE; D: not read by NODE
+// ET: the element type of the (nnz, N) tensors S, D, dS and dD in memory -- float, or uint16_t for bf16 (pattern_pass.h's typed attn_load /
+// attn_store: fp32 in the registers either way).  The node tensors are fp32.
+template <class ET>
+struct VectorAttnArgsT {
+    const ET *S;
+    const float *V;             // not read by EDGE
+    const ET *D;                // not read by NODE
     const float *C, *lse, *G;   // backward
     float *out, *out_lse;       // forward; out_lse may be null
-    float *dS, *dV, *dD;        // backward, each may be null
+    ET *dS;                     // backward, each may be null
+    float *dV;
+    ET *dD;
     long long lds, ldv, ldd, ldc, ldlse, ldg, ldds, lddv, lddd;
     int H;                      // column tiles (the bodies' "heads")
     int N, tile;                // tile: floats per tile = 4 T P
 };
+using VectorAttnArgs = VectorAttnArgsT<float>;
 
 // the message: at most one rounded operation (the operand a mode does not read comes in as 0 and is not used)
 template <int MSG>
@@ -45,21 +53,21 @@ __device__ __forceinline__ float vatt_message(float v, float d) {
 }
 
 // One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
-template <int PASS, int MSG, int T_, int P_, int U_>
+template <int PASS, int MSG, int T_, int P_, int U_, class ET = float>
 struct VectorAttnPass {
-    using Args = VectorAttnArgs;
+    using Args = VectorAttnArgsT<ET>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr int NF = PASS == kAttnForward ? 3 * W : PASS == kAttnBackwardCols ? W : 1;   // forward: m, z, acc per float; cols: dV
     static constexpr bool kMerge = PASS != kAttnBackwardRows;                                     // rows: nothing to merge
     static constexpr bool kV = MSG != kVattEdge, kD = MSG != kVattNode;                           // the message reads V / D
-    const VectorAttnArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0, n = 0;        // the tile and its valid floats
     float x[W], y[W], z[W];  // rows: the own row's C, lse and G
     float f[NF];
 
-    __device__ __forceinline__ VectorAttnPass(const VectorAttnArgs &a_, const int *ci_, const int *perm_, int t_)
+    __device__ __forceinline__ VectorAttnPass(const Args &a_, const int *ci_, const int *perm_, int t_)
         : a(a_), ci(ci_), perm(perm_), t(t_) {}
 
     __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {

@@ -7,7 +7,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import api
-from ._op_aggregate import _EDGE_OPS, _any_elements, _check_edge_operands, _rowmajor_ld, _tiled_entry
+from ._op_aggregate import _EDGE_OPS, _any_elements, _check_edge_operands, _edge_bf16, _rowmajor_ld, _tiled_entry
 from ._op_cache import _cut, _cut_grad, _f32, _index_tensors, _keep_pattern, _kept_pattern_entry, _ptr, _ptr_nonempty
 
 __all__ = ["spmm_edge_softagg"]
@@ -16,11 +16,13 @@ __all__ = ["spmm_edge_softagg"]
 def _edge_softagg_forward(A, B, E, t, op, fast, want_lse):
     """(C, lse, tp) of the engine's edge-feature softmax aggregation: C and lse (M, Np) with N padded up to a multiple of 8 (zero columns
     of B and E), lse None unless asked for; tp the (Np,) fp32 temperatures handed to the kernel (padded columns: 1), None for t = 1
-    everywhere.  B is None for EDGE_COPY."""
+    everywhere.  B is None for EDGE_COPY.  A bf16 E that the kernel can read where it lies goes to the bf16 entry point as it is: the same
+    bits, no fp32 copy of E."""
     nnz, N = E.shape
     M, K, Np, ent, stream, _ = _tiled_entry(A, N, fast)
+    bf16 = _edge_bf16(E, N)
     Brm, ldb = _rowmajor_ld(B, K, N, Np)
-    Erm, lde = _rowmajor_ld(E, nnz, N, Np)
+    Erm, lde = _rowmajor_ld(E, nnz, N, Np, torch.bfloat16 if bf16 else torch.float32)
     tp = None
     if t is not None:
         tp = torch.ones((Np,), dtype=torch.float32, device=A.device)
@@ -28,8 +30,8 @@ def _edge_softagg_forward(A, B, E, t, op, fast, want_lse):
     C = _f32(A.device, M, Np)
     lse = _f32(A.device, M, Np) if want_lse else None
     if _any_elements(C):
-        ent.eng.spmm_edge_softagg_device_rm(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr(tp), _ptr_nonempty(C), Np,
-                                            _ptr_nonempty(lse), Np, stream)
+        call = ent.eng.spmm_edge_softagg_device_rm_bf16 if bf16 else ent.eng.spmm_edge_softagg_device_rm
+        call(op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr(tp), _ptr_nonempty(C), Np, _ptr_nonempty(lse), Np, stream)
     return C, lse, tp
 
 
@@ -38,7 +40,8 @@ class _SpmmEdgeSoftaggFunction(torch.autograd.Function):
     ONE backward call (sextans_spmm_edge_softagg_backward_device_rm) for the gradients that are wanted: a column pass over A^T for dB, a
     row pass that stores dE and the rows' share of dt, the fixed-order sum over the rows for dt.  t is the (N,) tensor or None (= 1, no
     gradient); the workspace exists only when t wants a gradient.  A's values never enter: no gradient for A, no value refresh.  Not twice
-    differentiable."""
+    differentiable.  A bf16 E that went to the bf16 forward as it lies goes to sextans_spmm_edge_softagg_backward_device_rm_bf16 the same
+    way, and the kernel writes dE in bf16: the bits of the fp32 dE rounded to E's dtype, without the fp32 tensors."""
 
     @staticmethod
     def forward(ctx, A, B, E, t, op, fast):
@@ -66,16 +69,17 @@ class _SpmmEdgeSoftaggFunction(torch.autograd.Function):
         ent, stream = _kept_pattern_entry(ctx, crow, col, val)
         Grm, ldg = _rowmajor_ld(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
         Brm, ldb = _rowmajor_ld(B, K, N, Np)
-        Erm, lde = _rowmajor_ld(E, nnz, N, Np)
+        bf16 = _edge_bf16(E, N)                            # (the forward's route: one dtype for E and dE)
+        e_dtype = torch.bfloat16 if bf16 else torch.float32
+        Erm, lde = _rowmajor_ld(E, nnz, N, Np, e_dtype)
         dB = _f32(G.device, K, Np) if want_b else None
-        dE = _f32(G.device, nnz, Np) if want_e else None
+        dE = torch.empty((nnz, Np), dtype=e_dtype, device=G.device) if want_e else None
         dt = _f32(G.device, Np) if want_t else None
         work = _f32(G.device, max(ent.eng.spmm_edge_softagg_workspace_floats(Np), 1)) if want_t else None
         if _any_elements(dB, dE, dt):
-            ent.eng.spmm_edge_softagg_backward_device_rm(ctx.op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(tp),
-                                                         _ptr_nonempty(C), Np, _ptr_nonempty(lse), Np, _ptr_nonempty(Grm), ldg,
-                                                         _ptr_nonempty(dB), Np, _ptr_nonempty(dE), Np, _ptr_nonempty(dt), _ptr_nonempty(work),
-                                                         stream)
+            call = ent.eng.spmm_edge_softagg_backward_device_rm_bf16 if bf16 else ent.eng.spmm_edge_softagg_backward_device_rm
+            call(ctx.op, Np, _ptr_nonempty(Brm), ldb, _ptr_nonempty(Erm), lde, _ptr_nonempty(tp), _ptr_nonempty(C), Np, _ptr_nonempty(lse), Np,
+                 _ptr_nonempty(Grm), ldg, _ptr_nonempty(dB), Np, _ptr_nonempty(dE), Np, _ptr_nonempty(dt), _ptr_nonempty(work), stream)
         gt = _cut(dt, N).to(ctx.t_dtype) if want_t else None
         return None, _cut_grad(dB, N, B), _cut_grad(dE, N, E), gt, None, None
 
@@ -99,7 +103,10 @@ def spmm_edge_softagg(A, B, E, op="mul", t=1.0, eps=0.0, return_lse=False, fast=
     that requires grad (a 0-d t gets the sum over the columns); only the gradients asked for are computed; they lose digits where
     |t (m - C)| is large.  return_lse=True: also the (M, N) log-sum-exp of the scores t m (-inf in an empty row; not differentiable; of
     the messages without eps).  An N that is not a multiple of 8, and operands the kernel cannot read where they lie, are copied with
-    zero padding, as torch_op.spmm_edge() does; `fast` only selects the cached engine."""
+    zero padding, as torch_op.spmm_edge() does; `fast` only selects the cached engine.  A bf16 E (autocast) with N % 8 == 0 that is
+    row-major and 16-byte aligned is read as it lies and its gradient written in bf16 by the kernel
+    (sextans_spmm_edge_softagg_device_rm_bf16 / _backward_device_rm_bf16): the bits of the fp32 route, without an fp32 (nnz, N) tensor;
+    C and lse stay fp32."""
     _check_edge_operands(A, B, E, op, "spmm_edge_softagg")
     N = E.shape[1]
     if isinstance(t, torch.Tensor):

@@ -9,7 +9,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import api
-from ._op_aggregate import _any_elements, _rowmajor_ld, _tiled_entry
+from ._op_aggregate import _any_elements, _edge_bf16, _rowmajor_ld, _tiled_entry
 from ._op_cache import _check_sparse, _cut, _cut_grad, _f32, _index_tensors, _keep_pattern, _kept_pattern_entry, _ptr_nonempty
 
 __all__ = ["vector_attention"]
@@ -19,26 +19,38 @@ def _mode(V, D):
     return api.VATT_NODE if D is None else api.VATT_EDGE if V is None else api.VATT_ADD
 
 
+def _edges_bf16(S, D, N):
+    """do the edge tensors of a call go to the bf16 entry points as they lie: EVERY one that is given -- S, and D if present -- is bf16,
+    N % 8 == 0, row-major, aligned (one dtype per call: a mixed or non-qualifying call takes the fp32 copies)"""
+    return _edge_bf16(S, N) and (D is None or _edge_bf16(D, N))
+
+
 def _vector_attention_forward(A, S, V, D, fast, want_lse):
     """(C, lse) of the engine's vector attention: (M, Np) with N padded up to a multiple of 8 (zero columns of S, V and D, which are cut
-    again), lse None unless asked for.  V is None for VATT_EDGE, D for VATT_NODE."""
+    again), lse None unless asked for.  V is None for VATT_EDGE, D for VATT_NODE.  bf16 S and D that the kernel can read where they lie
+    go to the bf16 entry point as they are: the same bits, no fp32 copy of either."""
     nnz, N = S.shape
     M, K, Np, ent, stream, _ = _tiled_entry(A, N, fast)
-    Srm, lds = _rowmajor_ld(S, nnz, N, Np)
+    bf16 = _edges_bf16(S, D, N)
+    e_dtype = torch.bfloat16 if bf16 else torch.float32
+    Srm, lds = _rowmajor_ld(S, nnz, N, Np, e_dtype)
     Vrm, ldv = _rowmajor_ld(V, K, N, Np)
-    Drm, ldd = _rowmajor_ld(D, nnz, N, Np)
+    Drm, ldd = _rowmajor_ld(D, nnz, N, Np, e_dtype)
     C = _f32(A.device, M, Np)
     lse = _f32(A.device, M, Np) if want_lse else None
     if _any_elements(C):
-        ent.eng.vector_attention_device_rm(_mode(V, D), Np, _ptr_nonempty(Srm), lds, _ptr_nonempty(Vrm), ldv, _ptr_nonempty(Drm), ldd,
-                                           _ptr_nonempty(C), Np, _ptr_nonempty(lse), Np, stream)
+        call = ent.eng.vector_attention_device_rm_bf16 if bf16 else ent.eng.vector_attention_device_rm
+        call(_mode(V, D), Np, _ptr_nonempty(Srm), lds, _ptr_nonempty(Vrm), ldv, _ptr_nonempty(Drm), ldd, _ptr_nonempty(C), Np,
+             _ptr_nonempty(lse), Np, stream)
     return C, lse
 
 
 class _VectorAttentionFunction(torch.autograd.Function):
     """vector_attention(): ONE forward call (sextans_vector_attention_device_rm) that keeps C and the log-sum-exp of every (row, column),
     ONE backward call (sextans_vector_attention_backward_device_rm) for the gradients that are wanted: a row pass that stores dS and dD,
-    a column pass over A^T for dV.  A's values never enter: no gradient for A, no value refresh.  Not twice differentiable."""
+    a column pass over A^T for dV.  A's values never enter: no gradient for A, no value refresh.  Not twice differentiable.
+    bf16 S and D that went to the bf16 forward as they lie go to sextans_vector_attention_backward_device_rm_bf16 the same way, and the
+    kernel writes dS and dD in bf16: the bits of the fp32 gradients rounded to their dtype, without the fp32 tensors."""
 
     @staticmethod
     def forward(ctx, A, S, V, D, fast):
@@ -64,16 +76,18 @@ class _VectorAttentionFunction(torch.autograd.Function):
             return (None,) * 5
         ent, stream = _kept_pattern_entry(ctx, crow, col, val)
         Grm, ldg = _rowmajor_ld(G, M, N, Np)               # (a copy when G has zero strides, e.g. after .sum(), or N % 8 != 0)
-        Srm, lds = _rowmajor_ld(S, nnz, N, Np)
+        bf16 = _edges_bf16(S, D, N)                        # (the forward's route: one dtype for S, D, dS and dD)
+        e_dtype = torch.bfloat16 if bf16 else torch.float32
+        Srm, lds = _rowmajor_ld(S, nnz, N, Np, e_dtype)
         Vrm, ldv = _rowmajor_ld(V, K, N, Np)
-        Drm, ldd = _rowmajor_ld(D, nnz, N, Np)
-        dS = _f32(G.device, nnz, Np) if want_s else None
+        Drm, ldd = _rowmajor_ld(D, nnz, N, Np, e_dtype)
+        dS = torch.empty((nnz, Np), dtype=e_dtype, device=G.device) if want_s else None
         dV = _f32(G.device, K, Np) if want_v else None
-        dD = _f32(G.device, nnz, Np) if want_d else None
+        dD = torch.empty((nnz, Np), dtype=e_dtype, device=G.device) if want_d else None
         if _any_elements(dS, dV, dD):
-            ent.eng.vector_attention_backward_device_rm(_mode(V, D), Np, _ptr_nonempty(Srm), lds, _ptr_nonempty(Vrm), ldv, _ptr_nonempty(Drm),
-                                                        ldd, _ptr_nonempty(C), Np, _ptr_nonempty(lse), Np, _ptr_nonempty(Grm), ldg,
-                                                        _ptr_nonempty(dS), Np, _ptr_nonempty(dV), Np, _ptr_nonempty(dD), Np, stream)
+            call = ent.eng.vector_attention_backward_device_rm_bf16 if bf16 else ent.eng.vector_attention_backward_device_rm
+            call(_mode(V, D), Np, _ptr_nonempty(Srm), lds, _ptr_nonempty(Vrm), ldv, _ptr_nonempty(Drm), ldd, _ptr_nonempty(C), Np,
+                 _ptr_nonempty(lse), Np, _ptr_nonempty(Grm), ldg, _ptr_nonempty(dS), Np, _ptr_nonempty(dV), Np, _ptr_nonempty(dD), Np, stream)
         return None, _cut_grad(dS, N, S), _cut_grad(dV, N, V, want_v), _cut_grad(dD, N, D, want_d), None
 
 
@@ -110,7 +124,11 @@ def vector_attention(A, S, V=None, D=None, return_lse=False, fast=False):
     no atomics -- the same bits on every run.  Differentiable in S, V and D; only the gradients asked for are computed (a row pass for
     dS and dD, a column pass over A^T for dV); not twice differentiable.  return_lse=True: also the (M, ...) log-sum-exp of the scores
     (-inf in an empty row; not differentiable).  An N that is not a multiple of 8, and operands the kernel cannot read where they lie,
-    are copied with zero padding, as torch_op.spmm_edge() does; `fast` only selects the cached engine."""
+    are copied with zero padding, as torch_op.spmm_edge() does; `fast` only selects the cached engine.  bf16 S and D (autocast) with
+    N % 8 == 0 that are row-major and 16-byte aligned -- every edge tensor that is given, S alone in the first form -- are read as they
+    lie and their gradients written in bf16 by the kernel (sextans_vector_attention_device_rm_bf16 / _backward_device_rm_bf16): the
+    bits of the fp32 route, without an fp32 (nnz, N) tensor; C and lse stay fp32.  A mixed call (a bf16 S with an fp32 D, say) takes
+    the fp32 copies as before."""
     _check_operands(A, S, V, D)
     M, K = A.shape
     tail = tuple(S.shape[1:])
