@@ -1400,6 +1400,32 @@ int sextans_spmm_edge_softagg_backward_device_rm_bf16(sextans_handle_t h, int op
                                                       int64_t ldlse, const float *d_G, int64_t ldg, float *d_dB, int64_t lddb, uint16_t *d_dE,
                                                       int64_t ldde, float *d_dt, float *d_work, void *stream);
 
+/* The same for the gated aggregation (GatedGCN / ResGatedGraphConv), in which the (nnz, N) tensors weigh most: E, z, Gz and dE of
+ * sextans_spmm_gated*_device_rm in bf16, read and written where they lie.  The contract above, unchanged: ONE dtype for all edge
+ * tensors of a call; everything of node size (xdst, xsrc, V, C, den, G, the gn workspace, dxdst, dxsrc, dV), every operation, every sum
+ * and every merge are fp32, in the fp32 twin's order (same tiles, slots, entries in flight and dealing).  A bf16 value is widened
+ * exactly, a bf16 output is the fp32 value the twin would have stored, rounded ONCE to nearest even (NaN stays a quiet NaN, +-inf and
+ * -0 stay, a value at or above 0x7f7f8000 becomes inf).  The rounded value never feeds back: the gate is computed from the unrounded
+ * fp32 z_e in all three passes, and dxdst and dxsrc sum the unrounded fp32 dz_e.  So for either mode and every pass
+ *     a bf16 output (z, dE) is round_bf16(the fp32 entry point's output on the widened inputs), bit for bit;
+ *     an fp32 output (C, den, dxdst, dxsrc, dV) is the fp32 entry point's output on the widened inputs, bit for bit.
+ * The structs have the layouts of sextans_gated_in / sextans_gated_grad.  Arguments, modes, what a call reads and ignores, NULL rules
+ * (d_e == NULL with a d_z: z without E, rounded; d_de without d_e: the gradient of z), pass skipping, degenerate matrices and
+ * determinism are the fp32 twin's.  No atomics, no value refresh, no workspace beyond the twin's: sextans_spmm_gated_workspace_floats
+ * serves both dtypes.  Capturable into a hipGraph after sextans_prepare(h, N, SEXTANS_LAYOUT_ROWMAJOR_T, stream), as the twins are.
+ * Leading dimensions are counted in ELEMENTS of their tensor: >= N and multiples of 4 for the bf16 tensors too, under the twin's rules
+ * for which of them count.  Every pointer 16-byte aligned.
+ * sextans_last_kernel: "spmm_gated_bf16" / "spmm_gated_backward_bf16", "+long_rows" appended when the workgroup path ran.
+ * Errors: the fp32 twin's, in its order, all before any device is touched. */
+typedef struct { const float *d_xdst, *d_xsrc, *d_v; const uint16_t *d_e; int64_t ld_xdst, ld_xsrc, ld_v, ld_e; } sextans_gated_in_bf16;
+typedef struct { float *d_dxdst, *d_dxsrc, *d_dv; uint16_t *d_de; int64_t ld_dxdst, ld_dxsrc, ld_dv, ld_de; } sextans_gated_grad_bf16;
+int sextans_spmm_gated_device_rm_bf16(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in_bf16 *in,
+                                      float *d_C, int64_t ldc, float *d_den, int64_t ldden, uint16_t *d_z, int64_t ldz, void *stream);
+int sextans_spmm_gated_backward_device_rm_bf16(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in_bf16 *in,
+                                               const float *d_C, int64_t ldc, const float *d_den, int64_t ldden,
+                                               const float *d_G, int64_t ldg, const uint16_t *d_Gz, int64_t ldgz,
+                                               const sextans_gated_grad_bf16 *out, float *d_work, void *stream);
+
 /* Row-range form: computes rows [row_begin, row_end) only.  d_C_in / d_C_out address row_begin as
  * their row 0 (ldc_in, ldc_out >= row_end - row_begin).  Used to pipeline a rank's slab in chunks so the
  * all-gather of chunk i overlaps the SpMM of chunk i+1.  flags: SEXTANS_ROWS_REUSE_B_PANELS = the B

@@ -129,6 +129,7 @@ _OPTIONAL_SYMBOLS = frozenset((
     "sextans_spmm_edge_device_rm_bf16", "sextans_spmm_edge_backward_device_rm_bf16",
     "sextans_vector_attention_device_rm_bf16", "sextans_vector_attention_backward_device_rm_bf16",
     "sextans_spmm_edge_softagg_device_rm_bf16", "sextans_spmm_edge_softagg_backward_device_rm_bf16",
+    "sextans_spmm_gated_device_rm_bf16", "sextans_spmm_gated_backward_device_rm_bf16",
     "sextans_edge_dot_device", "sextans_edge_dot_backward_device",
     "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
     "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
@@ -410,6 +411,8 @@ def lib():
     L.sextans_vector_attention_backward_device_rm_bf16.argtypes = L.sextans_vector_attention_backward_device_rm.argtypes
     L.sextans_spmm_edge_softagg_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_device_rm.argtypes
     L.sextans_spmm_edge_softagg_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_backward_device_rm.argtypes
+    L.sextans_spmm_gated_device_rm_bf16.argtypes = L.sextans_spmm_gated_device_rm.argtypes   # (the structs have the fp32 ones' layouts)
+    L.sextans_spmm_gated_backward_device_rm_bf16.argtypes = L.sextans_spmm_gated_backward_device_rm.argtypes
     L.sextans_edge_dot_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_edge_dot_backward_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
     L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
@@ -1242,6 +1245,23 @@ class Engine:
         _check(lib().sextans_spmm_gated_backward_device_rm(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den,
                                                            ldden, d_G, ldg, d_Gz, ldgz, C.byref(out) if out is not None else None, d_work,
                                                            stream), "spmm_gated_backward_device_rm")
+
+    def spmm_gated_device_rm_bf16(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
+        """spmm_gated_device_rm with E and z in bf16 (sextans_spmm_gated_device_rm_bf16): gin a GatedIn whose d_e addresses bf16 (the
+        struct's layout serves both), xdst, xsrc, V, C and den fp32.  E is widened exactly and the gate taken from the unrounded z -- C
+        and den are the bits of spmm_gated_device_rm on the widened E, z its z rounded once to nearest even.  ld_e and ldz count bf16
+        elements (multiples of 4)."""
+        _check(lib().sextans_spmm_gated_device_rm_bf16(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den,
+                                                       ldden, d_z, ldz, stream), "spmm_gated_device_rm_bf16")
+
+    def spmm_gated_backward_device_rm_bf16(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_G, ldg, d_Gz, ldgz, out, d_work, stream=None):
+        """spmm_gated_backward_device_rm with E, Gz and dE in bf16 (sextans_spmm_gated_backward_device_rm_bf16): gin a GatedIn and out a
+        GatedGrad whose d_e / d_de address bf16; everything else fp32, the workspace that of spmm_gated_workspace_floats(mode, N).  dxdst,
+        dxsrc and dV are the bits of spmm_gated_backward_device_rm on the widened E and Gz, dE its dE rounded once to nearest even.  ld_e,
+        ldgz and ld_de count bf16 elements."""
+        _check(lib().sextans_spmm_gated_backward_device_rm_bf16(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc,
+                                                                d_den, ldden, d_G, ldg, d_Gz, ldgz, C.byref(out) if out is not None else None,
+                                                                d_work, stream), "spmm_gated_backward_device_rm_bf16")
 
     def spmm_edge_multi_device_rm(self, op, N, d_B, ldb, d_E, lde, out, stream=None):
         """Several aggregations of edge-feature messages in one pass (sextans_spmm_edge_multi_device_rm): the message of the stored entry

@@ -19,7 +19,7 @@ BINDIR = os.path.join(ROOT, "sextans_amd", "bin")
 LIB = os.path.join(LIBDIR, "libsextans_amd.so")
 CLI = os.path.join(BINDIR, "sextans")
 
-LIB_SOURCES = ["engine_launch.hip", "engine.hip", "engine_spmm.hip", "engine_rowmajor.hip", "engine_host.hip", "engine_plan.hip", "engine_bell.hip", "engine_dist.hip", "plan_device.hip", "row_cluster.hip", "graph_cluster.hip", "csr_transpose.hip", "engine_transpose.hip", "engine_softmax.hip", "engine_attention.hip", "engine_attention_edge.hip", "engine_gat.hip", "engine_gatv2.hip", "engine_score.hip", "engine_reduce.hip", "engine_multi.hip", "engine_softagg.hip", "engine_edge.hip", "engine_gated.hip", "engine_edge_multi.hip", "engine_edge_multi_mul.hip", "engine_edge_multi_add.hip", "engine_edge_multi_add_relu.hip", "engine_edge_multi_copy.hip", "engine_edge_softagg.hip", "engine_vector_attention.hip", "engine_edge_op.hip", "engine_edge_dot.hip", "engine_edge_op_bf16.hip", "engine_edge_op_bf16_backward.hip", "engine_edge_bf16.hip", "engine_edge_bf16_backward.hip", "engine_vector_attention_bf16.hip", "engine_vector_attention_bf16_backward.hip", "engine_edge_softagg_bf16.hip", "engine_edge_softagg_bf16_backward.hip", "engine_refresh.hip", "synth.hip", "host_mtx.cpp", "panel_plan.cpp", "window_plan.cpp", "pack_api.cpp",
+LIB_SOURCES = ["engine_launch.hip", "engine.hip", "engine_spmm.hip", "engine_rowmajor.hip", "engine_host.hip", "engine_plan.hip", "engine_bell.hip", "engine_dist.hip", "plan_device.hip", "row_cluster.hip", "graph_cluster.hip", "csr_transpose.hip", "engine_transpose.hip", "engine_softmax.hip", "engine_attention.hip", "engine_attention_edge.hip", "engine_gat.hip", "engine_gatv2.hip", "engine_score.hip", "engine_reduce.hip", "engine_multi.hip", "engine_softagg.hip", "engine_edge.hip", "engine_gated.hip", "engine_edge_multi.hip", "engine_edge_multi_mul.hip", "engine_edge_multi_add.hip", "engine_edge_multi_add_relu.hip", "engine_edge_multi_copy.hip", "engine_edge_softagg.hip", "engine_vector_attention.hip", "engine_edge_op.hip", "engine_edge_dot.hip", "engine_edge_op_bf16.hip", "engine_edge_op_bf16_backward.hip", "engine_edge_bf16.hip", "engine_edge_bf16_backward.hip", "engine_vector_attention_bf16.hip", "engine_vector_attention_bf16_backward.hip", "engine_edge_softagg_bf16.hip", "engine_edge_softagg_bf16_backward.hip", "engine_gated_bf16.hip", "engine_gated_bf16_backward.hip", "engine_refresh.hip", "synth.hip", "host_mtx.cpp", "panel_plan.cpp", "window_plan.cpp", "pack_api.cpp",
                "edge_stream.cpp"]
 # every header of csrc/ (a header that is not listed here would change without anything being recompiled -- round 6 measured two
 # "new" kernels that were never built that way)

@@ -1,42 +1,38 @@
 // engine_gated.hip -- gated aggregation over the CSR pattern on an engine handle (include/sextans_amd.h):
 //   sextans_spmm_gated_device_rm            C[r, :] = sum over row r's entries of sigmoid(xdst[r] + xsrc[c] (+ E[e])) * V[c], as it is (SUM) or
 //                                           divided by the sum of the gates + eps (NORM); optionally the gates' sum and the pre-activations z
-//   sextans_spmm_gated_workspace_floats     the floats of workspace the backward needs (NORM: gn = G / (den + eps), M x N; SUM: none)
+//   sextans_spmm_gated_workspace_floats     the floats of workspace the backward needs (NORM: gn = G / (den + eps), M x N; SUM: none), for
+//                                           either element type
 //   sextans_spmm_gated_backward_device_rm   dxdst and dE (a row pass over A), dxsrc and dV (a column pass over A^T), each only when asked for
-// Kernels: spmm_gated_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h.  Only the pattern is
-// read: neither the engine's values nor any of its packed forms is read or touched.
-#include "pattern_launch.h"
-#include "spmm_gated_kernels.h"
+// Kernels: spmm_gated_kernels.h on the row walking of pattern_pass.h; the entry points' frame: pattern_launch.h; the checks and the passes
+// of both entry points: gated_launch.h, here for fp32 edge tensors (bf16: engine_gated_bf16.hip and engine_gated_bf16_backward.hip).  Only
+// the pattern is read: neither the engine's values nor any of its packed forms is read or touched.
+#include "gated_launch.h"
+
+namespace sx {
+
+// gn = G / (den + eps), M x N at leading dimension N: both backward passes read these bits
+__global__ __launch_bounds__(256) void gated_gn(long long rows, int n4, const float *__restrict__ G, long long ldg, const float *__restrict__ den,
+                                                long long ldden, float eps, float *__restrict__ gn) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows * n4) return;
+    const long long r = i / n4;
+    const int c = 4 * (int)(i % n4);
+    const float4 g = *reinterpret_cast<const float4 *>(G + r * ldg + c), d = *reinterpret_cast<const float4 *>(den + r * ldden + c);
+    *reinterpret_cast<float4 *>(gn + r * (4LL * n4) + c) = make_float4(__fdiv_rn(g.x, __fadd_rn(d.x, eps)), __fdiv_rn(g.y, __fadd_rn(d.y, eps)),
+                                                                        __fdiv_rn(g.z, __fadd_rn(d.z, eps)), __fdiv_rn(g.w, __fadd_rn(d.w, eps)));
+}
+
+}  // namespace sx
 
 namespace sxe {
-namespace {
 
-// e: the engine whose CSR arrays and softmax tables the pass walks (the column pass: the companion).  N is cut into tiles of the smallest
-// of 8 / 16 / 32 / 64 floats that holds min(N, kMaxTile); the last tile may be partial; the tiles sit in the grid in every pass (an (entry,
-// tile) of z and dE belongs to one slot).  The tile is capped at 64 floats as engine_multi.hip's is and for its reason: the forward keeps
-// 2 W floats of state and the own xdst pieces next to up to three loaded tiles per entry in flight, the column pass up to five.
-// Entries in flight per slot (U): 4 in the forward (three loads per entry), 2 in the backward passes (four and five); UNTUNED -- chosen from
-// the resource listing (profiles/spmm_gated_kernel_resources.txt): no scratch, no spills at any width.
-constexpr int kMaxTile = 64;
-
-template <int PASS>
-void launch_pass(const sextans_engine *e, const sx::GatedArgs &a, const int *perm, hipStream_t s) {
-    for_width(a.N < kMaxTile ? a.N : kMaxTile, [&](auto w) {
-        using W = decltype(w);
-        constexpr int U = PASS == sx::kAttnForward ? 4 : 2;
-        if constexpr (4 * W::T * W::P <= kMaxTile) launch_pattern<sx::GatedPass<PASS, W::T, W::P, U>>(e, tiled<W>(a), perm, false, s);
-    });
+void gated_normalize(int64_t M, int N, const float *d_G, int64_t ldg, const float *d_den, int64_t ldden, float eps, float *d_gn, hipStream_t s) {
+    const long long items = (long long)M * (N / 4);
+    hipLaunchKernelGGL(sx::gated_gn, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (long long)M, N / 4, d_G, (long long)ldg, d_den,
+                       (long long)ldden, eps, d_gn);
 }
 
-bool bad_mode(int mode) { return mode != SEXTANS_GATE_SUM && mode != SEXTANS_GATE_NORM; }
-bool bad_eps(int mode, float eps) { return mode == SEXTANS_GATE_NORM && (!(eps > 0.0f) || std::isinf(eps)); }
-// the operand struct: xdst, xsrc and V with their leading dimensions always, E's when it is given
-bool bad_in(const sextans_gated_in *in, int N) {
-    return bad_ld(in->ld_xdst, N) || bad_ld(in->ld_xsrc, N) || bad_ld(in->ld_v, N) || bad_ld_of(in->d_e, in->ld_e, N) ||
-           misaligned(in->d_xdst, in->d_xsrc, in->d_v, in->d_e);
-}
-
-}  // namespace
 }  // namespace sxe
 
 using namespace sxe;
@@ -45,24 +41,7 @@ extern "C" {
 
 int sextans_spmm_gated_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in, float *d_C, int64_t ldc,
                                  float *d_den, int64_t ldden, float *d_z, int64_t ldz, void *stream) {
-    if (!h || !in || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;   // nothing here needs a device
-    if (bad_in(in, N) || bad_ld(ldc, N) || bad_ld_of(d_den, ldden, N) || bad_ld_of(d_z, ldz, N)) return SEXTANS_ERR_INVALID;
-    if (misaligned(d_C, d_den, d_z)) return SEXTANS_ERR_INVALID;
-    PatternCall call{h};
-    if (int rc = call.open(!in->d_xdst || !in->d_xsrc || !in->d_v || !d_C, stream)) return rc;
-    if (call.degenerate()) {   // every row is empty (z has no element)
-        attention_fill(d_C, h->M, N, ldc, 0.0f, call.s);
-        attention_fill(d_den, h->M, N, ldden, 0.0f, call.s);
-        return call.done();
-    }
-    if (int rc = call.tables(false)) return rc;
-    sx::GatedArgs a{};
-    a.xdst = in->d_xdst; a.xsrc = in->d_xsrc; a.V = in->d_v; a.E = in->d_e;
-    a.ld_xdst = in->ld_xdst; a.ld_xsrc = in->ld_xsrc; a.ld_v = in->ld_v; a.ld_e = in->ld_e;
-    a.out = d_C; a.den = d_den; a.z = d_z; a.ldc = ldc; a.ldden = ldden; a.ldz = ldz;
-    a.norm = mode == SEXTANS_GATE_NORM; a.eps = eps; a.N = N;
-    call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnForward>(e, a, perm, call.s); });
-    return call.close("spmm_gated");
+    return gated_forward<float>(h, mode, eps, N, in, d_C, ldc, d_den, ldden, d_z, ldz, stream, "spmm_gated");
 }
 
 int64_t sextans_spmm_gated_workspace_floats(sextans_handle_t h, int mode, int N) {
@@ -74,42 +53,7 @@ int64_t sextans_spmm_gated_workspace_floats(sextans_handle_t h, int mode, int N)
 int sextans_spmm_gated_backward_device_rm(sextans_handle_t h, int mode, float eps, int N, const sextans_gated_in *in, const float *d_C, int64_t ldc,
                                           const float *d_den, int64_t ldden, const float *d_G, int64_t ldg, const float *d_Gz, int64_t ldgz,
                                           const sextans_gated_grad *out, float *d_work, void *stream) {
-    if (!h || !in || !out || bad_mode(mode) || bad_eps(mode, eps) || bad_n(N) || too_many_tiles(N, kMaxTile)) return SEXTANS_ERR_INVALID;
-    const bool norm = mode == SEXTANS_GATE_NORM;
-    if (!norm) d_C = d_den = nullptr;   // SUM ignores them
-    if (bad_in(in, N) || bad_ld_of(d_C, ldc, N) || bad_ld_of(d_den, ldden, N) || bad_ld(ldg, N) || bad_ld_of(d_Gz, ldgz, N)) return SEXTANS_ERR_INVALID;
-    if (bad_ld_of(out->d_dxdst, out->ld_dxdst, N) || bad_ld_of(out->d_dxsrc, out->ld_dxsrc, N) || bad_ld_of(out->d_dv, out->ld_dv, N) ||
-        bad_ld_of(out->d_de, out->ld_de, N))
-        return SEXTANS_ERR_INVALID;
-    if (misaligned(d_C, d_den, d_G, d_Gz, out->d_dxdst, out->d_dxsrc, out->d_dv, out->d_de, d_work)) return SEXTANS_ERR_INVALID;
-    if (!out->d_dxdst && !out->d_dxsrc && !out->d_dv && !out->d_de) return SEXTANS_ERR_INVALID;   // nothing to compute
-    PatternCall call{h};
-    if (int rc = call.open(!in->d_xdst || !in->d_xsrc || !in->d_v || !d_G || (norm && (!d_C || !d_den || !d_work)), stream)) return rc;
-    if (call.degenerate()) {   // (dE has no element)
-        attention_fill(out->d_dxdst, h->M, N, out->ld_dxdst, 0.0f, call.s);
-        attention_fill(out->d_dxsrc, h->K, N, out->ld_dxsrc, 0.0f, call.s);
-        attention_fill(out->d_dv, h->K, N, out->ld_dv, 0.0f, call.s);
-        return call.done();
-    }
-    const bool rows = out->d_dxdst || out->d_de, cols = out->d_dxsrc || out->d_dv;
-    if (int rc = call.tables(cols)) return rc;
-    sx::GatedArgs a{};
-    a.xdst = in->d_xdst; a.xsrc = in->d_xsrc; a.V = in->d_v; a.E = in->d_e;
-    a.ld_xdst = in->ld_xdst; a.ld_xsrc = in->ld_xsrc; a.ld_v = in->ld_v; a.ld_e = in->ld_e;
-    a.C = d_C; a.ldc = ldc; a.Gz = d_Gz; a.ldgz = ldgz;
-    a.gn = d_G; a.ldgn = ldg;
-    a.dxdst = out->d_dxdst; a.dxsrc = out->d_dxsrc; a.dV = out->d_dv; a.dE = out->d_de;
-    a.ld_dxdst = out->ld_dxdst; a.ld_dxsrc = out->ld_dxsrc; a.ld_dv = out->ld_dv; a.ld_de = out->ld_de;
-    a.norm = norm; a.eps = eps; a.N = N;
-    if (norm) {   // gn once, for both passes
-        const long long items = (long long)h->M * (N / 4);
-        hipLaunchKernelGGL(sx::gated_gn, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, call.s, (long long)h->M, N / 4, d_G, (long long)ldg,
-                           d_den, (long long)ldden, eps, d_work);
-        a.gn = d_work; a.ldgn = N;
-    }
-    if (cols) call.cols([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardCols>(e, a, perm, call.s); });
-    if (rows) call.rows([&](const sextans_engine *e, const int *perm) { launch_pass<sx::kAttnBackwardRows>(e, a, perm, call.s); });
-    return call.close("spmm_gated_backward");
+    return gated_backward<float>(h, mode, eps, N, in, d_C, ldc, d_den, ldden, d_G, ldg, d_Gz, ldgz, out, d_work, stream, "spmm_gated_backward");
 }
 
 }  // extern "C"

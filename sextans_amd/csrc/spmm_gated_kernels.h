@@ -6,7 +6,7 @@
 //   g_e[n] = gate_sigmoid(z_e[n])                    the SAME function in the three passes: the backward recomputes the forward's bits
 //   forward        num[r, n] = sum_e fma(g_e, V[c, n], num)   den[r, n] = sum_e g_e   (__fadd_rn merges; an empty row: both +0)
 //                  C = num (SUM) | num / (den + eps) (NORM);  z_e is stored when asked for: the layer's new edge features
-//   backward, gn = G (SUM) | G / (den + eps) (NORM, written once by gated_gn), C == 0 in SUM:
+//   backward, gn = G (SUM) | G / (den + eps) (NORM, written once by engine_gated.hip's gated_gn), C == 0 in SUM:
 //                  dg = gn (v - C)     dz_e = fma(dg, g (1 - g), Gz[e])      (Gz: the upstream gradient of the z output, or absent)
 //     rows         dE[e, n] = dz_e (one store per (entry, tile));  dxdst[r, n] = sum_e dz_e
 //     cols (A^T)   dxsrc[c, n] = sum over the entries of column c of dz_e;  dV[c, n] = sum of fma(g_e, gn[r, n], dV)
@@ -21,17 +21,25 @@
 
 namespace sx {
 
-struct GatedArgs {
-    const float *xdst, *xsrc, *V, *E;          // E may be null
-    const float *C, *gn, *Gz;                  // backward; C null: SUM mode (C == 0); Gz may be null
-    float *out, *den, *z;                      // forward; den and z may be null
-    float *dxdst, *dxsrc, *dV, *dE;            // backward, each may be null
+// ET: the element type of the (nnz, N) tensors E, z, Gz and dE in memory -- float, or uint16_t for bf16 (pattern_pass.h's typed attn_load /
+// attn_store: fp32 in the registers either way, a bf16 store rounds its copy only).  Everything of node size is fp32.
+template <class ET>
+struct GatedArgsT {
+    const float *xdst, *xsrc, *V;
+    const ET *E;                               // may be null
+    const float *C, *gn;                       // backward; C null: SUM mode (C == 0)
+    const ET *Gz;                              // backward; may be null
+    float *out, *den;                          // forward; den may be null
+    ET *z;                                     // forward; may be null
+    float *dxdst, *dxsrc, *dV;                 // backward, each may be null
+    ET *dE;
     long long ld_xdst, ld_xsrc, ld_v, ld_e, ldc, ldden, ldz, ldgn, ldgz, ld_dxdst, ld_dxsrc, ld_dv, ld_de;
     float eps;
     int norm;                                  // forward: C = num / (den + eps)
     int H;                                     // column tiles (the bodies' "heads")
     int N, tile;                               // tile: floats per tile = 4 T P
 };
+using GatedArgs = GatedArgsT<float>;
 
 // 1 / (1 + exp(-z)), the division rounded to nearest: exactly 1 once exp(-z) vanishes against 1 (z >= 17), exactly +0 once it overflows
 // (z <= -89: 1 / inf), never inf; a NaN stays one.
@@ -48,27 +56,15 @@ __device__ __forceinline__ float gate_dz(float g, float gn, float v, float c, fl
     return has_gz ? __fmaf_rn(dg, s, gz) : __fmul_rn(dg, s);
 }
 
-// gn = G / (den + eps), M x N at leading dimension N: both backward passes read these bits
-__global__ __launch_bounds__(256) void gated_gn(long long rows, int n4, const float *__restrict__ G, long long ldg, const float *__restrict__ den,
-                                                long long ldden, float eps, float *__restrict__ gn) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * n4) return;
-    const long long r = i / n4;
-    const int c = 4 * (int)(i % n4);
-    const float4 g = *reinterpret_cast<const float4 *>(G + r * ldg + c), d = *reinterpret_cast<const float4 *>(den + r * ldden + c);
-    *reinterpret_cast<float4 *>(gn + r * (4LL * n4) + c) = make_float4(__fdiv_rn(g.x, __fadd_rn(d.x, eps)), __fdiv_rn(g.y, __fadd_rn(d.y, eps)),
-                                                                        __fdiv_rn(g.z, __fadd_rn(d.z, eps)), __fdiv_rn(g.w, __fadd_rn(d.w, eps)));
-}
-
 // One slot's view of a pass: the interface of AttnPass.  "own" is the row walked (the column pass: a column of A), ci[e] the other index.
-template <int PASS, int T_, int P_, int U_>
+template <int PASS, int T_, int P_, int U_, class ET = float>
 struct GatedPass {
-    using Args = GatedArgs;
+    using Args = GatedArgsT<ET>;
     static constexpr int T = T_, P = P_, U = U_, W = 4 * P_;
     static constexpr bool kCols = PASS == kAttnBackwardCols;
     static constexpr int NF = PASS == kAttnBackwardRows ? W : 2 * W;   // forward: num, den; rows: dxdst; cols: dV, dxsrc
     static constexpr bool kMerge = true;
-    const GatedArgs &a;
+    const Args &a;
     const int *ci, *perm;
     const int t;
     int h = 0, n = 0;                       // the tile and its valid floats
@@ -77,7 +73,7 @@ struct GatedPass {
     float c[PASS == kAttnBackwardRows ? W : 1];   // rows: the own row's C (SUM: 0)
     float f[NF];
 
-    __device__ __forceinline__ GatedPass(const GatedArgs &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
+    __device__ __forceinline__ GatedPass(const Args &a_, const int *ci_, const int *perm_, int t_) : a(a_), ci(ci_), perm(perm_), t(t_) {}
 
     __device__ __forceinline__ void begin(bool act, int own, int tile, bool) {
         h = tile;

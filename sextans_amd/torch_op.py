@@ -62,7 +62,8 @@ the edge -> node reduction of MeshGraphNets; u_mul_e_sum, u_add_e_sum, copy_e_su
     A, perm = from_edge_index(edge_index, num_dst, num_src)   the sparse_csr A of a PyG edge list, and perm with E = edge_attr[perm]
 
 The gated aggregation of ResGatedGraphConv / GatedGCN (a per-channel sigmoid gate per entry from both endpoints and the entry's features)
-lives in a module of its own, on the same cached engines: sextans_amd.gated.spmm_gated(A, x_dst, x_src, V, E=None, normalize=False, ...).
+lives in a module of its own, on the same cached engines: sextans_amd.gated.spmm_gated(A, x_dst, x_src, V, E=None, normalize=False, ...)
+(with the (nnz, N) tensors in bf16: sextans_amd.gated_bf16.spmm_gated_bf16).
 So does the softmax aggregation of edge-feature messages (GENConv / DeeperGCN with edge features: relu(x_j + e_ij) + eps under a softmax
 with a learnable temperature): sextans_amd.edge_softagg.spmm_edge_softagg(A, B, E, op="mul", t=1.0, eps=0.0, return_lse=False).
 And Point Transformer's channel-wise attention from per-channel scores: sextans_amd.vector_attention.vector_attention(A, S, V=None, D=None).

@@ -11,7 +11,7 @@ sextans_amd/build.py (no GPU needed) and compares them kernel by kernel:
                                        # its replacement, applied to the whole assembly text) before they are matched with the first tree's
 
 Without units: every sextans_amd/csrc/*.hip of the second tree that includes pattern_launch.h or one of the family launch headers over it
-(edge_multi_launch.h, edge_op_launch.h, edge_launch.h, vector_attention_launch.h, edge_softagg_launch.h).  Either kind of
+(edge_multi_launch.h, edge_op_launch.h, edge_launch.h, vector_attention_launch.h, edge_softagg_launch.h, gated_launch.h).  Either kind of
 change may reorder template instantiation, so the functions are compared per symbol, not in file order, after the function's index is taken
 out of its local labels (.LBB<k>_<n>, .Lfunc_end<k>).  What is compared per symbol: the instructions, the kernel descriptor, the
 resource figures and the code-object metadata entry.  Exit status 1 when anything differs."""
@@ -105,7 +105,7 @@ def main():
     parent, branch, units = argv[0], argv[1], argv[2:]
     if not units:
         for f in sorted(os.listdir(os.path.join(branch, CSRC))):
-            if f.endswith(".hip") and re.search(r'#include "(pattern|edge_multi|edge_op|edge|vector_attention|edge_softagg)_launch\.h"',
+            if f.endswith(".hip") and re.search(r'#include "(pattern|edge_multi|edge_op|edge|vector_attention|edge_softagg|gated)_launch\.h"',
                                                 open(os.path.join(branch, CSRC, f)).read()):
                 units.append(os.path.join(CSRC, f))
     bad = 0
