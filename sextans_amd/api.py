@@ -1,5 +1,9 @@
 """ctypes mirror of include/sextans_amd.h -- the host-side call surface of the engine.
 
+Every C entry point is declared once: a line of _PROTOTYPES where the Python side marshals, @_entry(<C types>) on the def line of an
+Engine method that only forwards.  To add one: the prototype in the header, then one of the two; tests/test_abi_header.py holds the
+table to the header, and the name is optional for older builds by derivation (_OPTIONAL_SYMBOLS).
+
 Function names follow the reference's host library (src/sparse_helper.h, src/sextans-host.cpp) so
 tests read like the reference's own harness:
 
@@ -62,10 +66,6 @@ class Dropout(C.Structure):
         super().__init__(p, int(seed) & 0xFFFFFFFFFFFFFFFF, d_step)
 
 
-def _drop_ref(drop):
-    return C.byref(drop) if drop is not None else None
-
-
 class MultiOut(C.Structure):
     """sextans_multi_out: the outputs of spmm_multi_device_rm, each a device address (None: not computed) with its own leading dimension
     -- they may be column slices of one (M, k N) buffer.  ld_arg serves both args."""
@@ -102,42 +102,6 @@ class SextansError(RuntimeError):
         super().__init__(f"{where}: [{code}] {msg}" + (f" ({detail})" if detail else ""))
 
 
-# Entry points added after round 4: the only ones a comparison against an OLDER build (tools/nasa_ab.py loads the libraries of earlier
-# rounds for same-box A/Bs) may lack.  Any other missing name is a typo or a broken build and fails the load.
-_OPTIONAL_SYMBOLS = frozenset((
-    "sextans_spmm_device_rm", "sextans_dist_spmm_rm", "sextans_spmm_bell_device2", "sextans_dist_spmm_bell", "sextans_profile_read_post",
-    "sextans_gen_kron_host", "sextans_gen_kron_device", "sextans_csr_slice_rows_device", "sextans_csr_permute_symmetric_device",
-    "sextans_export_row_order", "sextans_mtx_read_cached", "sextans_matrix_save", "sextans_matrix_load",
-    "sextans_prepare", "sextans_dist_prepare", "sextans_dist_bind_library", "sextans_device_alloc", "sextans_device_copy",
-    "sextans_csr_transpose_device", "sextans_spmm_t_device_rm", "sextans_sddmm_device_rm",
-    "sextans_update_values", "sextans_update_values_device",
-    "sextans_spmm_device_rm_bf16", "sextans_spmm_t_device_rm_bf16", "sextans_prepare_rm_bf16",
-    "sextans_row_softmax_device", "sextans_row_softmax_backward_device",
-    "sextans_attention_device", "sextans_attention_backward_device",
-    "sextans_gat_attention_device", "sextans_gat_attention_backward_device",
-    "sextans_gatv2_workspace_floats", "sextans_gatv2_attention_device", "sextans_gatv2_attention_backward_device",
-    "sextans_spmm_reduce_device_rm", "sextans_spmm_reduce_backward_device_rm",
-    "sextans_spmm_multi_device_rm", "sextans_spmm_multi_backward_device_rm",
-    "sextans_spmm_softagg_device_rm", "sextans_spmm_softagg_workspace_floats", "sextans_spmm_softagg_backward_device_rm",
-    "sextans_spmm_edge_device_rm", "sextans_spmm_edge_backward_device_rm",
-    "sextans_spmm_gated_device_rm", "sextans_spmm_gated_workspace_floats", "sextans_spmm_gated_backward_device_rm",
-    "sextans_spmm_edge_multi_device_rm", "sextans_spmm_edge_multi_backward_device_rm",
-    "sextans_spmm_edge_softagg_device_rm", "sextans_spmm_edge_softagg_workspace_floats", "sextans_spmm_edge_softagg_backward_device_rm",
-    "sextans_vector_attention_device_rm", "sextans_vector_attention_backward_device_rm",
-    "sextans_edge_op_device_rm", "sextans_edge_op_backward_device_rm",
-    "sextans_edge_op_device_rm_bf16", "sextans_edge_op_backward_device_rm_bf16",
-    "sextans_spmm_edge_device_rm_bf16", "sextans_spmm_edge_backward_device_rm_bf16",
-    "sextans_vector_attention_device_rm_bf16", "sextans_vector_attention_backward_device_rm_bf16",
-    "sextans_spmm_edge_softagg_device_rm_bf16", "sextans_spmm_edge_softagg_backward_device_rm_bf16",
-    "sextans_spmm_gated_device_rm_bf16", "sextans_spmm_gated_backward_device_rm_bf16",
-    "sextans_edge_dot_device", "sextans_edge_dot_backward_device",
-    "sextans_attention_dropout_device", "sextans_attention_dropout_backward_device",
-    "sextans_gat_attention_dropout_device", "sextans_gat_attention_dropout_backward_device",
-    "sextans_gatv2_attention_dropout_device", "sextans_gatv2_attention_dropout_backward_device",
-    "sextans_dropout_mask_device", "sextans_dropout_keep_host",
-    "sextans_attention_edge_device", "sextans_attention_edge_backward_device",
-    "sextans_score_attention_device", "sextans_score_attention_backward_device"))
-
 DTYPE_F32, DTYPE_BF16 = 0, 1   # SEXTANS_DTYPE_*: the type of C_in / C_out on the bf16 entry points
 REDUCE_MAX, REDUCE_MIN = 1, 2  # SEXTANS_REDUCE_*: the op of spmm_reduce_device_rm
 EDGE_MUL, EDGE_ADD, EDGE_ADD_RELU, EDGE_COPY = 1, 2, 3, 4  # SEXTANS_EDGE_*: the op of spmm_edge_device_rm
@@ -147,21 +111,145 @@ EDGEOP_ADD, EDGEOP_SUB, EDGEOP_MUL, EDGEOP_DST, EDGEOP_SRC = 1, 2, 3, 4, 5  # SE
 SCORE_SOFTMAX, SCORE_WEIGHT = 1, 2  # SEXTANS_SCORE_*: the mode of score_attention_device
 
 
-class _Optional:
-    """ctypes library proxy for lib(): declaring the prototype of an entry point that an OLDER build lacks is skipped instead of
-    failing the whole load -- for the names in _OPTIONAL_SYMBOLS only; anything else raises AttributeError (a misspelled name would
-    otherwise lose its prototype silently and ctypes would truncate 64-bit arguments to int)."""
-    class _Missing:
-        argtypes = restype = None
-    def __init__(self, L):
-        object.__setattr__(self, "_L", L)
-    def __getattr__(self, name):
+# ---- the binding: one declaration per C entry point.  _PROTOTYPES maps the C name to (restype, argtypes); lib() applies it in one loop and
+# tests/test_abi_header.py compares it with include/sextans_amd.h.  A function with marshalling of its own is declared in the table below;
+# an Engine method that only forwards its arguments is declared by @_entry on its def line, which adds the table entry and builds the body.
+i, l, f, p = C.c_int, C.c_int64, C.c_float, C.c_void_p
+ref = C.POINTER    # ref(T): a struct parameter, passed C.byref(x), or None as a null pointer
+_str, _dbl, _u64 = C.c_char_p, C.c_double, C.c_uint64
+_ip, _lp, _dp, _pp = C.POINTER(i), C.POINTER(l), C.POINTER(_dbl), C.POINTER(p)
+_ipp, _fpp, _u16pp = C.POINTER(_ip), C.POINTER(C.POINTER(f)), C.POINTER(C.POINTER(C.c_uint16))
+_u16p = np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")
+
+_PROTOTYPES = {
+    "sextans_error_string": (_str, [i]),
+    "sextans_last_error": (_str, []),
+    # host sparse library
+    "sextans_mtx_read": (i, [_str, i, _ip, _ip, _ip, _ipp, _ipp, _fpp]),
+    "sextans_mtx_read_cached": (i, [_str, _str, i, _ip, _ip, _ip, _ipp, _ipp, _fpp, _ip]),
+    "sextans_mtx_write": (i, [_str, i, i, _i32p, _i32p, _f32p]),
+    "sextans_matrix_save": (i, [_str, i, i, i, i, _i32p, _i32p, _f32p]),
+    "sextans_matrix_load": (i, [_str, _ip, _ip, _ip, _ip, _ipp, _ipp, _fpp]),
+    "sextans_host_free": (None, [p]),
+    "sextans_csc_to_csr": (i, [i, i, i, _i32p, _i32p, _f32p, _i32p, _i32p, _f32p]),
+    "sextans_init_dense_B": (None, [i, i, _f32p]),
+    "sextans_init_dense_C": (None, [i, i, _f32p]),
+    "sextans_round_up_n": (i, [i]),
+    "sextans_verify": (i, [i, i, _f32p, _f32p, C.POINTER(f)]),
+    "sextans_gflops": (_dbl, [i, i, l, _dbl]),
+    "sextans_selfcheck_golden": (i, [i, i, i, f, _i32p, _i32p, _f32p, _f32p, f, _f32p]),
+    "sextans_spmm_csr": (i, [i, i, i, i, f, _i32p, _i32p, _f32p, _f32p, f, _f32p]),
+    "sextans_pack_csr": (i, [i, i, _i32p, _i32p, _f32p, i, i, C.POINTER(Packed)]),
+    "sextans_packed_free": (None, [C.POINTER(Packed)]),
+    "sextans_unpack_csr": (i, [C.POINTER(Packed), _i32p, _i32p, _f32p]),
+    "sextans_window_pack_csr": (i, [i, i, _i32p, _i32p, _f32p, i, i, C.POINTER(WindowPacked)]),
+    "sextans_window_packed_free": (None, [C.POINTER(WindowPacked)]),
+    "sextans_partition_rows_by_nnz": (i, [i, _i32p, i, _i32p]),
+    "sextans_dropout_keep_host": (i, [l, l, i, f, _u64, _u64, p]),
+    # the accelerator's own buffer formats
+    "sextans_edges_pack_csc": (i, [i, i, i, _i32p, _i32p, _f32p, C.POINTER(Edges)]),
+    "sextans_edges_free": (None, [C.POINTER(Edges)]),
+    "sextans_edges_decode_csr": (i, [_i32p, _pp, i, i, i, _lp, _ipp, _ipp, _fpp]),
+    "sextans_edges_save": (i, [_str, C.POINTER(Edges)]),
+    "sextans_edges_load": (i, [_str, C.POINTER(Edges)]),
+    "sextans_chan_b_colsize": (l, [i, i]),
+    "sextans_chan_b_len": (l, [i, i, i]),
+    "sextans_chan_c_colsize": (l, [i]),
+    "sextans_chan_c_len": (l, [i, i]),
+    "sextans_chan_pack_b": (i, [i, i, i, _f32p, _pp]),
+    "sextans_chan_unpack_b": (i, [i, i, i, _pp, _f32p]),
+    "sextans_chan_pack_c": (i, [i, i, _f32p, _pp]),
+    "sextans_chan_unpack_c": (i, [i, i, _pp, _f32p]),
+    # the engine: the entry points whose Engine method marshals (the forwarding ones are declared by @_entry)
+    "sextans_device_count": (i, [_ip]),
+    "sextans_create": (i, [_pp, i]),
+    "sextans_destroy": (i, [p]),
+    "sextans_set_option": (i, [p, _str, l]),
+    "sextans_get_option": (i, [p, _str, _lp]),
+    "sextans_get_stat": (i, [p, _str, _dp]),
+    "sextans_align_row": (i, [p, i, i, _ip]),
+    "sextans_reassociated_rows": (i, [p, _i32p, i, _ip]),
+    "sextans_export_plan": (i, [p, i, C.POINTER(Packed)]),
+    "sextans_export_row_order": (i, [p, _i32p, _ip]),
+    "sextans_set_matrix_csr": (i, [p, i, i, l, _i32p, _i32p, _f32p]),
+    "sextans_set_matrix_csr_device": (i, [p, i, i, l, p, p, p]),
+    "sextans_set_matrix_edges": (i, [p, _i32p, _pp, i, i, i, i]),
+    "sextans_set_matrix_bell": (i, [p, i, i, i, _i32p, _u16p]),
+    "sextans_update_values": (i, [p, p]),
+    "sextans_prepare": (i, [p, i, i, p]),
+    "sextans_prepare_rm_bf16": (i, [p, i, i, i, p]),
+    "sextans_spmm_host": (i, [p, i, f, _f32p, f, _f32p, i, _dp]),
+    "sextans_invoke": (i, [p, p, _pp, _pp, i, _pp, _pp, i, i, i, i, i, i, i, _dp]),
+    "sextans_spmm_device_rows": (i, [p, i, f, p, l, f, p, l, p, l, i, i, i, p]),
+    "sextans_profile_read": (i, [p, _dp, _lp, _dp]),
+    "sextans_profile_read_post": (i, [p, _dp, _lp]),
+    "sextans_phase_timing_read": (i, [p, _lp]),
+    "sextans_last_kernel": (_str, [p]),
+    # several GPUs
+    "sextans_dist_bind_library": (i, [_str]),
+    "sextans_dist_unique_id": (i, [_str]),
+    "sextans_dist_comm_init": (i, [_pp, i, i, i, _str]),
+    "sextans_dist_comm_destroy": (i, [p]),
+    "sextans_dist_prepare": (i, [p, p, i, i, _i32p, i, i, i, p]),
+    "sextans_dist_spmm": (i, [p, p, i, i, _i32p, i, f, p, l, f, p, l, p, l, i, p]),
+    "sextans_dist_spmm_rm": (i, [p, p, i, i, _i32p, i, f, p, l, f, p, l, p, l, p]),
+    "sextans_dist_spmm_bell": (i, [p, p, i, i, _i32p, i, f, p, l, f, p, l, p, l, p]),
+    # synthetic inputs and device memory
+    "sextans_gen_csr_host": (i, [i, i, _dbl, i, _u64, i, i, _ipp, _ipp, _fpp, _lp]),
+    "sextans_gen_csr_device": (i, [i, i, i, _dbl, i, _u64, i, i, _pp, _pp, _pp, _lp]),
+    "sextans_gen_stencil2d_host": (i, [i, i, i, i, _u64, i, i, _ipp, _ipp, _fpp, _lp]),
+    "sextans_gen_stencil2d_device": (i, [i, i, i, i, i, _u64, i, i, _pp, _pp, _pp, _lp]),
+    "sextans_gen_kkt_host": (i, [i, i, _u64, i, i, _ipp, _ipp, _fpp, _lp]),
+    "sextans_gen_kkt_device": (i, [i, i, i, _u64, i, i, _pp, _pp, _pp, _lp]),
+    "sextans_gen_fem3d_host": (i, [i, i, i, i, _u64, i, i, _ipp, _ipp, _fpp, _lp]),
+    "sextans_gen_fem3d_device": (i, [i, i, i, i, i, _u64, i, i, _pp, _pp, _pp, _lp]),
+    "sextans_gen_powerlaw_host": (i, [i, i, i, i, i, _u64, i, i, _ipp, _ipp, _fpp, _lp]),
+    "sextans_gen_powerlaw_device": (i, [i, i, i, i, i, i, _u64, i, i, _pp, _pp, _pp, _lp]),
+    "sextans_gen_kron_host": (i, [i, i, i, _i32p, _i32p, i, _u64, i, i, _ipp, _ipp, _fpp, _lp, _ip]),
+    "sextans_gen_kron_device": (i, [i, i, i, i, _i32p, _i32p, i, _u64, i, i, _pp, _pp, _pp, _lp, _ip]),
+    "sextans_gen_bell_host": (i, [i, i, i, _u64, _ipp, _u16pp]),
+    "sextans_gen_bell_device": (i, [i, i, i, i, _u64, _pp, _pp]),
+    "sextans_gen_bell_banded_host": (i, [i, i, i, _u64, _ipp, _u16pp]),
+    "sextans_gen_bell_banded_device": (i, [i, i, i, i, _u64, _pp, _pp]),
+    "sextans_gen_uniform_host": (i, [_f32p, l, _u64]),
+    "sextans_gen_uniform_device": (i, [i, p, l, _u64, p]),
+    "sextans_gen_uniform_bf16_host": (i, [_u16p, l, _u64]),
+    "sextans_gen_uniform_bf16_device": (i, [i, p, l, _u64, p]),
+    "sextans_device_alloc": (i, [i, C.c_size_t, _pp]),
+    "sextans_device_copy": (i, [i, p, p, C.c_size_t, i]),
+    "sextans_device_free": (i, [i, p]),
+    "sextans_csr_transpose_device": (i, [i, i, i, l, p, p, p, _pp, _pp, _pp, p]),
+    "sextans_csr_permute_symmetric_device": (i, [i, i, l, p, p, p, p, _pp, _pp, _pp]),
+    "sextans_csr_slice_rows_device": (i, [i, i, i, p, _pp, _lp, _lp]),
+}
+
+# The entry points that existed by round 4: the only ones every build must export.  The set never grows; every later name is optional
+# (_OPTIONAL_SYMBOLS, at the end of this module), so that the library of an earlier round still loads for a same-box A/B (tools/nasa_ab.py).
+_ROUND4_SYMBOLS = frozenset("sextans_" + name for name in """
+    align_row chan_b_colsize chan_b_len chan_c_colsize chan_c_len chan_pack_b chan_pack_c chan_unpack_b chan_unpack_c create
+    csc_to_csr destroy device_count device_free dist_comm_destroy dist_comm_init dist_spmm dist_unique_id edges_decode_csr edges_free
+    edges_load edges_pack_csc edges_save error_string export_plan gen_bell_banded_device gen_bell_banded_host gen_bell_device
+    gen_bell_host gen_csr_device gen_csr_host gen_fem3d_device gen_fem3d_host gen_kkt_device gen_kkt_host gen_powerlaw_device
+    gen_powerlaw_host gen_stencil2d_device gen_stencil2d_host gen_uniform_bf16_device gen_uniform_bf16_host gen_uniform_device
+    gen_uniform_host get_option get_stat gflops host_free init_dense_B init_dense_C invoke last_error last_kernel mtx_read pack_csr
+    packed_free partition_rows_by_nnz phase_timing_read profile_read profile_reset reassociated_rows round_up_n selfcheck_golden
+    set_matrix_bell set_matrix_bell_device set_matrix_csr set_matrix_csr_device set_matrix_edges set_option spmm_bell_device spmm_csr
+    spmm_device spmm_device2 spmm_device_rows spmm_host unpack_csr verify window_pack_csr window_packed_free""".split())
+
+
+def _bind(L):
+    """Declare every prototype of _PROTOTYPES on the library L.  An entry point that L lacks is skipped when it is optional -- calling it
+    later fails with ctypes' own AttributeError -- and fails the load when it is one of _ROUND4_SYMBOLS: a typo or a broken build (without
+    its prototype ctypes would truncate 64-bit arguments to int)."""
+    for name, (restype, argtypes) in _PROTOTYPES.items():
         try:
-            return getattr(self._L, name)
+            fn = getattr(L, name)
         except AttributeError:
-            if name in _OPTIONAL_SYMBOLS:
-                return _Optional._Missing()
-            raise
+            if name in _ROUND4_SYMBOLS:
+                raise
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
+    return L
 
 
 def lib():
@@ -178,256 +266,45 @@ def lib():
         import torch  # noqa: F401
     except Exception:
         pass
-    raw = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    L = _Optional(raw)      # (prototypes of entry points an older build lacks are skipped)
-    pi, pf = C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.POINTER(C.c_float))
-    ip = C.POINTER(C.c_int)
-    L.sextans_error_string.restype = C.c_char_p
-    L.sextans_error_string.argtypes = [C.c_int]
-    L.sextans_last_error.restype = C.c_char_p
-    L.sextans_mtx_read.argtypes = [C.c_char_p, C.c_int, ip, ip, ip, pi, pi, pf]
-    L.sextans_mtx_read_cached.argtypes = [C.c_char_p, C.c_char_p, C.c_int, ip, ip, ip, pi, pi, pf, ip]
-    L.sextans_matrix_save.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p]
-    L.sextans_matrix_load.argtypes = [C.c_char_p, ip, ip, ip, ip, pi, pi, pf]
-    L.sextans_host_free.argtypes = [C.c_void_p]
-    L.sextans_host_free.restype = None
-    L.sextans_csc_to_csr.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _i32p, _i32p,
-                                     _f32p]
-    L.sextans_init_dense_B.argtypes = [C.c_int, C.c_int, _f32p]
-    L.sextans_init_dense_B.restype = None
-    L.sextans_init_dense_C.argtypes = [C.c_int, C.c_int, _f32p]
-    L.sextans_init_dense_C.restype = None
-    L.sextans_round_up_n.argtypes = [C.c_int]
-    L.sextans_verify.argtypes = [C.c_int, C.c_int, _f32p, _f32p, C.POINTER(C.c_float)]
-    L.sextans_gflops.restype = C.c_double
-    L.sextans_gflops.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_double]
-    L.sextans_selfcheck_golden.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, _i32p, _i32p,
-                                           _f32p, _f32p, C.c_float, _f32p]
-    L.sextans_pack_csr.argtypes = [C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_int, C.POINTER(Packed)]
-    L.sextans_packed_free.argtypes = [C.POINTER(Packed)]
-    L.sextans_packed_free.restype = None
-    L.sextans_unpack_csr.argtypes = [C.POINTER(Packed), _i32p, _i32p, _f32p]
-    L.sextans_window_pack_csr.argtypes = [C.c_int, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_int,
-                                          C.POINTER(WindowPacked)]
-    L.sextans_window_packed_free.argtypes = [C.POINTER(WindowPacked)]
-    L.sextans_window_packed_free.restype = None
-    L.sextans_get_stat.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]
-    L.sextans_align_row.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    L.sextans_reassociated_rows.argtypes = [C.c_void_p, _i32p, C.c_int, C.POINTER(C.c_int)]
-    L.sextans_export_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(Packed)]
-    L.sextans_partition_rows_by_nnz.argtypes = [C.c_int, _i32p, C.c_int, _i32p]
-    L.sextans_dist_unique_id.argtypes = [C.c_char_p]
-    L.sextans_dist_comm_init.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_char_p]
-    L.sextans_dist_comm_destroy.argtypes = [C.c_void_p]
-    L.sextans_dist_spmm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_float, C.c_void_p,
-                                    C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int,
-                                    C.c_void_p]
-    if hasattr(raw, "sextans_dist_spmm_rm"):
-        L.sextans_dist_spmm_rm.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_float, C.c_void_p,
-                                           C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    pp = C.POINTER(C.c_void_p)
-    L.sextans_edges_pack_csc.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, C.POINTER(Edges)]
-    L.sextans_edges_free.argtypes = [C.POINTER(Edges)]
-    L.sextans_edges_free.restype = None
-    L.sextans_edges_decode_csr.argtypes = [_i32p, pp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), pi, pi, pf]
-    L.sextans_edges_save.argtypes = [C.c_char_p, C.POINTER(Edges)]
-    L.sextans_edges_load.argtypes = [C.c_char_p, C.POINTER(Edges)]
-    for fn in ("sextans_chan_b_colsize", "sextans_chan_b_len", "sextans_chan_c_colsize", "sextans_chan_c_len"):
-        getattr(L, fn).restype = C.c_int64
-    L.sextans_chan_b_colsize.argtypes = [C.c_int, C.c_int]
-    L.sextans_chan_b_len.argtypes = [C.c_int, C.c_int, C.c_int]
-    L.sextans_chan_c_colsize.argtypes = [C.c_int]
-    L.sextans_chan_c_len.argtypes = [C.c_int, C.c_int]
-    L.sextans_chan_pack_b.argtypes = [C.c_int, C.c_int, C.c_int, _f32p, pp]
-    L.sextans_chan_unpack_b.argtypes = [C.c_int, C.c_int, C.c_int, pp, _f32p]
-    L.sextans_chan_pack_c.argtypes = [C.c_int, C.c_int, _f32p, pp]
-    L.sextans_chan_unpack_c.argtypes = [C.c_int, C.c_int, pp, _f32p]
-    L.sextans_set_matrix_edges.argtypes = [C.c_void_p, _i32p, pp, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.sextans_invoke.argtypes = [C.c_void_p, C.c_void_p, pp, pp, C.c_int, pp, pp, C.c_int, C.c_int, C.c_int,
-                                 C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
-    L.sextans_device_count.argtypes = [ip]
-    L.sextans_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    L.sextans_destroy.argtypes = [C.c_void_p]
-    L.sextans_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-    L.sextans_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
-    L.sextans_set_matrix_csr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, _i32p, _i32p,
-                                         _f32p]
-    L.sextans_set_matrix_csr_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_host.argtypes = [C.c_void_p, C.c_int, C.c_float, _f32p, C.c_float, _f32p,
-                                    C.c_int, C.POINTER(C.c_double)]
-    L.sextans_spmm_device.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64,
-                                      C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_spmm_device2.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    if hasattr(raw, "sextans_spmm_device_rm"):      # (absent from the older builds tools/nasa_ab.py compares against)
-        L.sextans_spmm_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_spmm_device_rows.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                           C.c_int, C.c_void_p]
-    L.sextans_spmm_csr.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _i32p, _i32p,
-                                   _f32p, _f32p, C.c_float, _f32p]
-    L.sextans_profile_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                       C.POINTER(C.c_double)]
-    L.sextans_profile_read_post.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    L.sextans_profile_reset.argtypes = [C.c_void_p]
-    L.sextans_phase_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-    L.sextans_last_kernel.restype = C.c_char_p
-    L.sextans_last_kernel.argtypes = [C.c_void_p]
-    L.sextans_gen_csr_host.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                       pi, pi, pf, C.POINTER(C.c_int64)]
-    L.sextans_gen_csr_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64,
-                                         C.c_int, C.c_int, C.POINTER(C.c_void_p),
-                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                         C.POINTER(C.c_int64)]
-    L.sextans_gen_stencil2d_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, pi, pi, pf,
-                                             C.POINTER(C.c_int64)]
-    L.sextans_gen_stencil2d_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                               C.POINTER(C.c_int64)]
-    L.sextans_gen_kkt_host.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, pi, pi, pf, C.POINTER(C.c_int64)]
-    L.sextans_gen_kkt_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_void_p),
-                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    L.sextans_gen_fem3d_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                         pi, pi, pf, C.POINTER(C.c_int64)]
-    L.sextans_gen_fem3d_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
-                                           C.c_int, C.c_int, C.POINTER(C.c_void_p),
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                           C.POINTER(C.c_int64)]
-    L.sextans_gen_powerlaw_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                            pi, pi, pf, C.POINTER(C.c_int64)]
-    L.sextans_gen_powerlaw_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
-                                              C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                              C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-    u16p = np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")
-    L.sextans_set_matrix_bell.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, u16p]
-    L.sextans_set_matrix_bell_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_bell_device.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    if hasattr(raw, "sextans_dist_spmm_bell"):
-        L.sextans_spmm_bell_device2.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                                C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-        L.sextans_dist_spmm_bell.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_float, C.c_void_p,
-                                             C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_gen_bell_banded_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, pi, C.POINTER(C.POINTER(C.c_uint16))]
-    L.sextans_gen_bell_banded_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.POINTER(C.c_void_p),
-                                                 C.POINTER(C.c_void_p)]
-    L.sextans_gen_bell_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint64, pi,
-                                        C.POINTER(C.POINTER(C.c_uint16))]
-    L.sextans_gen_bell_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64,
-                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
-    L.sextans_gen_uniform_bf16_host.argtypes = [u16p, C.c_int64, C.c_uint64]
-    L.sextans_gen_uniform_bf16_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p]
-    L.sextans_gen_uniform_host.argtypes = [_f32p, C.c_int64, C.c_uint64]
-    L.sextans_gen_uniform_device.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.c_uint64,
-                                             C.c_void_p]
-    L.sextans_device_free.argtypes = [C.c_int, C.c_void_p]
-    L.sextans_device_alloc.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
-    L.sextans_device_copy.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    L.sextans_prepare.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.sextans_csr_transpose_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
-    L.sextans_spmm_t_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float,
-                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_sddmm_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float,
-                                          C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_device_rm_bf16.argtypes = L.sextans_spmm_t_device_rm_bf16.argtypes = [
-        C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    L.sextans_prepare_rm_bf16.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.sextans_row_softmax_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_row_softmax_backward_device.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.sextans_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                    C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                                    C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                                    C.c_void_p]
-    L.sextans_gat_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                               C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.sextans_gat_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                                        C.c_void_p]
-    L.sextans_gatv2_workspace_floats.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.sextans_gatv2_workspace_floats.restype = C.c_int64
-    L.sextans_gatv2_attention_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.sextans_gatv2_attention_backward_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                          C.c_void_p, C.c_void_p]
-    dp = C.POINTER(Dropout)
-    for name in ("attention", "gat_attention", "gatv2_attention"):   # the plain entry's arguments with the dropout pointer before the stream
-        for suffix in ("device", "backward_device"):
-            plain = getattr(L, "sextans_%s_%s" % (name, suffix)).argtypes
-            getattr(L, "sextans_%s_dropout_%s" % (name, suffix)).argtypes = plain[:-1] + [dp, C.c_void_p]
-    L.sextans_dropout_mask_device.argtypes = [C.c_void_p, C.c_int, dp, C.c_void_p, C.c_void_p]
-    L.sextans_dropout_keep_host.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p]
-    L.sextans_spmm_reduce_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_spmm_reduce_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                         C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_multi_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiOut), C.c_void_p]
-    L.sextans_spmm_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MultiGrad),
-                                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_softagg_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                                 C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_spmm_softagg_workspace_floats.argtypes = [C.c_void_p, C.c_int]
-    L.sextans_spmm_softagg_workspace_floats.restype = C.c_int64
-    L.sextans_spmm_softagg_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                                          C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_edge_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                              C.c_int64, C.c_void_p]
-    L.sextans_spmm_edge_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    L.sextans_spmm_edge_multi_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                    C.POINTER(MultiOut), C.c_void_p]
-    L.sextans_spmm_edge_multi_backward_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                                             C.POINTER(MultiGrad), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    vp, i64 = C.c_void_p, C.c_int64
-    L.sextans_spmm_gated_device_rm.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.POINTER(GatedIn), vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_spmm_gated_workspace_floats.argtypes = [vp, C.c_int, C.c_int]
-    L.sextans_spmm_gated_workspace_floats.restype = i64
-    L.sextans_spmm_gated_backward_device_rm.argtypes = [vp, C.c_int, C.c_float, C.c_int, C.POINTER(GatedIn), vp, i64, vp, i64, vp, i64, vp, i64,
-                                                        C.POINTER(GatedGrad), vp, vp]
-    L.sextans_spmm_edge_softagg_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp]
-    L.sextans_spmm_edge_softagg_workspace_floats.argtypes = [vp, C.c_int]
-    L.sextans_spmm_edge_softagg_workspace_floats.restype = i64
-    L.sextans_spmm_edge_softagg_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64,
-                                                               vp, i64, vp, vp, vp]
-    L.sextans_vector_attention_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_vector_attention_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
-                                                              vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_edge_op_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_edge_op_backward_device_rm.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    # the bf16 twins take the same frames: only the element type behind the (nnz, N) pointers differs
-    L.sextans_edge_op_device_rm_bf16.argtypes = L.sextans_edge_op_device_rm.argtypes
-    L.sextans_edge_op_backward_device_rm_bf16.argtypes = L.sextans_edge_op_backward_device_rm.argtypes
-    L.sextans_spmm_edge_device_rm_bf16.argtypes = L.sextans_spmm_edge_device_rm.argtypes
-    L.sextans_spmm_edge_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_backward_device_rm.argtypes
-    L.sextans_vector_attention_device_rm_bf16.argtypes = L.sextans_vector_attention_device_rm.argtypes
-    L.sextans_vector_attention_backward_device_rm_bf16.argtypes = L.sextans_vector_attention_backward_device_rm.argtypes
-    L.sextans_spmm_edge_softagg_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_device_rm.argtypes
-    L.sextans_spmm_edge_softagg_backward_device_rm_bf16.argtypes = L.sextans_spmm_edge_softagg_backward_device_rm.argtypes
-    L.sextans_spmm_gated_device_rm_bf16.argtypes = L.sextans_spmm_gated_device_rm.argtypes   # (the structs have the fp32 ones' layouts)
-    L.sextans_spmm_gated_backward_device_rm_bf16.argtypes = L.sextans_spmm_gated_backward_device_rm.argtypes
-    L.sextans_edge_dot_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_edge_dot_backward_device.argtypes = [vp, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp]
-    L.sextans_attention_edge_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
-                                                vp, vp, i64, vp, dp, vp]
-    L.sextans_attention_edge_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_float, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
-                                                         vp, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, dp, vp]
-    L.sextans_score_attention_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, dp, vp]
-    L.sextans_score_attention_backward_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, i64,
-                                                          dp, vp]
-    L.sextans_update_values.argtypes = [C.c_void_p, C.c_void_p]
-    L.sextans_update_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_dist_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.sextans_dist_bind_library.argtypes = [C.c_char_p]
-    _lib = raw
-    return raw
+    _lib = _bind(C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL))
+    return _lib
+
+
+_FORWARD = """def {name}(self, {params}):
+    _check(lib().sextans_{name}(self._h, {args}), "{name}")
+"""
+_COUNT = """def {name}(self, {params}):
+    n = lib().sextans_{name}(self._h, {args})
+    if n < 0:
+        _check(int(-n), "{name}")
+    return int(n)
+"""
+
+
+def _entry(*kinds, result=i):
+    """Declare the Engine method under it as the C entry point sextans_<its name>(handle, <kinds>[, stream]): kinds are the C types of
+    its parameters between self and a trailing `stream`, one each (checked here, at import).  The prototype goes into _PROTOTYPES; the
+    method keeps its def line and docstring and gets its body from a template compiled once, as collections.namedtuple does: the plain
+    forwarding call, a ref(T) parameter passed by address; with result=l, a count whose negative value is the error code."""
+    def declare(fn):
+        names = fn.__code__.co_varnames[1:fn.__code__.co_argcount]
+        streamed = names[-1:] == ("stream",)
+        if len(kinds) != len(names) - streamed:
+            raise TypeError(f"{fn.__name__}: {len(kinds)} C types for {len(names) - streamed} parameters")
+        _PROTOTYPES["sextans_" + fn.__name__] = (result, [p, *kinds] + [p] * streamed)
+        args = [f"C.byref({n}) if {n} is not None else None" if issubclass(k, C._Pointer) else n for n, k in zip(names, kinds)]
+        scope = {}
+        exec((_FORWARD if result is i else _COUNT).format(name=fn.__name__, params=", ".join(names),
+                                                         args=", ".join(args + ["stream"] * streamed)), globals(), scope)
+        new = scope[fn.__name__]
+        new.__defaults__, new.__doc__, new.__qualname__ = fn.__defaults__, fn.__doc__, fn.__qualname__
+        return new
+    return declare
+
+
+def _frame(method):
+    """The kinds of an Engine method declared above, for a twin that takes the same frame."""
+    return _PROTOTYPES["sextans_" + method][1][1:-1]
 
 
 def _check(rc, where):
@@ -759,10 +636,8 @@ class Engine:
 
     def export_row_order(self):
         """(order, kind): order[i] = row at position i of the clustered plan (identity when kind == 0); see include/sextans_amd.h."""
-        L = lib()
-        L.sextans_export_row_order.argtypes = [C.c_void_p, _i32p, C.POINTER(C.c_int)]
         order, kind = np.empty(max(self.M, 1), np.int32), C.c_int()
-        _check(L.sextans_export_row_order(self._h, order, C.byref(kind)), "export_row_order")
+        _check(lib().sextans_export_row_order(self._h, order, C.byref(kind)), "export_row_order")
         return order[:self.M], kind.value
 
     def reassociated_rows(self):
@@ -809,11 +684,11 @@ class Engine:
             raise ValueError("update_values needs one value per stored entry of the matrix that is set")
         _check(lib().sextans_update_values(self._h, v.ctypes.data if v.size else None), "update_values")
 
+    @_entry(p)
     def update_values_device(self, d_val, stream=None):
         """The same for a device array (sextans_update_values_device): it BECOMES the value array of a matrix set with
         set_matrix_csr_device (not copied; may be the pointer as before = changed in place), and is copied into the array of a matrix the
         engine owns.  Enqueued on `stream`; with default options it allocates nothing and does not synchronise (capturable)."""
-        _check(lib().sextans_update_values_device(self._h, d_val, stream), "update_values_device")
 
     def spmm(self, N, alpha, B, beta, C_inout, rp_time=1):
         """Host buffers, C updated in place (cpu_spmm_CSR semantics).  Returns device ns for all
@@ -855,25 +730,26 @@ class Engine:
         self.M, self.K = M, K
         return cout, ns.value
 
+    @_entry(i, f, p, l, f, p, p, l)
     def spmm_device(self, N, alpha, d_B, ldb, beta, d_C_in, d_C_out, ldc, stream=None):
-        _check(lib().sextans_spmm_device(self._h, N, alpha, d_B, ldb, beta, d_C_in, d_C_out, ldc,
-                                         stream), "spmm_device")
+        ...
 
     # ---- blocked-ELL bf16 path (BASELINE config 5)
     def set_matrix_bell(self, M, K, ell_width, block_col, block_val_bf16):
         _check(lib().sextans_set_matrix_bell(self._h, M, K, ell_width, _buf(block_col, np.int32),
                                              _buf(block_val_bf16, np.uint16)), "set_matrix_bell")
 
+    @_entry(i, i, i, p, p)
     def set_matrix_bell_device(self, M, K, ell_width, d_block_col, d_block_val):
-        _check(lib().sextans_set_matrix_bell_device(self._h, M, K, ell_width, d_block_col, d_block_val),
-               "set_matrix_bell_device")
+        ...
 
+    @_entry(i, f, p, l, f, p, p, l)
     def spmm_bell_device(self, N, alpha, d_B_bf16, ldb, beta, d_C_in, d_C_out, ldc, stream=None):
-        _check(lib().sextans_spmm_bell_device(self._h, N, alpha, d_B_bf16, ldb, beta, d_C_in, d_C_out, ldc,
-                                              stream), "spmm_bell_device")
+        ...
 
+    @_entry(i, f, p, l, f, p, l, p, l)
     def spmm_bell_device2(self, N, alpha, d_B_bf16, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, stream=None):
-        _check(lib().sextans_spmm_bell_device2(self._h, N, alpha, d_B_bf16, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, stream), "spmm_bell_device2")
+        ...
 
     def dist_spmm_bell(self, comm, world, rank, ranges, N, alpha, d_B_bf16, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, stream=None):
         """Blocked-ELL over several GPUs (sextans_dist_spmm_bell): this engine holds the block rows of ranges[rank]."""
@@ -881,437 +757,370 @@ class Engine:
         _check(lib().sextans_dist_spmm_bell(self._h, comm, world, rank, rr, N, alpha, d_B_bf16, ldb, beta, d_C_in, ldc_in, d_C_out, ldc, stream),
                "dist_spmm_bell")
 
+    @_entry(i, f, p, l, f, p, l, p, l)
     def spmm_device2(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream=None):
-        _check(lib().sextans_spmm_device2(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out,
-                                          ldc_out, stream), "spmm_device2")
+        ...
 
+    @_entry(i, f, p, l, f, p, l, p, l)
     def spmm_device_rm(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream=None):
         """ROW-major operands (B[k * ldb + n], C[m * ldc + n]): no layout pass on the LDS-panel paths (include/sextans_amd.h)."""
-        _check(lib().sextans_spmm_device_rm(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream),
-               "spmm_device_rm")
 
+    @_entry(i, f, p, l, f, p, l, p, l)
     def spmm_t_device_rm(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream=None):
         """C (K x N) = alpha * A^T * B + beta * C_in, B M x N, all ROW-major; A^T is built once and served by a companion engine with
         this engine's options (sextans_spmm_t_device_rm)."""
-        _check(lib().sextans_spmm_t_device_rm(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, stream),
-               "spmm_t_device_rm")
 
+    @_entry(i, f, p, l, f, p, l, p, l, i)
     def spmm_device_rm_bf16(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype=DTYPE_F32, stream=None):
         """ROW-major operands with B in bf16 and C_in / C_out both fp32 (DTYPE_F32) or bf16 (DTYPE_BF16); ld in elements.  The fp32
         result has the bits of spmm_device_rm on the widened operands; native on the gather path, through fp32 copies elsewhere
         (sextans_spmm_device_rm_bf16; stats "bf16_native_calls" / "bf16_converted_calls")."""
-        _check(lib().sextans_spmm_device_rm_bf16(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype, stream),
-               "spmm_device_rm_bf16")
 
+    @_entry(*_frame("spmm_device_rm_bf16"))
     def spmm_t_device_rm_bf16(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype=DTYPE_F32, stream=None):
         """The same for A^T (B is M x N, C is K x N), on the companion engine of spmm_t_device_rm (sextans_spmm_t_device_rm_bf16)."""
-        _check(lib().sextans_spmm_t_device_rm_bf16(self._h, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, c_dtype, stream),
-               "spmm_t_device_rm_bf16")
 
     def prepare_rm_bf16(self, N, c_dtype, transposed=False, stream=None):
         """Everything a later bf16 call for (N, c_dtype) would build or allocate, built now (sextans_prepare_rm_bf16)."""
         _check(lib().sextans_prepare_rm_bf16(self._h, N, c_dtype, 1 if transposed else 0, stream), "prepare_rm_bf16")
 
+    @_entry(i, f, p, l, p, l, f, p, p)
     def sddmm_device_rm(self, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream=None):
         """vals_out[e] = alpha * sum_n X[r, n] * Y[c, n] (+ beta * vals_in[e]) for every entry e = (r, c) of A, in CSR order, with the
         reference's rounding (sextans_sddmm_device_rm); d_vals_in may be None."""
-        _check(lib().sextans_sddmm_device_rm(self._h, N, alpha, d_X, ldx, d_Y, ldy, beta, d_vals_in, d_vals_out, stream),
-               "sddmm_device_rm")
 
+    @_entry(f, p, p)
     def row_softmax_device(self, scale, d_x, d_p, stream=None):
         """p = softmax(scale * x) over the stored entries of every row of A (sextans_row_softmax_device): nnz floats each, in CSR entry
         order -- what sddmm_device_rm writes and update_values_device reads; d_p may be d_x."""
-        _check(lib().sextans_row_softmax_device(self._h, scale, d_x, d_p, stream), "row_softmax_device")
 
+    @_entry(f, p, p, p)
     def row_softmax_backward_device(self, scale, d_p, d_g, d_dx, stream=None):
         """dx = scale * p * (g - sum_row p g) (sextans_row_softmax_backward_device); d_dx may be d_g or d_p."""
-        _check(lib().sextans_row_softmax_backward_device(self._h, scale, d_p, d_g, d_dx, stream), "row_softmax_backward_device")
 
+    @_entry(i, i, i, f, p, l, p, l, p, l, p, p, l, p)
     def attention_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, stream=None):
         """Fused multi-head attention on A's pattern (sextans_attention_device): O[r, h, :] = softmax_e(scale * (<Q[r, h, :], K[c, h, :]> +
         bias_e)) V[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads floats).  Heads lie side
         by side in a row (a contiguous (rows, heads, d) tensor); d_bias: None, or nnz floats in CSR entry order shared by all heads.  A's
         own values are not read."""
-        _check(lib().sextans_attention_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, stream),
-               "attention_device")
 
+    @_entry(*_frame("attention_device"), p, l, p, p, l, p, l, p, l, p)
     def attention_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta,
                                   d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, stream=None):
         """dQ, dK, dV (and, d_dbias not None, the bias gradient: nnz floats) of attention_device from its O and lse and the upstream
         gradient G (sextans_attention_backward_device); d_delta: M * heads floats of workspace the call writes."""
-        _check(lib().sextans_attention_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
-                                                       d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, stream),
-               "attention_backward_device")
 
+    @_entry(i, i, f, p, l, p, l, p, l, p, p, l, p)
     def gat_attention_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, stream=None):
         """Fused graph attention on A's pattern (sextans_gat_attention_device): O[r, h, :] = softmax_e(LeakyReLU((adst[r, h] + asrc[c, h]) +
         bias_e)) V[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads floats).  adst is
         M x heads, asrc K x heads (ld >= heads), V K x (heads * dv) with the heads side by side; d_bias: None, or nnz floats in CSR entry
         order shared by all heads.  A's own values are not read."""
-        _check(lib().sextans_gat_attention_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo,
-                                                  d_lse, stream), "gat_attention_device")
 
+    @_entry(*_frame("gat_attention_device"), p, l, p, p, l, p, l, p, l, p)
     def gat_attention_backward_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg,
                                       d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, stream=None):
         """dadst, dasrc, dV (and, d_dbias not None, the bias gradient: nnz floats) of gat_attention_device from its O and lse and the
         upstream gradient G (sextans_gat_attention_backward_device); d_delta: M * heads floats of workspace the call writes."""
-        _check(lib().sextans_gat_attention_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias,
-                                                           d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv,
-                                                           d_dbias, stream), "gat_attention_backward_device")
 
+    @_entry(i, i, result=l)
     def gatv2_workspace_floats(self, heads, d):
         """Floats of workspace gatv2_attention_backward_device needs on this matrix (sextans_gatv2_workspace_floats):
         M * heads * d for datt_rows plus ceil(M / 256) * heads * d for the chunk sums."""
-        n = lib().sextans_gatv2_workspace_floats(self._h, heads, d)
-        if n < 0:
-            _check(int(-n), "gatv2_workspace_floats")
-        return int(n)
 
+    @_entry(i, i, f, p, l, p, l, p, p, p, l, p)
     def gatv2_attention_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, stream=None):
         """Fused GATv2 attention on A's pattern (sextans_gatv2_attention_device): O[r, h, :] = softmax_e(<att[h, :], LeakyReLU(x_dst[r, h, :] +
         x_src[c, h, :])> + bias_e) x_src[c, h, :] over the stored entries e = (r, c) of row r, lse[r, h] the row's log-sum-exp (M * heads
         floats).  x_dst is M x (heads * d), x_src K x (heads * d) with the heads side by side, att heads * d floats; d_bias: None, or nnz
         floats in CSR entry order shared by all heads.  A's own values are not read."""
-        _check(lib().sextans_gatv2_attention_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse,
-                                                    stream), "gatv2_attention_device")
 
+    @_entry(*_frame("gatv2_attention_device"), p, l, p, p, l, p, l, p, p, p)
     def gatv2_attention_backward_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G, ldg,
                                         d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias, stream=None):
         """dx_dst, dx_src, datt (heads * d floats, summed over the rows in a fixed two-level order) and, d_dbias not None, the bias gradient
         of gatv2_attention_device from its O and lse and the upstream gradient G (sextans_gatv2_attention_backward_device); d_delta:
         M * heads floats, d_work: gatv2_workspace_floats(heads, d) floats of workspace the call writes (datt_rows, then the chunk sums)."""
-        _check(lib().sextans_gatv2_attention_backward_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo,
-                                                             d_lse, d_G, ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias,
-                                                             stream), "gatv2_attention_backward_device")
 
     # Attention dropout (sextans_*_dropout_device): the entries above with `drop`, a Dropout or None, before the stream.  drop None or
     # drop.p == 0: exactly the entry above.  The backward call takes the Dropout of its forward.
+    @_entry(*_frame("attention_device"), ref(Dropout))
     def attention_dropout_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, drop, stream=None):
-        _check(lib().sextans_attention_dropout_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
-                                                      _drop_ref(drop), stream), "attention_dropout_device")
+        ...
 
+    @_entry(*_frame("attention_backward_device"), ref(Dropout))
     def attention_dropout_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta,
                                           d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, drop, stream=None):
-        _check(lib().sextans_attention_dropout_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_bias, d_O, ldo, d_lse,
-                                                               d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dbias, _drop_ref(drop),
-                                                               stream), "attention_dropout_backward_device")
+        ...
 
+    @_entry(*_frame("gat_attention_device"), ref(Dropout))
     def gat_attention_dropout_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse, drop,
                                      stream=None):
-        _check(lib().sextans_gat_attention_dropout_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O,
-                                                          ldo, d_lse, _drop_ref(drop), stream), "gat_attention_dropout_device")
+        ...
 
+    @_entry(*_frame("gat_attention_backward_device"), ref(Dropout))
     def gat_attention_dropout_backward_device(self, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv, d_bias, d_O, ldo, d_lse,
                                               d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc, d_dV, lddv, d_dbias, drop, stream=None):
-        _check(lib().sextans_gat_attention_dropout_backward_device(self._h, heads, dv, negative_slope, d_adst, ldadst, d_asrc, ldasrc, d_V, ldv,
-                                                                   d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dadst, lddadst, d_dasrc, lddasrc,
-                                                                   d_dV, lddv, d_dbias, _drop_ref(drop), stream),
-               "gat_attention_dropout_backward_device")
+        ...
 
+    @_entry(*_frame("gatv2_attention_device"), ref(Dropout))
     def gatv2_attention_dropout_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, drop,
                                        stream=None):
-        _check(lib().sextans_gatv2_attention_dropout_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo,
-                                                            d_lse, _drop_ref(drop), stream), "gatv2_attention_dropout_device")
+        ...
 
+    @_entry(*_frame("gatv2_attention_backward_device"), ref(Dropout))
     def gatv2_attention_dropout_backward_device(self, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias, d_O, ldo, d_lse, d_G,
                                                 ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt, d_work, d_dbias, drop, stream=None):
-        _check(lib().sextans_gatv2_attention_dropout_backward_device(self._h, heads, d, negative_slope, d_xdst, ldxd, d_xsrc, ldxs, d_att, d_bias,
-                                                                     d_O, ldo, d_lse, d_G, ldg, d_delta, d_dxdst, lddxd, d_dxsrc, lddxs, d_datt,
-                                                                     d_work, d_dbias, _drop_ref(drop), stream),
-               "gatv2_attention_dropout_backward_device")
+        ...
 
+    @_entry(i, ref(Dropout), p)
     def dropout_mask_device(self, heads, drop, d_mult, stream=None):
         """The nnz * heads dropout multipliers of this matrix, [e * heads + h]: 1 / (1 - p) where (entry, head) is kept, 0 where it is
         dropped (sextans_dropout_mask_device) -- what the fused dropout kernels recompute."""
-        _check(lib().sextans_dropout_mask_device(self._h, heads, _drop_ref(drop), d_mult, stream), "dropout_mask_device")
 
+    @_entry(i, i, p, p, l, p, l, p, l)
     def spmm_reduce_device_rm(self, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream=None):
         """Max / min aggregation (sextans_spmm_reduce_device_rm): C[r, n] = max (REDUCE_MAX) or min (REDUCE_MIN) over row r's stored
         entries e = (r, c) of d_val[e] * B[c, n], arg[r, n] (int32; d_arg None: not written) the winning entry's position in the CSR
         arrays -- first of equal products, first NaN; an empty row gives +0 and -1.  d_val: nnz floats in entry order, None = the
         engine's current values.  B, C and arg row-major, N % 8 == 0."""
-        _check(lib().sextans_spmm_reduce_device_rm(self._h, op, N, d_val, d_B, ldb, d_C, ldc, d_arg, ldarg, stream), "spmm_reduce_device_rm")
 
+    @_entry(i, p, p, l, p, l, p, l, p, l, p)
     def spmm_reduce_backward_device_rm(self, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream=None):
         """dB (K x N) and dval (nnz floats) of spmm_reduce_device_rm from its arg and the upstream gradient G
         (sextans_spmm_reduce_backward_device_rm): every position's gradient goes to the entry that won it.  d_dB or d_dval may be
         None (not both); d_B may be None when d_dval is."""
-        _check(lib().sextans_spmm_reduce_backward_device_rm(self._h, N, d_val, d_B, ldb, d_arg, ldarg, d_G, ldg, d_dB, lddb, d_dval, stream),
-               "spmm_reduce_backward_device_rm")
 
+    @_entry(i, p, p, l, ref(MultiOut))
     def spmm_multi_device_rm(self, N, d_val, d_B, ldb, out, stream=None):
         """Several aggregations of the messages d_val[e] * B[c, n] in one pass (sextans_spmm_multi_device_rm): out is a MultiOut whose
         given addresses receive the sum, the sum of squares, the max and the min over every row's entries (and the int32 args of the
         extrema, with the bits of spmm_reduce_device_rm); an empty row gives +0 and -1.  d_val None = the engine's current values."""
-        _check(lib().sextans_spmm_multi_device_rm(self._h, N, d_val, d_B, ldb, C.byref(out) if out is not None else None, stream),
-               "spmm_multi_device_rm")
 
+    @_entry(i, p, p, l, ref(MultiGrad), p, l, p)
     def spmm_multi_backward_device_rm(self, N, d_val, d_B, ldb, g, d_dB, lddb, d_dval, stream=None):
         """dB (K x N) and dval (nnz floats) of spmm_multi_device_rm from the upstream gradients and the args in g, a MultiGrad
         (sextans_spmm_multi_backward_device_rm): one column pass over A^T, one row pass over A.  d_dB or d_dval may be None (not both);
         d_B may be None when neither g.d_gsumsq nor d_dval is given."""
-        _check(lib().sextans_spmm_multi_backward_device_rm(self._h, N, d_val, d_B, ldb, C.byref(g) if g is not None else None, d_dB, lddb,
-                                                           d_dval, stream), "spmm_multi_backward_device_rm")
 
+    @_entry(i, p, p, l, p, p, l, p, l)
     def spmm_softagg_device_rm(self, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, stream=None):
         """Softmax aggregation (sextans_spmm_softagg_device_rm): C[r, n] = sum over row r's stored entries e = (r, c) of
         softmax_e(t[n] * p_e[n]) * p_e[n], p_e[n] = d_val[e] * B[c, n] -- a softmax per column over the row's messages; lse[r, n] its
         log-sum-exp (d_lse None: not written).  d_t: N floats, None = 1; d_val None = the engine's current values.  An empty row gives +0
         and -inf.  B, C and lse row-major, N % 8 == 0."""
-        _check(lib().sextans_spmm_softagg_device_rm(self._h, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, stream), "spmm_softagg_device_rm")
 
+    @_entry(i, result=l)
     def spmm_softagg_workspace_floats(self, N):
         """Floats of workspace spmm_softagg_backward_device_rm needs for dt on this matrix (sextans_spmm_softagg_workspace_floats):
         M * N for the rows' sums plus ceil(M / 256) * N for the chunk sums."""
-        n = lib().sextans_spmm_softagg_workspace_floats(self._h, N)
-        if n < 0:
-            _check(int(-n), "spmm_softagg_workspace_floats")
-        return int(n)
 
+    @_entry(*_frame("spmm_softagg_device_rm"), p, l, p, l, p, p, p)
     def spmm_softagg_backward_device_rm(self, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dval, d_dt, d_work,
                                         stream=None):
         """dB (K x N), dval (nnz floats) and dt (N floats, summed over the rows in a fixed two-level order) of spmm_softagg_device_rm from
         its C and lse and the upstream gradient G (sextans_spmm_softagg_backward_device_rm).  Any of d_dB, d_dval, d_dt may be None (not
         all three); d_dt needs d_work, spmm_softagg_workspace_floats(N) floats the call writes."""
-        _check(lib().sextans_spmm_softagg_backward_device_rm(self._h, N, d_val, d_B, ldb, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb,
-                                                             d_dval, d_dt, d_work, stream), "spmm_softagg_backward_device_rm")
 
+    @_entry(i, i, p, l, p, l, p, l)
     def spmm_edge_device_rm(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
         """SpMM with a feature vector per stored entry (sextans_spmm_edge_device_rm): C[r, n] = sum over row r's entries e = (r, c) of
         B[c, n] * E[e, n] (EDGE_MUL), B + E (EDGE_ADD), relu(B + E) (EDGE_ADD_RELU) or E[e, n] (EDGE_COPY: d_B may be None).  Only the
         pattern is used; E is (nnz, N) row-major in the CSR entry order.  B, E and C row-major, N % 8 == 0; an empty row gives +0."""
-        _check(lib().sextans_spmm_edge_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream), "spmm_edge_device_rm")
 
+    @_entry(i, i, p, l, p, l, p, l, p, l, p, l)
     def spmm_edge_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream=None):
         """dB (K x N) and dE (nnz x N) of spmm_edge_device_rm from the upstream gradient G (sextans_spmm_edge_backward_device_rm): a
         column pass over A^T and a row pass over A, no atomics.  d_dB or d_dE may be None (not both; d_dB must be None with EDGE_COPY);
         d_B / d_E may be None where the op's gradient does not read them."""
-        _check(lib().sextans_spmm_edge_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
-               "spmm_edge_backward_device_rm")
 
+    @_entry(*_frame("spmm_edge_device_rm"))
     def spmm_edge_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream=None):
         """spmm_edge_device_rm with E in bf16 (sextans_spmm_edge_device_rm_bf16): B and C fp32, E widened exactly -- the bits of
         spmm_edge_device_rm on the widened E.  lde counts bf16 elements (a multiple of 4)."""
-        _check(lib().sextans_spmm_edge_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_C, ldc, stream), "spmm_edge_device_rm_bf16")
 
+    @_entry(*_frame("spmm_edge_backward_device_rm"))
     def spmm_edge_backward_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream=None):
         """spmm_edge_backward_device_rm with E and dE in bf16 (sextans_spmm_edge_backward_device_rm_bf16): B, G and dB fp32; dB the bits
         of spmm_edge_backward_device_rm on the widened E, dE its dE rounded once to nearest even.  lde and ldde count bf16 elements."""
-        _check(lib().sextans_spmm_edge_backward_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_G, ldg, d_dB, lddb, d_dE, ldde, stream),
-               "spmm_edge_backward_device_rm_bf16")
 
+    @_entry(i, i, p, l, p, l, p, p, l, p, l)
     def spmm_edge_softagg_device_rm(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream=None):
         """Softmax aggregation of edge-feature messages (sextans_spmm_edge_softagg_device_rm): C[r, n] = sum over row r's stored entries
         e = (r, c) of softmax_e(t[n] * m_e[n]) * m_e[n], with the message m_e of spmm_edge_device_rm (B[c, n] * E[e, n], B + E, relu(B + E)
         or E[e, n] by op: EDGE_*; d_B may be None with EDGE_COPY) and the softmax per output column of spmm_softagg_device_rm; d_lse (may
         be None) gets log sum_e exp(t[n] m_e[n]).  Only A's pattern is read.  d_t: N temperatures, or None for 1.  An empty row: 0 and
         -inf.  N: a multiple of 8."""
-        _check(lib().sextans_spmm_edge_softagg_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream),
-               "spmm_edge_softagg_device_rm")
 
+    @_entry(i, result=l)
     def spmm_edge_softagg_workspace_floats(self, N):
         """Floats of workspace spmm_edge_softagg_backward_device_rm needs for dt on this matrix
         (sextans_spmm_edge_softagg_workspace_floats): M * N + ceil(M / 256) * N."""
-        n = lib().sextans_spmm_edge_softagg_workspace_floats(self._h, N)
-        if n < 0:
-            _check(int(-n), "spmm_edge_softagg_workspace_floats")
-        return int(n)
 
+    @_entry(*_frame("spmm_edge_softagg_device_rm"), p, l, p, l, p, l, p, p)
     def spmm_edge_softagg_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dE, ldde,
                                              d_dt, d_work, stream=None):
         """dB (K x N), dE (nnz x N) and dt (N floats, summed over the rows in a fixed two-level order) of spmm_edge_softagg_device_rm from
         its C and lse and the upstream gradient G (sextans_spmm_edge_softagg_backward_device_rm): a column pass over A^T for dB, a row pass
         over A that stores dE and the rows' share of dt, no atomics.  Any of d_dB, d_dE, d_dt may be None (not all three; d_dB must be
         with EDGE_COPY); d_dt needs d_work, spmm_edge_softagg_workspace_floats(N) floats the call writes."""
-        _check(lib().sextans_spmm_edge_softagg_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg,
-                                                                  d_dB, lddb, d_dE, ldde, d_dt, d_work, stream),
-               "spmm_edge_softagg_backward_device_rm")
 
+    @_entry(i, i, p, l, p, l, p, l, p, l, p, l)
     def vector_attention_device_rm(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream=None):
         """Channel-wise attention from per-channel scores (sextans_vector_attention_device_rm): C[r, n] = sum over row r's stored entries
         e = (r, c) of softmax_e(S[e, n]) * m_e[n], a softmax per output column over the row's scores, which are READ from the (nnz, N)
         tensor S in A's entry order; the message m_e is V[c, n] (VATT_NODE), V[c, n] + D[e, n] (VATT_ADD) or D[e, n] (VATT_EDGE); the
         operand a mode does not read is ignored and may be None.  d_lse (may be None) gets log sum_e exp(S[e, n]).  Only A's pattern is
         read.  A score of -inf masks its (entry, column).  An empty row: 0 and -inf.  N: a multiple of 8."""
-        _check(lib().sextans_vector_attention_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream),
-               "vector_attention_device_rm")
 
+    @_entry(*_frame("vector_attention_device_rm"), p, l, p, l, p, l, p, l)
     def vector_attention_backward_device_rm(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dS, ldds, d_dV,
                                             lddv, d_dD, lddd, stream=None):
         """dS (nnz x N), dV (K x N) and dD (nnz x N) of vector_attention_device_rm from its C and lse and the upstream gradient G
         (sextans_vector_attention_backward_device_rm): a row pass over A that stores dS and dD when either is given, a column pass over
         A^T for dV when it is given, no atomics.  Any of the three may be None, not all; d_dV must be None with VATT_EDGE, d_dD with
         VATT_NODE."""
-        _check(lib().sextans_vector_attention_backward_device_rm(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg,
-                                                                 d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
-               "vector_attention_backward_device_rm")
 
+    @_entry(*_frame("vector_attention_device_rm"))
     def vector_attention_device_rm_bf16(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream=None):
         """vector_attention_device_rm with S and D in bf16 (sextans_vector_attention_device_rm_bf16): V, C and lse fp32, S and D widened
         exactly (a bf16 -inf score still masks) -- the bits of vector_attention_device_rm on the widened S and D.  lds and ldd count bf16
         elements (multiples of 4)."""
-        _check(lib().sextans_vector_attention_device_rm_bf16(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, stream),
-               "vector_attention_device_rm_bf16")
 
+    @_entry(*_frame("vector_attention_backward_device_rm"))
     def vector_attention_backward_device_rm_bf16(self, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dS, ldds,
                                                  d_dV, lddv, d_dD, lddd, stream=None):
         """vector_attention_backward_device_rm with S, D, dS and dD in bf16 (sextans_vector_attention_backward_device_rm_bf16): V, C, lse,
         G and dV fp32; dV the bits of vector_attention_backward_device_rm on the widened S and D, dS and dD its dS and dD rounded once to
         nearest even.  lds, ldd, ldds and lddd count bf16 elements."""
-        _check(lib().sextans_vector_attention_backward_device_rm_bf16(self._h, msg, N, d_S, lds, d_V, ldv, d_D, ldd, d_C, ldc, d_lse, ldlse,
-                                                                      d_G, ldg, d_dS, ldds, d_dV, lddv, d_dD, lddd, stream),
-               "vector_attention_backward_device_rm_bf16")
 
+    @_entry(*_frame("spmm_edge_softagg_device_rm"))
     def spmm_edge_softagg_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream=None):
         """spmm_edge_softagg_device_rm with E in bf16 (sextans_spmm_edge_softagg_device_rm_bf16): B, t, C and lse fp32, E widened exactly
         -- the bits of spmm_edge_softagg_device_rm on the widened E.  lde counts bf16 elements (a multiple of 4)."""
-        _check(lib().sextans_spmm_edge_softagg_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, stream),
-               "spmm_edge_softagg_device_rm_bf16")
 
+    @_entry(*_frame("spmm_edge_softagg_backward_device_rm"))
     def spmm_edge_softagg_backward_device_rm_bf16(self, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G, ldg, d_dB, lddb, d_dE,
                                                   ldde, d_dt, d_work, stream=None):
         """spmm_edge_softagg_backward_device_rm with E and dE in bf16 (sextans_spmm_edge_softagg_backward_device_rm_bf16): everything else
         fp32, the workspace that of spmm_edge_softagg_workspace_floats(N); dB and dt the bits of spmm_edge_softagg_backward_device_rm on
         the widened E, dE its dE rounded once to nearest even.  lde and ldde count bf16 elements."""
-        _check(lib().sextans_spmm_edge_softagg_backward_device_rm_bf16(self._h, op, N, d_B, ldb, d_E, lde, d_t, d_C, ldc, d_lse, ldlse, d_G,
-                                                                       ldg, d_dB, lddb, d_dE, ldde, d_dt, d_work, stream),
-               "spmm_edge_softagg_backward_device_rm_bf16")
 
+    @_entry(i, i, p, l, p, l, p, l, p, l)
     def edge_op_device_rm(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream=None):
         """Edge-output op from both endpoints (sextans_edge_op_device_rm): for every stored entry e = (r, c), in the CSR entry order,
         Z[e, n] = xdst[r, n] + / - / * xsrc[c, n] (EDGEOP_ADD / EDGEOP_SUB / EDGEOP_MUL), xdst[r, n] (EDGEOP_DST) or xsrc[c, n]
         (EDGEOP_SRC), one rounded fp32 operation, plus E[e, n] (a second rounded add) when d_E is given.  The operand an op does not read
         is ignored and may be None.  Only A's pattern is read.  N: a multiple of 8."""
-        _check(lib().sextans_edge_op_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream), "edge_op_device_rm")
 
+    @_entry(i, i, p, l, p, l, p, l, p, l, p, l)
     def edge_op_backward_device_rm(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc, lddxsrc, stream=None):
         """dxdst (M x N) and dxsrc (K x N) of edge_op_device_rm from the upstream gradient Gz of Z (sextans_edge_op_backward_device_rm):
         a sum over every row's entries and the same pass over A^T's rows, no atomics; dE is Gz itself.  Either may be None (not both;
         d_dxdst must be None with EDGEOP_SRC, d_dxsrc with EDGEOP_DST): its pass is skipped, and without d_dxsrc A^T is never built.
         xsrc is read only for EDGEOP_MUL's dxdst, xdst only for EDGEOP_MUL's dxsrc."""
-        _check(lib().sextans_edge_op_backward_device_rm(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc,
-                                                        lddxsrc, stream), "edge_op_backward_device_rm")
 
+    @_entry(*_frame("edge_op_device_rm"))
     def edge_op_device_rm_bf16(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream=None):
         """edge_op_device_rm with E (optional) and Z in bf16 (sextans_edge_op_device_rm_bf16): xdst and xsrc fp32, E widened exactly, the
         same fp32 operations, Z rounded once to nearest even -- round_bf16 of edge_op_device_rm's Z on the widened E.  lde and ldz count
         bf16 elements (multiples of 4)."""
-        _check(lib().sextans_edge_op_device_rm_bf16(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_E, lde, d_Z, ldz, stream),
-               "edge_op_device_rm_bf16")
 
+    @_entry(*_frame("edge_op_backward_device_rm"))
     def edge_op_backward_device_rm_bf16(self, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst, d_dxsrc, lddxsrc,
                                         stream=None):
         """edge_op_backward_device_rm with Gz in bf16 (sextans_edge_op_backward_device_rm_bf16): dxdst and dxsrc fp32, the bits of
         edge_op_backward_device_rm on the widened Gz.  ldgz counts bf16 elements (a multiple of 4)."""
-        _check(lib().sextans_edge_op_backward_device_rm_bf16(self._h, op, N, d_xdst, ldxdst, d_xsrc, ldxsrc, d_Gz, ldgz, d_dxdst, lddxdst,
-                                                             d_dxsrc, lddxsrc, stream), "edge_op_backward_device_rm_bf16")
 
+    @_entry(i, i, p, l, p, l, p, l)
     def edge_dot_device(self, heads, d, d_X, ldx, d_Y, ldy, d_S, lds, stream=None):
         """Per-head dot product of both endpoints (sextans_edge_dot_device, DGL's u_dot_v): for every stored entry e = (r, c), in the CSR
         entry order, and every head h, S[e * lds + h] = sum_n X[r, h, n] * Y[c, h, n], every product and sum rounded to fp32 in column
         order (sddmm_device_rm's bits on the head's slice), all heads in one launch dealt by non-zeros.  X is M x heads*d, Y K x heads*d
         (score_attention_device's operands), d a multiple of 8 in [8, 128].  Only A's pattern is read."""
-        _check(lib().sextans_edge_dot_device(self._h, heads, d, d_X, ldx, d_Y, ldy, d_S, lds, stream), "edge_dot_device")
 
+    @_entry(i, i, p, l, p, l, p, l, p, l, p, l)
     def edge_dot_backward_device(self, heads, d, d_X, ldx, d_Y, ldy, d_Gs, ldgs, d_dX, lddx, d_dY, lddy, stream=None):
         """dX (M x heads*d) and dY (K x heads*d) of edge_dot_device from the upstream gradient Gs of S (sextans_edge_dot_backward_device):
         score_attention_device(SCORE_WEIGHT)'s O with S := Gs, V := Y, and score_attention_backward_device(SCORE_WEIGHT)'s dV with S := Gs,
         G := X, no atomics.  Either may be None (not both): its pass is skipped, and without d_dY A^T is never built.  X is read only
         for dY, Y only for dX."""
-        _check(lib().sextans_edge_dot_backward_device(self._h, heads, d, d_X, ldx, d_Y, ldy, d_Gs, ldgs, d_dX, lddx, d_dY, lddy, stream),
-               "edge_dot_backward_device")
 
+    @_entry(i, f, i, ref(GatedIn), p, l, p, l, p, l)
     def spmm_gated_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """Gated aggregation (sextans_spmm_gated_device_rm): for the stored entry e = (r, c), z_e = (xdst[r] + xsrc[c]) + E[e] and
         g_e = sigmoid(z_e) per column; C[r] = sum_e g_e * V[c] (GATE_SUM) or that sum / (sum_e g_e + eps) (GATE_NORM).  gin: a GatedIn
         (d_e None: no edge features).  d_den (M x N; the gates' sums) and d_z (nnz x N in the CSR entry order; the new edge features)
         may be None.  Only the pattern is used; everything row-major, N % 8 == 0; an empty row gives +0."""
-        _check(lib().sextans_spmm_gated_device_rm(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den, ldden,
-                                                  d_z, ldz, stream), "spmm_gated_device_rm")
 
+    @_entry(i, i, result=l)
     def spmm_gated_workspace_floats(self, mode, N):
         """Floats of workspace spmm_gated_backward_device_rm needs on this matrix (sextans_spmm_gated_workspace_floats): M * N in
         GATE_NORM mode (gn = G / (den + eps)), 0 in GATE_SUM mode."""
-        n = lib().sextans_spmm_gated_workspace_floats(self._h, mode, N)
-        if n < 0:
-            _check(int(-n), "spmm_gated_workspace_floats")
-        return int(n)
 
+    @_entry(i, f, i, ref(GatedIn), p, l, p, l, p, l, p, l, ref(GatedGrad), p)
     def spmm_gated_backward_device_rm(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_G, ldg, d_Gz, ldgz, out, d_work, stream=None):
         """The gradients of spmm_gated_device_rm named in out, a GatedGrad (sextans_spmm_gated_backward_device_rm): dxdst (M x N) and dE
         (nnz x N) from a row pass over A, dxsrc and dV (K x N) from a column pass over A^T; the gates are recomputed, no atomics.  d_G is
         the upstream gradient of C, d_Gz (None: absent) that of z.  d_C and d_den: the forward's, needed in GATE_NORM mode only, as is
         d_work, spmm_gated_workspace_floats(mode, N) floats the call writes."""
-        _check(lib().sextans_spmm_gated_backward_device_rm(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den,
-                                                           ldden, d_G, ldg, d_Gz, ldgz, C.byref(out) if out is not None else None, d_work,
-                                                           stream), "spmm_gated_backward_device_rm")
 
+    @_entry(*_frame("spmm_gated_device_rm"))
     def spmm_gated_device_rm_bf16(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_z, ldz, stream=None):
         """spmm_gated_device_rm with E and z in bf16 (sextans_spmm_gated_device_rm_bf16): gin a GatedIn whose d_e addresses bf16 (the
         struct's layout serves both), xdst, xsrc, V, C and den fp32.  E is widened exactly and the gate taken from the unrounded z -- C
         and den are the bits of spmm_gated_device_rm on the widened E, z its z rounded once to nearest even.  ld_e and ldz count bf16
         elements (multiples of 4)."""
-        _check(lib().sextans_spmm_gated_device_rm_bf16(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc, d_den,
-                                                       ldden, d_z, ldz, stream), "spmm_gated_device_rm_bf16")
 
+    @_entry(*_frame("spmm_gated_backward_device_rm"))
     def spmm_gated_backward_device_rm_bf16(self, mode, eps, N, gin, d_C, ldc, d_den, ldden, d_G, ldg, d_Gz, ldgz, out, d_work, stream=None):
         """spmm_gated_backward_device_rm with E, Gz and dE in bf16 (sextans_spmm_gated_backward_device_rm_bf16): gin a GatedIn and out a
         GatedGrad whose d_e / d_de address bf16; everything else fp32, the workspace that of spmm_gated_workspace_floats(mode, N).  dxdst,
         dxsrc and dV are the bits of spmm_gated_backward_device_rm on the widened E and Gz, dE its dE rounded once to nearest even.  ld_e,
         ldgz and ld_de count bf16 elements."""
-        _check(lib().sextans_spmm_gated_backward_device_rm_bf16(self._h, mode, eps, N, C.byref(gin) if gin is not None else None, d_C, ldc,
-                                                                d_den, ldden, d_G, ldg, d_Gz, ldgz, C.byref(out) if out is not None else None,
-                                                                d_work, stream), "spmm_gated_backward_device_rm_bf16")
 
+    @_entry(i, i, p, l, p, l, ref(MultiOut))
     def spmm_edge_multi_device_rm(self, op, N, d_B, ldb, d_E, lde, out, stream=None):
         """Several aggregations of edge-feature messages in one pass (sextans_spmm_edge_multi_device_rm): the message of the stored entry
         e = (r, c) is that of spmm_edge_device_rm (B[c, n] * E[e, n], B + E, relu(B + E) or E[e, n] by op: EDGE_*; d_B may be None with
         EDGE_COPY); out is a MultiOut whose given addresses receive the sum, the sum of squares, the max and the min over every row's
         entries and the int32 entry positions of the extrema; an empty row gives +0 and -1.  Only the pattern is used."""
-        _check(lib().sextans_spmm_edge_multi_device_rm(self._h, op, N, d_B, ldb, d_E, lde, C.byref(out) if out is not None else None, stream),
-               "spmm_edge_multi_device_rm")
 
+    @_entry(i, i, p, l, p, l, ref(MultiGrad), p, l, p, l)
     def spmm_edge_multi_backward_device_rm(self, op, N, d_B, ldb, d_E, lde, g, d_dB, lddb, d_dE, ldde, stream=None):
         """dB (K x N) and dE (nnz x N) of spmm_edge_multi_device_rm from the upstream gradients and the args in g, a MultiGrad
         (sextans_spmm_edge_multi_backward_device_rm): a column pass over A^T and a row pass over A, no atomics.  d_dB or d_dE may be None
         (not both; d_dB must be None with EDGE_COPY); d_E is always needed, d_B unless EDGE_COPY."""
-        _check(lib().sextans_spmm_edge_multi_backward_device_rm(self._h, op, N, d_B, ldb, d_E, lde, C.byref(g) if g is not None else None,
-                                                                d_dB, lddb, d_dE, ldde, stream), "spmm_edge_multi_backward_device_rm")
 
+    @_entry(i, i, i, f, p, l, p, l, p, l, p, l, p, l, p, p, l, p, ref(Dropout))
     def attention_edge_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias, d_O, ldo, d_lse,
                               drop=None, stream=None):
         """Fused attention with a feature vector per stored entry on the key and on the value side (sextans_attention_edge_device):
         s_e = scale * (<Q[r, h, :], K[c, h, :] + Ek[e, h, :]> + bias_e), O[r, h, :] = sum_e softmax_e(s) (V[c, h, :] + Ev[e, h, :]).
         Ek is (nnz, heads * d), Ev (nnz, heads * dv), row-major in the CSR entry order; either may be None (no edge term on that side;
         both None: attention_dropout_device).  drop: a Dropout or None."""
-        _check(lib().sextans_attention_edge_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias,
-                                                   d_O, ldo, d_lse, _drop_ref(drop), stream), "attention_edge_device")
 
+    @_entry(i, i, i, f, p, l, p, l, p, l, p, l, p, l, p, p, l, p, p, l, p, p, l, p, l, p, l, p, l, p, l, p, ref(Dropout))
     def attention_edge_backward_device(self, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev, d_bias, d_O, ldo, d_lse,
                                        d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv, d_dEk, lddek, d_dEv, lddev, d_dbias,
                                        drop=None, stream=None):
         """dQ, dK, dV, dEk (nnz x heads * d), dEv (nnz x heads * dv) and, d_dbias not None, the bias gradient of attention_edge_device
         from its O and lse and the upstream gradient G (sextans_attention_edge_backward_device).  d_dEk / d_dEv may each be None; the
         same address for both (both E given, d == dv, lddek == lddev) stores the sum dEk + dEv once.  drop: the Dropout of the forward."""
-        _check(lib().sextans_attention_edge_backward_device(self._h, heads, d, dv, scale, d_Q, ldq, d_K, ldk, d_V, ldv, d_Ek, ldek, d_Ev, ldev,
-                                                            d_bias, d_O, ldo, d_lse, d_G, ldg, d_delta, d_dQ, lddq, d_dK, lddk, d_dV, lddv,
-                                                            d_dEk, lddek, d_dEv, lddev, d_dbias, _drop_ref(drop), stream),
-               "attention_edge_backward_device")
 
+    @_entry(i, i, i, p, l, p, l, p, l, p, ref(Dropout))
     def score_attention_device(self, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, drop=None, stream=None):
         """Attention from caller-supplied scores (sextans_score_attention_device).  S is (nnz, heads), element (e, h) at S[e * lds + h], in the
         CSR entry order.  SCORE_SOFTMAX: O[r, h, :] = sum_e softmax_e(S[:, h] over row r) V[c, h, :] and lse (M x heads);
         SCORE_WEIGHT: O[r, h, :] = sum_e S[e, h] V[c, h, :] (d_lse is not touched and may be None).  drop: a Dropout or None (SOFTMAX only)."""
-        _check(lib().sextans_score_attention_device(self._h, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, _drop_ref(drop), stream),
-               "score_attention_device")
 
+    @_entry(i, i, i, p, l, p, l, p, l, p, p, l, p, l, p, l, ref(Dropout))
     def score_attention_backward_device(self, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, d_G, ldg, d_dS, ldds, d_dV, lddv,
                                         drop=None, stream=None):
         """dS (nnz x heads, element (e, h) at dS[e * ldds + h]: one plain store each) and dV of score_attention_device from the upstream
         gradient G -- SCORE_SOFTMAX: and its O and lse; SCORE_WEIGHT: d_O and d_lse are not read and may be None
         (sextans_score_attention_backward_device).  d_dS or d_dV may be None (not both): that pass is skipped.  drop: the forward's."""
-        _check(lib().sextans_score_attention_backward_device(self._h, mode, heads, dv, d_S, lds, d_V, ldv, d_O, ldo, d_lse, d_G, ldg, d_dS, ldds,
-                                                             d_dV, lddv, _drop_ref(drop), stream), "score_attention_backward_device")
 
     def spmm_device_rows(self, N, alpha, d_B, ldb, beta, d_C_in, ldc_in, d_C_out, ldc_out, row_begin, row_end,
                          reuse_b_panels=False, stream=None):
@@ -1336,8 +1145,9 @@ class Engine:
         _check(lib().sextans_phase_timing_read(self._h, out), "phase_timing_read")
         return list(out)
 
+    @_entry()
     def profile_reset(self):
-        _check(lib().sextans_profile_reset(self._h), "profile_reset")
+        ...
 
     def last_kernel(self):
         return lib().sextans_last_kernel(self._h).decode()
@@ -1433,8 +1243,6 @@ def permute_symmetric_device(device, M, nnz, d_rp, d_ci, d_v, new_of_old):
     p, i, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
     no = np.ascontiguousarray(new_of_old, np.int32)
     L = lib()
-    L.sextans_csr_permute_symmetric_device.argtypes = [C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     _check(L.sextans_csr_permute_symmetric_device(device, M, nnz, d_rp, d_ci, d_v, no.ctypes.data, C.byref(p), C.byref(i), C.byref(v)),
            "csr_permute_symmetric_device")
     return p.value, i.value, v.value
@@ -1444,7 +1252,6 @@ def slice_rows_device(device, r0, r1, d_rp, d_ci, d_v):
     """Rows [r0, r1) of a device CSR matrix as (rp, ci, v, nnz): rp is a new device array (device_free), ci / v point INTO the originals."""
     p, first, nnz = C.c_void_p(), C.c_int64(), C.c_int64()
     L = lib()
-    L.sextans_csr_slice_rows_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _check(L.sextans_csr_slice_rows_device(device, r0, r1, d_rp, C.byref(p), C.byref(first), C.byref(nnz)), "csr_slice_rows_device")
     return p.value, d_ci + 4 * first.value, d_v + 4 * first.value, nnz.value
 
@@ -1508,9 +1315,6 @@ def gen_kron_host(n, p_rp, p_ci, pk, variant, seed, r0=0, r1=None):
     p_rp = np.ascontiguousarray(p_rp, np.int32); p_ci = np.ascontiguousarray(p_ci, np.int32)
     pm = len(p_rp) - 1
     r1 = n * pm if r1 is None else r1
-    L.sextans_gen_kron_host.argtypes = [C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                        C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.POINTER(C.c_float)),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int)]
     p, i, v = C.POINTER(C.c_int)(), C.POINTER(C.c_int)(), C.POINTER(C.c_float)()
     nnz, K = C.c_int64(), C.c_int()
     _check(L.sextans_gen_kron_host(n, pm, pk, p_rp, p_ci, variant, seed, r0, r1, C.byref(p), C.byref(i), C.byref(v), C.byref(nnz),
@@ -1527,9 +1331,6 @@ def gen_kron_device(device, n, p_rp, p_ci, pk, variant, seed, r0=0, r1=None):
     p_rp = np.ascontiguousarray(p_rp, np.int32); p_ci = np.ascontiguousarray(p_ci, np.int32)
     pm = len(p_rp) - 1
     r1 = n * pm if r1 is None else r1
-    L.sextans_gen_kron_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_uint64, C.c_int, C.c_int,
-                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                                          C.POINTER(C.c_int)]
     p, i, v = C.c_void_p(), C.c_void_p(), C.c_void_p()
     nnz, K = C.c_int64(), C.c_int()
     _check(L.sextans_gen_kron_device(device, n, pm, pk, p_rp, p_ci, variant, seed, r0, r1, C.byref(p), C.byref(i), C.byref(v),
@@ -1654,3 +1455,7 @@ def csr_transpose_device(device, M, K, nnz, d_rp, d_ci, d_v, stream=None):
 
 def device_free(device, d_ptr):
     _check(lib().sextans_device_free(device, d_ptr), "device_free")
+
+
+# Every entry point added after round 4 -- the only ones an OLDER build may lack.  Derived: a new entry point is optional with no further edit.
+_OPTIONAL_SYMBOLS = frozenset(_PROTOTYPES) - _ROUND4_SYMBOLS

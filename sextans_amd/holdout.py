@@ -74,6 +74,5 @@ def write_mtx(path, rp, ci, v, M, K):
     """Matrix-Market `real general` file of a host CSR matrix (sextans_mtx_write: %.9g keeps every fp32 value exactly)."""
     import ctypes as C
     L = api.lib()
-    L.sextans_mtx_write.argtypes = [C.c_char_p, C.c_int, C.c_int, api._i32p, api._i32p, api._f32p]
     api._check(L.sextans_mtx_write(path.encode(), M, K, np.ascontiguousarray(rp, np.int32), np.ascontiguousarray(ci, np.int32),
                                    np.ascontiguousarray(v, np.float32)), "mtx_write")

@@ -28,19 +28,6 @@ PARENT_LIB = os.path.join(ROOT, "tools", "bin", "libsextans_parent.so")
 ROUNDS, MIN_SECONDS = 5, 0.5
 
 
-def load_parent():
-    L = C.CDLL(PARENT_LIB)
-    L.sextans_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
-    L.sextans_destroy.argtypes = [C.c_void_p]
-    L.sextans_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-    L.sextans_set_matrix_csr_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sextans_spmm_device_rm.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_int64, C.c_void_p,
-                                         C.c_int64, C.c_void_p]
-    L.sextans_last_kernel.argtypes = [C.c_void_p]
-    L.sextans_last_kernel.restype = C.c_char_p
-    return L
-
-
 def child(matrix, Ns, out):
     sys.path.insert(0, ROOT)
     import torch
@@ -57,7 +44,7 @@ def child(matrix, Ns, out):
         p, i, v, nnz = api.gen_fem3d_device(0, 110, 110, 110, 3, 3)
     st = torch.cuda.current_stream().cuda_stream
     e = api.Engine(0)
-    P = load_parent()
+    P = api._bind(C.CDLL(PARENT_LIB))   # (the parent's library beside this tree's, with the same prototypes)
     ph = C.c_void_p()
     assert P.sextans_create(C.byref(ph), 0) == 0
     if fast:
